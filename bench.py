@@ -2,9 +2,19 @@
 """Headline benchmark: grids/s of one full training step (forward + loss + backward + Adam [+ RCCL gradient all-reduce]) of
 Homogeneous_Poisson_NN_Legacy(hpnn.json) on synthetic data resident in HBM.
 
-  python bench.py --gpus N --steps K --warmup W [--workload c4|c3|small]
+  python bench.py --gpus N --steps K --warmup W [--workload c4|c3|small] [--full] [--dump-outputs DIR]
     c4 (default): 8 x 1024^2 Dirichlet grids per GPU, data-parallel weak scaling (BASELINE.json configs[3])
     c3          : 32 x 512^2 grids per GPU (BASELINE.json configs[2])
+
+Plain and full runs.  A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, the outputs (--dump-outputs)
+and the result line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, `rank_ms_per_step`).  Everything else described
+below - the `roofline` block and its single-stream region, `collective_ms`, `inference`, the appended `c3` block, `cpu_baseline`, `dataset`
+and the detail file's `filter_cache` - is measured only with --full (the --no-* switches then skip single blocks as before).
+
+--dump-outputs DIR: what the timed path computed in its LAST timed step of the headline mode, written by rank 0 right after the timed region
+(before any other block runs) as DIR/<name>.npy: `loss` and `mse` (float64, one element each: the train step's logs), `weights` (the flat parameter
+bucket after the step's Adam update, float32), `gradient` (the flat gradient bucket of that step, float32) and `bn_moving_stats` (float32).
+The inputs (weights seed 0, batch seeded per rank) are the same in every run with the same arguments, so two builds compare output by output.
 
 Launching.  N > 1 works both ways: under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (RANK / WORLD_SIZE
 in the environment: this process IS one rank), or bare (`python bench.py --gpus N`): the parent then starts N fresh child processes - one
@@ -13,7 +23,7 @@ and exits with the worst child status.
 
 What is timed.  W warm-up + K timed steps, the timed region bracketed by barrier + synchronize, MAX over ranks:
   * `value` / `ms_per_step` / `dtype` / `roofline`: math mode "fp32" - exact fp32 products and sums, the library default and the
-    reference's precision (experiments/hpnn.json:78).  This is ALL the default run times;
+    reference's precision (experiments/hpnn.json:78).  This is ALL the default run times (`roofline` with --full only);
   * `--modes split_f16,fp32` adds a `split_f16` block: the opt-in 3 x fp16 split mode, timed the same way in the same
     run, with `accuracy_vs_fp32` (forward output and flat gradient of THIS benchmark batch in split mode against fp32 mode).  Since round 4 the
     mode is no faster than fp32 on the shipped model, so the default run no longer spends a third of its GPU time on it.
@@ -27,7 +37,7 @@ kernels; `kernels` (detail file) the per-kernel table of the stamped summary.  `
 same time - a speed-up measure, not a roofline fraction.  `roofline.hbm_bound` is the north star's "conv forward vs HBM roofline" figure: the conv
 launches whose arithmetic intensity is below the fp32 ridge (3x3 tail, <= 8 channels), algorithmic bytes / time, with the transposed-convolution
 and resize forward kernels beside it.
-The default c4 run appends a `c3` block (32 x 512^2, fp32: ms/step, grids/s, the same roofline figures) so that both halves of BASELINE.json's
+The --full c4 run appends a `c3` block (32 x 512^2, fp32: ms/step, grids/s, the same roofline figures) so that both halves of BASELINE.json's
 metric are timed by one command (--no-c3 skips it; at --gpus N > 1 only with --c3: one number per lease); `rank_ms_per_step` lists every rank's own step time, `collective_ms` the gradient
 all-reduce timed on its own (N > 1).
 `cpu_baseline` times the oracle's torch-CPU twin of the same graph (fp32, host cores) on one 512^2 grid - a stand-in for the reference's
@@ -59,10 +69,14 @@ def parse_args(argv=None):
     ap.add_argument('--workload', default='c4', choices=sorted(WORKLOADS),
                     help="launch-check: no model - rendezvous, barrier, all-reduce of the 22.2 MB gradient bucket and the JSON line only "
                          "(runs on CPU/gloo; exercises the N > 1 launch path without a GPU)")
+    ap.add_argument('--full', action='store_true', help='also measure everything beyond the headline: roofline (a second, single-stream region), '
+                                                         'collective_ms, inference, the c3 block, cpu_baseline, dataset, filter_cache (a few minutes)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (loss, mse, weights, gradient, BN moving statistics) as DIR/<name>.npy')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-dataset', action='store_true')
     ap.add_argument('--no-inference', action='store_true', help='skip the forward-only block (a few seconds)')
-    ap.add_argument('--no-c3', action='store_true', help='skip the 32 x 512^2 block that the default c4 run appends')
+    ap.add_argument('--no-c3', action='store_true', help='skip the 32 x 512^2 block that the --full c4 run appends')
     ap.add_argument('--modes', default='fp32', help='math modes to time, in order; the LAST one is the headline.  Default: fp32 only (the library default); '
                                                     '"split_f16,fp32" also times the opt-in split mode with its accuracy gate (a third more GPU time)')
     ap.add_argument('--c3', action='store_true', help='append the 32 x 512^2 block also at --gpus N > 1 (default there: headline workload only - one number per lease)')
@@ -260,6 +274,8 @@ def launch_check(args, dp):
     dp.barrier()
     elapsed = dp.max_over_ranks(time.perf_counter() - t0)
     per_rank = [1e3 * v / args.steps for v in dp.gather_over_ranks(local)]
+    if dp.rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'bucket': bucket.cpu().numpy()})
     if dp.rank == 0:
         print(json.dumps({'metric': 'launch-check (no model)', 'dry_run': True, 'value': args.steps / elapsed, 'unit': 'all-reduces/s (22.2 MB fp32 bucket)',
                           'n_gpus': dp.world_size, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': 1e3 * elapsed / args.steps,
@@ -296,17 +312,20 @@ def compact_line(d):
     if d.get('affinity'):
         out['affinity'] = d['affinity']
     out['collective_ms'] = _r(d.get('collective_ms'), 4)
-    out['roofline'] = {'bound': rf.get('bound'), 'kernel': 'all conv launches of a step (spectral + direct + narrow)', 'achieved': _r(rf.get('achieved'), 1),
-                       'peak': rf.get('peak'), 'unit': rf.get('unit'), 'frac': _r(rf.get('frac')), 'traffic': rf.get('traffic'),
-                       'achieved_is': 'algorithmic bytes (SURVEY 8d) / HIP-event time of all conv launches',
-                       'algorithmic_bytes': rf.get('algorithmic_bytes_per_step'),
-                       'executed_frac': _r(rf.get('executed_frac')), 'executed_is': 'PMC bytes (traffic) / the same time' if rf.get('traffic') else 'no stamped PMC summary',
-                       'traffic_over_algorithmic': _r(rf.get('traffic_over_algorithmic'), 3), 'mfma_busy': _r(rf.get('mfma_busy')),
-                       'conv_ms_per_step': _r(rf.get('conv_kernel_ms_per_step'), 2), 'single_stream_ms_per_step': _r(rf.get('single_stream_ms_per_step'), 2), 'hbm_bound_frac': _r(hbm.get('frac')),
-                       'fused_stage_frac': _r((rf.get('fused_stage') or {}).get('frac')),
-                       'dominant_kernel': None if dom is None else {'name': str(dom['kernel'])[:40], 'ms_per_step': _r(dom['ms_per_step'], 2),
-                                                                    'avg_launch_ms': _r(dom.get('avg_launch_ms')), 'hbm_frac': _r(dom.get('hbm_frac'), 3),
-                                                                    'mfma_busy': _r(dom.get('mfma_busy_frac'), 3)}}
+    if not rf:                         # a plain run (no --full) measures no roofline
+        out['roofline'] = None
+    else:
+        out['roofline'] = {'bound': rf.get('bound'), 'kernel': 'all conv launches of a step (spectral + direct + narrow)', 'achieved': _r(rf.get('achieved'), 1),
+                           'peak': rf.get('peak'), 'unit': rf.get('unit'), 'frac': _r(rf.get('frac')), 'traffic': rf.get('traffic'),
+                           'achieved_is': 'algorithmic bytes (SURVEY 8d) / HIP-event time of all conv launches',
+                           'algorithmic_bytes': rf.get('algorithmic_bytes_per_step'),
+                           'executed_frac': _r(rf.get('executed_frac')), 'executed_is': 'PMC bytes (traffic) / the same time' if rf.get('traffic') else 'no stamped PMC summary',
+                           'traffic_over_algorithmic': _r(rf.get('traffic_over_algorithmic'), 3), 'mfma_busy': _r(rf.get('mfma_busy')),
+                           'conv_ms_per_step': _r(rf.get('conv_kernel_ms_per_step'), 2), 'single_stream_ms_per_step': _r(rf.get('single_stream_ms_per_step'), 2), 'hbm_bound_frac': _r(hbm.get('frac')),
+                           'fused_stage_frac': _r((rf.get('fused_stage') or {}).get('frac')),
+                           'dominant_kernel': None if dom is None else {'name': str(dom['kernel'])[:40], 'ms_per_step': _r(dom['ms_per_step'], 2),
+                                                                        'avg_launch_ms': _r(dom.get('avg_launch_ms')), 'hbm_frac': _r(dom.get('hbm_frac'), 3),
+                                                                        'mfma_busy': _r(dom.get('mfma_busy_frac'), 3)}}
     cb = d.get('cpu_baseline')
     if cb:
         out['cpu_baseline'] = {'value': _r(cb.get('value')), 'unit': cb.get('unit'), 'cores': cb.get('cores'), 'kind': cb.get('kind'), 'sample': str(cb.get('sample'))[:160]}
@@ -347,6 +366,25 @@ def emit(detail, path):
     print(line, flush=True)
 
 
+DUMP_LIMIT = 64 * 10 ** 6   # bytes, all arrays of one --dump-outputs together
+
+
+def dump_outputs(path, arrays):
+    """rank 0: every array of `arrays` ({name: float32 / float64 numpy array}) to path/<name>.npy."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    for k, v in arrays.items():
+        if v.dtype not in (np.float32, np.float64):
+            raise TypeError('--dump-outputs: %s is %s, not float32 / float64' % (k, v.dtype))
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT:
+        raise RuntimeError('--dump-outputs: %d bytes exceed the %d-byte limit' % (total, DUMP_LIMIT))
+    os.makedirs(path, exist_ok=True)
+    if not os.listdir(path):          # a directory of outputs only: keep it out of version control wherever it is placed
+        with open(os.path.join(path, '.gitignore'), 'w') as f:
+            f.write('*\n')
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + '.npy'), v)
 
 
 def pmc_summary(math, workload):
@@ -422,7 +460,7 @@ def run(args):
         note('accuracy gate: forward rel-L2 %.3g, gradient rel-L2 %.3g' % (acc['forward_output']['rel_l2'], acc['flat_gradient']['rel_l2']))
         return acc
 
-    def timed(mode, batch, steps, warmup):
+    def timed(mode, batch, steps, warmup, dump=False):
         ops.set_math_mode(mode)
         for _ in range(warmup):
             model.train_step(batch)
@@ -442,16 +480,23 @@ def run(args):
             dp.barrier()
             elapsed = time.perf_counter() - t0
             ops.set_kernel_timer(None)
-            return dp.max_over_ranks(elapsed), local, float(logs['loss'])
-        # THE timed region: exactly `steps` steps of the library as shipped.  With the side stream on, no per-launch events are recorded in it.
-        prof = None if overlap else ops.KernelTimer()
-        elapsed, local, loss = region(prof)
+            return dp.max_over_ranks(elapsed), local, logs
+        # THE timed region: exactly `steps` steps of the library as shipped.  With the side stream on, no per-launch events are recorded in it;
+        # without --full there is no roofline, so no events at all.
+        prof = ops.KernelTimer() if (args.full and not overlap) else None
+        elapsed, local, logs = region(prof)
+        loss = float(logs['loss'])
+        if dump and dp.rank == 0:      # what the last timed step computed, before anything else runs on the model
+            S = model.store
+            dump_outputs(args.dump_outputs, {'loss': np.float64(loss), 'mse': np.float64(float(logs['mse'])), 'weights': S.flat_w.cpu().numpy(),
+                                             'gradient': S.flat_g.cpu().numpy(), 'bn_moving_stats': S.flat_stats.cpu().numpy()})
+            note('%s: outputs of the last timed step written to %s' % (mode, args.dump_outputs))
         # per-rank view of the same region (before the closing barrier): load imbalance between ranks shows as max > min
         per_rank = [1e3 * v / steps for v in dp.gather_over_ranks(local)]
         rank_ms = {'max': max(per_rank), 'min': min(per_rank), 'ranks': per_rank}
         note('%s: timed region %.3f s' % (mode, elapsed))
         single = None
-        if overlap:                    # roofline region: the same steps on ONE stream, HIP events around every convolution launch
+        if overlap and args.full:      # roofline region: the same steps on ONE stream, HIP events around every convolution launch
             model.ctx.use_side = False
             try:
                 model.train_step(batch)
@@ -463,8 +508,9 @@ def run(args):
                 model.ctx.use_side = True
         # every rank's own convolution-kernel time per step (HIP events of the single-stream region): with rank_ms_per_step.ranks this tells a slow
         # rank (clock, NUMA placement) from collective cost on a scaling curve
-        conv_s = sum(prof.totals(k)[1] for k in ('conv_fwd', 'conv_wgrad', 'conv_bwd_fused', 'conv_stage', 'conv_fwd_post')) if prof is not None else 0.0
-        rank_ms['conv_ms_per_step'] = [1e3 * v / steps for v in dp.gather_over_ranks(conv_s)]
+        if prof is not None:
+            conv_s = sum(prof.totals(k)[1] for k in ('conv_fwd', 'conv_wgrad', 'conv_bwd_fused', 'conv_stage', 'conv_fwd_post'))
+            rank_ms['conv_ms_per_step'] = [1e3 * v / steps for v in dp.gather_over_ranks(conv_s)]
         return elapsed, prof, loss, rank_ms, single
 
     def collective_ms(reps=10):
@@ -545,16 +591,16 @@ def run(args):
                               'deconv_fwd': {'achieved': db / ds / 1e9 if ds else None, 'frac': db / ds / 1e9 / PEAK_HBM_GBS if ds else None, 'launches': dc},
                               'resize_fwd': {'achieved': rb / rs / 1e9 if rs else None, 'frac': rb / rs / 1e9 / PEAK_HBM_GBS if rs else None, 'launches': rc}}}
 
-    def bench_workload(workload, wl_modes, steps, warmup, gate):
+    def bench_workload(workload, wl_modes, steps, warmup, gate, dump=False):
         per_gpu, H, batch = make_batch(workload)
         gbs = per_gpu * dp.world_size
         model.compile(loss=loss_wrapper(global_batch_size=gbs, **full['training']['loss_parameters']), optimizer=Adam(**full['training']['optimizer_parameters']))
         accuracy = accuracy_gate(per_gpu, batch) if (gate and 'split_f16' in wl_modes and 'fp32' in wl_modes) else None
         blocks = {}
         for mode in wl_modes:
-            elapsed, prof, loss, rank_ms, single = timed(mode, batch, steps, warmup)
+            elapsed, prof, loss, rank_ms, single = timed(mode, batch, steps, warmup, dump=dump and mode == wl_modes[-1])
             blocks[mode] = {'value': gbs * steps / elapsed, 'unit': 'grids/s', 'ms_per_step': 1e3 * elapsed / steps, 'dtype': DTYPE[mode], 'final_loss': loss,
-                            'rank_ms_per_step': rank_ms, 'roofline': roofline(mode, prof, workload, steps) if dp.rank == 0 else None}
+                            'rank_ms_per_step': rank_ms, 'roofline': roofline(mode, prof, workload, steps) if (dp.rank == 0 and prof is not None) else None}
             if blocks[mode]['roofline'] is not None:
                 blocks[mode]['roofline']['single_stream_ms_per_step'] = single
                 blocks[mode]['roofline']['measured_in'] = ('a second region of the same %d steps with every launch on one stream (the timed region overlaps the direct / narrow '
@@ -565,8 +611,8 @@ def run(args):
             blocks['split_f16']['accuracy_vs_fp32'] = accuracy
         return per_gpu, H, gbs, blocks
 
-    per_gpu, H, gbs, blocks = bench_workload(args.workload, modes, args.steps, args.warmup, True)
-    coll_ms = collective_ms()
+    per_gpu, H, gbs, blocks = bench_workload(args.workload, modes, args.steps, args.warmup, True, dump=bool(args.dump_outputs))
+    coll_ms = collective_ms() if args.full else None
 
     def inference_block(workload, reps=5):
         """Forward only (model([rhs, dx]), the reference's inference path) on the headline batch: ms per batch and the HBM-bound view of its narrow
@@ -600,15 +646,15 @@ def run(args):
                 'all_conv_fwd': {'algorithmic_GBs': ab / as_ / 1e9 if as_ else None, 'frac': ab / as_ / 1e9 / PEAK_HBM_GBS if as_ else None, 'launches': ac // reps,
                                  'ms': 1e3 * as_ / reps}}
     inference = None
-    if dp.world_size == 1 and not args.no_inference:
+    if args.full and dp.world_size == 1 and not args.no_inference:
         note('inference block (forward only) ...')
         try:
             inference = inference_block(args.workload)
         except Exception as e:   # noqa: BLE001 - a side measurement must not kill the headline
             inference = {'error': repr(e)}
-    # the other half of BASELINE.json's metric ("at 512^2 & 1024^2"): the default c4 run appends the 32 x 512^2 workload, fp32 mode, same timing rules
+    # the other half of BASELINE.json's metric ("at 512^2 & 1024^2"): the --full c4 run appends the 32 x 512^2 workload, fp32 mode, same timing rules
     c3 = None
-    if args.workload == 'c4' and not args.no_c3 and modes[-1] == 'fp32' and (dp.world_size == 1 or args.c3):
+    if args.full and args.workload == 'c4' and not args.no_c3 and modes[-1] == 'fp32' and (dp.world_size == 1 or args.c3):
         note('c3 block (32 x 512^2, fp32) ...')
         p3, H3, g3, b3 = bench_workload('c3', ['fp32'], args.steps, args.warmup, False)
         c3 = dict(b3['fp32'], metric='grids/sec (fwd+bwd) at %d^2' % H3, steps=args.steps, warmup=args.warmup,
@@ -636,19 +682,20 @@ def run(args):
         out['inference'] = inference
     if c3 is not None:
         out['c3'] = c3
-    if dp.world_size == 1 and not args.no_cpu_baseline:
+    if args.full and dp.world_size == 1 and not args.no_cpu_baseline:
         note('cpu baseline (bounded sample: one %d^2 grid) ...' % args.cpu_baseline_hw)
         out['cpu_baseline'] = cpu_baseline(args.cpu_baseline_hw, with_1024=(args.workload == 'c4' and not args.no_cpu_baseline_1024))
-    if dp.world_size == 1 and not args.no_dataset:
+    if args.full and dp.world_size == 1 and not args.no_dataset:
         note('dataset generator block ...')
         try:
             out['dataset'] = dataset_block()
         except Exception as e:   # the headline must not die on the side measurement
             out['dataset'] = {'error': repr(e)}
-    try:                                       # detail file only: what the kept filter spectra cost (pcnn_set_filter_version)
-        out['filter_cache'] = dict(ops.filter_cache_stats(), enabled=bool(ops.filter_version()))
-    except Exception as e:
-        out['filter_cache'] = {'error': repr(e)}
+    if args.full:
+        try:                                   # detail file only: what the kept filter spectra cost (pcnn_set_filter_version)
+            out['filter_cache'] = dict(ops.filter_cache_stats(), enabled=bool(ops.filter_version()))
+        except Exception as e:
+            out['filter_cache'] = {'error': repr(e)}
     emit(out, args.detail)
 
 

@@ -1,4 +1,4 @@
-"""Generates tests/golden/atsize_golden.npz: fp64 ORACLE vectors at BASELINE.json's full grid sizes.
+"""Generates tests/golden/atsize/part_NN.npz (one fixture split into files below 1 MiB; load_golden() puts it together): fp64 ORACLE vectors at BASELINE.json's full grid sizes.
 
   C1: hpnn.json model, forward of the single 128^2 Dirichlet grid of BASELINE configs[0] (seed 1, dx = 0.02).
   C2: hpnn.json model, forward of ONE sample (index 5) of the 16 x 256^2 Dirichlet batch (seed 2).  Samples are independent
@@ -25,6 +25,7 @@ in the build container.  Run time on 8 cores: about 15 min
 
     python tests/golden/make_atsize_golden.py [c1] [c2] [c3] [c3tanh] [c4] [c4grad]        (c4 alone: about 10 minutes)
 """
+import glob
 import os
 import sys
 import time
@@ -38,8 +39,56 @@ from oracle import hpnn as ohpnn, torch_twin, loss as oloss  # noqa: E402
 from poisson_cnn_amd import configs  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-PATH = os.path.join(HERE, 'atsize_golden.npz')
+DIR = os.path.join(HERE, 'atsize')
+PART_BYTES = 768 * 1024        # raw bytes per part file: compressed, every committed part stays below 1 MiB
 WEIGHT_SEED, WEIGHT_GAIN = 11, 1.6
+
+
+def save_golden(out):
+    """Writes {name: array} as DIR/part_NN.npz.  An array larger than PART_BYTES is stored flat in chunks `<name>#<k>`, its shape as `<name>#shape`."""
+    items = []
+    for k, v in out.items():
+        v = np.asarray(v)
+        if v.nbytes <= PART_BYTES:
+            items.append((k, v))
+            continue
+        flat, n = v.reshape(-1), PART_BYTES // v.itemsize
+        items.append((k + '#shape', np.array(v.shape, dtype=np.int64)))
+        items += [('%s#%d' % (k, i), flat[j:j + n]) for i, j in enumerate(range(0, flat.size, n))]
+    parts, cur, size = [], {}, 0
+    for k, v in items:
+        if cur and size + v.nbytes > PART_BYTES:
+            parts.append(cur)
+            cur, size = {}, 0
+        cur[k] = v
+        size += v.nbytes
+    if cur:
+        parts.append(cur)
+    os.makedirs(DIR, exist_ok=True)
+    for f in glob.glob(os.path.join(DIR, 'part_*.npz')):
+        os.remove(f)
+    for i, p in enumerate(parts):
+        np.savez_compressed(os.path.join(DIR, 'part_%02d.npz' % i), **p)
+
+
+def load_golden():
+    """{name: array} of the fixture that save_golden wrote (empty if there is none), chunked arrays put back together."""
+    out, shapes, chunks = {}, {}, {}
+    for f in sorted(glob.glob(os.path.join(DIR, 'part_*.npz'))):
+        with np.load(f) as z:
+            for k in z.files:
+                if '#' not in k:
+                    out[k] = z[k]
+                    continue
+                name, tag = k.rsplit('#', 1)
+                out.setdefault(name, None)
+                if tag == 'shape':
+                    shapes[name] = tuple(int(d) for d in z[k])
+                else:
+                    chunks.setdefault(name, []).append((int(tag), z[k]))
+    for name, shape in shapes.items():
+        out[name] = np.concatenate([c for _, c in sorted(chunks[name], key=lambda t: t[0])]).reshape(shape)
+    return out
 
 
 def c2_inputs():
@@ -130,7 +179,7 @@ C4_GRADS = ('pre/conv0/kernel', 'pre/conv2/kernel', 'final/out0/kernel', 'final/
 
 def main():
     which = set(sys.argv[1:]) or {'c2', 'c3', 'c4'}
-    out = dict(np.load(PATH)) if os.path.exists(PATH) else {}
+    out = load_golden()
     torch.set_num_threads(max(1, os.cpu_count() or 1))
     full = configs.hpnn()
     if 'c1' in which:
@@ -142,7 +191,7 @@ def main():
             y = ohpnn.forward(torch_twin, cfg, {n: torch.tensor(v) for n, v in p.items()}, torch.tensor(rhs.astype(np.float64)), torch.tensor(dx.astype(np.float64)))
         out['c1_out'] = y.numpy().astype(np.float32)
         print('c1: %.1f s, max|y| %.4g' % (time.time() - t0, np.abs(out['c1_out']).max()), flush=True)
-        np.savez_compressed(PATH, **out)
+        save_golden(out)
     if 'c2' in which:
         cfg = full['model']
         p = ohpnn.init_params(cfg, seed=WEIGHT_SEED, gain=WEIGHT_GAIN, randomize_all=True)
@@ -155,7 +204,7 @@ def main():
         out['c2_sample'] = np.int64(k)
         out['c2_out'] = y.numpy().astype(np.float32)
         print('c2: %.1f s, max|y| %.4g' % (time.time() - t0, np.abs(out['c2_out']).max()), flush=True)
-        np.savez_compressed(PATH, **out)
+        save_golden(out)
     if 'c4' in which:
         cfg = full['model']
         p = ohpnn.init_params(cfg, seed=WEIGHT_SEED, gain=WEIGHT_GAIN, randomize_all=True)
@@ -168,7 +217,7 @@ def main():
         out['c4_sample'] = np.int64(k)
         out['c4_out'] = y.numpy().astype(np.float32)
         print('c4: %.1f s, max|y| %.4g' % (time.time() - t0, np.abs(out['c4_out']).max()), flush=True)
-        np.savez_compressed(PATH, **out)
+        save_golden(out)
     if 'c4grad' in which:
         import threading
         import psutil
@@ -211,7 +260,7 @@ def main():
             # the wide-filter gradients are kept in float32: the rounding (6e-8) is far below the test tolerance and the fixture stays a few MB
             out['c4_grad:%s' % n.replace('/', '.')] = g.astype(np.float32 if g.size > 4096 else np.float64)
         print('c4grad: %.1f s, loss %.6g, pred vs c4_out %.3g' % (time.time() - t0, float(loss.detach()), float(out['c4_pred_vs_c4_out'])), flush=True)
-        np.savez_compressed(PATH, **out)
+        save_golden(out)
         del pt, pred, loss
     if 'c3tanh' in which:
         rhs, dx, tgt = c3_inputs()
@@ -231,7 +280,7 @@ def main():
         out['c3tanh_grad_norms'] = np.array([float(pt[n].grad.norm()) for n in names])
         out['c3tanh_grad_sub'] = np.concatenate([pt[n].grad.numpy().reshape(-1)[::C3T_STRIDE] for n in names]).astype(np.float64)
         print('c3tanh: %.1f s, loss %.6g, %d sampled gradient entries' % (time.time() - t0, float(loss.detach()), out['c3tanh_grad_sub'].size), flush=True)
-        np.savez_compressed(PATH, **out)
+        save_golden(out)
         del pt, pred, loss
     if 'c3' in which:
         rhs, dx, tgt = c3_inputs()
@@ -254,7 +303,7 @@ def main():
             for n in ('pre/conv0/kernel', 'final/out0/kernel', 'final/out0/bias', 'final/out1/kernel', 'final/out1/bias', 'final/stage0/conv/bias'):
                 out['c3_%s_grad:%s' % (bc, n.replace('/', '.'))] = pt[n].grad.numpy().astype(np.float64)
             print('c3 %s: %.1f s, loss %.6g' % (bc, time.time() - t0, float(loss.detach())), flush=True)
-            np.savez_compressed(PATH, **out)
+            save_golden(out)
             del pt, pred, loss
     print({k: getattr(v, 'shape', v) for k, v in out.items()})
 

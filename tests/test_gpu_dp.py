@@ -119,7 +119,7 @@ def test_bench_two_ranks_bare_invocation_on_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
     env['PCNN_DIST_BACKEND'] = 'gloo'
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--workload', 'small', '--steps', '1', '--warmup', '1',
-                        '--no-cpu-baseline', '--no-dataset', '--modes', 'split_f16,fp32'], env=env, capture_output=True, text=True, timeout=900)
+                        '--full', '--no-cpu-baseline', '--no-dataset', '--modes', 'split_f16,fp32'], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
     assert len(lines) == 1, r.stdout
@@ -132,6 +132,29 @@ def test_bench_two_ranks_bare_invocation_on_gpu():
         detail = json.load(f)
     assert detail['split_f16']['accuracy_vs_fp32']['forward_output']['rel_l2'] < 1e-5 and detail['roofline']['bound'] == 'hbm'
 
+
+
+def test_bench_plain_run_times_the_headline_only_and_dumps_its_last_step(tmp_path):
+    """`python bench.py` without --full: the timed steps and the result line only (no roofline, c3, inference, cpu_baseline or dataset block);
+    --dump-outputs writes the last timed step's loss, mse, weights, gradient and BN statistics (float32 / float64, <= 64 MB in all)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out_dir = tmp_path / 'outputs'
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--workload', 'small', '--steps', '2', '--warmup', '1',
+                        '--dump-outputs', str(out_dir), '--detail', str(tmp_path / 'detail.json')], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    assert out['steps'] == 2 and out['ms_per_step'] > 0 and out['value'] > 0 and out['dtype'] == 'f32' and out['higher_is_better'] is True
+    assert out['roofline'] is None and not any(k in out for k in ('c3', 'inference', 'cpu_baseline', 'dataset'))
+    arrays = {f[:-4]: np.load(out_dir / f) for f in os.listdir(out_dir) if f.endswith('.npy')}
+    assert set(arrays) == {'loss', 'mse', 'weights', 'gradient', 'bn_moving_stats'}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 * 10 ** 6
+    assert arrays['weights'].shape == arrays['gradient'].shape == (5556956,) and float(np.abs(arrays['gradient']).max()) > 0
 
 def test_c_abi_collective_single_rank():
     """pcnn_comm_unique_id / pcnn_comm_init / pcnn_allreduce / pcnn_broadcast (RCCL bound inside libpcnn, include/pcnn.h) with world size 1:

@@ -200,6 +200,16 @@ def test_bench_parent_enforces_the_launch_timeout():
     assert time.monotonic() - t0 < 60
 
 
+
+def test_bench_dump_outputs_writes_what_the_last_step_computed(tmp_path):
+    """--dump-outputs DIR on the launch path: rank 0 writes the bucket after the last timed all-reduce as DIR/bucket.npy (float32; the ranks
+    start from 1 and 2, so after 1 warm-up + 2 timed sums of two ranks every element is 3 * 2 * 2)."""
+    import numpy as np
+    r = _bare_bench(['--gpus', '2', '--dump-outputs', str(tmp_path / 'out')])
+    assert r.returncode == 0, r.stderr[-2000:]
+    b = np.load(tmp_path / 'out' / 'bucket.npy')
+    assert b.dtype == np.float32 and b.shape == (5556956,) and np.all(b == 12.0)
+
 def test_compact_bench_line_from_a_recorded_full_result():
     """round 3's bench line was 22 959 bytes and reached the driver cut off (parsed: null).  The compact line built from
     that very record must parse, stay under the limit and still carry the contract's fields, `roofline` and `cpu_baseline`."""
