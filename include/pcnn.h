@@ -301,6 +301,56 @@ size_t pcnn_deconv_wgrad_workspace(int N, int hc, int wc, int Cin, int Cout, int
 int pcnn_deconv_bwd_filter(pcnn_handle h, int N, int hc, int wc, int Cin, int H, int W, int Cout, int f, const float* x, int ldx,
                            const float* dy, int lddy, float alpha, float* dk, float* dbias, void* workspace, size_t workspace_bytes);
 
+/* ---- wide-channel convolutions of the UNet baseline (models/UNet.py; csrc/conv_wide.hip) -----------------------------------------------
+ * Any Cin, Cout >= 1 (channel tails masked), NHWC with channel strides, implicit GEMMs on v_mfma_f32_32x32x2_f32.  These kernels compute exact
+ * fp32 products with fp32 accumulation in EVERY math mode (pcnn_set_math_mode does not apply to them).
+ * One descriptor for every call; it describes the operation in the direction it runs: input (N,H,W,Cin) with channel stride ldx, output
+ * (N,Ho,Wo,Cout) with stride ldy.  `k`: the odd filter size of a SAME convolution (Ho = H, Wo = W), or f = kernel = stride of a transposed one.
+ * Forward calls: epilogue z = acc + bias[co]; dropout (rate > 0) z = keep ? z / (1 - rate) : 0; y = act(z).
+ * Data-gradient calls: dx = acc * act'(act_out) [* dropout mask / (1 - rate)] where act / dropout / act_out (stride ld_act_out) describe the
+ * layer that PRODUCED the tensor whose gradient is formed (act' is taken from that layer's output: ReLU' = [a > 0], and with ReLU the mask is
+ * implied by a > 0, so it is not recomputed); act_out == NULL: no epilogue.  accumulate = 1: y += result instead of y = result.
+ * Dropout mask (stateless; element idx = pixel * C + channel of the dense NHWC tensor of C channels being produced, pixel = (n*H + y)*W + x):
+ *   fmix(h) = murmur3 finaliser: h ^= h>>16; h *= 0x85EBCA6B; h ^= h>>13; h *= 0xC2B2AE35; h ^= h>>16  (uint32 arithmetic)
+ *   h = fmix(seed ^ (layer * 0x9E3779B9)); h = fmix(h ^ (idx >> 32)); h = fmix(h ^ (idx & 0xFFFFFFFF))
+ *   keep iff h >= floor(min((double)rate * 2^32, 2^32 - 1))
+ * The Keras inverted dropout of ConvBlock (models/UNet.py:69-75 `layers.Dropout(rate)` under training=True). */
+typedef struct {
+  int N, H, W, Cin, ldx;          /* input  */
+  int Ho, Wo, Cout, ldy;          /* output */
+  int k;
+  int act; float act_alpha;
+  float dropout_rate; uint32_t dropout_seed; uint32_t dropout_layer;
+  int ld_act_out;
+  int accumulate;
+} pcnn_wide_desc;
+/* tf.keras.layers.Conv2D(filters, k, padding='same') + Dropout + Activation of ConvBlock (models/UNet.py:46-77) and the 1x1 head (:260-265):
+ * w (k,k,Cin,Cout) Keras HWIO, bias (Cout) or NULL. */
+int pcnn_wide_conv2d_fwd(pcnn_handle h, const pcnn_wide_desc* d, const float* x, const float* w, const float* bias, float* y);
+/* Its data gradient (tf.nn.conv2d backprop-input under the GradientTape of models/UNet.py:169-177): the same engine on
+ * wf = pcnn_conv2d_flip_transpose_weights(w) (k,k,Cout_fwd,Cin_fwd); d: input dz (Cin = the forward Cout), output dx (Cout = the forward Cin). */
+int pcnn_wide_conv2d_dgrad(pcnn_handle h, const pcnn_wide_desc* d, const float* dz, const float* wf, const float* act_out, float* dx);
+/* Filter gradient dw[i,j,ci,co] = sum_p x[p + (i,j) - k/2, ci] dz[p, co] and dbias[co] = sum_p dz[p, co] (NULL = skip); d = the FORWARD
+ * descriptor (dz has stride ldy).  Split-K over the pixels into `workspace` (pcnn_wide_conv2d_wgrad_workspace bytes), reduced in a fixed order:
+ * deterministic. */
+size_t pcnn_wide_conv2d_wgrad_workspace(const pcnn_wide_desc* d);
+int pcnn_wide_conv2d_wgrad(pcnn_handle h, const pcnn_wide_desc* d, const float* x, const float* dz, float* dw, float* dbias, void* workspace,
+                           size_t workspace_bytes);
+/* deconvupscale with kernel_size == upsample_ratio = f (layers/deconvupscale.py:100-109, models/UNet.py:246): tf.nn.conv2d_transpose(x, k,
+ * (N,Ho,Wo,Cout), strides=f, padding='SAME') + bias + act, k (f,f,Cout,Cin); H = ceil(Ho/f), W = ceil(Wo/f):
+ *   y[n,Y,X,co] = act(bias[co] + sum_ci x[n,(Y+py)/f,(X+px)/f,ci] * k[(Y+py)%f,(X+px)%f,co,ci]),  py = (H*f - Ho)/2, px = (W*f - Wo)/2.
+ * A per-input-pixel GEMM (Cin x f*f*Cout) followed by depth-to-space in the epilogue.  No dropout, no accumulate. */
+int pcnn_wide_deconv_fwd(pcnn_handle h, const pcnn_wide_desc* d, const float* x, const float* k, const float* bias, float* y);
+/* Its data gradient: d: input dz on the fine grid (N,H,W,Cin = the deconvolution's Cout, stride ldx), output dx on the coarse grid
+ * (N,Ho,Wo,Cout = the deconvolution's Cin, stride ldy), Ho = ceil(H/f); dz is the gradient AFTER the deconvolution's own activation backward;
+ * epilogue as for every data gradient. */
+int pcnn_wide_deconv_bwd_data(pcnn_handle h, const pcnn_wide_desc* d, const float* dz, const float* k, const float* act_out, float* dx);
+/* Its filter gradient dk (f,f,Cout,Cin); d = the FORWARD descriptor (x coarse stride ldx, dz fine stride ldy).  Deterministic split-K;
+ * the bias gradient is the channel sum of dz (pcnn_epilogue_bwd). */
+size_t pcnn_wide_deconv_bwd_filter_workspace(const pcnn_wide_desc* d);
+int pcnn_wide_deconv_bwd_filter(pcnn_handle h, const pcnn_wide_desc* d, const float* x, const float* dz, float* dk, void* workspace,
+                                size_t workspace_bytes);
+
 /* ---- tf.image.resize(antialias=False, half-pixel centres) (layers/Upsample.py:56-59) ------------------------
  * Separable 4-tap gather: idx_y/wt_y are (Ho,4) tables, idx_x/wt_x (Wo,4) (nearest/bilinear use fewer taps with
  * zero weights).  Tables come from pcnn_resize_tables (host, float32 arithmetic of the TF kernels).

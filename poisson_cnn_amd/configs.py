@@ -76,6 +76,32 @@ def hpnn_tiny():
     return cfg
 
 
+def unet():
+    """experiments/UNet.json: UNet(layer_depth=4, padding='same', the other arguments at their defaults) on the analytic dataset of hpnn.json."""
+    model = {'in_channels': 1, 'out_channels': 1, 'nx': None, 'ny': None, 'layer_depth': 4, 'final_activation': 'linear', 'padding': 'same'}
+    dataset = copy.deepcopy(hpnn()['dataset'])
+    training = {
+        'n_epochs': 200, 'precision': 'float32', 'optimizer': 'adam',
+        'optimizer_parameters': {'learning_rate': 1e-4, 'amsgrad': False}, 'min_learning_rate': 1e-7,
+        'loss_parameters': {
+            'ndims': 2, 'data_format': 'channels_first', 'mae_loss_weight': 1.0, 'integral_loss_weight': 0.0,
+            'integral_loss_config': {'n_quadpts': 47, 'Lp_norm_power': 2},
+            'physics_informed_loss_weight': 0.0,
+            'physics_informed_loss_config': {'stencil_sizes': [5, 5], 'orders': 2, 'normalize': False},
+            'scale_sample_loss_by_target_peak_magnitude': True},
+    }
+    return {'model': model, 'dataset': dataset, 'training': training}
+
+
+def unet_tiny():
+    """A depth-3, 8-filter UNet on small grids (tests)."""
+    cfg = unet()
+    cfg['model'].update(layer_depth=3, filters_root=8)
+    cfg['dataset'].update(batch_size=4, batches_per_epoch=2, random_output_shape_range=[[64, 96], [64, 96]])
+    cfg['training']['n_epochs'] = 1
+    return cfg
+
+
 def load_config(path):
     with open(path) as f:
         return json.load(f)

@@ -1221,3 +1221,120 @@ def grouped_deconv_bwd_filter(x, dy, f, dk_all, dbias_all=None):
     handle().call('pcnn_grouped_deconv_bwd_filter', c_int(N), c_int(hc), c_int(wc), c_int(Cin), c_int(H), c_int(W), c_int(Cout), c_int(f), _p(x), _p(dy), _p(dk_all),
                   ctypes.c_longlong(_row_stride(dk_all)), _p(dbias_all), ctypes.c_longlong(_row_stride(dbias_all) if dbias_all is not None else 0))
     return dk_all
+
+
+# ----------------------------------------------------------------------------- wide-channel convolutions (UNet baseline, csrc/conv_wide.hip)
+class WideDesc(ctypes.Structure):
+    """include/pcnn.h pcnn_wide_desc"""
+    _fields_ = [('N', c_int), ('H', c_int), ('W', c_int), ('Cin', c_int), ('ldx', c_int),
+                ('Ho', c_int), ('Wo', c_int), ('Cout', c_int), ('ldy', c_int), ('k', c_int),
+                ('act', c_int), ('act_alpha', c_float), ('dropout_rate', c_float), ('dropout_seed', ctypes.c_uint32),
+                ('dropout_layer', ctypes.c_uint32), ('ld_act_out', c_int), ('accumulate', c_int)]
+
+
+def wide_desc(x_shape, ldx, out_shape, ldy, k, act='linear', dropout=None, ld_act=0, accumulate=False):
+    """dropout: None or (rate, seed, layer id) - the forward layer's mask (include/pcnn.h "Dropout mask")."""
+    N, H, W, Cin = x_shape
+    _, Ho, Wo, Cout = out_shape
+    rate, seed, layer = dropout if dropout is not None else (0.0, 0, 0)
+    return WideDesc(N, H, W, Cin, ldx, Ho, Wo, Cout, ldy, int(k), ACTS[act], LEAKY_ALPHA, float(rate), int(seed) & 0xFFFFFFFF,
+                    int(layer) & 0xFFFFFFFF, ld_act, 1 if accumulate else 0)
+
+
+def wide_conv2d_fwd(x, w, bias=None, *, act='linear', dropout=None, out=None):
+    """SAME k x k convolution (odd k <= 7, any channel counts) + bias [+ dropout] + act: pcnn_wide_conv2d_fwd.  `out` may be a channel slice."""
+    N, H, W, Cin = x.shape
+    k, _, ci, Cout = w.shape
+    assert ci == Cin and w.is_contiguous(), (tuple(w.shape), tuple(x.shape))
+    y = out if out is not None else empty((N, H, W, Cout), x.device)
+    d = wide_desc(x.shape, _ld(x), y.shape, _ld(y), k, act, dropout)
+    _launch('wide_fwd', 2.0 * N * H * W * k * k * Cin * Cout,
+            lambda: handle().call('pcnn_wide_conv2d_fwd', byref(d), _p(x), _p(w), _p(bias), _p(y)))
+    return y
+
+
+def wide_conv2d_dgrad(dz, wf, *, act_out=None, act='relu', dropout=None, out=None, accumulate=False):
+    """dx of the SAME convolution whose flipped / transposed filter is wf (flip_transpose_weights), times act'(act_out) of the layer that produced x
+    (and its dropout mask where the activation does not imply it); accumulate: out += dx.  pcnn_wide_conv2d_dgrad."""
+    N, H, W, Co = dz.shape
+    k, _, co, Cin = wf.shape
+    assert co == Co and wf.is_contiguous()
+    if out is None:
+        out, accumulate = empty((N, H, W, Cin), dz.device), False
+    d = wide_desc(dz.shape, _ld(dz), out.shape, _ld(out), k, act if act_out is not None else 'linear', dropout,
+                  _ld(act_out) if act_out is not None else 0, accumulate)
+    _launch('wide_dgrad', 2.0 * N * H * W * k * k * Cin * Co,
+            lambda: handle().call('pcnn_wide_conv2d_dgrad', byref(d), _p(dz), _p(wf), _p(act_out), _p(out)))
+    return out
+
+
+def wide_conv2d_wgrad(x, dz, w_shape, *, dw=None, dbias=None, ws=None):
+    """dw (k,k,Cin,Cout) and dbias (Cout, optional) of the SAME convolution x -> dz: deterministic split-K, pcnn_wide_conv2d_wgrad."""
+    N, H, W, Cin = x.shape
+    k, _, ci, Cout = w_shape
+    d = wide_desc(x.shape, _ld(x), dz.shape, _ld(dz), k)
+    lib = _lib.load()
+    wsb = (ws or _default_ws).get(lib.pcnn_wide_conv2d_wgrad_workspace(byref(d)), x.device)
+    dw = dw if dw is not None else empty(tuple(w_shape), x.device)
+    assert dw.is_contiguous()
+    _launch('wide_wgrad', 2.0 * N * H * W * k * k * Cin * Cout,
+            lambda: handle().call('pcnn_wide_conv2d_wgrad', byref(d), _p(x), _p(dz), _p(dw), _p(dbias), _p(wsb), c_size_t(wsb.numel() * 4)))
+    return dw
+
+
+def wide_deconv_fwd(x, k, bias, out_hw, f, *, act='linear', out=None):
+    """tf.nn.conv2d_transpose(SAME, kernel = stride = f) + bias + act, k (f,f,Cout,Cin): pcnn_wide_deconv_fwd.  `out` may be a channel slice."""
+    N, hc, wc, Cin = x.shape
+    assert k.shape[0] == f and k.shape[1] == f and k.shape[3] == Cin and k.is_contiguous()
+    Cout = k.shape[2]
+    H, W = out_hw
+    y = out if out is not None else empty((N, H, W, Cout), x.device)
+    d = wide_desc(x.shape, _ld(x), y.shape, _ld(y), f, act)
+    _launch('wide_deconv_fwd', 2.0 * N * hc * wc * f * f * Cin * Cout,
+            lambda: handle().call('pcnn_wide_deconv_fwd', byref(d), _p(x), _p(k), _p(bias), _p(y)))
+    return y
+
+
+def wide_deconv_bwd_data(dz, k, coarse_hw, f, *, act_out=None, act='relu', dropout=None, out=None, accumulate=False):
+    """dx (coarse) of the transposed convolution from dz (the gradient after its own activation backward), times act'(act_out) of x's producer."""
+    N, H, W, Cout = dz.shape
+    Cin = k.shape[3]
+    hc, wc = coarse_hw
+    if out is None:
+        out, accumulate = empty((N, hc, wc, Cin), dz.device), False
+    d = wide_desc(dz.shape, _ld(dz), out.shape, _ld(out), f, act if act_out is not None else 'linear', dropout,
+                  _ld(act_out) if act_out is not None else 0, accumulate)
+    _launch('wide_deconv_dgrad', 2.0 * N * hc * wc * f * f * Cin * Cout,
+            lambda: handle().call('pcnn_wide_deconv_bwd_data', byref(d), _p(dz), _p(k), _p(act_out), _p(out)))
+    return out
+
+
+def wide_deconv_bwd_filter(x, dz, f, *, dk=None, ws=None):
+    """dk (f,f,Cout,Cin) of the transposed convolution x -> dz: deterministic split-K, pcnn_wide_deconv_bwd_filter."""
+    N, hc, wc, Cin = x.shape
+    Cout = dz.shape[3]
+    d = wide_desc(x.shape, _ld(x), dz.shape, _ld(dz), f)
+    lib = _lib.load()
+    wsb = (ws or _default_ws).get(lib.pcnn_wide_deconv_bwd_filter_workspace(byref(d)), x.device)
+    dk = dk if dk is not None else empty((f, f, Cout, Cin), x.device)
+    _launch('wide_deconv_wgrad', 2.0 * N * hc * wc * f * f * Cin * Cout,
+            lambda: handle().call('pcnn_wide_deconv_bwd_filter', byref(d), _p(x), _p(dz), _p(dk), _p(wsb), c_size_t(wsb.numel() * 4)))
+    return dk
+
+
+def dropout_keep_mask(shape, rate, seed, layer):
+    """Host restatement of the kernels' dropout mask (include/pcnn.h): bool array of `shape` (dense NHWC), True = kept."""
+    def fmix(h):
+        h = h ^ (h >> np.uint32(16))
+        h = h * np.uint32(0x85EBCA6B)
+        h = h ^ (h >> np.uint32(13))
+        h = h * np.uint32(0xC2B2AE35)
+        return h ^ (h >> np.uint32(16))
+    n = int(np.prod(shape))
+    idx = np.arange(n, dtype=np.uint64)
+    with np.errstate(over='ignore'):
+        h0 = fmix(np.uint32(int(seed) & 0xFFFFFFFF) ^ np.uint32((int(layer) * 0x9E3779B9) & 0xFFFFFFFF))
+        h = fmix(np.uint32(h0) ^ (idx >> np.uint64(32)).astype(np.uint32))
+        h = fmix(h ^ (idx & np.uint64(0xFFFFFFFF)).astype(np.uint32))
+    th = min(float(np.float32(rate)) * 4294967296.0, 4294967295.0)
+    return (h >= np.uint32(int(th))).reshape(shape)

@@ -189,9 +189,9 @@ def main(argv=None):
     p.add_argument('--dataset_type', type=lambda x: str(x).lower(), default='analytical')
     p.add_argument('--learning_rate', type=str, default=None)
     p.add_argument('--epochs', type=int, default=None)
-    p.add_argument('--model', type=lambda x: str(x).lower(), default='hpnn', choices=['hpnn', 'dbcnn', 'pcnn'],
+    p.add_argument('--model', type=lambda x: str(x).lower(), default='hpnn', choices=['hpnn', 'dbcnn', 'pcnn', 'unet'],
                    help='hpnn: train/hpnn_legacy_train.py (train/hpnn_train.py when the model section carries model_type); dbcnn: train/dbcnn_legacy_train.py; '
-                        'pcnn: train/pcnn_end_to_end.py')
+                        'pcnn: train/pcnn_end_to_end.py; unet: train/UNet.py')
     args = p.parse_args(argv)
     if args.dataset_type not in ('numerical', 'analytical'):
         raise ValueError('Invalid dataset type. Received: ' + args.dataset_type)
@@ -212,6 +212,10 @@ def main(argv=None):
         dataset = numerical_dataset_generator(randomize_boundary_smoothness=True, exclude_zero_boundaries=False, nonzero_boundaries=['left', 'right', 'top', 'bottom'],
                                               rhses='random', return_boundaries=True, return_dx=True, return_rhs=True, **dcfg)
         model = Poisson_CNN_Legacy(Homogeneous_Poisson_NN_Legacy(**config['hpnn_model']), Dirichlet_BC_NN_Legacy_2(**config['dbcnn_model']))
+    elif args.model == 'unet':     # train/UNet.py:22-34: dataset by --dataset_type, UNet(**config['model'])
+        from .unet import UNet
+        dataset = numerical_dataset_generator(**dcfg) if args.dataset_type == 'numerical' else reverse_poisson_dataset_generator(**dcfg)
+        model = UNet(**config['model'])
     elif 'model_type' in config['model']:      # train/hpnn_train.py:23-33: the config names the model class; analytic (reverse) dataset
         from .hpnn_models import Homogeneous_Poisson_NN, Homogeneous_Poisson_NN_Metalearning
         mcfg = dict(config['model'])
@@ -235,7 +239,8 @@ def main(argv=None):
     # the largest batch this run will see, for model.presize(): only where the generator draws its grid shape from a range (the analytic generators)
     rng_ = config['dataset'].get('random_output_shape_range')
     presize = None
-    if rng_ is not None and isinstance(model, Homogeneous_Poisson_NN_Legacy) and os.environ.get('PCNN_PRESIZE', '1') != '0':
+    from .unet import UNetModel
+    if rng_ is not None and isinstance(model, (Homogeneous_Poisson_NN_Legacy, UNetModel)) and os.environ.get('PCNN_PRESIZE', '1') != '0':
         r = np.asarray(rng_, dtype=np.int64)
         r = np.tile(r[None], (2, 1)) if r.ndim == 1 else r
         presize = (dcfg['batch_size'], int(r[0, 1]), int(r[1, 1]))
