@@ -258,8 +258,7 @@ int pcnn_conv2d_fwd_split(pcnn_handle h, const pcnn_conv_desc* d, const float* x
   if (d->kh > 15 || d->kw > 15 || d->Cout > 64) return -1;
   const int NT = d->Cout <= 32 ? 1 : 2;
   const int cin_pad = (d->Cin + 7) & ~7, ng = cin_pad >> 3, T = d->kh * d->kw, nT2 = (T + 1) >> 1;
-  static const int mt2_max_k = getenv("PCNN_SPLIT_MT2_MAXK") ? atoi(getenv("PCNN_SPLIT_MT2_MAXK")) : 640;
-  const int MTsel = (NT == 1 && T * cin_pad <= mt2_max_k && (2 * WAVES + d->kh - 1) * (TW + d->kw - 1) <= 256 * max_pix(2)) ? 2 : 4;       // 8-row tiles for layers with few MFMA steps per tile
+  const int MTsel = (NT == 1 && T * cin_pad <= 640 && (2 * WAVES + d->kh - 1) * (TW + d->kw - 1) <= 256 * max_pix(2)) ? 2 : 4;       // 8-row tiles for layers with few MFMA steps per tile
   const int TH = WAVES * MTsel;
   const int TR = TH + d->kh - 1, TC = TW + d->kw - 1;
   if (TR * TC > 256 * max_pix(MTsel)) return -1;

@@ -21,10 +21,6 @@ bool pcnn_conv_small_fwd_eligible(const pcnn_conv_desc* d);
 bool pcnn_conv_small_wgrad_eligible(const pcnn_conv_desc* d);
 size_t pcnn_conv_small_wgrad_workspace(const pcnn_conv_desc* d);
 
-#ifndef PCNN_SMALL_STUDY
-#define PCNN_SMALL_STUDY 0       // diagnostic builds only: 1 no FMA loop, 2 no global loads in the tile staging, 4 one epilogue store instead of all
-#endif
-
 namespace {
 
 constexpr int STH = 8, STW = 32;                       // output tile: 8 rows x 32 columns = 256 pixels = 256 threads
@@ -91,8 +87,7 @@ __device__ __forceinline__ void stage_tile_batched(float* __restrict__ lds, cons
     const int sy = pad_index_sel(y0 + r - pt, H, pad_mode), sx = pad_index_sel(x0 + c - pl, W, pad_mode);
     const bool ok = u < TOTAL && sy >= 0 && sx >= 0;
     const int64_t idx = ok ? ((int64_t)sy * W + sx) * ldx + 4 * q : 0;
-    if (PCNN_SMALL_STUDY & 2) v[i] = (f32x4){(float)u, 1.f, 2.f, 3.f};
-    else v[i] = *reinterpret_cast<const f32x4*>(xin + idx);
+    v[i] = *reinterpret_cast<const f32x4*>(xin + idx);
     okm |= ok ? (1u << i) : 0u;
   }
   const f32x4 padv = {pad_value, pad_value, pad_value, pad_value};
@@ -124,7 +119,7 @@ __global__ __launch_bounds__(256, (CI * CO <= 64 ? 8 : 4)) void conv_small_fwd_k
   for (int o = 0; o < CO; ++o) acc[o] = 0.f;
   const float* wp = p.wp;                                 // [K*K][CI][CO], zero padded: uniform addresses -> scalar loads
 #pragma unroll 1
-  for (int i = 0; i < ((PCNN_SMALL_STUDY & 1) ? 0 : K); ++i)  // filter rows stay a loop: K*K*CI*CO unrolled FMAs would not fit the register file
+  for (int i = 0; i < K; ++i)  // filter rows stay a loop: K*K*CI*CO unrolled FMAs would not fit the register file
 #pragma unroll
     for (int j = 0; j < K; ++j) {
       const float* px = lds + ((r + i) * TC + (c + j)) * CIS;
@@ -645,15 +640,13 @@ __global__ __launch_bounds__(256) void small_post_bias_kernel(const float* __res
 static int pad4(int c) { return (c + 3) & ~3; }
 
 bool pcnn_conv_small_fwd_eligible(const pcnn_conv_desc* d) {
-  static const int on = getenv("PCNN_SMALL_CONV") ? atoi(getenv("PCNN_SMALL_CONV")) : 1;
-  if (!on || d->kh != d->kw || (d->kh != 3 && d->kh != 5) || d->Cin > 16 || d->Cout > 16) return false;
+  if (d->kh != d->kw || (d->kh != 3 && d->kh != 5) || d->Cin > 16 || d->Cout > 16) return false;
   if (d->kh == 5 && pad4(d->Cin) * pad4(d->Cout) > 16 * 16) return false;
   return true;
 }
 
 bool pcnn_conv_small_wgrad_eligible(const pcnn_conv_desc* d) {
-  static const int on = getenv("PCNN_SMALL_CONV") ? atoi(getenv("PCNN_SMALL_CONV")) : 1;
-  return on && d->kh == d->kw && (d->kh == 3 || d->kh == 5) && d->Cin <= 16 && d->Cout <= 16;
+  return d->kh == d->kw && (d->kh == 3 || d->kh == 5) && d->Cin <= 16 && d->Cout <= 16;
 }
 
 size_t pcnn_conv_small_wgrad_workspace(const pcnn_conv_desc* d) {
@@ -672,8 +665,7 @@ int pcnn_conv_small_fwd(pcnn_handle h, const pcnn_conv_desc* d, const float* x, 
 // pcnn_conv2d_dgrad_post): eligible when the data-gradient convolution takes the narrow route and every tensor can be accessed in whole 16-byte channel quads.
 static bool quads_ok(const void* q, int ld) { return q == nullptr || ((reinterpret_cast<uintptr_t>(q) & 15) == 0 && ld % 4 == 0); }
 extern "C" int pcnn_conv2d_dgrad_post_eligible(pcnn_handle h, const pcnn_conv_desc* dg, const float* dz, const float* residual, const float* dx, const pcnn_post_desc* post) {
-  static const int on = getenv("PCNN_SMALL_POST") ? atoi(getenv("PCNN_SMALL_POST")) : 1;
-  if (!on || !h || !dg || !post || !post->act_out) return 0;
+  if (!h || !dg || !post || !post->act_out) return 0;
   if (dg->pad_mode != PCNN_PAD_CONSTANT || dg->act != PCNN_ACT_LINEAR || dg->N < 1) return 0;
   if (!pcnn_conv_small_fwd_eligible(dg) || !pcnn_conv_fwd_takes_narrow_route(h, dg)) return 0;
   if (dg->Cout % 4 != 0) return 0;                               // (the gradient coming in may have any channel count: the tile loader handles it)
@@ -753,8 +745,7 @@ int pcnn_conv_small_wgrad(pcnn_handle h, const pcnn_conv_desc* d, const float* x
 }
 
 extern "C" int pcnn_resnet3_fwd_eligible(pcnn_handle h, int C, int act) {
-  static const int on = getenv("PCNN_FUSED_STAGE") ? atoi(getenv("PCNN_FUSED_STAGE")) : 1;
-  return (h && on && (C == 4 || C == 8) && (act == PCNN_ACT_LINEAR || act == PCNN_ACT_RELU || act == PCNN_ACT_LEAKY_RELU)) ? 1 : 0;
+  return (h && (C == 4 || C == 8) && (act == PCNN_ACT_LINEAR || act == PCNN_ACT_RELU || act == PCNN_ACT_LEAKY_RELU)) ? 1 : 0;
 }
 
 extern "C" int pcnn_resnet3_fwd(pcnn_handle h, int N, int H, int W, int C, int act, float act_alpha, const float* x, const float* w0, const float* b0,
@@ -769,8 +760,7 @@ extern "C" int pcnn_resnet3_fwd(pcnn_handle h, int N, int H, int W, int C, int a
   p.x = x; p.w0 = w0; p.w1 = w1; p.w2 = w2; p.b0 = b0; p.b1 = b1; p.b2 = b2; p.o0 = o0; p.a1 = a1; p.o1 = o1; p.y = y;
   p.N = N; p.H = H; p.W = W; p.tiles_x = 0; p.tiles_y = 0;
   p.slope = act == PCNN_ACT_LINEAR ? 1.f : (act == PCNN_ACT_RELU ? 0.f : act_alpha);
-  static const int th = getenv("PCNN_STAGE_TH") ? atoi(getenv("PCNN_STAGE_TH")) : 16;
-  const bool tall = th == 16 && H > 8;
+  const bool tall = H > 8;
   if (C == 4) { if (tall) launch_stage<4, 16>(h, p); else launch_stage<4, 8>(h, p); }
   else { if (tall) launch_stage<8, 16>(h, p); else launch_stage<8, 8>(h, p); }
   PCNN_CHECK_LAUNCH(h, "pcnn_resnet3_fwd");

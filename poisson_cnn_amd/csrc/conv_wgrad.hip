@@ -697,8 +697,7 @@ size_t split_lds(const pcnn_conv_desc* pd, const WgradPlan& pls) { return (size_
 // re-read of the planes, not by latency.
 WgradPlan make_split_plan(const pcnn_conv_desc* pd) {
   WgradPlan pl = make_plan(pd);
-  static const int occ3 = getenv("PCNN_WG_OCC3") ? atoi(getenv("PCNN_WG_OCC3")) : 1;
-  if (occ3 && pl.TAPS >= 3 && split_xr(pd, pl) == 2 && split_lds(pd, pl) * 3 <= 160 * 1024) {
+  if (pl.TAPS >= 3 && split_xr(pd, pl) == 2 && split_lds(pd, pl) * 3 <= 160 * 1024) {
     // these variants are compiled for 3 workgroups per CU (168 VGPRs): size the grid for 768 slots
     int S = 8 * ((768 / 8 * 4) / (pd->kh * pl.gz));
     if (S < 8) S = (768 * 4) / (pd->kh * pl.gz);

@@ -21,16 +21,9 @@
 #include <algorithm>
 #include <stdlib.h>
 
-// Removal studies (what a kernel costs without its loads / stores) exist only in a diagnostic build: -DPCNN_REMOVAL_STUDY, bits from the
-// environment variable PCNN_DBG64 (forward: 1 no stores, 2 no loads; inverse: 4 no epilogue, 8 no loads).  The shipped library compiles the
-// forward kernel's tests out and never sets the bits; the INVERSE kernel keeps its two tests as run-time tests of a launch parameter that is
-// always 0: with them folded away the compiler moves 28 floats of the epilogue into scratch memory (private segment 8 -> 112 bytes) and the
-// kernel runs 1.00 instead of 0.66 ms per launch (profiles/r03, found by the per-kernel table).
-#ifdef PCNN_REMOVAL_STUDY
-#define DBG64(flags, bit) ((flags) & (bit))
-#else
-#define DBG64(flags, bit) 0
-#endif
+// The INVERSE kernel tests two bits of a launch parameter that the launcher never sets (p.cpt & 1, p.cpt & 2).  The tests are kept only as a
+// code-generation anchor: with them folded away the compiler moves 28 floats of the epilogue into scratch memory (private segment 8 -> 112 bytes)
+// and the kernel runs 1.00 instead of 0.66 ms per launch (profiles/r03, found by the per-kernel table).
 
 namespace pcnn_spec {
 
@@ -89,7 +82,6 @@ __device__ __forceinline__ int pad_sel(int i, int n, int mode) {
 template <bool MASKED>
 __device__ __forceinline__ void load_row64(const FwdParams& p, const Ctx64& cx, int y, int half, float (&lo)[16], float (&hi)[16]) {
   if (MASKED && y >= cx.ylim) return;
-  if (DBG64(p.cpt, 2)) return;                              // removal study: no window loads
   const int sy = pad_sel(cx.wy0 + y, p.H, p.pad_mode);
   const float* row = cx.img + (int64_t)sy * p.W * p.ld;
   if (cx.fast) {
@@ -245,7 +237,6 @@ __global__ __launch_bounds__(512, 2) void spec64_fwd_kernel(FwdParams p) {
       const int base = 128 + 128 * (fx - 1) + h;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        if (DBG64(p.cpt, 1) && r > 0) continue;                  // removal study: one store instead of sixteen
         const int m = 8 * (r >> 2) + 4 * hv + (r & 3);
         int r0 = base + 2 * m, r1 = r0 + 64;
         if (jj == 0 && special) { r0 = ry_row(h, m); r1 = 64 + r0; }      // the two real columns: half-complex rows of fx = 0 and fx = 32
@@ -389,7 +380,6 @@ __global__ __launch_bounds__(512, 2) void spec64_fwd4_kernel(FwdParams p) {
       const int base = 128 + 128 * (fx - 1) + h2;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        if (DBG64(p.cpt, 1) && r > 0) continue;                  // removal study: one store instead of sixteen
         const int m = 8 * (r >> 2) + 4 * hv + (r & 3);           // accumulator row: m < 16 Re, m >= 16 Im of fy = 4 (m & 15) + h2
         int row = base + 4 * (m & 15) + 64 * (m >> 4);
         if (jj == 0 && special) {                                // rows m < 16: the real column fx = 0, m >= 16: fx = 32; half-complex row order
@@ -449,7 +439,7 @@ __global__ __launch_bounds__(512, 2) void spec64_inv_kernel(InvParams p, int vyc
   auto load_pair = [&](const InvItem& it, int tau, float (&z)[32]) {
     int g4v = lane >> 4, cv = c;
     asm volatile("" : "+v"(g4v), "+v"(cv));                   // opaque: the row offsets are formed per call, not hoisted out of the item loop
-    if (p.cpt & 2) return;                                     // removal study (diagnostic builds set the bit; see DBG64 below for why this stays a run-time test)
+    if (p.cpt & 2) return;                                     // never set: a code-generation anchor (see the head of this file)
     const int iq = cv & 3;
     const float* in = p.sp + sp_item(it.tg, ROWS) + 16 * it.q + (cv & ~3);
     const int j = 4 * tau + s;
@@ -594,7 +584,7 @@ __global__ __launch_bounds__(512, 2) void spec64_inv_kernel(InvParams p, int vyc
 #pragma unroll
         for (int i = 0; i < NR; ++i) {
           const int y = wave + 8 * i;
-          if (y < ib.vy && nv > 0 && !(p.cpt & 1)) {             // (p.cpt & 1: removal study - no epilogue)
+          if (y < ib.vy && nv > 0 && !(p.cpt & 1)) {             // (p.cpt & 1: never set, a code-generation anchor)
             const int64_t rowpix = p.flip ? ((int64_t)n * p.Ho + (p.Ho - 1 - y0 - y)) * p.Wo + (p.Wo - 1 - x0) : ((int64_t)n * p.Ho + y0 + y) * p.Wo + x0;
             float* yrow = p.y + rowpix * p.ldy;
             float* arow = (!POST && p.act_out) ? p.act_out + rowpix * p.ld_act : nullptr;
@@ -793,15 +783,9 @@ void build_tables64(float* tab, int* slots) {
     for (int fy = 0; fy < T; ++fy) put(2 * T + 2 * T * (fx - 1) + fy, 2 * T + 2 * T * (fx - 1) + T + fy, 0);
 }
 
-#ifdef PCNN_REMOVAL_STUDY
-static int dbg64() { static const int v = getenv("PCNN_DBG64") ? atoi(getenv("PCNN_DBG64")) : 0; return v; }
-#else
-static int dbg64() { return 0; }
-#endif
-
 void launch_fwd64(pcnn_handle h, FwdParams p, int ntile) {
   p.ntile = ntile;
-  p.cpt = dbg64() & 3;
+  p.cpt = 0;
   const int ntg = ntile * p.groups;
   const int nitem = 2 * ((ntg + 7) & ~7);
   const unsigned grid = (unsigned)std::min((nitem + 15) & ~15, 256);
@@ -840,7 +824,7 @@ static void launch_inv64_t(pcnn_handle h, const InvParams& p, unsigned grid, int
 
 void launch_inv64(pcnn_handle h, InvParams p, int ntile) {
   p.ntile = ntile;
-  p.cpt = (dbg64() >> 2) & 3;
+  p.cpt = 0;
   // bit 2: every tensor the epilogue touches allows 16-byte accesses at channel offsets that are multiples of four
   auto al = [](const void* q, int ld) { return q == nullptr || ((reinterpret_cast<uintptr_t>(q) & 15) == 0 && (ld & 3) == 0); };
   if (al(p.y, p.ldy) && al(p.act_out, p.ld_act) && al(p.res, p.ld_res) && al(p.gact, p.ld_gact) && al(p.y2, p.ld_y2) && (p.cstride & 3) == 0) p.cpt |= 4;

@@ -11,33 +11,28 @@ namespace pcnn_spec {
 constexpr int RS = 32;                       // floats between consecutive spectrum rows of an item
 // floats between consecutive items: rows x RS plus SP_PAD - the per-frequency kernels gather the same row of many items, i.e. they walk
 // memory with the item stride; a power-of-two stride maps those accesses onto few HBM channels
-#ifndef PCNN_SP_PAD
-#define PCNN_SP_PAD 32
-#endif
-constexpr int SP_PAD = PCNN_SP_PAD;
+constexpr int SP_PAD = 32;
 __host__ __device__ __forceinline__ int64_t sp_item(int64_t item, int rows) { return item * ((int64_t)rows * RS + SP_PAD); }
 __host__ __device__ __forceinline__ size_t sp_bytes(size_t items, int rows) { return items * ((size_t)rows * RS + SP_PAD) * sizeof(float); }
 
 // ---- row order inside an item.  CANONICAL order (the matrix-core transform family, the debug exports and the tests): the header comment above.
-// The FFT family (spectral_fft.hip, the default) interleaves the real and the imaginary row of a frequency in blocks of PCNN_SP_P frequencies, so that
+// The FFT family (spectral_fft.hip, the default) interleaves the real and the imaginary row of a frequency in blocks of SP_P frequencies, so that
 // the per-frequency kernels - which read / write the (Re, Im) row pair of ONE frequency of every item - find the pair inside one 256 P-byte piece of the
 // item instead of T rows (4 / 8 KB) apart: row(k, part) = 2 P (k / P) + P part + k % P inside a column block, k = frequency index of the column (complex
 // column: fy = 0..T-1; real column: the pair index, k = 0 the two real frequencies fy = 0 | T/2, k >= 1: Re | Im of fy = k).  P = T (T/2 for the real
 // columns) IS the canonical order.  The mixing kernels only follow the slot tables (rr, ri), built from the same function for each family.
-#ifndef PCNN_SP_P
-#define PCNN_SP_P 1
-#endif
+constexpr int SP_P = 1;
 __host__ __device__ constexpr int sp_blk(int P, int k, int part) { return 2 * P * (k / P) + P * part + (k % P); }
 __host__ __device__ constexpr int sp_pc(int T, int P) { return P < T ? P : T; }             // block size of a complex column
 __host__ __device__ constexpr int sp_pr(int T, int P) { return P < T / 2 ? P : T / 2; }     // ... of a real column
 // complex column of a T-point tile: row (inside the column's 2 T rows) of part (0 real, 1 imaginary) of frequency fy
-__host__ __device__ constexpr int sp_row_c(int T, int fy, int part, int P = PCNN_SP_P) { return sp_blk(sp_pc(T, P), fy, part); }
+__host__ __device__ constexpr int sp_row_c(int T, int fy, int part, int P = SP_P) { return sp_blk(sp_pc(T, P), fy, part); }
 // real column: row (inside the column's T rows) of half-complex entry s (s <= T/2: Re fy = s; s > T/2: Im fy = s - T/2)
-__host__ __device__ constexpr int sp_row_r(int T, int s, int P = PCNN_SP_P) {
+__host__ __device__ constexpr int sp_row_r(int T, int s, int P = SP_P) {
   return s == T / 2 ? sp_blk(sp_pr(T, P), 0, 1) : (s < T / 2 ? sp_blk(sp_pr(T, P), s, 0) : sp_blk(sp_pr(T, P), s - T / 2, 1));
 }
 // canonical row r of an item -> its row in the order with block size P
-__host__ __device__ constexpr int sp_row_from_canonical(int T, int r, int P = PCNN_SP_P) {
+__host__ __device__ constexpr int sp_row_from_canonical(int T, int r, int P = SP_P) {
   return r < 2 * T ? (r / T) * T + sp_row_r(T, r % T, P) : 2 * T + ((r - 2 * T) / (2 * T)) * 2 * T + sp_row_c(T, (r - 2 * T) % T, ((r - 2 * T) % (2 * T)) / T, P);
 }
 static_assert(sp_row_from_canonical(32, 5, 64) == 5 && sp_row_from_canonical(32, 16, 64) == 16 && sp_row_from_canonical(32, 64 + 37, 64) == 64 + 37 && sp_row_from_canonical(64, 128 + 64 + 9, 64) == 128 + 64 + 9, "P >= T is the canonical order");
@@ -63,8 +58,6 @@ __device__ __forceinline__ f32x16 zero16() {
   return z;
 }
 __device__ __forceinline__ f32x4 zero4() { f32x4 z = {0.f, 0.f, 0.f, 0.f}; return z; }
-// All LDS reads issued so far have landed; nothing moves across.
-__device__ __forceinline__ void lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 // Workgroup barrier that orders LDS traffic only (__syncthreads() also drains vmcnt, i.e. waits for the next item's prefetch loads and the
 // spectrum stores in flight; the prefetched registers are waited for where they are consumed, global stores need no ordering here).
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }

@@ -34,14 +34,9 @@ using namespace pcnn_spec;
 
 // Non-temporal hints on the spectrum streams (a spectrum is written by one kernel and read once by the next, gigabytes apart).  Measured per
 // access at 8 x 1024^2, 7 and 9 taps (forward / weight gradient / fused backward of one layer, same box, against no hints):
-//   1  forward-transform stores   -1 % / -2.5 % / -2.3 %        2  mixing loads    +6 % / +1 % / +5 %       4  mixing stores   -0.5 % (noise)
-//   8  inverse-transform loads     0                            16  weight-gradient GEMM loads   0 / -1 % / -0.5 %
-// so the hint is kept on the forward transforms' stores (32- and 64-point) and on the weight-gradient loads: 1 + 16.
-#ifndef PCNN_NT
-#define PCNN_NT 17
-#endif
-#define NT_LOAD(bit, p) ((PCNN_NT & (bit)) ? __builtin_nontemporal_load(p) : *(p))
-#define NT_STORE(bit, v, p) do { if (PCNN_NT & (bit)) __builtin_nontemporal_store(v, p); else *(p) = (v); } while (0)
+//   forward-transform stores   -1 % / -2.5 % / -2.3 %        mixing loads    +6 % / +1 % / +5 %       mixing stores   -0.5 % (noise)
+//   inverse-transform loads     0                            weight-gradient GEMM loads   0 / -1 % / -0.5 %
+// so the hint is kept on the forward transforms' stores (32- and 64-point) and on the weight-gradient loads.
 
 namespace {
 
@@ -130,8 +125,7 @@ __device__ __forceinline__ f32x16 fwd_row_mfma(const FwdParams& p, const FwdItem
 // y axis: one radix-2 decimation-in-frequency step on the vector ALU (u[y] +- u[y + 16], in-lane), then the even / odd output frequencies
 // are two 16-point complex DFTs = two real 32 x 32 products (F2[0], F2[1]) - half the matrix-core work of the 64 x 64 real form.
 // MASKED: the window holds values only in its first ylim x xlim entries (gradient tiles): their zero rows / columns are skipped.
-// FENCE: fetch a unit's LDS operands as one burst before its MFMA chain (see lds_fence).
-template <bool MASKED, bool FENCE>
+template <bool MASKED>
 __global__ __launch_bounds__(512, 1) void spec_fwd_kernel(FwdParams p) {
   extern __shared__ __attribute__((aligned(16))) float U[];          // U[(y*32 + s)*32 + c]
   const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, c = lane & 31;
@@ -193,7 +187,6 @@ __global__ __launch_bounds__(512, 1) void spec_fwd_kernel(FwdParams p) {
           const float hi = (!MASKED || 16 + 2 * (ks & 7) < ylim) ? U[((y + 16) * 32 + sc) * 32 + c] : 0.f;     // rows beyond ylim are zero (uniform test)
           bu[ks] = h ? lo - hi : lo + hi;
         }
-        if (FENCE) lds_fence();
 #pragma unroll
         for (int ks = 0; ks < 16; ++ks) acc = mfma(freg[ks], bu[ks], acc);
         o = out + (64 + 64 * (fx - 1) + h) * RS;                     // accumulator row 16 part + m  ->  spectrum row 32 part + 2 m + h
@@ -202,7 +195,6 @@ __global__ __launch_bounds__(512, 1) void spec_fwd_kernel(FwdParams p) {
 #pragma unroll
         for (int ks = 0; ks < 16; ++ks)
           if (!MASKED || 2 * ks < ylim) bu[ks] = U[((2 * ks + half) * 32 + col) * 32 + c];
-        if (FENCE) lds_fence();
 #pragma unroll
         for (int ks = 0; ks < 16; ++ks)
           if (!MASKED || 2 * ks < ylim) acc = mfma(greg[ks], bu[ks], acc);
@@ -213,7 +205,7 @@ __global__ __launch_bounds__(512, 1) void spec_fwd_kernel(FwdParams p) {
       for (int r = 0; r < 16; ++r) {
         const int row = acc_row(r, half);
         const int srow = realcol ? row : 32 * (row >> 4) + 2 * (row & 15);
-        NT_STORE(1, acc[r], &o[(unsigned)(srow * RS + c)]);
+        __builtin_nontemporal_store(acc[r], &o[(unsigned)(srow * RS + c)]);
       }
     }
     if (next >= total) break;
@@ -232,11 +224,11 @@ __device__ __forceinline__ void inv_load_unit(const float* in, int q, int h, uns
   if (realcol) {
     const float* src = in + (h ? 32 : 0) * RS;
 #pragma unroll
-    for (int ks = 0; ks < 16; ++ks) b[ks] = NT_LOAD(8, &src[loff + (unsigned)(2 * RS) * ks]);                    // row 2 ks + half
+    for (int ks = 0; ks < 16; ++ks) b[ks] = src[loff + (unsigned)(2 * RS) * ks];                    // row 2 ks + half
   } else {
     const float* src = in + (64 + 64 * (q + 4 * u) + h) * RS;
 #pragma unroll
-    for (int ks = 0; ks < 16; ++ks) b[ks] = NT_LOAD(8, &src[2u * loff - (loff & 31u) + (unsigned)RS * (32 * (ks >> 3) + 4 * (ks & 7))]);   // row 32 part + 2 (2 (ks & 7) + half) + h
+    for (int ks = 0; ks < 16; ++ks) b[ks] = src[2u * loff - (loff & 31u) + (unsigned)RS * (32 * (ks >> 3) + 4 * (ks & 7))];   // row 32 part + 2 (2 (ks & 7) + half) + h
   }
 }
 
@@ -465,8 +457,8 @@ __global__ __launch_bounds__(256, 2) void spec_mix_kernel(MixParams p) {
     const float* base = p.xs + pcnn_spec::sp_item((int64_t)tile * GIN + gi, p.rows) + 16 * half;
 #pragma unroll
     for (int j4 = 0; j4 < 4; ++j4) {
-      a[0][j4] = NT_LOAD(2, reinterpret_cast<const f32x4*>(base + rr * RS + 4 * j4));
-      a[1][j4] = NT_LOAD(2, reinterpret_cast<const f32x4*>(base + ri * RS + 4 * j4));
+      a[0][j4] = *reinterpret_cast<const f32x4*>(base + rr * RS + 4 * j4);
+      a[1][j4] = *reinterpret_cast<const f32x4*>(base + ri * RS + 4 * j4);
     }
   };
   f32x4 a[2][4], an[2][4];
@@ -497,8 +489,8 @@ __global__ __launch_bounds__(256, 2) void spec_mix_kernel(MixParams p) {
     for (int r = 0; r < 16; ++r) {
       const int trow = mt * 32 + acc_row(r, half);
       float* o = &p.ys[pcnn_spec::sp_item((int64_t)trow * p.gout + go, p.rows) + c];              // rows >= ntile: padding of the buffer (pad32)
-      NT_STORE(4, acc[0][r] + acc[2][r], o + rr * RS);
-      NT_STORE(4, fmaf(s_cplx, acc[0][r], acc[1][r]), o + ri * RS);
+      o[rr * RS] = acc[0][r] + acc[2][r];
+      o[ri * RS] = fmaf(s_cplx, acc[0][r], acc[1][r]);
     }
   };
   // first M-tile outside the loop: every pass inside it then starts from the same memory-counter state (operand loads, then the previous
@@ -541,7 +533,7 @@ __global__ __launch_bounds__(256, 2) void spec_wmix_kernel(WMixParams p) {
       const int tt = tb + 2 * u + half;
       const unsigned tc = (unsigned)(tt < t1 ? tt : t0);
       const unsigned ix = (unsigned)pcnn_spec::sp_item((int64_t)tc * p.gin + gi, p.rows) + c, id = (unsigned)pcnn_spec::sp_item(tc, p.rows) + c;
-      a0[u] = NT_LOAD(16, &xr[ix]); a1[u] = NT_LOAD(16, &xi[ix]); b0[u] = NT_LOAD(16, &dr[id]); b1[u] = NT_LOAD(16, &di[id]);
+      a0[u] = __builtin_nontemporal_load(&xr[ix]); a1[u] = __builtin_nontemporal_load(&xi[ix]); b0[u] = __builtin_nontemporal_load(&dr[id]); b1[u] = __builtin_nontemporal_load(&di[id]);
     }
   };
   if (t0 < t1) load(t0, ar, ai, br, bi);
@@ -621,7 +613,7 @@ __global__ __launch_bounds__(256, 2) void spec_mixw_kernel(MixWParams p) {
     const int tt = mt * 32 + 8 * b + 2 * qi + half;
     const unsigned tc = (unsigned)(tt < p.ntile ? tt : 0);
     const unsigned ix = (unsigned)pcnn_spec::sp_item((int64_t)tc * p.gx + g, p.rows) + c4, id = (unsigned)pcnn_spec::sp_item(tc, p.rows) + c4;
-    w[0] = NT_LOAD(16, reinterpret_cast<const f32x4*>(&xr[ix])); w[1] = NT_LOAD(16, reinterpret_cast<const f32x4*>(&xi[ix]));
+    w[0] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(&xr[ix])); w[1] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(&xi[ix]));
     w[2] = *reinterpret_cast<const f32x4*>(&dr[id]); w[3] = *reinterpret_cast<const f32x4*>(&di[id]);
   };
   f32x16 accp[3] = {zero16(), zero16(), zero16()};                 // Q1, Q2, Q3 of spec_wmix_kernel (three real products per tile pair)
@@ -694,7 +686,7 @@ __global__ __launch_bounds__(256, 2) void spec_mixw_kernel(MixWParams p) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int trow = mt * 32 + acc_row(r, half);
-        NT_STORE(4, acc[nt][r], &p.ys[pcnn_spec::sp_item((int64_t)trow * p.gx + g, p.rows) + row * RS + c]);            // rows >= ntile: padding of the buffer (pad32)
+        p.ys[pcnn_spec::sp_item((int64_t)trow * p.gx + g, p.rows) + row * RS + c] = acc[nt][r];         // rows >= ntile: padding of the buffer (pad32)
       }
     }
   };
@@ -806,18 +798,8 @@ int chunk_tiles(int Tg) {
 // partial sums of the weight-gradient GEMM: S / 4 workgroups x 4 waves per (slot, channel group).  64-point tiles have 2 048 slots - one workgroup
 // per slot already fills the chip four times over, and half the partial sums (128 instead of 256 MB written and read back per layer) are worth
 // 0.06-0.08 ms per 13- / 15-tap layer; at 32 points (512 slots) 8 is the measured optimum (4: +0.05 ms at 9 taps, 12 / 16: +0.04 ... 0.08 ms).
-// PCNN_WSPLIT32 / PCNN_WSPLIT64 are developer switches (A/B timing): the kernels index their partial sums as blockIdx.y * 4 + wave, so a value is
-// rounded down to a positive multiple of 4 (at most 64); anything else - zero, negative, not a number - keeps the default.
-int wsplit_env(const char* name, int dflt) {
-  const char* e = getenv(name);
-  if (!e) return dflt;
-  const int v = atoi(e) & ~3;
-  return (v >= 4 && v <= 64) ? v : dflt;
-}
-int wgrad_splits(int Tg = 32) {
-  static const int s32 = wsplit_env("PCNN_WSPLIT32", 8), s64 = wsplit_env("PCNN_WSPLIT64", 4);
-  return Tg == 64 ? s64 : s32;
-}
+// (The kernels index their partial sums as blockIdx.y * 4 + wave: a multiple of 4.)
+int wgrad_splits(int Tg = 32) { return Tg == 64 ? 4 : 8; }
 
 // workspace header: the constant tables of both tile sizes; the per-call regions follow
 // (two slot tables per tile size: the canonical row order of the matrix-core transform family, and the FFT family's interleaved order - spectral_common.h)
@@ -842,8 +824,8 @@ int ensure_workspace(pcnn_handle h, size_t bytes_after_tables, char** rest) {
       tab64.resize(TAB64_FLOATS); slots64.resize(2048 * 4);
       build_tables64(tab64.data(), slots64.data());
       slots32f.resize(NSLOT * 4); slots64f.resize(2048 * 4);
-      pcnn_spec::sp_build_slots(32, PCNN_SP_P, slots32f.data());
-      pcnn_spec::sp_build_slots(64, PCNN_SP_P, slots64f.data());
+      pcnn_spec::sp_build_slots(32, SP_P, slots32f.data());
+      pcnn_spec::sp_build_slots(64, SP_P, slots64f.data());
     }
     char* b = static_cast<char*>(h->spec_ws);
     if (hipMemcpyAsync(b + O_TAB32, tab.data(), TAB_FLOATS * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
@@ -876,19 +858,16 @@ template <typename K>
 void set_lds(K kernel, size_t bytes = LDS_U) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); }
 
 // persistent kernels: one 8-wave workgroup per CU (128 KB of LDS each) walking the (tile, channel group) items
-template <bool MASKED, bool FENCE>
+template <bool MASKED>
 void launch_fwd_t(pcnn_handle h, const FwdParams& p, int ntile) {
-  set_lds(spec_fwd_kernel<MASKED, FENCE>);
-  hipLaunchKernelGGL((spec_fwd_kernel<MASKED, FENCE>), dim3((unsigned)std::min(ntile * p.groups, 256)), dim3(512), LDS_U, h->stream, p);
+  set_lds(spec_fwd_kernel<MASKED>);
+  hipLaunchKernelGGL((spec_fwd_kernel<MASKED>), dim3((unsigned)std::min(ntile * p.groups, 256)), dim3(512), LDS_U, h->stream, p);
 }
 void launch_fwd(pcnn_handle h, const Geom& gm, FwdParams p, int ntile) {
-  static const int fence = getenv("PCNN_SPEC_FENCE") ? atoi(getenv("PCNN_SPEC_FENCE")) : 0;
   p.ntile = ntile; p.tab = gm.tab;
   if (gm.T == 64) { if (h->spectral_xform == PCNN_XFORM_FFT) launch_fwd_fft64(h, p, ntile); else launch_fwd64(h, p, ntile); return; }
   if (h->spectral_xform == PCNN_XFORM_FFT) { launch_fwd_fft32(h, p, ntile); return; }
-  const bool masked = p.ylim < T || p.xlim < T;
-  if (masked) { if (fence) launch_fwd_t<true, true>(h, p, ntile); else launch_fwd_t<true, false>(h, p, ntile); }
-  else { if (fence) launch_fwd_t<false, true>(h, p, ntile); else launch_fwd_t<false, false>(h, p, ntile); }
+  if (p.ylim < T || p.xlim < T) launch_fwd_t<true>(h, p, ntile); else launch_fwd_t<false>(h, p, ntile);
 }
 template <bool TANH, bool RES>
 void launch_inv_t(pcnn_handle h, const InvParams& p, const dim3& grid) {
@@ -926,9 +905,8 @@ void launch_mix(pcnn_handle h, const Geom& gm, MixParams mx, int gin, int gout, 
 
 // tiles per lane group for a layer of Cin -> Cout channels: both sides must fit `cpt` lanes (a power of two >= 4)
 int pack_for(int Cin, int Cout) {
-  static const int on = getenv("PCNN_SPEC_PACK") ? atoi(getenv("PCNN_SPEC_PACK")) : 1;
   const int c = std::max(Cin, Cout);
-  if (!on || c > 16) return 1;
+  if (c > 16) return 1;
   return c <= 4 ? 8 : (c <= 8 ? 4 : 2);
 }
 
@@ -1280,7 +1258,7 @@ __global__ __launch_bounds__(256) void spec_canonical_rows_kernel(const float* _
   }
 }
 static int canonical_copy(pcnn_handle h, const float* sp, float* out, int T, int items) {
-  const int P = h->spectral_xform == PCNN_XFORM_FFT ? PCNN_SP_P : 64;
+  const int P = h->spectral_xform == PCNN_XFORM_FFT ? SP_P : 64;
   hipLaunchKernelGGL(spec_canonical_rows_kernel, dim3(16, items), dim3(256), 0, h->stream, sp, out, T, T * T, P);
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }
@@ -1422,29 +1400,16 @@ static int bwd_spectral_impl(pcnn_handle h, const pcnn_conv_desc* d, const pcnn_
     iv.y2 = post->raw_out; iv.ld_y2 = post->ld_raw; iv.bsum = post->dbias ? bsum : nullptr;
     if (iv.bsum && hipMemsetAsync(bsum, 0, bs_b, h->stream) != hipSuccess) PCNN_FAIL(h, "pcnn_conv2d_bwd_spectral_post: memset failed");
   }
-  MixParams mx;
-  mx.xs = zs; mx.ys = ys; mx.wsp = fsp; mx.gin = gz; mx.gout = gx; mx.Cin = dg->Cin; mx.cpt = cpt;
-  WMixParams wm;
-  wm.xs = xs; wm.ds = zs; wm.part = part; wm.slots = gm.slots; wm.gin = gx; wm.S = S / 4; wm.rows = rows; wm.nslot = nslot;
-  static const int fused_mix = getenv("PCNN_SPEC_MIXW") ? atoi(getenv("PCNN_SPEC_MIXW")) : 1;   // developer switch (A/B timing): 0 = two kernels
-  MixWParams mw;
+  MixWParams mw;                                         // one pass over D^ for both gradients (spec_mixw_kernel)
   mw.zs = zs; mw.xs = xs; mw.ys = ys; mw.part = part; mw.wsp = fsp; mw.slots = gm.slots; mw.gx = gx; mw.rows = rows; mw.nslot = nslot;
   mw.Cz = dg->Cin; mw.cpt = cpt;
   for (int64_t t0 = 0; t0 < ntile; t0 += chunk) {
     const int nt = (int)std::min<int64_t>(chunk, ntile - t0);
-    fz.tile0 = (int)t0; fxm.tile0 = (int)t0; iv.tile0 = (int)t0; wm.ntile = nt; wm.accumulate = t0 > 0;
+    fz.tile0 = (int)t0; fxm.tile0 = (int)t0; iv.tile0 = (int)t0; mw.ntile = nt; mw.accumulate = t0 > 0;
     launch_fwd(h, gm, fz, nt);
-    if (fused_mix) {                                     // one pass over D^ for both gradients (spec_mixw_kernel)
-      launch_fwd(h, gm, fxm, nt);
-      mw.ntile = nt; mw.accumulate = t0 > 0;
-      hipLaunchKernelGGL(spec_mixw_kernel, dim3(nslot, S / 4, gx), dim3(256), 0, h->stream, mw);
-      launch_inv(h, gm, iv, nt);
-      continue;
-    }
-    launch_mix(h, gm, mx, gz, gx, nt);
-    launch_inv(h, gm, iv, nt);
     launch_fwd(h, gm, fxm, nt);
-    hipLaunchKernelGGL(spec_wmix_kernel, dim3(nslot, S / 4, gx), dim3(256), 0, h->stream, wm);
+    hipLaunchKernelGGL(spec_mixw_kernel, dim3(nslot, S / 4, gx), dim3(256), 0, h->stream, mw);
+    launch_inv(h, gm, iv, nt);
   }
   if (post && post->dbias) {
     if (Tg == 64 && h->spectral_xform == PCNN_XFORM_FFT) launch_post_bias_fft64(h, bsum, 256, dg->Cout, post->dbias);

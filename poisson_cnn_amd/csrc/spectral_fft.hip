@@ -21,23 +21,6 @@
 #include "spectral_common.h"
 #include "fft_regs.h"
 #include <algorithm>
-#include <stdlib.h>
-
-#ifndef PCNN_NT
-#define PCNN_NT 17
-#endif
-#define NT_LOAD(bit, p) ((PCNN_NT & (bit)) ? __builtin_nontemporal_load(p) : *(p))
-#define NT_STORE(bit, v, p) do { if (PCNN_NT & (bit)) __builtin_nontemporal_store(v, p); else *(p) = (v); } while (0)
-
-// Removal studies (what a kernel costs without its loads / stores / arithmetic / LDS traffic) exist only in a diagnostic build: -DPCNN_FFT_STUDY, bits
-// from the environment variable PCNN_FFT_STUDY (1 no spectrum / pixel stores, 2 no global loads, 4 no FFT arithmetic, 8 no LDS reads, 16 no LDS
-// writes).  The shipped library compiles every test out.
-#ifdef PCNN_FFT_STUDY
-__constant__ int g_fft_study;
-#define FFT_STUDY(bit) (g_fft_study & (bit))
-#else
-#define FFT_STUDY(bit) 0
-#endif
 
 namespace pcnn_spec {
 
@@ -61,7 +44,7 @@ __device__ __forceinline__ int pad_sel(int i, int n, int mode) {
 // by hand with s_waitcnt vmcnt(32), so that the x phase starts while the previous item's 32 spectrum stores are still draining - the compiler's own
 // waits are merged conservatively over the kernel's paths.  Correct in the shipped build (all spectral tests) and not faster: 7 taps forward 1.86 vs
 // 1.84 ms - the kernel sits at the copy ceiling either way.  Removed because it is fragile: the compiler does not know the
-// destination registers are in flight and may copy or reuse them; the diagnostic build of the very same source (-DPCNN_FFT_STUDY) faulted.)
+// destination registers are in flight and may copy or reuse them; a diagnostic build of the very same source faulted.)
 // what a lane keeps of an item between requesting its window row and consuming it
 struct FwdRow {
   float fill;            // lane: value of a row that is not read from memory (0: beyond ylim / no such channel; the padding constant)
@@ -94,7 +77,7 @@ __device__ __forceinline__ void fwd_request(const FwdParams& p, int item, int wa
   it.cl = 0; it.cr = T;
   const int wx_first = txg * p.pack * p.Vx - p.ox, wx_last = wx_first + (p.pack - 1) * p.Vx;
   it.fast = wx_first >= 0 && wx_last + T <= p.W;                               // uniform
-  if (2 * wave >= ylim || FFT_STUDY(2)) return;                                // uniform: both rows of this wave are zero rows - nothing to fetch
+  if (2 * wave >= ylim) return;                                               // uniform: both rows of this wave are zero rows - nothing to fetch
   const int sy = pad_sel(gy, p.H, p.pad_mode);
   const unsigned ch = (unsigned)(cok ? chan : 0);
   if (it.fast) {
@@ -158,7 +141,7 @@ __device__ __forceinline__ void fft32_fwd_body(const FwdParams& p, float* U, con
   // ---- x axis: this lane's window row, real -> half-complex, into LDS
   auto x_phase = [&]() {
     fwd_consume<MASKED>(p, cur, R);
-    if (!FFT_STUDY(4)) rfft_fwd<32>(R);
+    rfft_fwd<32>(R);
     float* u = U + (y * 32) * 32 + c;
 #pragma unroll
     for (int s = 0; s < T; ++s) u[s * 32] = hc_get(R, s);
@@ -177,11 +160,11 @@ __device__ __forceinline__ void fft32_fwd_body(const FwdParams& p, float* U, con
       const float* u = U + (half ? 16 : 0) * 32 + c;
 #pragma unroll
       for (int yy = 0; yy < T; ++yy) V[yy] = u[yy * 1024];
-      if (!FFT_STUDY(4)) rfft_fwd<32>(V);
+      rfft_fwd<32>(V);
       // (stores: uniform base + 32-bit lane offset + immediate - no 64-bit address per 4 KB window in vector registers)
       const unsigned lo = (unsigned)((half ? 32 : 0) * RS + c);
 #pragma unroll
-      for (int s = 0; s < T; ++s) if (!FFT_STUDY(1)) NT_STORE(1, hc_get(V, s), &(out + (sp_row_r(T, s) * RS))[lo]);
+      for (int s = 0; s < T; ++s) __builtin_nontemporal_store(hc_get(V, s), &(out + (sp_row_r(T, s) * RS))[lo]);
     } else {
       // complex column fx = wave; lane half = parity of the output frequencies: Z[2m + par] = FFT16( (u[y] +- u[y + 16]) W32^(par y) )[m]
       const float* ur = U + wave * 32 + c, *ui = U + (16 + wave) * 32 + c;
@@ -201,16 +184,15 @@ __device__ __forceinline__ void fft32_fwd_body(const FwdParams& p, float* U, con
           vi[yy] = fma_(ar, wi, ai * wr);
         }
       }
-      if (!FFT_STUDY(4)) cfft_dif<16, -1>(vr, vi);
+      cfft_dif<16, -1>(vr, vi);
       // register q holds Z[2 bitrev(q) + par]: rows sp_row_c(fy = 2m + par, part) of the column's 64 (spectral_common.h; the odd frequency of a
       // pair lies a constant number of rows behind the even one: the lane half's offset)
       float* o = out + (64 + 64 * (wave - 1)) * RS;                   // uniform
       const unsigned lo = (unsigned)(half * (sp_row_c(T, 1, 0) - sp_row_c(T, 0, 0)) * RS + c);
 #pragma unroll
       for (int m = 0; m < 16; ++m) {
-        if (FFT_STUDY(1)) continue;
-        NT_STORE(1, vr[bitrev(m, 16)], &(o + (sp_row_c(T, 2 * m, 0) * RS))[lo]);
-        NT_STORE(1, vi[bitrev(m, 16)], &(o + (sp_row_c(T, 2 * m, 1) * RS))[lo]);
+        __builtin_nontemporal_store(vr[bitrev(m, 16)], &(o + (sp_row_c(T, 2 * m, 0) * RS))[lo]);
+        __builtin_nontemporal_store(vi[bitrev(m, 16)], &(o + (sp_row_c(T, 2 * m, 1) * RS))[lo]);
       }
     }
     if (next >= total) break;
@@ -253,15 +235,12 @@ __global__ __launch_bounds__(1024) void fft32_fwd_multi_kernel(const FwdParams* 
 //   * NO store sits behind a branch: a pixel beyond vx re-stores the row's first pixel (same address, same value) - with a static number of memory
 //     operations per burst the compiler's waits name exactly what they need.  (First version: `if (x < vx) store` - every store in a basic block of
 //     its own, re-using one data register: an s_waitcnt vmcnt(0) per pixel, i.e. every store COMPLETED before the next pixel was formed; the
-//     64-point inverse spent half its time there - tools/study_fft.sh.)
+//     64-point inverse spent half its time there, by a removal study.)
 // Round 6: a whole burst beyond the row's end is skipped (the round-5 form re-stored the row's first pixel for every pixel beyond vx so that the number of
 // memory operations per row stayed static; with bursts of four, a quarter of the bursts of an 11-tap layer and an eighth of a 7-tap layer's lie wholly beyond
-// the end).  One uniform branch per burst; measured on the 32-point inverse (profiles/r06_step_ab_epilogue_skip.txt): -3 % on the pipelined variants (bit 1),
-// -2...3 % on the others (bit 2); on the 64-point inverse (bit 4; bursts of eight: a 15-tap row has 50 of 64 pixels) -3...7 % per variant - round 5 had measured
+// the end).  One uniform branch per burst; measured on the 32-point inverse (profiles/r06_step_ab_epilogue_skip.txt): -3 % on the pipelined variants,
+// -2...3 % on the others; on the 64-point inverse (bursts of eight: a 15-tap row has 50 of 64 pixels) -3...7 % per variant - round 5 had measured
 // -1.3 % forward / +2 % backward for the same idea, before the stores went non-temporal.
-#ifndef PCNN_EPI_SKIP
-#define PCNN_EPI_SKIP 7
-#endif
 struct NoBetween { __device__ __forceinline__ void operator()(int) const {} };
 // `between(b)` runs after the stores of burst b: the 32-point inverse issues a slice of the NEXT item's spectrum loads there (inv32_pipe)
 template <bool TANH, bool RES, bool POST, int NPIX, int BURST, bool NT, typename Between = NoBetween>
@@ -272,9 +251,7 @@ __device__ __forceinline__ void epilogue_row(const InvParams& p, const float* X,
   float first_y = 0.f, first_a = 0.f, first_y2 = 0.f;              // what the row's first pixel stores (pixels beyond vx repeat it)
 #pragma unroll
   for (int x0b = 0; x0b < NPIX; x0b += BURST) {
-#if PCNN_EPI_SKIP
     if (x0b >= vx_uniform) { between(x0b / BURST); continue; }      // a whole burst beyond the row's end (uniform): nothing to re-store
-#endif
     float rv[BURST], gv[BURST], oy[BURST], oa[BURST], oy2[BURST];
     if (RES) {
 #pragma unroll
@@ -336,25 +313,16 @@ __device__ __forceinline__ void epilogue_row(const InvParams& p, const float* X,
 __device__ __forceinline__ void inv_request(const float* in, int wave, int half, int c, float (&B)[32]) {
   const float* sp = in + (wave == 0 ? 0 : (64 + 64 * (wave - 1)) * RS);
   const unsigned lo = (unsigned)((wave == 0 ? 32 : sp_row_c(T, 1, 0) - sp_row_c(T, 0, 0)) * RS * half + c);
-  if constexpr (PCNN_SP_P == 1) {
-    // Re | Im adjacent: entry j = (m = j & 15, part = j >> 4) sits at row 2 m + part of a real column and at row 4 m + part (+ 2 par: the lane offset) of
-    // a complex one - ONE code path with a uniform row step on the scalar ALU, as with the canonical order (a per-entry select between two row constants
-    // costs a scalar select per load: the inverse kernels ran 4-9 % slower with it)
-    static_assert(sp_row_r(T, 17, 1) == 3 && sp_row_r(T, 16, 1) == 1 && sp_row_c(T, 6, 1, 1) == 13, "row order the stepping form assumes");
-    const int step = (wave == 0 ? 2 : 4) * RS;
+  // Re | Im adjacent: entry j = (m = j & 15, part = j >> 4) sits at row 2 m + part of a real column and at row 4 m + part (+ 2 par: the lane offset) of
+  // a complex one - ONE code path with a uniform row step on the scalar ALU (a per-entry select between two row constants costs a scalar select per
+  // load: the inverse kernels ran 4-9 % slower with it)
+  static_assert(sp_row_r(T, 17, 1) == 3 && sp_row_r(T, 16, 1) == 1 && sp_row_c(T, 6, 1, 1) == 13, "row order the stepping form assumes");
+  const int step = (wave == 0 ? 2 : 4) * RS;
 #pragma unroll
-    for (int part = 0; part < 2; ++part) {
-      const float* q = sp + part * RS;
+  for (int part = 0; part < 2; ++part) {
+    const float* q = sp + part * RS;
 #pragma unroll
-      for (int m = 0; m < 16; ++m) { B[16 * part + m] = FFT_STUDY(2) ? 1.f : NT_LOAD(8, &q[lo]); q += step; }
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < T; ++j) {
-      // wave 0: half-complex entry j of the real column; wave fx: Re (j < 16) / Im of Z[2 (j & 15) + par] - a uniform (scalar) choice between two row constants
-      const int row = wave == 0 ? sp_row_r(T, j) : sp_row_c(T, 2 * (j & 15), j >> 4);
-      B[j] = FFT_STUDY(2) ? 1.f : NT_LOAD(8, &(sp + row * RS)[lo]);
-    }
+    for (int m = 0; m < 16; ++m) { B[16 * part + m] = q[lo]; q += step; }
   }
 }
 
@@ -365,28 +333,18 @@ __device__ __forceinline__ void inv_request_slice(const float* in, int wave, int
   const unsigned lo = (unsigned)((wave == 0 ? 32 : 2) * RS * half + c);
   const int step = (wave == 0 ? 2 : 4) * RS;
 #pragma unroll
-  for (int j = J0; j < J0 + NJ; ++j) B[j] = FFT_STUDY(2) ? 1.f : NT_LOAD(8, &(sp + (j >> 4) * RS + (j & 15) * step)[lo]);
+  for (int j = J0; j < J0 + NJ; ++j) B[j] = (sp + (j >> 4) * RS + (j & 15) * step)[lo];
 }
 
-// Prefetch of the next item's spectrum column (32 registers that stay live through the x axis and the epilogue): with it the epilogue variants spill
-// 20-26 registers, and a spill costs more than the prefetch hides (scratch traffic shares the memory pipe) - off; measured both ways, DESIGN.md 4.8.
-#ifndef PCNN_INV32_PREFETCH
-#define PCNN_INV32_PREFETCH 0
-#endif
-constexpr bool INV32_PREFETCH = PCNN_INV32_PREFETCH;
+// (Measured and rejected: a prefetch of the whole next spectrum column at the top of the item (32 registers that stay live through the x axis and the
+// epilogue) - the epilogue variants spill 20-26 registers, and a spill costs more than the prefetch hides (scratch traffic shares the memory pipe))
 // Round 6: the next item's 32 spectrum loads issued in slices BETWEEN the epilogue's store bursts (each slice into the registers of the pixels the burst has just
 // stored), so that their latency runs under the rest of the epilogue and the barrier instead of behind this item's stores in the in-order memory counter.  Measured per
 // epilogue variant on one box (profiles/r06_step_ab_inv32_pipe.txt, ms per train step, plain / bursts of 4 / bursts of 4 + pipelined loads): plain epilogue
 // 16.1 / 16.1 / 15.6, residual + POST 3.30 / 3.29 / 3.2 - but POST alone 7.4 / 8.0 / 8.2 and residual alone 4.1 / 4.5 / 4.7 (their bursts of 8 hide more than the
-// pipelining returns).  So: pipelined with bursts of four where the epilogue has neither or both extra inputs, the round-5 form otherwise.  PCNN_INV32_PIPE=0: off.
-#ifndef PCNN_INV32_PIPE
-#define PCNN_INV32_PIPE 1
-#endif
-template <bool RES, bool POST> constexpr bool inv32_pipe() { return PCNN_INV32_PIPE && !PCNN_INV32_PREFETCH && PCNN_SP_P == 1 && RES == POST; }
+// pipelining returns).  So: pipelined with bursts of four where the epilogue has neither or both extra inputs, the round-5 form otherwise.
+template <bool RES, bool POST> constexpr bool inv32_pipe() { return RES == POST; }
 
-#ifndef PCNN_ST32_NT
-#define PCNN_ST32_NT 0
-#endif
 // TANH = false: linear / relu / leaky-relu as one select with the negative-side slope in p.alpha (1 / 0 / alpha)
 template <bool TANH, bool RES, bool POST>
 __global__ __launch_bounds__(1024) void fft32_inv_kernel(InvParams p) {
@@ -398,7 +356,7 @@ __global__ __launch_bounds__(1024) void fft32_inv_kernel(InvParams p) {
   if (item >= total) return;
   constexpr bool INV32_PIPE = inv32_pipe<RES, POST>();
   float B[32];
-  if (INV32_PREFETCH || INV32_PIPE) inv_request(p.sp + sp_item32(item), wave, half, c, B);
+  if (INV32_PIPE) inv_request(p.sp + sp_item32(item), wave, half, c, B);
   float ymax = 0.f, bsum = 0.f;
   constexpr int BURST = (RES == POST) ? 4 : 8;                       // pixels per epilogue burst (registers: 128 per lane; epilogue_row keeps up to 5 values per pixel)
   for (;;) {
@@ -406,15 +364,14 @@ __global__ __launch_bounds__(1024) void fft32_inv_kernel(InvParams p) {
     // ---- y axis inverse (unnormalised: the 1 / 1024 of both axes is applied once, after the x axis)
     {
       float V[32];
-      if (!INV32_PREFETCH && !INV32_PIPE) inv_request(p.sp + sp_item32(item), wave, half, c, B);
+      if (!INV32_PIPE) inv_request(p.sp + sp_item32(item), wave, half, c, B);
 #pragma unroll
       for (int i = 0; i < 32; ++i) V[i] = B[i];
-      if (INV32_PREFETCH && next < total) inv_request(p.sp + sp_item32(next), wave, half, c, B);      // lands under the rest of this item
       if (wave == 0) {
         float W[32];
 #pragma unroll
         for (int s = 0; s < T; ++s) hc_put(W, s, V[s]);
-        if (!FFT_STUDY(4)) rfft_inv<32>(W);                                             // W[y] = 32 u[y]
+        rfft_inv<32>(W);                                             // W[y] = 32 u[y]
         float* e = U + (half ? 16 : 0) * 32 + c;
 #pragma unroll
         for (int yy = 0; yy < 16; ++yy) {
@@ -423,7 +380,7 @@ __global__ __launch_bounds__(1024) void fft32_inv_kernel(InvParams p) {
         }
       } else {
         float* vr = V, *vi = V + 16;
-        if (!FFT_STUDY(4)) cfft_dif<16, +1>(vr, vi);                                    // register q: E (par = 0) or O-before-twiddle (par = 1) at y = bitrev(q)
+        cfft_dif<16, +1>(vr, vi);                                    // register q: E (par = 0) or O-before-twiddle (par = 1) at y = bitrev(q)
         float* er = U + (half ? EO : 0) + wave * 32 + c, *ei = er + 16 * 32;
         int par = half;
         asm volatile("" : "+v"(par));                                // opaque: the per-lane twiddle selects are formed here, not hoisted out of the item loop
@@ -472,7 +429,7 @@ __global__ __launch_bounds__(1024) void fft32_inv_kernel(InvParams p) {
             __builtin_amdgcn_sched_barrier(0);
           }
         }
-        if (!FFT_STUDY(4)) rfft_inv<32>(X);                                             // X[x] = 1024 * pixel (yy, x)
+        rfft_inv<32>(X);                                             // X[x] = 1024 * pixel (yy, x)
         const float bias = (p.bias && cok) ? p.bias[chan] : 0.f;
         const float sc = (p.bn_scale && cok) ? p.bn_scale[chan] : 1.f, sh = (p.bn_scale && cok) ? p.bn_shift[chan] : 0.f;
         // addresses: a uniform IMAGE base per tensor plus an unsigned 32-bit lane offset (scalar base + vector offset form: no 64-bit address
@@ -500,17 +457,17 @@ __global__ __launch_bounds__(1024) void fft32_inv_kernel(InvParams p) {
               else if (b == 6) inv_request_slice<24, 4>(nin, wave, half, c, B); else inv_request_slice<28, 4>(nin, wave, half, c, B);
             }
           };
-          if (rowok && !FFT_STUDY(1)) {
-            epilogue_row<TANH, RES, POST, T, BURST, PCNN_ST32_NT != 0>(p, X, 1.f / 1024.f, vx, pix0, sgn, chv, bias, sc, sh, yimg, aimg, rimg, gimg, y2img, ymax, bsum, between,
-                                                                       p.pack > 1 ? T : __builtin_amdgcn_readfirstlane(min(p.Vx, p.Wo - x0)));
+          if (rowok) {
+            epilogue_row<TANH, RES, POST, T, BURST, false>(p, X, 1.f / 1024.f, vx, pix0, sgn, chv, bias, sc, sh, yimg, aimg, rimg, gimg, y2img, ymax, bsum, between,
+                                                           p.pack > 1 ? T : __builtin_amdgcn_readfirstlane(min(p.Vx, p.Wo - x0)));
           } else {
             inv_request(nin, wave, half, c, B);
           }
           piped = true;
         } else
-        if (rowok && !FFT_STUDY(1))
-          epilogue_row<TANH, RES, POST, T, BURST, PCNN_ST32_NT != 0>(p, X, 1.f / 1024.f, vx, pix0, sgn, chv, bias, sc, sh, yimg, aimg, rimg, gimg, y2img, ymax, bsum, NoBetween(),
-                                                                     (PCNN_EPI_SKIP & 2) ? (p.pack > 1 ? T : __builtin_amdgcn_readfirstlane(min(p.Vx, p.Wo - x0))) : T);
+        if (rowok)
+          epilogue_row<TANH, RES, POST, T, BURST, false>(p, X, 1.f / 1024.f, vx, pix0, sgn, chv, bias, sc, sh, yimg, aimg, rimg, gimg, y2img, ymax, bsum, NoBetween(),
+                                                         p.pack > 1 ? T : __builtin_amdgcn_readfirstlane(min(p.Vx, p.Wo - x0)));
       }
       if (INV32_PIPE && !piped) inv_request(nin, wave, half, c, B);    // waves without an output row in this tile
     }
@@ -589,8 +546,7 @@ struct FwdRow64 {
 };
 
 // describes virtual item v (window, column map) and the unit's row y (lane: y = 4 unit + lane group)
-template <int NU>
-__device__ __forceinline__ void fwd64_describe_t(const FwdParams& p, int v, int lane, int c16, FwdItem64& it, FwdRow64 (&row)[2], int unit0) {
+__device__ __forceinline__ void fwd64_describe(const FwdParams& p, int v, int lane, int c16, FwdItem64& it, FwdRow64 (&row)[2], int unit0) {
   int tg, hf;
   item64(v, tg, hf);
   const int g = tg % p.groups;
@@ -611,7 +567,7 @@ __device__ __forceinline__ void fwd64_describe_t(const FwdParams& p, int v, int 
   // instructions per pixel, and no index arithmetic per load
   it.voff = (unsigned)(pad_sel(wx0 + lane, p.W, p.pad_mode) * p.ld);
 #pragma unroll
-  for (int u = 0; u < NU; ++u) {
+  for (int u = 0; u < 2; ++u) {
     const int y = 4 * (unit0 + u) + (lane >> 4);
     const int gy = wy0 + y;
     const bool rowconst = p.pad_mode == PCNN_PAD_CONSTANT && (unsigned)gy >= (unsigned)p.H;
@@ -629,7 +585,7 @@ __device__ __forceinline__ void fwd64_request(const FwdItem64& it, const FwdRow6
 #pragma unroll
   for (int x = 0; x < T64; ++x) {
     const float* rp = it.img + (unsigned)__builtin_amdgcn_readlane((int)it.voff, x);
-    R[Un][x] = (row[Un].fetch && !FFT_STUDY(2)) ? rp[row[Un].lo] : 0.f;                   // (defined on every path: otherwise R is carried around the item loop)
+    R[Un][x] = row[Un].fetch ? rp[row[Un].lo] : 0.f;                     // (defined on every path: otherwise R is carried around the item loop)
   }
 }
 
@@ -672,23 +628,11 @@ __device__ __forceinline__ void y64_gather(const float* U, int offr, int offi, i
 }
 
 // 8 waves of up to 256 registers, two units per wave and phase (unit u of wave w: window rows 4 (2w + u) + lane group, column 2w + u); an item's two
-// rows of 64 values per lane are requested at the top of the item (no prefetch: see PCNN_PF64_NONE below).  (A 16-wave build of the same phases - 128
-// registers - cannot hold a row of 64 beside the y-axis state: it spilled 50-110 registers in every arrangement tried.)
-#ifndef PCNN_PF64_ONE
-#define PCNN_PF64_ONE 0
-#endif
-#ifndef PCNN_PF64_FULL
-#define PCNN_PF64_FULL 0
-#endif
-#ifndef PCNN_PF64_NONE
-#define PCNN_PF64_NONE 1
-#endif
-constexpr bool PF64_NONE = PCNN_PF64_NONE; // 8-wave form WITHOUT any prefetch (both rows requested at the top of the item): the shipped form since the end of round 5 -
-                                           // unit 0's row held across the even y phase (PCNN_PF64_NONE=0) costs 29 spilled registers, and the spill-free kernel is 2.4 %
-                                           // faster per 15-tap forward although its loads are exposed (profiles/r05_probe_fwd64_no_prefetch.txt)
-constexpr bool PF64_FULL = PCNN_PF64_FULL; // 8-wave form: request BOTH rows of the next item under the even y phase (128 registers in flight: spills ~60)
-constexpr bool PF64_ONE = PCNN_PF64_ONE;   // 16-wave form: request the next item's row under the even y phase (64 registers in flight)
-template <bool MASKED, int NU>
+// rows of 64 values per lane are requested at the top of the item, without prefetch: unit 0's row of the next item requested under the even y phase costs
+// 29 spilled registers, and the spill-free kernel is 2.4 % faster per 15-tap forward although its loads are exposed (profiles/r05_probe_fwd64_no_prefetch.txt);
+// both rows requested there (128 registers in flight) spill 60-66.  (A 16-wave build of the same phases - 128 registers - cannot hold a row of 64 beside the
+// y-axis state: it spilled 50-110 registers in every arrangement tried.)
+template <bool MASKED>
 __device__ __forceinline__ void fft64_fwd_body(const FwdParams& p, const int nvirt, float* U, const int bid, const int gdim) {   // U[(y*32 + s)*16 + c16], y < 64, s < 32: one x-parity phase
   const int tid = threadIdx.x, lane = tid & 63, lg = lane >> 4, c16 = lane & 15;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -703,30 +647,25 @@ __device__ __forceinline__ void fft64_fwd_body(const FwdParams& p, const int nvi
   FwdRow64 row[2];
   // the padded tail of the virtual item list (tg >= ntg) runs as a copy of a real item that stores nothing: the workgroup keeps its barriers
   auto safe = [&](int vv) { int tg, hf; item64(vv, tg, hf); return tg < ntg ? vv : (vv & 8); };
-  fwd64_describe_t<NU>(p, safe(v), lane, c16, cur, row, NU * wave);
-  if ((NU == 2 && !PF64_NONE) || PF64_ONE) fwd64_request<0>(cur, row, R);
-  if (NU == 2 && PF64_FULL) fwd64_request<1>(cur, row, R);
+  fwd64_describe(p, safe(v), lane, c16, cur, row, 2 * wave);
   for (;;) {
     const int next = v + gdim;
     const bool more = next < nvirt;
-    // (unit 0's row was requested a phase ahead - below; unit 1's here: the registers cannot hold both beside the y-axis state)
-    if (NU == 2 && PF64_NONE) fwd64_request<0>(cur, row, R);
-    if (NU == 2 && !PF64_FULL) fwd64_request<1>(cur, row, R);
-    else if (NU == 1 && !PF64_ONE) fwd64_request<0>(cur, row, R);
+    fwd64_request<0>(cur, row, R);
+    fwd64_request<1>(cur, row, R);
     // ---- x axis: the whole real FFT of this lane's two rows.  The ODD bins go through LDS first (16 complex columns, every unit the same path)
     // while the even bins wait in R[u][0..32).
 #pragma unroll
-    for (int u = 0; u < NU; ++u) {
+    for (int u = 0; u < 2; ++u) {
       __builtin_amdgcn_sched_barrier(0);                                 // one unit after the other: interleaved, the two transforms need twice the registers
       fwd64_consume<MASKED>(p, cur, row[u], R[u]);
-      if (!FFT_STUDY(4)) rfft_fwd<64>(R[u]);
+      rfft_fwd<64>(R[u]);
       pin<32>(R[u]);
-      int uoff = ((4 * (NU * wave + u) + lg) * 32) * 16 + c16;
+      int uoff = ((4 * (2 * wave + u) + lg) * 32) * 16 + c16;
       asm volatile("" : "+v"(uoff));
       float* urow = U + uoff;
 #pragma unroll
       for (int m = 0; m < 16; ++m) {                                     // C[m] = X[4m + 1]: Re at s = m, Im at s = 16 + m
-        if (FFT_STUDY(16)) continue;
         urow[m * 16] = R[u][32 + bitrev(m, 16)];
         urow[(16 + m) * 16] = R[u][48 + bitrev(m, 16)];
       }
@@ -734,66 +673,60 @@ __device__ __forceinline__ void fft64_fwd_body(const FwdParams& p, const int nvi
     lds_barrier();
     int tg, hf;
     item64(v, tg, hf);
-    const bool store = tg < ntg && !FFT_STUDY(1);
+    const bool store = tg < ntg;
     float* out = p.sp + sp_item64(store ? tg : 0) + 16 * hf;              // uniform; the lane adds (class row) * RS + c16
     int cl = lg;
     asm volatile("" : "+v"(cl));                                     // opaque: the per-lane constants of a phase are formed in the phase, not hoisted
 #pragma unroll
-    for (int u = 0; u < NU; ++u) {
+    for (int u = 0; u < 2; ++u) {
       // ---- y axis, odd fx.  column index q = 2 wave + u: fx = 2q + 1; q even: fx = 4j + 1 = C[j] (j = q / 2); q odd: fx = 4j + 3 = conj C[15 - j]
       __builtin_amdgcn_sched_barrier(0);
-      const int q = NU * wave + u;
+      const int q = 2 * wave + u;
       const int mcol = (q & 1) ? 15 - (q >> 1) : (q >> 1);
       float V[32];
       float* vr = V, *vi = V + 16;
-      if (FFT_STUDY(8)) { for (int i = 0; i < 32; ++i) V[i] = 1.f; } else y64_gather(U, mcol * 16 + c16, (16 + mcol) * 16 + c16, cl, (q & 1) ? -1.f : 1.f, tw, vr, vi);
-      if (!FFT_STUDY(4)) cfft_dif<16, -1>(vr, vi);
+      y64_gather(U, mcol * 16 + c16, (16 + mcol) * 16 + c16, cl, (q & 1) ? -1.f : 1.f, tw, vr, vi);
+      cfft_dif<16, -1>(vr, vi);
       if (store) {
         float* o = out + (128 + 128 * (2 * q)) * RS;
         const unsigned lo = (unsigned)(sp_row_c(64, cl, 0) * RS + c16);     // row(4 m + cl) = row(4 m) + row(cl) for every block size (spectral_common.h)
 #pragma unroll
         for (int m = 0; m < 16; ++m) {
-          NT_STORE(1, vr[bitrev(m, 16)], &(o + (sp_row_c(64, 4 * m, 0) * RS))[lo]);
-          NT_STORE(1, vi[bitrev(m, 16)], &(o + (sp_row_c(64, 4 * m, 1) * RS))[lo]);
+          __builtin_nontemporal_store(vr[bitrev(m, 16)], &(o + (sp_row_c(64, 4 * m, 0) * RS))[lo]);
+          __builtin_nontemporal_store(vi[bitrev(m, 16)], &(o + (sp_row_c(64, 4 * m, 1) * RS))[lo]);
         }
       }
     }
     lds_barrier();                                                       // the odd phase has been read: U is free
 #pragma unroll
-    for (int u = 0; u < NU; ++u) {
-      int uoff = ((4 * (NU * wave + u) + lg) * 32) * 16 + c16;
+    for (int u = 0; u < 2; ++u) {
+      int uoff = ((4 * (2 * wave + u) + lg) * 32) * 16 + c16;
       asm volatile("" : "+v"(uoff));
       float* urow = U + uoff;
       float (&E)[32] = *reinterpret_cast<float (*)[32]>(&R[u][0]);
 #pragma unroll
-      for (int s2 = 0; s2 < 32; ++s2) if (!FFT_STUDY(16)) urow[s2 * 16] = hc_get(E, s2);     // s <= 16: Re X[2s], s > 16: Im X[2 (s - 16)]
+      for (int s2 = 0; s2 < 32; ++s2) urow[s2 * 16] = hc_get(E, s2);     // s <= 16: Re X[2s], s > 16: Im X[2 (s - 16)]
     }
-    // R is free: unit 0's row of the next item is requested here and lands under the even y phase (both rows - 128 registers - beside the y-axis
-    // state spill 66 registers; during the odd phase the even bins still occupy 64)
-    if (more) {
-      fwd64_describe_t<NU>(p, safe(next), lane, c16, cur, row, NU * wave);
-      if ((NU == 2 && !PF64_NONE) || PF64_ONE) fwd64_request<0>(cur, row, R);
-      if (NU == 2 && PF64_FULL) fwd64_request<1>(cur, row, R);
-    }
+    if (more) fwd64_describe(p, safe(next), lane, c16, cur, row, 2 * wave);
     lds_barrier();
     asm volatile("" : "+v"(cl));
     // ---- y axis, even fx.  q = 0..14: complex column fx = 2 (q + 1) (Re at s = q + 1, Im at s = 17 + q); q = 15: the two real columns
 #pragma unroll
-    for (int u = 0; u < NU; ++u) {
+    for (int u = 0; u < 2; ++u) {
       __builtin_amdgcn_sched_barrier(0);
-      const int q = NU * wave + u;
+      const int q = 2 * wave + u;
       float V[32];
       float* vr = V, *vi = V + 16;
       if (q < 15) {
-        if (FFT_STUDY(8)) { for (int i = 0; i < 32; ++i) V[i] = 1.f; } else y64_gather(U, (q + 1) * 16 + c16, (17 + q) * 16 + c16, cl, 1.f, tw, vr, vi);
-        if (!FFT_STUDY(4)) cfft_dif<16, -1>(vr, vi);
+        y64_gather(U, (q + 1) * 16 + c16, (17 + q) * 16 + c16, cl, 1.f, tw, vr, vi);
+        cfft_dif<16, -1>(vr, vi);
         if (store) {
           float* o = out + (128 + 128 * (2 * (q + 1) - 1)) * RS;
           const unsigned lo = (unsigned)(sp_row_c(64, cl, 0) * RS + c16);     // row(4 m + cl) = row(4 m) + row(cl) for every block size (spectral_common.h)
 #pragma unroll
           for (int m = 0; m < 16; ++m) {
-            NT_STORE(1, vr[bitrev(m, 16)], &(o + (sp_row_c(64, 4 * m, 0) * RS))[lo]);
-            NT_STORE(1, vi[bitrev(m, 16)], &(o + (sp_row_c(64, 4 * m, 1) * RS))[lo]);
+            __builtin_nontemporal_store(vr[bitrev(m, 16)], &(o + (sp_row_c(64, 4 * m, 0) * RS))[lo]);
+            __builtin_nontemporal_store(vi[bitrev(m, 16)], &(o + (sp_row_c(64, 4 * m, 1) * RS))[lo]);
           }
         }
       } else {
@@ -806,12 +739,12 @@ __device__ __forceinline__ void fft64_fwd_body(const FwdParams& p, const int nvi
         if ((cl & 1) == 0) {
 #pragma unroll
           for (int yy = 0; yy < 32; ++yy) V[yy] = uu[yy * 512] + uu[(yy + 32) * 512];
-          if (!FFT_STUDY(4)) rfft_fwd<32>(V);
+          rfft_fwd<32>(V);
           if (store) {
 #pragma unroll
-            for (int k = 0; k <= 16; ++k) NT_STORE(1, hc_get(V, k), &(o + (sp_row_r(64, 2 * k) * RS))[lo]);                 // Re Z[2k]: half-complex entry 2k of the column
+            for (int k = 0; k <= 16; ++k) __builtin_nontemporal_store(hc_get(V, k), &(o + (sp_row_r(64, 2 * k) * RS))[lo]);                 // Re Z[2k]: half-complex entry 2k of the column
 #pragma unroll
-            for (int k = 1; k < 16; ++k) NT_STORE(1, hc_get(V, 16 + k), &(o + (sp_row_r(64, 32 + 2 * k) * RS))[lo]);        // Im Z[2k]: entry 32 + 2k
+            for (int k = 1; k < 16; ++k) __builtin_nontemporal_store(hc_get(V, 16 + k), &(o + (sp_row_r(64, 32 + 2 * k) * RS))[lo]);        // Im Z[2k]: entry 32 + 2k
           }
         } else {
           // d[n] = u[n] - u[n + 32]; c[n] = (d[n] - i d[n + 16]) W64^n, n < 16; C[m] = Z[4m + 1]; Z[4m + 3] = conj C[15 - m]
@@ -820,14 +753,14 @@ __device__ __forceinline__ void fft64_fwd_body(const FwdParams& p, const int nvi
             const float dr = uu[n2 * 512] - uu[(n2 + 32) * 512], di = uu[(n2 + 48) * 512] - uu[(n2 + 16) * 512];
             mul_tw<64, -1>(n2, dr, di, vr[n2], vi[n2]);
           }
-          if (!FFT_STUDY(4)) cfft_dif<16, -1>(vr, vi);
+          cfft_dif<16, -1>(vr, vi);
           if (store) {
 #pragma unroll
             for (int m = 0; m < 8; ++m) {
-              NT_STORE(1, vr[bitrev(m, 16)], &(o + (sp_row_r(64, 4 * m + 1) * RS))[lo]);
-              NT_STORE(1, vi[bitrev(m, 16)], &(o + (sp_row_r(64, 32 + 4 * m + 1) * RS))[lo]);
-              NT_STORE(1, vr[bitrev(15 - m, 16)], &(o + (sp_row_r(64, 4 * m + 3) * RS))[lo]);
-              NT_STORE(1, -vi[bitrev(15 - m, 16)], &(o + (sp_row_r(64, 32 + 4 * m + 3) * RS))[lo]);
+              __builtin_nontemporal_store(vr[bitrev(m, 16)], &(o + (sp_row_r(64, 4 * m + 1) * RS))[lo]);
+              __builtin_nontemporal_store(vi[bitrev(m, 16)], &(o + (sp_row_r(64, 32 + 4 * m + 1) * RS))[lo]);
+              __builtin_nontemporal_store(vr[bitrev(15 - m, 16)], &(o + (sp_row_r(64, 4 * m + 3) * RS))[lo]);
+              __builtin_nontemporal_store(-vi[bitrev(15 - m, 16)], &(o + (sp_row_r(64, 32 + 4 * m + 3) * RS))[lo]);
             }
           }
         }
@@ -839,10 +772,10 @@ __device__ __forceinline__ void fft64_fwd_body(const FwdParams& p, const int nvi
   }
 }
 
-template <bool MASKED, int NU>
-__global__ __launch_bounds__(1024 / NU) void fft64_fwd_kernel(FwdParams p, int nvirt) {
+template <bool MASKED>
+__global__ __launch_bounds__(512) void fft64_fwd_kernel(FwdParams p, int nvirt) {
   extern __shared__ __attribute__((aligned(16))) float U[];
-  fft64_fwd_body<MASKED, NU>(p, nvirt, U, blockIdx.x, gridDim.x);
+  fft64_fwd_body<MASKED>(p, nvirt, U, blockIdx.x, gridDim.x);
 }
 
 // the table form (fft32_fwd_multi_kernel): blockIdx.y = entry; gridDim.x is a multiple of 16 (a workgroup keeps one 16-channel half)
@@ -850,7 +783,7 @@ __global__ __launch_bounds__(512) void fft64_fwd_multi_kernel(const FwdParams* _
   extern __shared__ __attribute__((aligned(16))) float U[];
   const FwdParams p = load_fwd_params(tab + blockIdx.y);
   const int ntg = p.ntile * p.groups;
-  fft64_fwd_body<true, 2>(p, 2 * ((ntg + 7) & ~7), U, blockIdx.x, gridDim.x);
+  fft64_fwd_body<true>(p, 2 * ((ntg + 7) & ~7), U, blockIdx.x, gridDim.x);
 }
 
 // ------------------------------------------------------------------------------------------------------------------ 64-point inverse + epilogue
@@ -863,10 +796,6 @@ __global__ __launch_bounds__(512) void fft64_fwd_multi_kernel(const FwdParams* _
 constexpr int G_YS = 528, G_CS = 16 * G_YS + 16;                     // floats between rows / class planes of the LDS image (odd multiples of 16: no bank conflicts)
 constexpr size_t LDS64I_BYTES = (4 * G_CS + 128) * sizeof(float);
 
-#ifndef PCNN_ST64_NT
-#define PCNN_ST64_NT 1
-#endif
-#define ST64(v, p) do { if (PCNN_ST64_NT) __builtin_nontemporal_store(v, p); else *(p) = (v); } while (0)
 template <bool TANH, bool RES, bool POST>
 __global__ __launch_bounds__(512) void fft64_inv_kernel(InvParams p, int nvirt) {
   extern __shared__ __attribute__((aligned(16))) float G[];          // G[cl * G_CS + y * G_YS + s * 16 + c16], y < 16, s < 32
@@ -879,10 +808,7 @@ __global__ __launch_bounds__(512) void fft64_inv_kernel(InvParams p, int nvirt) 
   if (tid < 64) { TW[2 * tid] = cos64(((tid >> 4) * (tid & 15)) & 63); TW[2 * tid + 1] = -sin64(((tid >> 4) * (tid & 15)) & 63); }
   const float* const tw = TW + lg * 32;
   float ymax = 0.f, bsum = 0.f;
-#ifndef PCNN_INV64_BURST
-#define PCNN_INV64_BURST 8
-#endif
-  constexpr int BURST = PCNN_INV64_BURST;
+  constexpr int BURST = 8;
   for (;;) {
     const int next = v + gridDim.x;
     int tg, hf;
@@ -913,8 +839,8 @@ __global__ __launch_bounds__(512) void fft64_inv_kernel(InvParams p, int nvirt) 
             const float sg = fy <= 32 ? 1.f : -1.f;
             const bool hasim = fp != 0 && fp != 32;
             const unsigned rr = (unsigned)(sp_row_r(64, fp) * RS), ri = (unsigned)(sp_row_r(64, 32 + (hasim ? fp : 1)) * RS);     // (per-lane: fp depends on the class)
-            const float ar = FFT_STUDY(2) ? 1.f : NT_LOAD(8, &in[lo + rr]), br = FFT_STUDY(2) ? 1.f : NT_LOAD(8, &(in + 64 * RS)[lo + rr]);
-            float ai = FFT_STUDY(2) ? 1.f : NT_LOAD(8, &in[lo + ri]), bi = FFT_STUDY(2) ? 1.f : NT_LOAD(8, &(in + 64 * RS)[lo + ri]);
+            const float ar = in[lo + rr], br = (in + 64 * RS)[lo + rr];
+            float ai = in[lo + ri], bi = (in + 64 * RS)[lo + ri];
             ai = hasim ? sg * ai : 0.f; bi = hasim ? sg * bi : 0.f;
             vr[m] = ar - bi; vi[m] = ai + br;
           }
@@ -928,11 +854,11 @@ __global__ __launch_bounds__(512) void fft64_inv_kernel(InvParams p, int nvirt) 
           const unsigned lo = (unsigned)(sp_row_c(64, cl, 0) * RS + c16);
 #pragma unroll
           for (int m = 0; m < 16; ++m) {
-            vr[m] = FFT_STUDY(2) ? 1.f : NT_LOAD(8, &(src + sp_row_c(64, 4 * m, 0) * RS)[lo]);
-            vi[m] = FFT_STUDY(2) ? 1.f : NT_LOAD(8, &(src + sp_row_c(64, 4 * m, 1) * RS)[lo]);
+            vr[m] = (src + sp_row_c(64, 4 * m, 0) * RS)[lo];
+            vi[m] = (src + sp_row_c(64, 4 * m, 1) * RS)[lo];
           }
         }
-        if (!FFT_STUDY(4)) cfft_dif<16, +1>(vr, vi);                                      // register j: y = bitrev(j)
+        cfft_dif<16, +1>(vr, vi);                                      // register j: y = bitrev(j)
         int goff = cl * G_CS + sre * 16 + c16;
         asm volatile("" : "+v"(goff));                                 // opaque: LDS addresses are lane constants - left alone, ~100 of them are hoisted
         float* g = G + goff;                                           // out of the item loop into registers of their own (everything else then spills)
@@ -1016,13 +942,13 @@ __global__ __launch_bounds__(512) void fft64_inv_kernel(InvParams p, int nvirt) 
         const int unit = 2 * wave + u;
         if (4 * unit >= vy) continue;                                  // uniform: none of the unit's four rows is an output row
         const int yy = 4 * unit + lg;
-        if (!FFT_STUDY(4)) rfft_inv<64>(R[u]);                                            // R[u][x] = 4096 * pixel (yy, x)
+        rfft_inv<64>(R[u]);                                            // R[u][x] = 4096 * pixel (yy, x)
         const int prow = p.flip ? p.Ho - 1 - y0 - yy : y0 + yy, pcol = p.flip ? p.Wo - 1 - x0 : x0;
         unsigned pix0 = (unsigned)(prow * p.Wo + pcol);
         asm volatile("" : "+v"(pix0));                               // opaque: per-pixel offsets are recomputed, not hoisted into registers per tensor
-        if (cok && yy < vy && !FFT_STUDY(1))
-          epilogue_row<TANH, RES, POST, T64, BURST, PCNN_ST64_NT != 0>(p, R[u], 1.f / 4096.f, vx, pix0, sgn, chv, bias, sc, sh, yimg, aimg, rimg, gimg, y2img, ymax, bsum, NoBetween(),
-                                                                       (PCNN_EPI_SKIP & 4) ? __builtin_amdgcn_readfirstlane(vx) : T64);
+        if (cok && yy < vy)
+          epilogue_row<TANH, RES, POST, T64, BURST, true>(p, R[u], 1.f / 4096.f, vx, pix0, sgn, chv, bias, sc, sh, yimg, aimg, rimg, gimg, y2img, ymax, bsum, NoBetween(),
+                                                          __builtin_amdgcn_readfirstlane(vx));
       }
     }
     if (next >= nvirt) break;
@@ -1068,14 +994,7 @@ void launch_inv_t(pcnn_handle h, const InvParams& p, const dim3& grid) {
 }  // namespace
 
 // persistent kernels: one 16-wave workgroup per CU (128 KB of LDS) walking the (tile, channel group) items
-#ifdef PCNN_FFT_STUDY
-static void study_init() { static int once = 0; if (!once) { once = 1; const int v = getenv("PCNN_FFT_STUDY") ? atoi(getenv("PCNN_FFT_STUDY")) : 0; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_fft_study), &v, sizeof(int)); } }
-#else
-static void study_init() {}
-#endif
-
 void launch_fwd_fft32(pcnn_handle h, FwdParams p, int ntile) {
-  study_init();
   p.ntile = ntile;
   const dim3 grid((unsigned)std::min(ntile * p.groups, 256));
   if (p.ylim < T || p.xlim < T) {
@@ -1105,23 +1024,16 @@ void launch_post_bias_fft32(pcnn_handle h, const float* bsum, int pack, int cpt,
 
 void launch_fwd_fft64(pcnn_handle h, FwdParams p, int ntile) {
   p.ntile = ntile;
-  study_init();
   const int ntg = ntile * p.groups;
   const int nvirt = 2 * ((ntg + 7) & ~7);                            // (tile-and-group) x two 16-channel halves, in blocks of 8 + 8 (item64)
   const dim3 grid((unsigned)std::min((nvirt + 15) & ~15, 256));
   const bool masked = p.ylim < T64 || p.xlim < T64 || p.ext_y < (1 << 29) || p.ext_x < (1 << 29);
-  static const int nu = getenv("PCNN_FFT64_UNITS") ? atoi(getenv("PCNN_FFT64_UNITS")) : 2;    // developer switch (A/B): 1 = 16 waves x 1 unit, 2 = 8 waves x 2 units
-  if (nu == 1) {
-    if (masked) { set_lds(fft64_fwd_kernel<true, 1>, LDS64_BYTES); hipLaunchKernelGGL((fft64_fwd_kernel<true, 1>), grid, dim3(1024), LDS64_BYTES, h->stream, p, nvirt); }
-    else { set_lds(fft64_fwd_kernel<false, 1>, LDS64_BYTES); hipLaunchKernelGGL((fft64_fwd_kernel<false, 1>), grid, dim3(1024), LDS64_BYTES, h->stream, p, nvirt); }
-    return;
-  }
   if (masked) {
-    set_lds(fft64_fwd_kernel<true, 2>, LDS64_BYTES);
-    hipLaunchKernelGGL((fft64_fwd_kernel<true, 2>), grid, dim3(512), LDS64_BYTES, h->stream, p, nvirt);
+    set_lds(fft64_fwd_kernel<true>, LDS64_BYTES);
+    hipLaunchKernelGGL((fft64_fwd_kernel<true>), grid, dim3(512), LDS64_BYTES, h->stream, p, nvirt);
   } else {
-    set_lds(fft64_fwd_kernel<false, 2>, LDS64_BYTES);
-    hipLaunchKernelGGL((fft64_fwd_kernel<false, 2>), grid, dim3(512), LDS64_BYTES, h->stream, p, nvirt);
+    set_lds(fft64_fwd_kernel<false>, LDS64_BYTES);
+    hipLaunchKernelGGL((fft64_fwd_kernel<false>), grid, dim3(512), LDS64_BYTES, h->stream, p, nvirt);
   }
 }
 
@@ -1132,7 +1044,6 @@ static void launch_inv64_t(pcnn_handle h, const InvParams& p, const dim3& grid, 
 }
 
 void launch_inv_fft64(pcnn_handle h, InvParams p, int ntile) {
-  study_init();
   p.ntile = ntile;
   const int ntg = ntile * p.groups;
   const int nvirt = 2 * ((ntg + 7) & ~7);
@@ -1156,7 +1067,6 @@ void launch_post_bias_fft64(pcnn_handle h, const float* bsum, int nblocks, int C
 }
 
 void launch_inv_fft32(pcnn_handle h, InvParams p, int ntile) {
-  study_init();
   p.ntile = ntile;
   const dim3 grid((unsigned)std::min(ntile * p.groups, 256));
   if (p.gact) {                                                      // data gradient + the producer's activation backward (linear conv epilogue)

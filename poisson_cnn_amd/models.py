@@ -409,8 +409,6 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
         exactly (equal-weight means of equal-size blocks), so only the factors without a divisor read the full tensor.  {f: (tensor, parent g)}"""
         N, H, W, _ = x.shape
         fs = sorted({b.f for b in blocks if b.down_conv is None and b.pool in ('average', 'avg') and H % b.f == 0 and W % b.f == 0})
-        if os.environ.get('PCNN_POOL_PYRAMID', '1') == '0':
-            fs = []
         pyr = {}
         for f in fs:
             parent = max([g for g in pyr if f % g == 0], default=None)

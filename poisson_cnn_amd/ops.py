@@ -536,14 +536,11 @@ def pad_fold_bwd(gp, out_hw, pads, pad_mode, out=None, accumulate=False):
     return gx
 
 
-_fold_post = __import__('os').environ.get('PCNN_FOLD_POST', '1') != '0'          # developer switch (A/B timing): 0 = fold and activation backward as two passes
-
-
 def pad_fold_bwd_post(gp, out_hw, pads, pad_mode, post, add_to=None, ws=None):
     """pad_fold_bwd AND the producer's activation backward in one pass (pcnn_pad_fold_bwd_post): returns dz = (fold(gp) [+ add_to]) * act'(post.a), sets
     post.applied / post.raw (the un-multiplied gradient, if post.want_raw) and writes post.dbias - or returns None (nothing done) where the shape is not
     eligible or the fusion is switched off (PCNN_POST_FUSION=0): the caller then folds and lets the producer run its own epilogue pass."""
-    if not _post_fusion or not _fold_post:
+    if not _post_fusion:
         return None
     N, Hp, Wp, C = gp.shape
     H, W = out_hw
@@ -762,13 +759,10 @@ class ResizeSrc(ctypes.Structure):
     _fields_ = [('x', c_void_p), ('hc', c_int), ('wc', c_int), ('ldx', c_int), ('idx_y', c_void_p), ('wt_y', c_void_p), ('idx_x', c_void_p), ('wt_x', c_void_p)]
 
 
-_resize_multi = __import__('os').environ.get('PCNN_RESIZE_MULTI', '1') != '0'      # developer switch (A/B): 0 = one resize_fwd per branch
-
-
 def resize_fwd_multi(xs, out_hw, methods, *, alpha, beta, out):
     """out = beta out + alpha (resize(xs[0]) + resize(xs[1]) [+ resize(xs[2])]) with ONE read-modify-write pass over `out` (pcnn_resize_fwd_multi): bit-identical to
     len(xs) consecutive resize_fwd calls with beta, 1, 1.  Returns out, or None when the library declines (channel count, alignment, more than three sources)."""
-    if not _resize_multi or not 2 <= len(xs) <= 3:
+    if not 2 <= len(xs) <= 3:
         return None
     N, _, _, C = xs[0].shape
     Ho, Wo = out_hw
