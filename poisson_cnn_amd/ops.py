@@ -463,7 +463,7 @@ def conv2d_bwd_fused(x, dz, w_shape, wf, *, pad_top, pad_left, pad_mode='CONSTAN
     if mode == 'CONSTANT':
         out_hw, dpt, dpl = (H, W), kh - 1 - pad_top, kw - 1 - pad_left
     else:
-        out_hw, dpt, dpl = (H + kh - 1, W + kw - 1), kh - 1, kw - 1
+        out_hw, dpt, dpl = (dz.shape[1] + kh - 1, dz.shape[2] + kw - 1), kh - 1, kw - 1      # the padded domain (H + kh - 1 where Ho = H)
         residual = None
     ldo = Cin
     dg = conv_desc(dz.shape, _ld(dz), (kh, kw, Cout, Cin), out_hw, ldo, dpt, dpl, 'CONSTANT', 0.0, 'linear', _ld(residual) if residual is not None else 0, 0)
