@@ -18,6 +18,8 @@
  *  - Every call is asynchronous on the handle's stream and returns 0 on success, non-zero on error
  *    (pcnn_last_error(handle) gives the message).  No exceptions cross the boundary.
  *  - One handle per (thread, device, stream).
+ *  - The recurrent layers of models/Dirichlet_BC_RNN.py are the pcnn_rnn_* calls at the end of this header: one launch per layer and direction
+ *    for the whole sequence; their time-parallel products are pcnn_wide_conv2d_* calls.
  *  - Environment variables read by the library are DEVELOPER switches for A/B timing and tests, not part of the interface; each is validated
  *    where it is read (an invalid value keeps the default): PCNN_MATH, PCNN_SPECTRAL, PCNN_SPEC_T (same as the pcnn_set_* calls),
  *    PCNN_SPEC_XFORM (transform kernels of the spectral route: "fft" in-register vector-ALU FFT, "mfma" DFT-as-GEMM), PCNN_SPEC_CHUNK (a size),
@@ -559,6 +561,42 @@ int pcnn_set_first_row(pcnn_handle h, int N, int X, int L, const float* bc, floa
  * axes, scaled per sample by alpha[n] (NULL = 1) and optionally accumulated into out (the five-term sum of models/Poisson_CNN_Legacy.py:48) */
 int pcnn_flip_rotate(pcnn_handle h, int N, int Ho, int Wo, int transpose, int flip_y, int flip_x, const float* in, const float* alpha,
                      int accumulate, float* out);
+
+/* ---- recurrent layers of Dirichlet_BC_RNN (models/Dirichlet_BC_RNN.py:24-30,46-48; kernels in csrc/rnn.hip) -------------------------------
+ * tf.keras.layers.LSTM / GRU(units, activation, return_sequences=True, time_major=False), zero initial state, TF 2 semantics:
+ *   LSTM  z = x W + h U + b, gate blocks i, f, c~, o:  c' = rec(f) c + rec(i) act(c~),  h' = rec(o) act(c')
+ *   GRU (reset_after=True), blocks z, r, h~, bias (2, 3u):  mx = x W + b[0], mh = h U + b[1],
+ *         z = rec(mx_z + mh_z), r = rec(mx_r + mh_r), h~ = act(mx_h + r mh_h),  h' = z h + (1 - z) h~
+ * The time-parallel products (x W + b for all t; dX, dW, dU, db in the backward) are 1x1 convolutions over the N T rows: pcnn_wide_conv2d_*.
+ * The two calls below are the dependent chain: ONE kernel launch for the whole sequence, one workgroup per sample (no cooperation between
+ * workgroups), U held in registers, exact fp32 FMAs in a fixed order in every math mode, no atomics, no allocation, no synchronisation.
+ * Every (N, T, C) tensor is addressed as base + n * sn + t * ld + c (floats).  reverse = go_backwards: step s reads its input at position
+ * T - 1 - s; outputs stay in processing order (Keras does not flip them back).  1 <= units <= PCNN_RNN_MAX_UNITS. */
+enum { PCNN_RNN_LSTM = 0, PCNN_RNN_GRU = 1 };
+enum { PCNN_RNN_ACT_LINEAR = 0, PCNN_RNN_ACT_TANH = 1, PCNN_RNN_ACT_SIGMOID = 2, PCNN_RNN_ACT_RELU = 3 };   /* the layer's `activation` */
+enum { PCNN_RNN_SIGMOID = 0, PCNN_RNN_HARD_SIGMOID = 1 };   /* `recurrent_activation`; hard_sigmoid = clip(0.2 x + 0.5, 0, 1) */
+enum { PCNN_RNN_MAX_UNITS = 128 };
+typedef struct {
+  int cell, N, T, units;
+  int act, rec_act, reverse;
+  int64_t sn_zx; int ld_zx;       /* projected gates x W + b (N, T, G units), G = 4 (LSTM) / 3 (GRU), indexed by INPUT position */
+  int64_t sn_h; int ld_h;         /* h (N, T, units), processing order */
+  int64_t sn_h2; int ld_h2;       /* optional second copy of h (forward) */
+  int64_t sn_dh; int ld_dh;       /* incoming dL/dh_s (N, T, units), processing order (backward) */
+  int64_t sn_dzx; int ld_dzx;     /* dL/d(x W + b) (N, T, G units), by INPUT position (backward) */
+  int64_t sn_dzh; int ld_dzh;     /* dL/d(h U [+ b1]) (N, T, G units), processing order (backward) */
+} pcnn_rnn_desc;
+/* floats of `saved` = N T (G + 1) units: per step the activated gates and c' (LSTM) or (h U + b1)_h (GRU), dense */
+size_t pcnn_rnn_saved_floats(const pcnn_rnn_desc* d);
+/* The recurrence of LSTM.call / GRU.call (models/Dirichlet_BC_RNN.py:46-48).  U (units, G units) Keras recurrent_kernel; rbias: the GRU's
+ * b[1] (3 units) or NULL; hout2: NULL or a second destination of h (e.g. the dense image the Upsample layer reads, :50-52). */
+int pcnn_rnn_fwd(pcnn_handle h, const pcnn_rnn_desc* d, const float* zx, const float* U, const float* rbias, float* hout, float* hout2,
+                 float* saved);
+/* Its gradient under the GradientTape of models/Dirichlet_BC_RNN.py:66-70: from dh (the gradient of every h_s) to dzx and dzh; these feed
+ * pcnn_wide_conv2d_dgrad (dX) and pcnn_wide_conv2d_wgrad (dW, db from dzx with x; dU, db[1] from dzh with h_{s-1}).  dzh may be the same
+ * buffer as dzx for an LSTM with reverse = 0 (the two are then equal). */
+int pcnn_rnn_bwd(pcnn_handle h, const pcnn_rnn_desc* d, const float* U, const float* saved, const float* hout, const float* dh, float* dzx,
+                 float* dzh);
 
 #ifdef __cplusplus
 }

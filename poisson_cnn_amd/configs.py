@@ -102,6 +102,34 @@ def unet_tiny():
     return cfg
 
 
+def dbcnn_rnn():
+    """experiments/dbcnn_rnn.json: Dirichlet_BC_RNN, six LSTM layers of 100 units along the boundary, on the numerical dataset of dbcnn.json."""
+    model = {'data_format': 'channels_first', 'activations': 'tanh', 'units': [100, 100, 100, 100, 100, 100], 'resize_method': 'bilinear', 'RNN_type': 'lstm'}
+    dataset = {'batch_size': 50, 'batches_per_epoch': 200, 'random_output_shape_range': [[192, 384], [192, 384]], 'random_dx_range': [5e-3, 5e-2],
+               'solver_method': 'multigrid', 'boundary_random_smoothness_range': {'left': [3, 8], 'right': [3, 8], 'top': [3, 8], 'bottom': [3, 8]}}
+    training = {
+        'n_epochs': 200, 'precision': 'float32', 'optimizer': 'adam',
+        'optimizer_parameters': {'learning_rate': 1e-4, 'amsgrad': False}, 'min_learning_rate': 1e-7,
+        'loss_parameters': {
+            'ndims': 2, 'data_format': 'channels_first', 'mae_loss_weight': 1.0, 'integral_loss_weight': 0.4,
+            'integral_loss_config': {'n_quadpts': 47, 'Lp_norm_power': 2},
+            'physics_informed_loss_weight': 0.0,
+            'physics_informed_loss_config': {'stencil_sizes': [5, 5], 'orders': 2, 'normalize': False},
+            'scale_sample_loss_by_target_peak_magnitude': False},
+    }
+    return {'model': model, 'dataset': dataset, 'training': training}
+
+
+def dbcnn_rnn_tiny():
+    """Two layers (12 and 9 units) on small grids (tests)."""
+    cfg = dbcnn_rnn()
+    cfg['model'].update(units=[12, 9])
+    cfg['dataset'].update(batch_size=2, batches_per_epoch=2, random_output_shape_range=[[40, 56], [40, 56]])
+    cfg['training']['n_epochs'] = 2
+    cfg['training']['loss_parameters']['integral_loss_config']['n_quadpts'] = 11
+    return cfg
+
+
 def load_config(path):
     with open(path) as f:
         return json.load(f)

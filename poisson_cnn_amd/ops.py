@@ -1332,3 +1332,85 @@ def dropout_keep_mask(shape, rate, seed, layer):
         h = fmix(h ^ (idx & np.uint64(0xFFFFFFFF)).astype(np.uint32))
     th = min(float(np.float32(rate)) * 4294967296.0, 4294967295.0)
     return (h >= np.uint32(int(th))).reshape(shape)
+
+
+# ----------------------------------------------------------------------------- recurrent layers (Dirichlet_BC_RNN, csrc/rnn.hip)
+RNN_CELLS = {'lstm': 0, 'gru': 1}
+RNN_GATES = {'lstm': 4, 'gru': 3}
+RNN_ACTS = {'linear': 0, 'tanh': 1, 'sigmoid': 2, 'relu': 3}
+RNN_REC_ACTS = {'sigmoid': 0, 'hard_sigmoid': 1}
+RNN_MAX_UNITS = 128
+
+
+class RnnDesc(ctypes.Structure):
+    """include/pcnn.h pcnn_rnn_desc"""
+    _fields_ = [('cell', c_int), ('N', c_int), ('T', c_int), ('units', c_int), ('act', c_int), ('rec_act', c_int), ('reverse', c_int),
+                ('sn_zx', c_int64), ('ld_zx', c_int), ('sn_h', c_int64), ('ld_h', c_int), ('sn_h2', c_int64), ('ld_h2', c_int),
+                ('sn_dh', c_int64), ('ld_dh', c_int), ('sn_dzx', c_int64), ('ld_dzx', c_int), ('sn_dzh', c_int64), ('ld_dzh', c_int)]
+
+
+def _seq(t, N, T, C, name):
+    """(sample stride, time stride) of an (N, T, C) sequence tensor: any strides over n and t (slices of padded or wider buffers), unit stride over c."""
+    if t.dtype != torch.float32 or not t.is_cuda:
+        raise ValueError('%s must be a CUDA float32 tensor' % name)
+    if tuple(t.shape) != (N, T, C):
+        raise ValueError('%s must have shape %s, got %s' % (name, (N, T, C), tuple(t.shape)))
+    if C > 1 and t.stride(2) != 1:
+        raise ValueError('%s must have unit stride over its last axis' % name)
+    ld = t.stride(1) if T > 1 else C
+    sn = t.stride(0) if N > 1 else T * ld
+    if ld < C or sn < 0:
+        raise ValueError('%s: unsupported strides %s' % (name, t.stride()))
+    return sn, ld
+
+
+def _rnn_desc(cell, N, T, units, act, rec_act, reverse):
+    if not 1 <= units <= RNN_MAX_UNITS:
+        raise NotImplementedError('recurrent layers are implemented for 1 <= units <= %d, got %d' % (RNN_MAX_UNITS, units))
+    d = RnnDesc()
+    d.cell, d.N, d.T, d.units = RNN_CELLS[cell], N, T, units
+    d.act, d.rec_act, d.reverse = RNN_ACTS[act], RNN_REC_ACTS[rec_act], 1 if reverse else 0
+    return d
+
+
+def rnn_fwd(zx, U, rbias=None, *, cell='lstm', act='tanh', rec_act='sigmoid', reverse=False, h=None, h2=None, saved=None):
+    """The recurrence of one LSTM / GRU layer over the whole sequence in ONE kernel launch (pcnn_rnn_fwd).  zx (N, T, G u): the projected gates
+    x W + b by input position; U (u, G u); rbias: the GRU's b[1] (3u).  Returns (h (N, T, u) in processing order, saved) - `saved` is what
+    rnn_bwd needs.  h / h2 (an optional second copy) / saved may be preallocated; h and h2 may be strided views."""
+    N, T, Gu = zx.shape
+    G = RNN_GATES[cell]
+    u = Gu // G
+    assert Gu == G * u and tuple(U.shape) == (u, Gu) and U.is_contiguous(), (tuple(zx.shape), tuple(U.shape))
+    d = _rnn_desc(cell, N, T, u, act, rec_act, reverse)
+    d.sn_zx, d.ld_zx = _seq(zx, N, T, Gu, 'zx')
+    h = h if h is not None else empty((N, T, u), zx.device)
+    d.sn_h, d.ld_h = _seq(h, N, T, u, 'h')
+    if h2 is not None:
+        d.sn_h2, d.ld_h2 = _seq(h2, N, T, u, 'h2')
+    n_saved = N * T * (G + 1) * u
+    saved = saved if saved is not None else empty((n_saved,), zx.device)
+    assert saved.is_contiguous() and saved.numel() >= n_saved and saved.dtype == torch.float32
+    if rbias is not None:
+        assert cell == 'gru' and rbias.numel() == Gu and rbias.is_contiguous()
+    _launch('rnn_fwd', 2.0 * N * T * u * Gu, lambda: handle().call('pcnn_rnn_fwd', byref(d), _p(zx), _p(U), _p(rbias), _p(h), _p(h2), _p(saved)))
+    return h, saved
+
+
+def rnn_bwd(U, saved, h, dh, *, cell='lstm', act='tanh', rec_act='sigmoid', reverse=False, dzx=None, dzh=None):
+    """Backward of rnn_fwd in ONE kernel launch (pcnn_rnn_bwd): dh (N, T, u) is the gradient of every h_s (processing order).  Returns
+    (dzx, dzh), the gradients at x W + b (by input position) and at h U [+ b1] (processing order); for a forward-running LSTM they are one tensor."""
+    N, T, u = dh.shape
+    G = RNN_GATES[cell]
+    Gu = G * u
+    assert tuple(U.shape) == (u, Gu) and U.is_contiguous()
+    d = _rnn_desc(cell, N, T, u, act, rec_act, reverse)
+    d.sn_h, d.ld_h = _seq(h, N, T, u, 'h')
+    d.sn_dh, d.ld_dh = _seq(dh, N, T, u, 'dh')
+    dzx = dzx if dzx is not None else empty((N, T, Gu), dh.device)
+    if dzh is None:
+        dzh = dzx if (cell == 'lstm' and not reverse) else empty((N, T, Gu), dh.device)
+    d.sn_dzx, d.ld_dzx = _seq(dzx, N, T, Gu, 'dzx')
+    d.sn_dzh, d.ld_dzh = _seq(dzh, N, T, Gu, 'dzh')
+    assert saved.is_contiguous() and saved.numel() >= N * T * (G + 1) * u
+    _launch('rnn_bwd', 2.0 * N * T * u * Gu, lambda: handle().call('pcnn_rnn_bwd', byref(d), _p(U), _p(saved), _p(h), _p(dh), _p(dzx), _p(dzh)))
+    return dzx, dzh

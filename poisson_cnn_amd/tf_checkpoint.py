@@ -464,6 +464,9 @@ def keras_object_paths(model):
         m = {'hpnn/' + n: 'hpnn/' + v for n, v in keras_object_paths(model.hpnn).items()}
         m.update({'dbcnn/' + n: 'dbcnn/' + v for n, v in keras_object_paths(model.dbcnn).items()})
         return m
+    from .rnn import Dirichlet_BC_RNN
+    if isinstance(model, Dirichlet_BC_RNN):                        # models/Dirichlet_BC_RNN.py:24-30: self.RNN_layers[i], whose variables belong to its .cell
+        return {n: 'RNN_layers/%d/cell/%s' % (i, n.rsplit('/', 1)[1]) for i, lyr in enumerate(model.layers) for n in lyr[:3] if n is not None}
     from .dbcnn_models import Dirichlet_BC_NN_Metalearning
     if isinstance(model, (Dirichlet_BC_NN_Legacy_2, Dirichlet_BC_NN_Metalearning)):
         m = _dbcnn_paths(model) if isinstance(model, Dirichlet_BC_NN_Legacy_2) else _dbcnn_meta_paths(model)

@@ -189,9 +189,9 @@ def main(argv=None):
     p.add_argument('--dataset_type', type=lambda x: str(x).lower(), default='analytical')
     p.add_argument('--learning_rate', type=str, default=None)
     p.add_argument('--epochs', type=int, default=None)
-    p.add_argument('--model', type=lambda x: str(x).lower(), default='hpnn', choices=['hpnn', 'dbcnn', 'pcnn', 'unet'],
+    p.add_argument('--model', type=lambda x: str(x).lower(), default='hpnn', choices=['hpnn', 'dbcnn', 'pcnn', 'unet', 'dbcnn_rnn'],
                    help='hpnn: train/hpnn_legacy_train.py (train/hpnn_train.py when the model section carries model_type); dbcnn: train/dbcnn_legacy_train.py; '
-                        'pcnn: train/pcnn_end_to_end.py; unet: train/UNet.py')
+                        'pcnn: train/pcnn_end_to_end.py; unet: train/UNet.py; dbcnn_rnn: train/dbcnn_rnn_train.py')
     args = p.parse_args(argv)
     if args.dataset_type not in ('numerical', 'analytical'):
         raise ValueError('Invalid dataset type. Received: ' + args.dataset_type)
@@ -204,10 +204,17 @@ def main(argv=None):
     dcfg['batch_size'] = dp.local_batch(gbs)
     if dp.world_size > 1:       # every rank draws the step's grid shape from one shared stream and its samples from its own (dataset._streams)
         dcfg['shard'] = (dp.rank, dp.world_size)
-    if args.model == 'dbcnn':      # train/dbcnn_legacy_train.py:26-31: one non-zero edge, zero right-hand side
+    from .unet import UNetModel
+    from .rnn import Dirichlet_BC_RNN
+    monitors = ('loss', 'loss')    # what ModelCheckpoint / ReduceLROnPlateau watch
+    if args.model in ('dbcnn', 'dbcnn_rnn'):      # train/dbcnn_legacy_train.py:26-31 and train/dbcnn_rnn_train.py:26: one non-zero edge, zero right-hand side
         dataset = numerical_dataset_generator(randomize_boundary_smoothness=True, exclude_zero_boundaries=True, nonzero_boundaries=['left'], rhses='zero',
                                               return_boundaries=True, return_dx=True, return_rhs=False, **dcfg)
-        model = Dirichlet_BC_NN_Legacy_2(**config['model'])
+        if args.model == 'dbcnn':
+            model = Dirichlet_BC_NN_Legacy_2(**config['model'])
+        else:                      # train/dbcnn_rnn_train.py:31,38-39: the checkpoint follows 'mse', the learning rate 'loss'
+            model = Dirichlet_BC_RNN(**config['model'])
+            monitors = ('mse', 'loss')
     elif args.model == 'pcnn':     # train/pcnn_end_to_end.py:28-34: all four edges + a random right-hand side, both sub-models trained jointly
         dataset = numerical_dataset_generator(randomize_boundary_smoothness=True, exclude_zero_boundaries=False, nonzero_boundaries=['left', 'right', 'top', 'bottom'],
                                               rhses='random', return_boundaries=True, return_dx=True, return_rhs=True, **dcfg)
@@ -239,14 +246,14 @@ def main(argv=None):
     # the largest batch this run will see, for model.presize(): only where the generator draws its grid shape from a range (the analytic generators)
     rng_ = config['dataset'].get('random_output_shape_range')
     presize = None
-    from .unet import UNetModel
-    if rng_ is not None and isinstance(model, (Homogeneous_Poisson_NN_Legacy, UNetModel)) and os.environ.get('PCNN_PRESIZE', '1') != '0':
+    if rng_ is not None and isinstance(model, (Homogeneous_Poisson_NN_Legacy, UNetModel, Dirichlet_BC_RNN)) and os.environ.get('PCNN_PRESIZE', '1') != '0':
         r = np.asarray(rng_, dtype=np.int64)
         r = np.tile(r[None], (2, 1)) if r.ndim == 1 else r
         presize = (dcfg['batch_size'], int(r[0, 1]), int(r[1, 1]))
     model.compile(loss=loss, optimizer=optimizer, max_input_shape=presize)
     dp.attach(model)
-    cb = [ModelCheckpoint(args.checkpoint_dir + '/chkpt.checkpoint'), ReduceLROnPlateau(patience=4, min_lr=config['training']['min_learning_rate']),
+    cb = [ModelCheckpoint(args.checkpoint_dir + '/chkpt.checkpoint', monitor=monitors[0]),
+          ReduceLROnPlateau(patience=4, monitor=monitors[1], min_lr=config['training']['min_learning_rate']),
           TerminateOnNaN()]
     load_model_checkpoint(model, args.continue_from_checkpoint)
     if args.learning_rate is not None:
