@@ -19,19 +19,18 @@ reference has no test or config for this model: PARITY UNPINNED, checked against
 """
 import copy
 
-import numpy as np
 import torch
 
 from . import layers as L
 from . import metalearning as M
 from . import ops
-from .models import _ModelBase, _as_device
-from .utils import get_init_arguments_from_config, split_indices
+from .models import _BoundaryTables, _ModelBase, _as_device, _dx_tiled
+from .utils import get_init_arguments_from_config
 
 _CONV_FIELDS = (['filters', 'kernel_sizes'], ['filters', 'kernel_size'])
 
 
-class Dirichlet_BC_NN_Metalearning(_ModelBase):
+class Dirichlet_BC_NN_Metalearning(_BoundaryTables, _ModelBase):
     model_name = 'Dirichlet_BC_NN_Metalearning'
 
     def __init__(self, ndims=2, data_format='channels_first', boundary_conv_config=None, spp_config=None, domain_info_mlp_config=None,
@@ -48,9 +47,7 @@ class Dirichlet_BC_NN_Metalearning(_ModelBase):
             raise ValueError('Provide a config for the domain convolutions.')
         if domain_info_mlp_config is None:
             raise ValueError('Provide a config for the domain info MLP.')
-        if device is None and not torch.cuda.is_available():
-            raise RuntimeError('Dirichlet_BC_NN_Metalearning needs an AMD GPU: the HIP kernels are the only compute path')
-        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        self._init_device(device)
         self.ndims, self.data_format, self.use_batchnorm = 2, data_format, use_batchnorm
         assert boundary_conv_config['filters'][-1] == domain_info_mlp_config['units'][-1]       # reference :33
         self.x_dir_nmodes = nm = int(boundary_conv_config['filters'][-1])
@@ -105,28 +102,7 @@ class Dirichlet_BC_NN_Metalearning(_ModelBase):
         self.postsmoother = L.JacobiIterationLayer(postsmoother_iterations) if postsmoother_iterations > 0 else None
         S.finalize(self.device)
         S.initialize(seed)
-        self.optimizer = self.loss_fn = self.grad_sync = None
         self._bins, self._sinh = {}, {}
-
-    def _bin_table(self, Lh):
-        if Lh not in self._bins:
-            bins = []
-            for lv in self.spp_levels:
-                ix = split_indices(Lh, lv)
-                if (np.diff(ix) <= 0).any():
-                    raise ValueError('boundary too short for the spatial pyramid: %d bins over %d points' % (lv, Lh))
-                bins += [[0, 1, ix[b], ix[b + 1]] for b in range(lv)]
-            self._bins[Lh] = torch.tensor(np.array(bins, dtype=np.int32), device=self.device)
-        return self._bins[Lh]
-
-    def _sinh_table(self, X):
-        """build_series_x_dir_components (:103-110): input-independent, tabulated on the host in fp64 and rounded once."""
-        if X not in self._sinh:
-            xbar = np.linspace(0.0, 1.0, X)
-            v = np.sinh(np.outer(np.arange(1, self.x_dir_nmodes + 1, dtype=np.float64), np.pi * (xbar - 1.0)))
-            v = v / np.abs(v).max(axis=1, keepdims=True)
-            self._sinh[X] = torch.from_numpy(v.astype(np.float32)).to(self.device).contiguous()
-        return self._sinh[X]
 
     def call(self, inp, training=False):
         """reference :124-183."""
@@ -203,18 +179,12 @@ class Dirichlet_BC_NN_Metalearning(_ModelBase):
         self.ctx.join()
         self.store.finish_bn_grads()
 
-    def _train_step_cf(self, data):
-        """reference :185-205: dx tiled to both axes, the loss sees rhs = 0."""
+    def _forward_backward(self, data):
+        """reference :185-205: dx tiled to both axes (:192), the loss sees rhs = 0."""
         (bc, dx), y_true = data
         bc, dx, y_true = _as_device(bc, self.device), _as_device(dx, self.device), _as_device(y_true, self.device)
-        dx = dx.reshape(dx.shape[0], -1)
-        if dx.shape[1] == 1:
-            dx = dx.repeat(1, 2)                                                      # tf.tile(dx, [1, ndims]) (:192)
-        dx = dx.contiguous()
+        dx = _dx_tiled(dx).contiguous()
         pred = self.call([bc, dx, y_true.shape[2]], training=True)
         loss, dpred = self.loss_fn.value_and_grad(y_true, pred, torch.zeros_like(y_true), dx)
         self.backward(dpred)
-        if self.grad_sync is not None:
-            self.grad_sync(self.store.flat_g)
-        self.optimizer.apply_gradients()
-        return self._logs(loss, self.loss_fn.mse_metric(y_true, pred))
+        return loss, y_true, pred

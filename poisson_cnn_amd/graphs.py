@@ -137,33 +137,16 @@ class GraphedTrainStep(_Captured):
         inputs, y = example_data
         self.static_in = [_static(v, self.device) for v in inputs]
         self.static_y = _static(y, self.device)
-        opt = model.optimizer
-        real_apply, real_sync, real_metric = opt.apply_gradients, model.grad_sync, getattr(model, 'metric_sync', None)
-        snap = [(s, s.flat_w.clone(), s.flat_stats.clone()) for s in model.stores]
-        opt.apply_gradients = lambda *a, **k: None
-        model.grad_sync = None
-        model.metric_sync = None                                      # no collective inside the graph: the LOCAL loss / mse tensors are recorded
-        try:
-            self.logs = self._capture(lambda: model.train_step((self.static_in, self.static_y)))
-        finally:
-            opt.apply_gradients, model.grad_sync, model.metric_sync = real_apply, real_sync, real_metric
-            del opt.__dict__['apply_gradients']                       # back to the class's method (the instance attribute shadowed it)
-        for s, w, st in snap:                                         # warm-up and capture ran the step without an optimizer: only the BN statistics
-            s.flat_w.copy_(w); s.flat_stats.copy_(st)                 # of a training-mode-BN model could have moved
+        snap = [(s, s.flat_stats.clone()) for s in model.stores]
+        # model._local_step holds no optimizer and no collective: the LOCAL loss / mse tensors are recorded
+        loss, mse = self._capture(lambda: model._local_step((self.static_in, self.static_y)))
+        self.logs = {'loss': loss, 'mse': mse}
+        for s, st in snap:                                            # the warm-up and capture steps moved nothing but the BN statistics of a
+            s.flat_stats.copy_(st)                                    # training-mode-BN model
 
     def __call__(self, data):
         inputs, y = data
         _refill(self.static_in, inputs)
         _refill([self.static_y], [y])
         self.graph.replay()
-        m = self.model
-        if m.grad_sync is not None:
-            for s in m.stores:
-                m.grad_sync(s.flat_g)
-        m.optimizer.apply_gradients()
-        logs = dict(self.logs)                                        # static local loss / mse tensors of the replay
-        if getattr(m, 'metric_sync', None) is not None:               # data parallel: the global metrics, eagerly, as train_step reports them
-            logs['loss'], logs['mse'] = m.metric_sync(logs['loss'], logs['mse'])
-        if 'lr' in logs:
-            logs['lr'] = m.optimizer.learning_rate                    # the host scalar as it is NOW (ReduceLROnPlateau), not at capture time
-        return logs
+        return self.model._finish_step(self.logs['loss'], self.logs['mse'])     # eager, on the replay's static loss / mse tensors

@@ -24,7 +24,7 @@ import torch
 from . import layers as L
 from . import metalearning as M
 from . import ops
-from .models import _ModelBase, _as_device, process_normalizations, process_output_scaling_modes
+from .models import _ModelBase, _as_device, _dx_tiled, process_normalizations, process_output_scaling_modes
 from .utils import get_init_arguments_from_config
 
 _CONV_FIELDS = (['filters', 'kernel_sizes'], ['filters', 'kernel_size'])
@@ -43,16 +43,14 @@ def _bottleneck_fields(cfg, deconv):
 class _ChainModel(_ModelBase):
     """Input assembly, output scaling and the training step the two models share; subclasses provide _forward_body / _backward_body."""
 
-    def _init_common(self, ndims, data_format, input_normalization, output_scaling, use_batchnorm, bottleneck_upsampling, device, what):
+    def _init_common(self, ndims, data_format, input_normalization, output_scaling, use_batchnorm, bottleneck_upsampling, device):
         if ndims != 2:
             raise NotImplementedError('ndims = 2 only (the hot path of BASELINE.json)')
         if data_format not in ('channels_first', 'channels_last'):
             raise ValueError('data_format must be channels_first or channels_last')
         if bottleneck_upsampling not in ('deconv', 'multilinear'):
             raise ValueError('Invalid bottleneck block upsampling method')
-        if device is None and not torch.cuda.is_available():
-            raise RuntimeError('%s needs an AMD GPU: the HIP kernels are the only compute path' % what)
-        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        self._init_device(device)
         self.ndims, self.data_format = 2, data_format
         self.input_normalization = process_normalizations(input_normalization)       # kept, unused: the reference's normalisation is commented out
         self.output_scaling = process_output_scaling_modes(output_scaling)
@@ -62,7 +60,6 @@ class _ChainModel(_ModelBase):
         self.bottleneck_upsampling = bottleneck_upsampling
         self.store = L.ParamStore()
         self.ctx = L.Context()
-        self.optimizer = self.loss_fn = self.grad_sync = None
 
     # ------------------------------------------------------------------ scale_outputs (reference :197-214)
     def _scale_factors(self, rhs, max_domain_sizes):
@@ -80,9 +77,7 @@ class _ChainModel(_ModelBase):
         if rhs.dim() != 4 or rhs.shape[1] != 1:
             raise ValueError('rhs must have shape (N,1,H,W)')
         N, _, H, W = rhs.shape
-        dx = dx.reshape(N, -1)
-        if dx.shape[1] == 1:
-            dx = dx.repeat(1, 2)
+        dx = _dx_tiled(dx)
         if dx.shape[1] != 2:
             raise ValueError('dx must have shape (N,2)')
         self.store.refresh_bn()
@@ -119,20 +114,15 @@ class _ChainModel(_ModelBase):
         self.ctx.join()
         self.store.finish_bn_grads()
 
-    def _train_step_cf(self, data):
-        """reference :279-309: loss_fn(y_true, y_pred, rhs, dx), gradients, optimizer step; returns loss and mse."""
+    def _forward_backward(self, data):
+        """reference :279-309: loss_fn(y_true, y_pred, rhs, dx) and its gradients."""
         (rhs, dx), y_true = data
         rhs, dx, y_true = _as_device(rhs, self.device), _as_device(dx, self.device), _as_device(y_true, self.device)
-        dx = dx.reshape(dx.shape[0], -1)
-        if dx.shape[1] == 1:
-            dx = dx.repeat(1, 2)
+        dx = _dx_tiled(dx)
         pred = self.call([rhs, dx], training=True)
         loss, dpred = self.loss_fn.value_and_grad(y_true, pred, rhs, dx.contiguous())
         self.backward(dpred)
-        if self.grad_sync is not None:
-            self.grad_sync(self.store.flat_g)
-        self.optimizer.apply_gradients()
-        return self._logs(loss, self.loss_fn.mse_metric(y_true, pred))
+        return loss, y_true, pred
 
     def _finish_init(self, seed):
         self.store.finalize(self.device)
@@ -152,7 +142,7 @@ class Homogeneous_Poisson_NN_Metalearning(_ChainModel):
             raise ValueError('Provide a config for bottleneck blocks')
         if final_convolutions_config is None:
             raise ValueError('Provide a config for final convolutions')
-        self._init_common(ndims, data_format, input_normalization, output_scaling, use_batchnorm, bottleneck_upsampling, device, self.model_name)
+        self._init_common(ndims, data_format, input_normalization, output_scaling, use_batchnorm, bottleneck_upsampling, device)
         S, C, DF = self.store, self.ctx, 4                                           # dense_inp has 2 * ndims features
         shared = dict(store=S, ctx=C, dense_input_features=DF)
         # pre-bottleneck convolutions (:113-126): metalearning_conv('same') [+ BatchNormalization]
@@ -245,7 +235,7 @@ class Homogeneous_Poisson_NN(_ChainModel):
             raise ValueError('Provide a config for bottleneck blocks')
         if final_convolutions_config is None:
             raise ValueError('Provide a config for final convolutions')
-        self._init_common(ndims, data_format, input_normalization, output_scaling, use_batchnorm, bottleneck_upsampling, device, self.model_name)
+        self._init_common(ndims, data_format, input_normalization, output_scaling, use_batchnorm, bottleneck_upsampling, device)
         S, C = self.store, self.ctx
         C.enable_side_stream()
 

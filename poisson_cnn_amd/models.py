@@ -14,7 +14,7 @@ import torch
 
 from . import layers as L
 from . import ops
-from .utils import get_init_arguments_from_config
+from .utils import get_init_arguments_from_config, split_indices
 
 
 def process_normalizations(normalizations):
@@ -43,6 +43,27 @@ def _as_device(t, device):
     if isinstance(t, np.ndarray):
         t = torch.from_numpy(np.ascontiguousarray(t))
     return t.to(device=device, dtype=torch.float32).contiguous()
+
+
+# what the constructors' "needs an AMD GPU" error adds about device="cpu" (_ModelBase._init_device)
+_CPU_NOTE = ' (device="cpu" builds the parameter structure only)'
+_CPU_NOTE_RAISES = ' (device="cpu" builds the parameter structure only; calling the model will raise)'
+
+
+def _dx_column(dx):
+    """A user's dx -> the (N,1) column the Legacy-family models work with: the first column of whatever width was given."""
+    return dx.reshape(dx.shape[0], -1)[:, :1].contiguous()
+
+
+def _dx_pair(dx):
+    """That (N,1) column -> the (N,2) [dx, dx] which the loss and the Jacobi post-smoother take."""
+    return torch.cat([dx, dx], 1)
+
+
+def _dx_tiled(dx):
+    """The _ChainModel / metalearning family's dx: one column is repeated for both axes (tf.tile(dx, [1, ndims])), two columns are kept."""
+    dx = dx.reshape(dx.shape[0], -1)
+    return dx.repeat(1, 2) if dx.shape[1] == 1 else dx
 
 
 def _host_logs(logs):
@@ -110,8 +131,22 @@ class _Prefetcher:
 
 
 class _ModelBase:
-    """What the three model classes share: the Keras-style weight API over a ParamStore, compile(), fit()."""
+    """What every model class shares: the Keras-style weight API over its ParamStore(s), compile(), presize(), the training step and fit().
+
+    A model provides call(inp, training), backward(dpred) and ONE hook, _forward_backward(data) -> (loss, y_true, pred): channels-first data to the
+    device, call, loss_fn.value_and_grad, backward - the gradient lands in every store's flat_g; no optimizer, no collective.  train_step is
+    _local_step (that hook plus the mse metric: what graphs.GraphedTrainStep records) followed by _finish_step (gradient all-reduce, optimizer
+    update, logs: the only place in the package that runs this sequence)."""
     model_name = 'model'
+
+    def _init_device(self, device, cpu_note='', name=None):
+        """The constructors' prologue: self.device (`device`, or the current GPU - there must be one) and the attributes compile() and
+        parallel.DataParallel.attach fill in."""
+        if device is None and not torch.cuda.is_available():
+            raise RuntimeError('%s needs an AMD GPU: the HIP kernels are the only compute path%s' % (name or self.model_name, cpu_note))
+        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        self.optimizer = self.loss_fn = None
+        self.grad_sync = None    # set by parallel.DataParallel: called with each store's flat gradient bucket before the optimizer step
 
     # ------------------------------------------------------------------ weights
     @property
@@ -147,7 +182,7 @@ class _ModelBase:
             return save_tf_checkpoint(self, str(path))
         if save_format not in (None, 'npz'):
             raise ValueError('save_format must be None / "npz" / "tf" (HDF5 is not supported)')
-        np.savez(path, **{n.replace('/', '.'): w for n, w in zip(self.store.names, self.get_weights())})
+        np.savez(path, **{n.replace('/', '.'): w for n, w in zip(self.weight_names, self.get_weights())})
 
     def load_weights(self, path):
         path = str(path)
@@ -155,7 +190,7 @@ class _ModelBase:
             from .tf_checkpoint import load_tf_checkpoint
             return load_tf_checkpoint(self, path)
         with np.load(path if path.endswith('.npz') else path + '.npz') as z:
-            self.set_weights({n: z[n.replace('/', '.')] for n in self.store.names})
+            self.set_weights({n: z[n.replace('/', '.')] for n in self.weight_names})
 
     def count_params(self):
         return self.store.n_trainable
@@ -189,9 +224,29 @@ class _ModelBase:
     def __call__(self, inp, training=False):
         return self._cl(self.call([self._cf(v) for v in inp], training=training))
 
+    # ------------------------------------------------------------------ the training step
     def train_step(self, data):
+        return self._finish_step(*self._local_step(data))
+
+    def _local_step(self, data):
+        """The part of a step that is a fixed launch sequence on this process: forward, loss, backward (the gradient in every store's flat_g) and
+        the mse metric -> the device scalars (loss, mse) of the LOCAL batch."""
         inputs, y_true = data
-        return self._train_step_cf(([self._cf(v) for v in inputs], self._cf(y_true)))
+        loss, y_true, pred = self._forward_backward(([self._cf(v) for v in inputs], self._cf(y_true)))
+        return loss, self.loss_fn.mse_metric(y_true, pred)
+
+    def _finish_step(self, loss, mse):
+        """Gradient all-reduce (data parallel), the optimizer update, and the dict train_step returns."""
+        if self.grad_sync is not None:
+            for store in self.stores:
+                self.grad_sync(store.flat_g)
+        extra = self._extra_logs()
+        self.optimizer.apply_gradients()
+        return self._logs(loss, mse, extra)
+
+    def _extra_logs(self):
+        """Further train_step entries, computed on the synchronised gradient in front of the update (UNetModel: its gradient norm)."""
+        return {}
 
     @property
     def stores(self):
@@ -226,18 +281,18 @@ class _ModelBase:
         torch.cuda.synchronize()
 
     def _dummy_batch(self, shape):
-        raise NotImplementedError('%s: presize() is implemented for Homogeneous_Poisson_NN_Legacy' % type(self).__name__)
+        raise NotImplementedError('%s: presize() needs a _dummy_batch(shape), which this model does not have' % type(self).__name__)
 
     metric_sync = None   # set by parallel.DataParallel.attach: (loss, mse) -> their GLOBAL values (one tiny all-reduce)
 
-    def _logs(self, loss, mse):
-        """What train_step returns.  Under data parallelism each rank's loss is its share of the global-batch loss (already divided by
-        the global batch size, losses/loss_wrapper.py:46-49) and its mse the mean over its own samples; callbacks (ReduceLROnPlateau,
+    def _logs(self, loss, mse, extra):
+        """What train_step returns (`extra`: the model's own entries, placed before 'lr').
+        Under data parallelism each rank's loss is its share of the global-batch loss (already divided by the global batch size, losses/loss_wrapper.py:46-49) and its mse the mean over its own samples; callbacks (ReduceLROnPlateau,
         TerminateOnNaN, ModelCheckpoint) must see the same GLOBAL numbers on every rank or the replicas' learning rates / stop decisions
         diverge - MirroredStrategy reduces the per-replica results the same way before Keras hands them to callbacks."""
         if self.metric_sync is not None:
             loss, mse = self.metric_sync(loss, mse)
-        return {'loss': loss, 'mse': mse, 'lr': self.optimizer.learning_rate}
+        return {'loss': loss, 'mse': mse, **extra, 'lr': self.optimizer.learning_rate}
 
     def fit(self, dataset, epochs=1, callbacks=(), verbose=1, steps_per_epoch=None):
         """Minimal Keras-style loop over a Sequence-like dataset (`__len__`, `__getitem__` -> ([rhs, dx], soln)).
@@ -312,10 +367,7 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
             raise ValueError('Provide a config for final convolutions')
         if bc_type.lower() not in ('dirichlet', 'neumann'):
             raise ValueError('bc_type can only be neumann or dirichlet.')
-        if device is None and not torch.cuda.is_available():
-            raise RuntimeError('Homogeneous_Poisson_NN_Legacy needs an AMD GPU: the HIP kernels are the only compute path '
-                               '(device="cpu" builds the parameter structure only; calling the model will raise)')
-        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        self._init_device(device, _CPU_NOTE_RAISES)
         self.ndims = 2
         self.data_format = data_format
         self.gradient_accumulation_steps = gradient_accumulation_steps
@@ -394,9 +446,6 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
         self.scaling = L.Scaling(S, C, 'scaling', **scaling_config) if use_scaling else None
         S.finalize(self.device)
         S.initialize(seed)
-        self.optimizer = None
-        self.loss_fn = None
-        self.grad_sync = None    # set by parallel.DataParallel: called with the flat gradient bucket before the optimizer step
         self._acc = None
 
     COARSE_FACTOR = int(os.environ.get('PCNN_COARSE_FACTOR', '2'))     # bottleneck branches from this down-sampling factor on (default: all of them) run their
@@ -422,7 +471,7 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
         dx = _as_device(dx, self.device)
         if rhs.dim() != 4 or rhs.shape[1] != 1:
             raise ValueError('rhs must have shape (N,1,H,W)')
-        dx = dx.reshape(dx.shape[0], -1)[:, :1].contiguous()
+        dx = _dx_column(dx)
         N, _, H, W = rhs.shape
         S = self.store
         S.refresh_bn()
@@ -512,8 +561,7 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
             x = self.scaling.forward(x, rhs_hw.view(N, H, W, 1), training=training)
         x = ops.bc_ring_fwd(x, self.neumann)                      # :251
         if self.postsmoother is not None:
-            dx2 = torch.cat([dx, dx], 1).contiguous()
-            x = self.postsmoother.forward(x, rhs_hw.view(N, H, W, 1), dx2, training=training)
+            x = self.postsmoother.forward(x, rhs_hw.view(N, H, W, 1), _dx_pair(dx), training=training)
         return x.view(N, 1, H, W)
 
     # ------------------------------------------------------------------ backward
@@ -601,7 +649,7 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
     # ------------------------------------------------------------------ training (reference :259-296)
     def _loss_and_grads(self, rhs, dx, y_true):
         pred = self.call([rhs, dx], training=True)
-        loss, dpred = self.loss_fn.value_and_grad(y_true, pred, rhs, torch.cat([dx, dx], 1))
+        loss, dpred = self.loss_fn.value_and_grad(y_true, pred, rhs, _dx_pair(dx))
         self.backward(dpred)
         return loss, pred
 
@@ -611,24 +659,16 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
         rhs = (torch.rand((N, 1, H, W), generator=g) * 2 - 1).to(self.device)
         return (rhs, torch.full((N, 1), 0.02, device=self.device)), (torch.rand((N, 1, H, W), generator=g) * 0.1).to(self.device)
 
-    def _train_step_cf(self, data):
-        loss, gt, pred = self._forward_backward(data)
-        if self.grad_sync is not None:
-            self.grad_sync(self.store.flat_g)
-        self.optimizer.apply_gradients()
-        return self._logs(loss, self.loss_fn.mse_metric(gt, pred))
-
     def _forward_backward(self, data):
         """forward, loss and backward of one batch (with the reference's gradient accumulation, :275-289): store.flat_g holds the gradient."""
         (rhs, dx), y_true = data
         rhs, dx, y_true = _as_device(rhs, self.device), _as_device(dx, self.device), _as_device(y_true, self.device)
-        dx = dx.reshape(dx.shape[0], -1)[:, :1].contiguous()
+        dx = _dx_column(dx)
         S = self.store
         if self.gradient_accumulation_steps is None:
             loss, pred = self._loss_and_grads(rhs, dx, y_true)
             gt = y_true
         else:
-            from .utils import split_indices
             steps = int(self.gradient_accumulation_steps)
             idx = split_indices(rhs.shape[0], steps)
             if self._acc is None:
@@ -643,7 +683,33 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
 
 
 # =====================================================================================================================
-class Dirichlet_BC_NN_Legacy_2(_ModelBase):
+class _BoundaryTables:
+    """The two input-independent device tables of the boundary models (they set spp_levels, x_dir_nmodes, device and the caches _bins, _sinh)."""
+
+    def _bin_table(self, Lh):
+        """The spatial pyramid's bins over a boundary of Lh points, as [y0, y1, x0, x1] rows."""
+        if Lh not in self._bins:
+            bins = []
+            for lv in self.spp_levels:
+                ix = split_indices(Lh, lv)
+                if (np.diff(ix) <= 0).any():
+                    raise ValueError('boundary too short for the spatial pyramid: %d bins over %d points' % (lv, Lh))
+                bins += [[0, 1, ix[b], ix[b + 1]] for b in range(lv)]
+            self._bins[Lh] = torch.tensor(np.array(bins, dtype=np.int32), device=self.device)
+        return self._bins[Lh]
+
+    def _sinh_table(self, X):
+        """build_series_x_dir_components (Dirichlet_BC_NN_Legacy.py:106-111, Dirichlet_BC_NN_Metalearning.py:103-110): input-independent, so
+        tabulated on the host (fp64, rounded once)."""
+        if X not in self._sinh:
+            xbar = np.linspace(0.0, 1.0, X)
+            v = np.sinh(np.outer(np.arange(1, self.x_dir_nmodes + 1, dtype=np.float64), np.pi * (xbar - 1.0)))
+            v = v / np.abs(v).max(axis=1, keepdims=True)
+            self._sinh[X] = torch.from_numpy(v.astype(np.float32)).to(self.device).contiguous()
+        return self._sinh[X]
+
+
+class Dirichlet_BC_NN_Legacy_2(_BoundaryTables, _ModelBase):
     """Drop-in for poisson_CNN/models/Dirichlet_BC_NN_Legacy.py:14-187: same constructor kwargs (the "model" section of
     experiments/dbcnn.json loads unchanged), `model([bc (N,1,L), dx (N,1), x_output_resolution]) -> (N,1,X,L)`,
     `train_step(((bc, dx), y))`.  1-D tensors are NHWC (N,1,L,C) inside; Conv1D kernels are stored as (1,k,Cin,Cout)."""
@@ -661,10 +727,7 @@ class Dirichlet_BC_NN_Legacy_2(_ModelBase):
             raise ValueError('Provide a config for the domain convolutions.')
         if domain_info_mlp_config is None:
             raise ValueError('Provide a config for the domain info MLP.')
-        if device is None and not torch.cuda.is_available():
-            raise RuntimeError('Dirichlet_BC_NN_Legacy_2 needs an AMD GPU: the HIP kernels are the only compute path '
-                               '(device="cpu" builds the parameter structure only; calling the model will raise)')
-        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        self._init_device(device, _CPU_NOTE_RAISES)
         self.ndims, self.data_format, self.use_batchnorm = 2, data_format, use_batchnorm
         assert boundary_conv_config['filters'][-1] == domain_info_mlp_config['units'][-1]       # reference :39
         self.x_dir_nmodes = M = domain_info_mlp_config['units'][-1]
@@ -722,29 +785,7 @@ class Dirichlet_BC_NN_Legacy_2(_ModelBase):
         self.postsmoother = L.JacobiIterationLayer(postsmoother_iterations) if postsmoother_iterations > 0 else None
         S.finalize(self.device)
         S.initialize(seed)
-        self.optimizer = self.loss_fn = self.grad_sync = None
         self._bins, self._sinh = {}, {}
-
-    def _bin_table(self, Lh):
-        if Lh not in self._bins:
-            from .utils import split_indices
-            bins = []
-            for lv in self.spp_levels:
-                ix = split_indices(Lh, lv)
-                if (np.diff(ix) <= 0).any():
-                    raise ValueError('boundary too short for the spatial pyramid: %d bins over %d points' % (lv, Lh))
-                bins += [[0, 1, ix[b], ix[b + 1]] for b in range(lv)]
-            self._bins[Lh] = torch.tensor(np.array(bins, dtype=np.int32), device=self.device)
-        return self._bins[Lh]
-
-    def _sinh_table(self, X):
-        """build_series_x_dir_components (:106-111): input-independent, so tabulated on the host (fp64, rounded once)."""
-        if X not in self._sinh:
-            xbar = np.linspace(0.0, 1.0, X)
-            v = np.sinh(np.outer(np.arange(1, self.x_dir_nmodes + 1, dtype=np.float64), np.pi * (xbar - 1.0)))
-            v = v / np.abs(v).max(axis=1, keepdims=True)
-            self._sinh[X] = torch.from_numpy(v.astype(np.float32)).to(self.device).contiguous()
-        return self._sinh[X]
 
     def call(self, inp, training=False):
         """reference :126-170."""
@@ -753,7 +794,7 @@ class Dirichlet_BC_NN_Legacy_2(_ModelBase):
         bc, dx = _as_device(bc, self.device), _as_device(dx, self.device)
         if bc.dim() != 3 or bc.shape[1] != 1:
             raise ValueError('bc must have shape (N,1,L)')
-        dx = dx.reshape(dx.shape[0], -1)[:, :1].contiguous()
+        dx = _dx_column(dx)
         N, _, Lh = bc.shape
         S = self.store
         S.refresh_bn()
@@ -786,8 +827,7 @@ class Dirichlet_BC_NN_Legacy_2(_ModelBase):
         if training:
             self._saved = {'bc_conv': bc_conv, 'mlp_out': d, 'sinh': sh, 'pre': pre, 'bins': bins, 'spp_arg': spp_arg, 'shape': (N, X, Lh)}
         if self.postsmoother is not None:
-            dx2 = torch.cat([dx, dx], 1).contiguous()
-            out = self.postsmoother.forward(out.view(N, X, Lh, 1), torch.zeros_like(out).view(N, X, Lh, 1), dx2, training=training).view(N, X, Lh)
+            out = self.postsmoother.forward(out.view(N, X, Lh, 1), torch.zeros_like(out).view(N, X, Lh, 1), _dx_pair(dx), training=training).view(N, X, Lh)
         return out.view(N, 1, X, Lh)
 
     def backward(self, dpred):
@@ -817,19 +857,15 @@ class Dirichlet_BC_NN_Legacy_2(_ModelBase):
         self.ctx.join()                                            # weight gradients of the side stream
         self.store.finish_bn_grads()
 
-    def _train_step_cf(self, data):
+    def _forward_backward(self, data):
         """reference :172-187: the loss sees rhs = 0 and dx repeated for both axes."""
         (bc, dx), y_true = data
         bc, dx, y_true = _as_device(bc, self.device), _as_device(dx, self.device), _as_device(y_true, self.device)
-        dx = dx.reshape(dx.shape[0], -1)[:, :1].contiguous()
+        dx = _dx_column(dx)
         pred = self.call([bc, dx, y_true.shape[2]], training=True)
-        loss, dpred = self.loss_fn.value_and_grad(y_true, pred, torch.zeros_like(y_true), torch.cat([dx, dx], 1))
+        loss, dpred = self.loss_fn.value_and_grad(y_true, pred, torch.zeros_like(y_true), _dx_pair(dx))
         self.backward(dpred)
-        if self.grad_sync is not None:
-            self.grad_sync(self.store.flat_g)
-        self.optimizer.apply_gradients()
-        return self._logs(loss, self.loss_fn.mse_metric(y_true, pred))
-
+        return loss, y_true, pred
 
     # ------------------------------------------------------------------ used by Poisson_CNN_Legacy: several calls per step share the weights
     def _stateful(self):
@@ -862,9 +898,8 @@ class Poisson_CNN_Legacy(_ModelBase):
             # the reference constructor dereferences an unimported module name here (Poisson_CNN_Legacy.py:11) and raises NameError
             raise NotImplementedError('Poisson_CNN_Legacy: jacobi_iterations > 0 is unreachable in the reference (NameError at construction)')
         self.hpnn, self.dbcnn = hpnn, dbcnn
-        self.device = hpnn.device
+        self._init_device(hpnn.device)
         self.data_format = getattr(hpnn, 'data_format', 'channels_first')
-        self.optimizer = self.loss_fn = self.grad_sync = None
 
     # weights: the two sub-models' lists, hpnn first (Keras tracks attributes in assignment order)
     @property
@@ -891,19 +926,6 @@ class Poisson_CNN_Legacy(_ModelBase):
             self.hpnn.set_weights(list(weights[:k]))
             self.dbcnn.set_weights(list(weights[k:]))
 
-    def save_weights(self, path, save_format=None):
-        if save_format in ('tf', 'tensorflow'):
-            from .tf_checkpoint import save_tf_checkpoint
-            return save_tf_checkpoint(self, str(path))
-        np.savez(path, **{n.replace('/', '.'): w for n, w in zip(self.weight_names, self.get_weights())})
-
-    def load_weights(self, path):
-        if os.path.exists(str(path) + '.index'):
-            from .tf_checkpoint import load_tf_checkpoint
-            return load_tf_checkpoint(self, str(path))
-        with np.load(path if str(path).endswith('.npz') else str(path) + '.npz') as z:
-            self.set_weights({n: z[n.replace('/', '.')] for n in self.weight_names})
-
     def count_params(self):
         return self.hpnn.count_params() + self.dbcnn.count_params()
 
@@ -918,7 +940,7 @@ class Poisson_CNN_Legacy(_ModelBase):
 
     def call(self, inp, training=False):
         rhs, left, top, right, bottom, dx = [_as_device(v, self.device) for v in inp]
-        dx = dx.reshape(dx.shape[0], -1)[:, :1].contiguous()
+        dx = _dx_column(dx)
         N, _, H, W = rhs.shape
         rhs_n, rhs_f = ops.set_max_magnitude_fwd(rhs.reshape(N, H * W), 1.0)                 # :24
         edges = {}
@@ -965,17 +987,12 @@ class Poisson_CNN_Legacy(_ModelBase):
             else:
                 ops.axpby_flat(1.0, acc, 1.0, g)                                              # the two passes share the weights
 
-    def _train_step_cf(self, data):
+    def _forward_backward(self, data):
         """reference :56-66."""
         inputs, y_true = data
         inputs = [_as_device(v, self.device) for v in inputs]
         y_true = _as_device(y_true, self.device)
-        dx = inputs[5].reshape(inputs[5].shape[0], -1)[:, :1].contiguous()
         pred = self.call(inputs, training=True)
-        loss, dpred = self.loss_fn.value_and_grad(y_true, pred, inputs[0], torch.cat([dx, dx], 1))
+        loss, dpred = self.loss_fn.value_and_grad(y_true, pred, inputs[0], _dx_pair(_dx_column(inputs[5])))
         self.backward(dpred)
-        if self.grad_sync is not None:
-            for s in self.stores:
-                self.grad_sync(s.flat_g)
-        self.optimizer.apply_gradients()
-        return self._logs(loss, self.loss_fn.mse_metric(y_true, pred))
+        return loss, y_true, pred

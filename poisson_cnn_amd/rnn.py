@@ -19,7 +19,7 @@ import torch
 
 from . import layers as L
 from . import ops
-from .models import _ModelBase, _as_device
+from .models import _CPU_NOTE, _ModelBase, _as_device, _dx_column, _dx_pair
 
 _RNN_ACTS = {'tanh': 'tanh', 'tf.nn.tanh': 'tanh', 'tf.math.tanh': 'tanh', 'tf.keras.activations.tanh': 'tanh',
              'sigmoid': 'sigmoid', 'tf.nn.sigmoid': 'sigmoid', 'tf.math.sigmoid': 'sigmoid', 'tf.keras.activations.sigmoid': 'sigmoid',
@@ -107,9 +107,7 @@ class Dirichlet_BC_RNN(_ModelBase):
             inits[k] = v.lower()
         if resize_method not in ops.RESIZE:
             raise ValueError('resize_method must be one of %s' % sorted(ops.RESIZE))
-        if device is None and not torch.cuda.is_available():
-            raise RuntimeError('Dirichlet_BC_RNN needs an AMD GPU: the HIP kernels are the only compute path (device="cpu" builds the parameter structure only)')
-        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        self._init_device(device, _CPU_NOTE)
         self.data_format, self.resize_method = data_format, resize_method
         self.G = G = ops.RNN_GATES[self.cell]
         self.store = S = L.ParamStore()
@@ -136,7 +134,6 @@ class Dirichlet_BC_RNN(_ModelBase):
                 if self.cell == 'lstm' and self.unit_forget_bias:              # Keras: [bias_initializer(u) | ones(u) | bias_initializer(2u)]
                     b[u:2 * u] = 1.0
                 S.w[bn].copy_(torch.from_numpy(b))
-        self.optimizer = self.loss_fn = self.grad_sync = None
         self._arena = None
         self._saved = None
 
@@ -264,15 +261,8 @@ class Dirichlet_BC_RNN(_ModelBase):
     def _forward_backward(self, data):
         (bc, dx), y_true = data
         bc, dx, y_true = _as_device(bc, self.device), _as_device(dx, self.device), _as_device(y_true, self.device)
-        dx = dx.reshape(dx.shape[0], -1)[:, :1].contiguous()
+        dx = _dx_column(dx)
         pred = self.call([bc, dx, y_true.shape[2]], training=True)                # x_output_resolution from the target's shape (:64)
-        loss, dpred = self.loss_fn.value_and_grad(y_true, pred, torch.zeros_like(y_true), torch.cat([dx, dx], 1))
+        loss, dpred = self.loss_fn.value_and_grad(y_true, pred, torch.zeros_like(y_true), _dx_pair(dx))
         self.backward(dpred)
         return loss, y_true, pred
-
-    def _train_step_cf(self, data):
-        loss, y_true, pred = self._forward_backward(data)
-        if self.grad_sync is not None:
-            self.grad_sync(self.store.flat_g)
-        self.optimizer.apply_gradients()
-        return self._logs(loss, self.loss_fn.mse_metric(y_true, pred))

@@ -11,7 +11,7 @@ import torch
 
 from . import layers as L
 from . import ops
-from .models import _ModelBase, _as_device
+from .models import _CPU_NOTE, _ModelBase, _as_device, _dx_column, _dx_pair
 from .utils import canonical_activation
 
 
@@ -40,9 +40,7 @@ class UNetModel(_ModelBase):
             raise ValueError('UNet: layer_depth must be >= 2')
         if canonical_activation(final_activation) != 'linear':
             raise NotImplementedError('UNet: final_activation other than linear is not implemented')
-        if device is None and not torch.cuda.is_available():
-            raise RuntimeError('UNet needs an AMD GPU: the HIP kernels are the only compute path (device="cpu" builds the parameter structure only)')
-        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        self._init_device(device, _CPU_NOTE, name='UNet')
         self.nx, self.ny = nx, ny
         self.in_channels, self.out_channels = int(in_channels), int(out_channels)
         self.depth, self.root, self.k, self.pool = int(layer_depth), int(filters_root), int(kernel_size), int(pool_size)
@@ -101,9 +99,6 @@ class UNetModel(_ModelBase):
                 v[bad] = rng.standard_normal(int(bad.sum()))
                 bad = np.abs(v) > 2.0
             S.w[name].copy_(torch.from_numpy((v * std).astype(np.float32).reshape(tuple(shape))))
-        self.optimizer = None
-        self.loss_fn = None
-        self.grad_sync = None
         self._acc = None
         self._saved = None
         self._drop_calls = 0
@@ -276,9 +271,8 @@ class UNetModel(_ModelBase):
         concat([dx, dx], 1)) and its gradient into store.flat_g."""
         (rhs, dx), y_true = data
         rhs, dx, y_true = _as_device(rhs, self.device), _as_device(dx, self.device), _as_device(y_true, self.device)
-        dx = dx.reshape(dx.shape[0], -1)[:, :1].contiguous()
         pred = self.call(rhs, training=False)
-        loss, dpred = self.loss_fn.value_and_grad(y_true, pred, rhs, torch.cat([dx, dx], 1))
+        loss, dpred = self.loss_fn.value_and_grad(y_true, pred, rhs, _dx_pair(_dx_column(dx)))
         self.backward(dpred, need_dx=False)
         return loss, y_true, pred
 
@@ -287,17 +281,8 @@ class UNetModel(_ModelBase):
         sums = torch.stack([self.store.g[n].double().square().sum() for n in self.store.trainable_names()])
         return sums.mean().sqrt().float()
 
-    def _train_step_cf(self, data):
-        loss, gt, pred = self._forward_backward(data)
-        if self.grad_sync is not None:
-            self.grad_sync(self.store.flat_g)
-        gl2 = self.grad_l2_norm()
-        self.optimizer.apply_gradients()
-        logs = self._logs(loss, self.loss_fn.mse_metric(gt, pred))
-        return {'loss': logs['loss'], 'mse': logs['mse'], 'grad L2 norm': gl2, 'lr': logs['lr']}
-
-    def train_step(self, data):
-        return self._train_step_cf(data)
+    def _extra_logs(self):
+        return {'grad L2 norm': self.grad_l2_norm()}
 
 
 def UNet(nx=None, ny=None, in_channels=1, out_channels=1, layer_depth=5, filters_root=64, kernel_size=3, pool_size=2, dropout_rate=0.5,
