@@ -700,10 +700,6 @@ __global__ __launch_bounds__(256) void spec_post_bias64_kernel(const float* __re
 
 }  // namespace
 
-void launch_post_bias64(pcnn_handle h, const float* bsum, int nblocks, int C, float* dbias) {
-  hipLaunchKernelGGL(spec_post_bias64_kernel, dim3((unsigned)C), dim3(256), 0, h->stream, bsum, nblocks, dbias);
-}
-
 // ------------------------------------------------------------------------------------------------------------------ host side
 void build_tables64(float* tab, int* slots) {
   const double tp = 2.0 * M_PI / T;
@@ -783,6 +779,8 @@ void build_tables64(float* tab, int* slots) {
     for (int fy = 0; fy < T; ++fy) put(2 * T + 2 * T * (fx - 1) + fy, 2 * T + 2 * T * (fx - 1) + T + fy, 0);
 }
 
+namespace {
+
 void launch_fwd64(pcnn_handle h, FwdParams p, int ntile) {
   p.ntile = ntile;
   p.cpt = 0;
@@ -795,31 +793,14 @@ void launch_fwd64(pcnn_handle h, FwdParams p, int ntile) {
   // runs 0.393 -> 0.415 ms).  PCNN_FWD64_RADIX = 2 | 4 forces one form for both (tests, A/B timing).
   const int forced = getenv("PCNN_FWD64_RADIX") ? atoi(getenv("PCNN_FWD64_RADIX")) : 0;
   const int radix = forced ? forced : (masked ? 2 : 4);
-  if (radix == 4) {
-    const size_t lds4 = (2 * SB_FLOATS + 3 * 4096) * sizeof(float);
-    if (masked) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(spec64_fwd4_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4);
-      hipLaunchKernelGGL(spec64_fwd4_kernel<true>, dim3(grid), dim3(512), lds4, h->stream, p);
-    } else {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(spec64_fwd4_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4);
-      hipLaunchKernelGGL(spec64_fwd4_kernel<false>, dim3(grid), dim3(512), lds4, h->stream, p);
-    }
-    return;
-  }
-  const size_t lds = (2 * SB_FLOATS + 6144) * sizeof(float);
-  if (masked) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(spec64_fwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(spec64_fwd_kernel<true>, dim3(grid), dim3(512), lds, h->stream, p);
-  } else {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(spec64_fwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(spec64_fwd_kernel<false>, dim3(grid), dim3(512), lds, h->stream, p);
-  }
-}
-
-template <bool TANH, bool RES>
-static void launch_inv64_t(pcnn_handle h, const InvParams& p, unsigned grid, int vycap, size_t lds) {
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(spec64_inv_kernel<TANH, RES>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((spec64_inv_kernel<TANH, RES>), dim3(grid), dim3(512), lds, h->stream, p, vycap);
+  const size_t lds = (2 * SB_FLOATS + (radix == 4 ? 3 * 4096 : 6144)) * sizeof(float);
+  auto launch = [&](auto kernel) {
+    set_lds(kernel, lds);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), lds, h->stream, p);
+  };
+  if (radix == 4) { if (masked) launch(spec64_fwd4_kernel<true>); else launch(spec64_fwd4_kernel<false>); }
+  else if (masked) launch(spec64_fwd_kernel<true>);
+  else launch(spec64_fwd_kernel<false>);
 }
 
 void launch_inv64(pcnn_handle h, InvParams p, int ntile) {
@@ -832,24 +813,23 @@ void launch_inv64(pcnn_handle h, InvParams p, int ntile) {
   const int ntg = ntile * p.groups;
   const unsigned grid = (unsigned)std::min((2 * ((ntg + 7) & ~7) + 15) & ~15, 256);
   const size_t lds = (8192 + 2 * (size_t)vycap * 256) * sizeof(float);
-  if (p.gact) {                                                  // data gradient + the producer's activation backward (linear conv epilogue)
-    p.alpha = 1.f;
-    p.galpha = p.gmode == PCNN_ACT_LINEAR ? 1.f : (p.gmode == PCNN_ACT_RELU ? 0.f : p.galpha);
-    if (p.res) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(spec64_inv_kernel<false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL((spec64_inv_kernel<false, true, true>), dim3(grid), dim3(512), lds, h->stream, p, vycap);
-    } else {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(spec64_inv_kernel<false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL((spec64_inv_kernel<false, false, true>), dim3(grid), dim3(512), lds, h->stream, p, vycap);
-    }
-    return;
-  }
-  if (p.act == PCNN_ACT_TANH) {
-    if (p.res) launch_inv64_t<true, true>(h, p, grid, vycap, lds); else launch_inv64_t<true, false>(h, p, grid, vycap, lds);
-  } else {
-    p.alpha = p.act == PCNN_ACT_LINEAR ? 1.f : (p.act == PCNN_ACT_RELU ? 0.f : p.alpha);
-    if (p.res) launch_inv64_t<false, true>(h, p, grid, vycap, lds); else launch_inv64_t<false, false>(h, p, grid, vycap, lds);
-  }
+  dispatch_epilogue(p, [&](auto TANH, auto RES, auto POST, const InvParams& q) {
+    constexpr auto kernel = spec64_inv_kernel<TANH.value, RES.value, POST.value>;
+    set_lds(kernel, lds);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), lds, h->stream, q, vycap);
+  });
 }
+
+// POST at 64 points: bsum holds 4 floats per (workgroup, wave, lane)
+void launch_post_bias64(pcnn_handle h, const float* bsum, int, int, int C, float* dbias) {
+  hipLaunchKernelGGL(spec_post_bias64_kernel, dim3((unsigned)C), dim3(256), 0, h->stream, bsum, POST_BLOCKS, dbias);
+}
+
+}  // namespace
+
+#ifndef __HIP_DEVICE_COMPILE__       // host data (launcher addresses): not for the device pass
+const Xform XFORM_MFMA64 = {PCNN_XFORM_MFMA, T, ROWS, ROWS / 2, T, O_TAB64, O_SLOTS64, launch_fwd64, launch_inv64, launch_post_bias64, nullptr,
+                            POST_BLOCKS * 8 * 4, nullptr, nullptr};
+#endif
 
 }  // namespace pcnn_spec

@@ -5,6 +5,7 @@
 // tools/spectral_model64.py).  T*T/2 mixing slots.
 #pragma once
 #include "pcnn_internal.h"
+#include <type_traits>
 
 namespace pcnn_spec {
 
@@ -79,23 +80,24 @@ __device__ __forceinline__ void quad_transpose(float& r0, float& r1, float& r2, 
 }
 
 struct FwdParams {
-  const float* x; float* sp; const float* tab;
-  int H, W, C, ld, groups, cstride, cvalid;
-  int tiles_x, tiles_y, tile0, ntile;
-  int Vy, Vx, oy, ox, pad_mode; float pad_value;
-  int ylim, xlim;        // the window holds values only in its first ylim x xlim entries (gradient / input tiles of the backward pass)
-  int ext_y, ext_x;      // ... and only where the tile grid coordinate (ty Vy + r, tx Vx + c) lies inside ext_y x ext_x
-  int pack, cpt, tgx;    // layers of <= 16 channels: `pack` x-adjacent tiles share the 32 lanes (lane = cpt * tile + channel, cpt = 32 / pack);
-                         // tgx = tile groups per tile row; an "item" is then a tile GROUP and tile0 / ntile count groups
+  const float* x = nullptr; float* sp = nullptr; const float* tab = nullptr;
+  int H = 0, W = 0, C = 0, ld = 0, groups = 1, cstride = 32, cvalid = 32;
+  int tiles_x = 1, tiles_y = 1, tile0 = 0, ntile = 1;
+  int Vy = 0, Vx = 0, oy = 0, ox = 0, pad_mode = PCNN_PAD_CONSTANT; float pad_value = 0.f;
+  int ylim = 0, xlim = 0;                    // the window holds values only in its first ylim x xlim entries (gradient / input tiles of the backward pass)
+  int ext_y = 1 << 30, ext_x = 1 << 30;      // ... and only where the tile grid coordinate (ty Vy + r, tx Vx + c) lies inside ext_y x ext_x
+  int pack = 1, cpt = 32, tgx = 1;           // layers of <= 16 channels: `pack` x-adjacent tiles share the 32 lanes (lane = cpt * tile + channel, cpt = 32 / pack);
+                                             // tgx = tile groups per tile row; an "item" is then a tile GROUP and tile0 / ntile count groups
 };
 
 struct InvParams {
-  const float* sp; const float* tab;
-  float* y; const float* bias; const float* bn_scale; const float* bn_shift; const float* res; float* act_out; unsigned* absmax;
-  int Ho, Wo, C, ldy, ld_res, ld_act, groups, cstride, cvalid, act; float alpha;
-  int tiles_x, tiles_y, tile0, ntile, Vy, Vx;
-  int flip;              // store output pixel (y, x) at (Ho-1-y, Wo-1-x): the input-partitioned weight gradient comes out tap-reversed
-  int pack, cpt, tgx;    // tile packing, as in FwdParams (flip requires pack == 1)
+  const float* sp = nullptr; const float* tab = nullptr;
+  float* y = nullptr; const float* bias = nullptr; const float* bn_scale = nullptr; const float* bn_shift = nullptr; const float* res = nullptr;
+  float* act_out = nullptr; unsigned* absmax = nullptr;
+  int Ho = 0, Wo = 0, C = 0, ldy = 0, ld_res = 0, ld_act = 0, groups = 1, cstride = 32, cvalid = 32, act = PCNN_ACT_LINEAR; float alpha = 0.f;
+  int tiles_x = 1, tiles_y = 1, tile0 = 0, ntile = 1, Vy = 0, Vx = 0;
+  int flip = 0;                    // store output pixel (y, x) at (Ho-1-y, Wo-1-x): the input-partitioned weight gradient comes out tap-reversed
+  int pack = 1, cpt = 32, tgx = 1; // tile packing, as in FwdParams (flip requires pack == 1)
   // POST (data-gradient launches only): the activation backward of the layer that PRODUCED this convolution's input, applied to the gradient
   // before it is stored - v = (conv + residual); y2 (if given) receives v, y receives v * act'(gact) where gact is that layer's saved
   // activation output, and every lane adds what it stored into bsum[(block 8 + wave) 64 + lane] (the bias gradient's partial sums)
@@ -103,23 +105,55 @@ struct InvParams {
   int ld_gact = 0, ld_y2 = 0, gmode = 0; float galpha = 1.f;
 };
 
-// 64-point tiles (spectral64.hip): table block, slots are built by build_tables64; the launchers take the same parameter blocks (pack = 1)
-constexpr int TAB64_FLOATS = 32768;
-void build_tables64(float* tab, int* slots);                 // TAB64_FLOATS floats, 2048 x int4 slots
-void launch_fwd64(pcnn_handle h, FwdParams p, int ntile);     // p.tab: the 64-point table block
-void launch_inv64(pcnn_handle h, InvParams p, int ntile);
-void launch_post_bias64(pcnn_handle h, const float* bsum, int nblocks, int C, float* dbias);   // POST at 64 points: bsum holds 4 floats per (block, wave, lane)
+// ---- host side shared by the four transform back ends (matrix-core / FFT family x 32 / 64 points)
+// workspace header: the constant tables of both tile sizes, then two slot tables per tile size (the canonical row order of the matrix-core family and
+// the FFT family's interleaved order, above); the per-call regions follow at O_REST
+constexpr int TAB32_FLOATS = 7168, TAB64_FLOATS = 32768;       // spectral_conv.hip build_tables / spectral64.hip build_tables64
+constexpr size_t O_TAB32 = 0, O_SLOTS32 = O_TAB32 + ((TAB32_FLOATS * 4 + 255) & ~255), O_TAB64 = O_SLOTS32 + 512 * 16,
+                 O_SLOTS64 = O_TAB64 + TAB64_FLOATS * 4, O_SLOTS32F = O_SLOTS64 + 2048 * 16, O_SLOTS64F = O_SLOTS32F + 512 * 16, O_REST = O_SLOTS64F + 2048 * 16;
+static_assert(O_REST % 256 == 0, "workspace header alignment");
+void build_tables64(float* tab, int* slots);                 // TAB64_FLOATS floats, 2048 x int4 slots (canonical order)
 
-// 32-point tiles as in-register FFTs on the vector ALUs (spectral_fft.hip); same parameter blocks, same spectrum layout.  16 waves per workgroup:
-// the POST partial sums hold one float per (block, wave, lane) with FFT_WAVES waves per block
-constexpr int FFT_WAVES = 16;
-void launch_fwd_fft32(pcnn_handle h, FwdParams p, int ntile);
-void launch_fwd_fft32_multi(pcnn_handle h, const FwdParams* tab, int count, int max_items);   // `count` one-tile transforms (filters) from a device table of parameter blocks
-void launch_fwd_fft64_multi(pcnn_handle h, const FwdParams* tab, int count, int max_items);
-void launch_inv_fft32(pcnn_handle h, InvParams p, int ntile);
-void launch_post_bias_fft32(pcnn_handle h, const float* bsum, int pack, int cpt, int C, float* dbias);     // POST partial sums of the FFT inverse in use -> dbias
-void launch_fwd_fft64(pcnn_handle h, FwdParams p, int ntile);       // 64-point tiles, item = (tile, 16 channels), 8 waves x 2 units
-void launch_inv_fft64(pcnn_handle h, InvParams p, int ntile);
-void launch_post_bias_fft64(pcnn_handle h, const float* bsum, int nblocks, int C, float* dbias);   // POST at 64 points: one float per (block, wave, lane)
+// POST: an inverse kernel runs at most POST_BLOCKS workgroups, and every (workgroup, wave) adds its lanes' bias-gradient partial sums into slots of 64 floats
+// of its own (Xform::post_slots of them); the fused backward sizes the buffer for the back end that needs most
+constexpr int POST_BLOCKS = 256, POST_SLOTS_MAX = POST_BLOCKS * 8 * 4;
+
+// One transform back end: everything the host side needs to know about it.  The four records are defined next to their kernels
+// (spectral_conv.hip, spectral64.hip, spectral_fft.hip); the launchers take the same parameter blocks and set p.ntile themselves.
+struct Xform {
+  int family;                      // PCNN_XFORM_MFMA | PCNN_XFORM_FFT
+  int T, rows, nslot;              // tile size, spectrum rows per item (T^2), mixing slots (T^2 / 2)
+  int P;                           // block size of its row order (sp_blk); >= T: the canonical order
+  size_t tab_off, slots_off;       // its table block and slot table in the workspace header
+  void (*fwd)(pcnn_handle h, FwdParams p, int ntile);
+  void (*inv)(pcnn_handle h, InvParams p, int ntile);
+  void (*post_bias)(pcnn_handle h, const float* bsum, int pack, int cpt, int C, float* dbias);   // POST partial sums of `inv` -> dbias
+  void (*fwd_multi)(pcnn_handle h, const FwdParams* tab, int count, int max_items);   // `count` one-tile transforms (filters) from a device table of parameter blocks in one launch; null: the back end has no such kernel
+  int post_slots;                  // 64-float POST partial-sum slots `inv` writes (<= POST_SLOTS_MAX)
+  const float* tab; const int4* slots;   // resolved against the handle's current workspace by xform_of (spectral_conv.hip)
+};
+extern const Xform XFORM_MFMA32, XFORM_MFMA64, XFORM_FFT32, XFORM_FFT64;
+
+// dynamic LDS beyond 64 KB has to be allowed per kernel before its first launch
+template <typename K>
+void set_lds(K kernel, size_t bytes) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); }
+
+// The epilogue variants of an inverse kernel, chosen once for all four back ends: launch(flag<TANH>, flag<RES>, flag<POST>, params) starts the
+// instantiation <TANH, RES, POST> with the back end's own launch geometry.  alpha / galpha arrive at the kernel as the slope of the negative side
+// (1 linear, 0 relu, the given slope for leaky relu); tanh has its own instantiation, and POST implies a linear convolution epilogue.
+template <bool B> using flag = std::integral_constant<bool, B>;
+template <typename Launch>
+void dispatch_epilogue(InvParams p, Launch launch) {
+  auto slope = [](int act, float alpha) { return act == PCNN_ACT_LINEAR ? 1.f : (act == PCNN_ACT_RELU ? 0.f : alpha); };
+  if (p.gact) {                                                        // data gradient + the producer's activation backward
+    p.alpha = 1.f; p.galpha = slope(p.gmode, p.galpha);
+    if (p.res) launch(flag<false>{}, flag<true>{}, flag<true>{}, p); else launch(flag<false>{}, flag<false>{}, flag<true>{}, p);
+  } else if (p.act == PCNN_ACT_TANH) {
+    if (p.res) launch(flag<true>{}, flag<true>{}, flag<false>{}, p); else launch(flag<true>{}, flag<false>{}, flag<false>{}, p);
+  } else {
+    p.alpha = slope(p.act, p.alpha);
+    if (p.res) launch(flag<false>{}, flag<true>{}, flag<false>{}, p); else launch(flag<false>{}, flag<false>{}, flag<false>{}, p);
+  }
+}
 
 }  // namespace pcnn_spec

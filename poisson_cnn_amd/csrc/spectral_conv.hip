@@ -21,6 +21,7 @@
 #include "spectral_common.h"
 #include <math.h>
 #include <stdlib.h>
+#include <array>
 #include <vector>
 
 int pcnn_spectral_conv_fwd(pcnn_handle h, const pcnn_conv_desc* d, const float* x, const float* w, const float* bias, const float* bn_scale,
@@ -43,7 +44,8 @@ namespace {
 constexpr int T = 32, ROWS = 1024, NSLOT = 512;
 // tables (all stored [k][m], 32 x 32): G / GI the real <-> half-complex 32-point transforms; F2[parity] / FI2[parity] the two 16-point complex
 // transforms of one radix-2 step of the 32-point complex DFT (see build_tables); GI2 the real-column inverse split into its two parities
-constexpr int TAB_G = 0, TAB_GI = 1024, TAB_F2 = 2048, TAB_FI2 = 4096, TAB_GI2 = 6144, TAB_FLOATS = 7168;
+constexpr int TAB_G = 0, TAB_GI = 1024, TAB_F2 = 2048, TAB_FI2 = 4096, TAB_GI2 = 6144, TAB_FLOATS = TAB32_FLOATS;
+static_assert(TAB_GI2 + 1024 == TAB_FLOATS, "table block");
 constexpr size_t LDS_U = (size_t)T * T * 32 * sizeof(float);   // 128 KB
 constexpr size_t LDS_INV = LDS_U + 1024 * sizeof(float);       // the inverse kernel keeps the real-column table (GI2) behind U: see spec_inv_kernel
 // (a storage order with rows blocked 32 tiles wide - whole DRAM pages for the per-frequency kernels - was measured in round 2: no gain)
@@ -779,9 +781,6 @@ void build_tables(std::vector<float>& tab, std::vector<int>& slots) {
     for (int fy = 0; fy < 32; ++fy) slots.insert(slots.end(), {64 + 64 * (fx - 1) + fy, 64 + 64 * (fx - 1) + 32 + fy, 0, 0});
 }
 
-// The transform geometry of one call: tile size, spectrum rows per item, mixing slots, and the device tables of that size.
-struct Geom { int T, rows, nslot; const float* tab; const int4* slots; };
-
 size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 // the channel-mixing kernel writes whole 32-tile M-tiles (unconditional stores: their number per pass is then static): its output spectra are
 // allocated for a multiple of 32 tiles; the rows of tiles that do not exist are never read
@@ -800,12 +799,6 @@ int chunk_tiles(int Tg) {
 // 0.06-0.08 ms per 13- / 15-tap layer; at 32 points (512 slots) 8 is the measured optimum (4: +0.05 ms at 9 taps, 12 / 16: +0.04 ... 0.08 ms).
 // (The kernels index their partial sums as blockIdx.y * 4 + wave: a multiple of 4.)
 int wgrad_splits(int Tg = 32) { return Tg == 64 ? 4 : 8; }
-
-// workspace header: the constant tables of both tile sizes; the per-call regions follow
-// (two slot tables per tile size: the canonical row order of the matrix-core transform family, and the FFT family's interleaved order - spectral_common.h)
-constexpr size_t O_TAB32 = 0, O_SLOTS32 = O_TAB32 + ((TAB_FLOATS * 4 + 255) & ~255), O_TAB64 = O_SLOTS32 + NSLOT * 16,
-                 O_SLOTS64 = O_TAB64 + TAB64_FLOATS * 4, O_SLOTS32F = O_SLOTS64 + 2048 * 16, O_SLOTS64F = O_SLOTS32F + NSLOT * 16, O_REST = O_SLOTS64F + 2048 * 16;
-static_assert(O_REST % 256 == 0, "workspace header alignment");
 
 // grows the handle's workspace (never beyond the caller's limit, pcnn_set_workspace_limit); the tables are (re)uploaded after every growth
 int ensure_workspace(pcnn_handle h, size_t bytes_after_tables, char** rest) {
@@ -840,67 +833,44 @@ int ensure_workspace(pcnn_handle h, size_t bytes_after_tables, char** rest) {
   return 0;
 }
 
-// under a caller's workspace limit the launches cover fewer tiles each (never fewer than 32): halve until the call's regions fit
-template <typename F>
-int fit_chunk(pcnn_handle h, int chunk, F bytes_for) {
-  while (h->spec_ws_limit && chunk > 32 && O_REST + bytes_for(chunk) > h->spec_ws_limit) chunk = std::max(32, chunk / 2);
-  return chunk;
+// A call's workspace regions behind the header, in address order: layout(chunk) gives their sizes (multiples of 256 bytes) for launches of `chunk`
+// tiles.  Under a caller's workspace limit the launches cover fewer tiles each (never fewer than 32): *chunk is halved until the regions fit.  Then the
+// workspace is grown to hold them and ptr[i] receives the start of region i.
+template <size_t N, typename Layout>
+int carve_workspace(pcnn_handle h, int* chunk, Layout layout, float* (&ptr)[N]) {
+  auto total = [&](int ch) { size_t t = 0; for (size_t b : layout(ch)) t += b; return t; };
+  while (h->spec_ws_limit && *chunk > 32 && O_REST + total(*chunk) > h->spec_ws_limit) *chunk = std::max(32, *chunk / 2);
+  char* r;
+  if (int rc = ensure_workspace(h, total(*chunk), &r)) return rc;
+  const std::array<size_t, N> bytes = layout(*chunk);
+  for (size_t i = 0; i < N; ++i) { ptr[i] = reinterpret_cast<float*>(r); r += bytes[i]; }
+  return 0;
 }
+size_t sp_region(size_t items, int rows) { return align256(sp_bytes(items, rows)); }      // a region of `items` spectrum items
 
-Geom geom_of(pcnn_handle h, int Tg) {
+// the back end of a transform family for tiles of Tg points, and the same with its tables resolved against the handle's current workspace (they move when
+// it grows: resolve after the call's ensure_workspace / carve_workspace)
+const Xform& xform_record(int family, int Tg) {
+  if (family == PCNN_XFORM_FFT) return Tg == 64 ? XFORM_FFT64 : XFORM_FFT32;
+  return Tg == 64 ? XFORM_MFMA64 : XFORM_MFMA32;
+}
+Xform xform_at(pcnn_handle h, const Xform& rec) {
+  Xform xf = rec;
   char* b = static_cast<char*>(h->spec_ws);
-  const bool fft = h->spectral_xform == PCNN_XFORM_FFT;                 // the row order belongs to the transform family (spectral_common.h)
-  if (Tg == 64) return Geom{64, 4096, 2048, reinterpret_cast<const float*>(b + O_TAB64), reinterpret_cast<const int4*>(b + (fft ? O_SLOTS64F : O_SLOTS64))};
-  return Geom{32, ROWS, NSLOT, reinterpret_cast<const float*>(b + O_TAB32), reinterpret_cast<const int4*>(b + (fft ? O_SLOTS32F : O_SLOTS32))};
+  xf.tab = reinterpret_cast<const float*>(b + rec.tab_off); xf.slots = reinterpret_cast<const int4*>(b + rec.slots_off);
+  return xf;
 }
+Xform xform_of(pcnn_handle h, int Tg) { return xform_at(h, xform_record(h->spectral_xform, Tg)); }
 
-template <typename K>
-void set_lds(K kernel, size_t bytes = LDS_U) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); }
+void launch_fwd(pcnn_handle h, const Xform& xf, FwdParams p, int ntile) { p.tab = xf.tab; xf.fwd(h, p, ntile); }
+void launch_inv(pcnn_handle h, const Xform& xf, InvParams p, int ntile) { p.tab = xf.tab; xf.inv(h, p, ntile); }
 
-// persistent kernels: one 8-wave workgroup per CU (128 KB of LDS each) walking the (tile, channel group) items
-template <bool MASKED>
-void launch_fwd_t(pcnn_handle h, const FwdParams& p, int ntile) {
-  set_lds(spec_fwd_kernel<MASKED>);
-  hipLaunchKernelGGL((spec_fwd_kernel<MASKED>), dim3((unsigned)std::min(ntile * p.groups, 256)), dim3(512), LDS_U, h->stream, p);
-}
-void launch_fwd(pcnn_handle h, const Geom& gm, FwdParams p, int ntile) {
-  p.ntile = ntile; p.tab = gm.tab;
-  if (gm.T == 64) { if (h->spectral_xform == PCNN_XFORM_FFT) launch_fwd_fft64(h, p, ntile); else launch_fwd64(h, p, ntile); return; }
-  if (h->spectral_xform == PCNN_XFORM_FFT) { launch_fwd_fft32(h, p, ntile); return; }
-  if (p.ylim < T || p.xlim < T) launch_fwd_t<true>(h, p, ntile); else launch_fwd_t<false>(h, p, ntile);
-}
-template <bool TANH, bool RES>
-void launch_inv_t(pcnn_handle h, const InvParams& p, const dim3& grid) {
-  set_lds(spec_inv_kernel<TANH, RES>, LDS_INV);
-  hipLaunchKernelGGL((spec_inv_kernel<TANH, RES>), grid, dim3(512), LDS_INV, h->stream, p);
-}
-void launch_inv(pcnn_handle h, const Geom& gm, InvParams p, int ntile) {
-  p.ntile = ntile; p.tab = gm.tab;
-  if (gm.T == 64) { if (h->spectral_xform == PCNN_XFORM_FFT) launch_inv_fft64(h, p, ntile); else launch_inv64(h, p, ntile); return; }
-  if (h->spectral_xform == PCNN_XFORM_FFT) { launch_inv_fft32(h, p, ntile); return; }
-  const dim3 grid((unsigned)std::min(ntile * p.groups, 256));
-  if (p.gact) {                                                      // data gradient + the producer's activation backward (linear conv epilogue)
-    p.alpha = 1.f;
-    p.galpha = p.gmode == PCNN_ACT_LINEAR ? 1.f : (p.gmode == PCNN_ACT_RELU ? 0.f : p.galpha);
-    set_lds(spec_inv_kernel<false, true, true>, LDS_INV); set_lds(spec_inv_kernel<false, false, true>, LDS_INV);
-    if (p.res) hipLaunchKernelGGL((spec_inv_kernel<false, true, true>), grid, dim3(512), LDS_INV, h->stream, p);
-    else hipLaunchKernelGGL((spec_inv_kernel<false, false, true>), grid, dim3(512), LDS_INV, h->stream, p);
-    return;
-  }
-  if (p.act == PCNN_ACT_TANH) {
-    if (p.res) launch_inv_t<true, true>(h, p, grid); else launch_inv_t<true, false>(h, p, grid);
-  } else {
-    p.alpha = p.act == PCNN_ACT_LINEAR ? 1.f : (p.act == PCNN_ACT_RELU ? 0.f : p.alpha);     // slope of the negative side
-    if (p.res) launch_inv_t<false, true>(h, p, grid); else launch_inv_t<false, false>(h, p, grid);
-  }
-}
-
-void launch_mix(pcnn_handle h, const Geom& gm, MixParams mx, int gin, int gout, int nt) {
-  mx.slots = gm.slots; mx.rows = gm.rows; mx.ntile = nt;
+void launch_mix(pcnn_handle h, const Xform& xf, MixParams mx, int gin, int gout, int nt) {
+  mx.slots = xf.slots; mx.rows = xf.rows; mx.ntile = nt;
   const int nMt = pcnn_cdiv(nt, 32);
   const int gy = std::max(1, std::min(pcnn_cdiv(nMt, 4), 3));
-  if (gin == 1) hipLaunchKernelGGL(spec_mix_kernel<1>, dim3(gm.nslot, gy, gout), dim3(256), 0, h->stream, mx);
-  else hipLaunchKernelGGL(spec_mix_kernel<2>, dim3(gm.nslot, gy, gout), dim3(256), 0, h->stream, mx);
+  if (gin == 1) hipLaunchKernelGGL(spec_mix_kernel<1>, dim3(xf.nslot, gy, gout), dim3(256), 0, h->stream, mx);
+  else hipLaunchKernelGGL(spec_mix_kernel<2>, dim3(xf.nslot, gy, gout), dim3(256), 0, h->stream, mx);
 }
 
 // tiles per lane group for a layer of Cin -> Cout channels: both sides must fit `cpt` lanes (a power of two >= 4)
@@ -953,7 +923,56 @@ __global__ __launch_bounds__(256) void spec_post_bias_kernel(const float* __rest
   if (t == 0) dbias[ch] = red[0];
 }
 
+// the 32-point matrix-core back end.  Persistent kernels: one 8-wave workgroup per CU (128 KB of LDS each) walking the (tile, channel group) items
+void launch_fwd32(pcnn_handle h, FwdParams p, int ntile) {
+  p.ntile = ntile;
+  const dim3 grid((unsigned)std::min(ntile * p.groups, 256));
+  if (p.ylim < T || p.xlim < T) {
+    set_lds(spec_fwd_kernel<true>, LDS_U);
+    hipLaunchKernelGGL((spec_fwd_kernel<true>), grid, dim3(512), LDS_U, h->stream, p);
+  } else {
+    set_lds(spec_fwd_kernel<false>, LDS_U);
+    hipLaunchKernelGGL((spec_fwd_kernel<false>), grid, dim3(512), LDS_U, h->stream, p);
+  }
+}
+void launch_inv32(pcnn_handle h, InvParams p, int ntile) {
+  p.ntile = ntile;
+  const dim3 grid((unsigned)std::min(ntile * p.groups, 256));
+  dispatch_epilogue(p, [&](auto TANH, auto RES, auto POST, const InvParams& q) {
+    constexpr auto kernel = spec_inv_kernel<TANH.value, RES.value, POST.value>;
+    set_lds(kernel, LDS_INV);
+    hipLaunchKernelGGL(kernel, grid, dim3(512), LDS_INV, h->stream, q);
+  });
+}
+void launch_post_bias32(pcnn_handle h, const float* bsum, int pack, int cpt, int C, float* dbias) {
+  hipLaunchKernelGGL(spec_post_bias_kernel, dim3((unsigned)C), dim3(256), 0, h->stream, bsum, XFORM_MFMA32.post_slots, pack, cpt, dbias);
+}
+
+// The tile grid of one call: tiles of T points with Vy x Vx valid outputs each, `pack` x-adjacent tiles per lane group (cpt = 32 / pack lanes per tile),
+// tgx tile groups per tile row; ntile counts tile groups (= tiles when pack == 1).  The kernels index items with 32-bit arithmetic: fewer than 2^30.
+struct TileGrid { int T, Vy, Vx, tiles_y, tiles_x, pack, cpt, tgx, rows, nslot, ntile; };
+// ... over N images of Ho x Wo outputs, with the valid region and the packing as given (the debug exports)
+int tile_grid_given(pcnn_handle h, int Tg, int Vy, int Vx, int pack, int N, int Ho, int Wo, TileGrid* g) {
+  g->T = Tg; g->Vy = Vy; g->Vx = Vx; g->tiles_y = pcnn_cdiv(Ho, Vy); g->tiles_x = pcnn_cdiv(Wo, Vx);
+  g->pack = pack; g->cpt = 32 / pack; g->tgx = pcnn_cdiv(g->tiles_x, pack);
+  g->rows = Tg * Tg; g->nslot = g->rows / 2;
+  const int64_t ntile = (int64_t)N * g->tiles_y * g->tgx;
+  PCNN_REQUIRE(h, ntile < (1ll << 30), "spectral convolution: too many tiles");
+  g->ntile = (int)ntile;
+  return 0;
+}
+// ... of a kh x kw convolution Cin -> Cout; `tile_of` is the descriptor that decides the tile size (pick_tile)
+int tile_grid(pcnn_handle h, const pcnn_conv_desc* tile_of, int kh, int kw, int N, int Ho, int Wo, int Cin, int Cout, TileGrid* g) {
+  const int Tg = pick_tile(h, tile_of);
+  return tile_grid_given(h, Tg, Tg - kh + 1, Tg - kw + 1, Tg == 64 ? 1 : pack_for(Cin, Cout), N, Ho, Wo, g);
+}
+
 }  // namespace
+
+#ifndef __HIP_DEVICE_COMPILE__       // host data (launcher addresses): not for the device pass
+const Xform pcnn_spec::XFORM_MFMA32 = {PCNN_XFORM_MFMA, T, ROWS, NSLOT, 64, O_TAB32, O_SLOTS32, launch_fwd32, launch_inv32, launch_post_bias32, nullptr,
+                                       POST_BLOCKS * 8, nullptr, nullptr};
+#endif
 
 extern "C" int pcnn_set_workspace_limit(pcnn_handle h, size_t bytes) {
   if (!h) return 1;
@@ -1009,24 +1028,42 @@ bool pcnn_conv_fwd_takes_narrow_route(pcnn_handle h, const pcnn_conv_desc* d) {
 }
 
 namespace {
+// the grid's share of a parameter block (FwdParams and InvParams name it alike).  A tile's channels take cpt lanes of a group: 32, or fewer when tiles are packed
+template <typename P>
+void place_on_grid(P& p, const TileGrid& g) {
+  p.tiles_x = g.tiles_x; p.tiles_y = g.tiles_y; p.Vy = g.Vy; p.Vx = g.Vx;
+  p.pack = g.pack; p.cpt = g.cpt; p.tgx = g.tgx; p.cstride = g.cpt; p.cvalid = g.cpt;
+}
+// forward transform of the grid's windows of an H x W x C image (row stride ld, `groups` channel groups), window origin (-oy, -ox): the full window, no extent mask
+FwdParams image_fwd_params(const TileGrid& g, const float* x, float* sp, int H, int W, int C, int ld, int groups, int oy, int ox, int pad_mode, float pad_value) {
+  FwdParams f;
+  f.x = x; f.sp = sp; f.H = H; f.W = W; f.C = C; f.ld = ld; f.groups = groups;
+  f.oy = oy; f.ox = ox; f.pad_mode = pad_mode; f.pad_value = pad_value; f.ylim = g.T; f.xlim = g.T;
+  place_on_grid(f, g);
+  return f;
+}
+// inverse transform of the grid's tiles into an Ho x Wo x C image: linear epilogue, optional residual; the callers add what else their epilogue carries
+InvParams image_inv_params(const TileGrid& g, const float* sp, float* y, int Ho, int Wo, int C, int ldy, int groups, const float* res, int ld_res) {
+  InvParams iv;
+  iv.sp = sp; iv.y = y; iv.Ho = Ho; iv.Wo = Wo; iv.C = C; iv.ldy = ldy; iv.groups = groups; iv.res = res; iv.ld_res = ld_res;
+  place_on_grid(iv, g);
+  return iv;
+}
 // the filter as a kh x kw one-tile "image" with Cin*Cout channels (group = ci [x output group], lane = co): its spectrum feeds the mixing matrices
-FwdParams filter_params(const Geom& gm, const float* w, float* wsp, int kh, int kw, int Cin, int Cout, int gout) {
+FwdParams filter_params(const Xform& xf, const float* w, float* wsp, int kh, int kw, int Cin, int Cout, int gout) {
   FwdParams fw;
-  fw.x = w; fw.sp = wsp; fw.tab = gm.tab; fw.H = kh; fw.W = kw; fw.C = Cin * Cout; fw.ld = Cin * Cout; fw.groups = Cin * gout;
+  fw.x = w; fw.sp = wsp; fw.tab = xf.tab; fw.H = kh; fw.W = kw; fw.C = Cin * Cout; fw.ld = Cin * Cout; fw.groups = Cin * gout;
   fw.cstride = gout > 1 ? 32 : Cout; fw.cvalid = gout > 1 ? 32 : Cout;     // group ci * gout + go holds output channels 32 go .. 32 go + 31
-  fw.tiles_x = 1; fw.tiles_y = 1; fw.tile0 = 0; fw.ntile = 1; fw.Vy = gm.T; fw.Vx = gm.T; fw.oy = 0; fw.ox = 0;
+  fw.Vy = xf.T; fw.Vx = xf.T;
   // the filter is a kh x kw corner of its tile: the masked form of the transform skips the zero rows / columns (same sums: only zero products are dropped)
-  fw.pad_mode = PCNN_PAD_CONSTANT; fw.pad_value = 0.f; fw.ylim = kh; fw.xlim = kw; fw.ext_y = 1 << 30; fw.ext_x = 1 << 30;
-  fw.pack = 1; fw.cpt = 32; fw.tgx = 1;
+  fw.ylim = kh; fw.xlim = kw;
   return fw;
 }
 // the weight gradient's spectrum C^ (one tile, Cin*Cout channels) back to its kh x kw taps
-InvParams taps_params(const Geom& gm, const float* csp, float* dw, int kh, int kw, int Cin, int Cout, int flip) {
+InvParams taps_params(const Xform& xf, const float* csp, float* dw, int kh, int kw, int Cin, int Cout, int flip) {
   InvParams iv;
-  iv.sp = csp; iv.tab = gm.tab; iv.y = dw; iv.bias = nullptr; iv.bn_scale = nullptr; iv.bn_shift = nullptr; iv.res = nullptr; iv.act_out = nullptr;
-  iv.absmax = nullptr; iv.Ho = kh; iv.Wo = kw; iv.C = Cin * Cout; iv.ldy = Cin * Cout; iv.ld_res = 0; iv.ld_act = 0;
-  iv.groups = Cin; iv.cstride = Cout; iv.cvalid = Cout; iv.act = PCNN_ACT_LINEAR; iv.alpha = 0.f;
-  iv.tiles_x = 1; iv.tiles_y = 1; iv.tile0 = 0; iv.ntile = 1; iv.Vy = gm.T; iv.Vx = gm.T; iv.flip = flip; iv.pack = 1; iv.cpt = 32; iv.tgx = 1;
+  iv.sp = csp; iv.tab = xf.tab; iv.y = dw; iv.Ho = kh; iv.Wo = kw; iv.C = Cin * Cout; iv.ldy = Cin * Cout;
+  iv.groups = Cin; iv.cstride = Cout; iv.cvalid = Cout; iv.Vy = xf.T; iv.Vx = xf.T; iv.flip = flip;
   return iv;
 }
 }  // namespace
@@ -1040,11 +1077,12 @@ InvParams taps_params(const Geom& gm, const float* csp, float* dw, int kh, int k
 // device memory and changes only when a filter is added), so a training step pays one or two launches instead of one per layer and direction.
 // Nothing is allocated or uploaded while the stream is being captured: a filter first seen under capture is transformed into the workspace as before.
 namespace {
-struct FilterEntry { const float* w; int kh, kw, Cin, Cout, gout, T, xform; float* buf; unsigned long long version; FwdParams fp; };
+struct FilterEntry { const float* w; int kh, kw, Cin, Cout, gout, T, xform; float* buf; unsigned long long version; FwdParams fp; };   // (T, xform): its Xform record
 struct FilterCache {
   std::vector<FilterEntry> e;
-  std::vector<FwdParams> host[2];                                   // [0]: 32-point entries, [1]: 64-point entries (FFT family), in the order of the device table
+  std::vector<FwdParams> host[2];                                   // [0]: 32-point entries, [1]: 64-point entries of the back ends with a fwd_multi, in the order of the device table
   FwdParams* dev[2] = {nullptr, nullptr};
+  decltype(Xform::fwd_multi) multi[2] = {nullptr, nullptr};         // ... and the launcher that walks the table
   size_t cap[2] = {0, 0};
   size_t bytes = 0;
 };
@@ -1052,46 +1090,41 @@ FilterCache* cache_of(pcnn_handle h) {
   if (!h->filter_cache) h->filter_cache = new FilterCache();
   return static_cast<FilterCache*>(h->filter_cache);
 }
-// every entry of the handle gets the current version: one table launch per tile size (FFT family), one launch per entry otherwise
+// every entry of the handle gets the current version: one table launch per tile size where the back end has a fwd_multi, one launch per entry otherwise
 void refresh_filters(pcnn_handle h, FilterCache* fc) {
   for (int ti = 0; ti < 2; ++ti) {
     if (fc->host[ti].empty()) continue;
     int max_items = 1;
     for (const FwdParams& f : fc->host[ti]) max_items = std::max(max_items, f.groups);
-    if (ti == 0) launch_fwd_fft32_multi(h, fc->dev[0], (int)fc->host[0].size(), max_items);
-    else launch_fwd_fft64_multi(h, fc->dev[1], (int)fc->host[1].size(), max_items);
+    fc->multi[ti](h, fc->dev[ti], (int)fc->host[ti].size(), max_items);
   }
   for (FilterEntry& en : fc->e) {
-    if (en.xform != PCNN_XFORM_FFT && en.version != h->filter_version) {
-      const Geom gm = geom_of(h, en.T);
-      en.fp.tab = gm.tab;                                           // the tables move when the workspace grows
-      launch_fwd(h, gm, en.fp, 1);
-    }
+    const Xform& rec = xform_record(en.xform, en.T);
+    if (!rec.fwd_multi && en.version != h->filter_version) launch_fwd(h, xform_at(h, rec), en.fp, 1);   // (with the tables where they are now: they move when the workspace grows)
     en.version = h->filter_version;
   }
   ++h->fc_refreshes;
 }
 // the spectrum of filter `w` ((kh, kw, Cin, Cout), output channel groups gout) for this call: a cached buffer, or `ws_slot` freshly filled
-const float* filter_spectrum(pcnn_handle h, const Geom& gm, const float* w, float* ws_slot, int kh, int kw, int Cin, int Cout, int gout) {
-  auto uncached = [&]() { launch_fwd(h, gm, filter_params(gm, w, ws_slot, kh, kw, Cin, Cout, gout), 1); return ws_slot; };
+const float* filter_spectrum(pcnn_handle h, const Xform& xf, const float* w, float* ws_slot, int kh, int kw, int Cin, int Cout, int gout) {
+  auto uncached = [&]() { launch_fwd(h, xf, filter_params(xf, w, ws_slot, kh, kw, Cin, Cout, gout), 1); return ws_slot; };
   if (h->filter_version == 0) return uncached();
   FilterCache* fc = cache_of(h);
   for (FilterEntry& en : fc->e)
-    if (en.w == w && en.kh == kh && en.kw == kw && en.Cin == Cin && en.Cout == Cout && en.gout == gout && en.T == gm.T && en.xform == h->spectral_xform) {
+    if (en.w == w && en.kh == kh && en.kw == kw && en.Cin == Cin && en.Cout == Cout && en.gout == gout && en.T == xf.T && en.xform == xf.family) {
       if (en.version != h->filter_version) refresh_filters(h, fc); else ++h->fc_hits;
       return en.buf;
     }
   // first sight of this filter: a buffer of its own - unless the stream is being captured (no allocation, no upload inside a capture)
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(h->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return uncached(); }
-  const size_t bytes = align256(sp_bytes((size_t)Cin * gout, gm.rows));
+  const size_t bytes = sp_region((size_t)Cin * gout, xf.rows);
   void* buf = nullptr;
   if (hipMalloc(&buf, bytes) != hipSuccess) { (void)hipGetLastError(); return uncached(); }
-  FilterEntry en{w, kh, kw, Cin, Cout, gout, gm.T, h->spectral_xform, static_cast<float*>(buf), h->filter_version,
-                 filter_params(gm, w, static_cast<float*>(buf), kh, kw, Cin, Cout, gout)};
-  en.fp.ntile = 1;
-  if (en.xform == PCNN_XFORM_FFT) {
-    const int ti = gm.T == 64 ? 1 : 0;
+  FilterEntry en{w, kh, kw, Cin, Cout, gout, xf.T, xf.family, static_cast<float*>(buf), h->filter_version,
+                 filter_params(xf, w, static_cast<float*>(buf), kh, kw, Cin, Cout, gout)};
+  if (xf.fwd_multi) {
+    const int ti = xf.T == 64 ? 1 : 0;
     const size_t n = fc->host[ti].size() + 1;
     if (n > fc->cap[ti]) {
       const size_t cap = std::max<size_t>(64, 2 * n);
@@ -1100,12 +1133,12 @@ const float* filter_spectrum(pcnn_handle h, const Geom& gm, const float* w, floa
       if (fc->dev[ti]) pcnn_release(h, fc->dev[ti]);
       fc->dev[ti] = static_cast<FwdParams*>(t); fc->cap[ti] = cap;
     }
-    fc->host[ti].push_back(en.fp);
+    fc->host[ti].push_back(en.fp); fc->multi[ti] = xf.fwd_multi;
     // (synchronous copy of the whole table: once per filter, in the first step that sees it; the stream may still be reading the old contents)
     (void)hipStreamSynchronize(h->stream);
     (void)hipMemcpy(fc->dev[ti], fc->host[ti].data(), n * sizeof(FwdParams), hipMemcpyHostToDevice);
   }
-  launch_fwd(h, gm, en.fp, 1);
+  launch_fwd(h, xf, en.fp, 1);
   fc->e.push_back(en);
   fc->bytes += bytes;
   ++h->fc_fills;
@@ -1147,96 +1180,62 @@ extern "C" int pcnn_filter_cache_stats(pcnn_handle h, long long* entries, long l
 
 int pcnn_spectral_conv_fwd(pcnn_handle h, const pcnn_conv_desc* d, const float* x, const float* w, const float* bias, const float* bn_scale,
                            const float* bn_shift, const float* residual, float* y, float* act_out) {
-  const int Tg = pick_tile(h, d);
-  const int Vy = Tg - d->kh + 1, Vx = Tg - d->kw + 1;
-  const int tiles_y = pcnn_cdiv(d->Ho, Vy), tiles_x = pcnn_cdiv(d->Wo, Vx);
-  const int pack = Tg == 64 ? 1 : pack_for(d->Cin, d->Cout), cpt = 32 / pack, tgx = pcnn_cdiv(tiles_x, pack);
-  const int64_t ntile = (int64_t)d->N * tiles_y * tgx;                       // tile groups (= tiles when pack == 1)
-  PCNN_REQUIRE(h, ntile < (1ll << 30), "spectral convolution: too many tiles");
+  TileGrid g;
+  if (int rc = tile_grid(h, d, d->kh, d->kw, d->N, d->Ho, d->Wo, d->Cin, d->Cout, &g)) return rc;
   const int gin = pcnn_cdiv(d->Cin, 32), gout = pcnn_cdiv(d->Cout, 32);
-  const int rows = Tg * Tg;
   // workspace: [filter spectrum | input spectra | output spectra]
-  const size_t wsp_b = align256(sp_bytes((size_t)d->Cin * gout, rows));
-  auto xs_bytes = [&](int ch) { return align256(sp_bytes((size_t)ch * gin, rows)); };
-  auto ys_bytes = [&](int ch) { return align256(sp_bytes((size_t)pad32(ch) * gout, rows)); };
-  const int chunk = fit_chunk(h, (int)std::min<int64_t>(chunk_tiles(Tg) / (gin > gout ? gin : gout), ntile), [&](int ch) { return wsp_b + xs_bytes(ch) + ys_bytes(ch); });
-  const size_t xs_b = xs_bytes(chunk), ys_b = ys_bytes(chunk);
-  char* r;
-  if (int rc = ensure_workspace(h, wsp_b + xs_b + ys_b, &r)) return rc;
-  const Geom gm = geom_of(h, Tg);
-  float* wsp = reinterpret_cast<float*>(r); r += wsp_b;
-  float* xs = reinterpret_cast<float*>(r); r += xs_b;
-  float* ys = reinterpret_cast<float*>(r);
-  const float* fsp = filter_spectrum(h, gm, w, wsp, d->kh, d->kw, d->Cin, d->Cout, gout);
+  int chunk = std::min(chunk_tiles(g.T) / (gin > gout ? gin : gout), g.ntile);
+  float* ws[3];
+  if (int rc = carve_workspace(h, &chunk, [&](int ch) {
+        return std::array<size_t, 3>{sp_region((size_t)d->Cin * gout, g.rows), sp_region((size_t)ch * gin, g.rows), sp_region((size_t)pad32(ch) * gout, g.rows)};
+      }, ws)) return rc;
+  float *wsp = ws[0], *xs = ws[1], *ys = ws[2];
+  const Xform xf = xform_of(h, g.T);
+  const float* fsp = filter_spectrum(h, xf, w, wsp, d->kh, d->kw, d->Cin, d->Cout, gout);
   PCNN_CHECK_LAUNCH(h, "spectral convolution (filter spectrum)");
-  FwdParams fx;
-  fx.x = x; fx.sp = xs; fx.tab = gm.tab; fx.H = d->H; fx.W = d->W; fx.C = d->Cin; fx.ld = d->ldx; fx.groups = gin; fx.cstride = 32; fx.cvalid = 32;
-  fx.tiles_x = tiles_x; fx.tiles_y = tiles_y; fx.Vy = Vy; fx.Vx = Vx; fx.oy = d->pad_top; fx.ox = d->pad_left; fx.pad_mode = d->pad_mode;
-  fx.pad_value = d->pad_value; fx.ylim = Tg; fx.xlim = Tg; fx.ext_y = 1 << 30; fx.ext_x = 1 << 30;
-  fx.pack = pack; fx.cpt = cpt; fx.tgx = tgx;
-  if (pack > 1) { fx.cstride = cpt; fx.cvalid = cpt; }
-  InvParams iv;
-  iv.sp = ys; iv.tab = gm.tab; iv.y = y; iv.bias = bias; iv.bn_scale = bn_scale; iv.bn_shift = bn_shift; iv.res = residual; iv.act_out = act_out;
-  iv.absmax = reinterpret_cast<unsigned*>(h->y_absmax);
-  iv.Ho = d->Ho; iv.Wo = d->Wo; iv.C = d->Cout; iv.ldy = d->ldy; iv.ld_res = d->ld_res; iv.ld_act = d->ld_act_out; iv.groups = gout; iv.cstride = 32; iv.cvalid = 32;
-  iv.act = d->act; iv.alpha = d->act_alpha; iv.tiles_x = tiles_x; iv.tiles_y = tiles_y; iv.Vy = Vy; iv.Vx = Vx; iv.flip = 0;
-  iv.pack = pack; iv.cpt = cpt; iv.tgx = tgx;
-  if (pack > 1) { iv.cstride = cpt; iv.cvalid = cpt; }
+  FwdParams fx = image_fwd_params(g, x, xs, d->H, d->W, d->Cin, d->ldx, gin, d->pad_top, d->pad_left, d->pad_mode, d->pad_value);
+  InvParams iv = image_inv_params(g, ys, y, d->Ho, d->Wo, d->Cout, d->ldy, gout, residual, d->ld_res);
+  iv.bias = bias; iv.bn_scale = bn_scale; iv.bn_shift = bn_shift; iv.act_out = act_out; iv.ld_act = d->ld_act_out;
+  iv.absmax = reinterpret_cast<unsigned*>(h->y_absmax); iv.act = d->act; iv.alpha = d->act_alpha;
   MixParams mx;
-  mx.xs = xs; mx.ys = ys; mx.wsp = fsp; mx.gin = gin; mx.gout = gout; mx.Cin = d->Cin; mx.cpt = cpt;
-  for (int64_t t0 = 0; t0 < ntile; t0 += chunk) {
-    const int nt = (int)std::min<int64_t>(chunk, ntile - t0);
-    fx.tile0 = (int)t0; iv.tile0 = (int)t0;
-    launch_fwd(h, gm, fx, nt);
-    launch_mix(h, gm, mx, gin, gout, nt);
-    launch_inv(h, gm, iv, nt);
+  mx.xs = xs; mx.ys = ys; mx.wsp = fsp; mx.gin = gin; mx.gout = gout; mx.Cin = d->Cin; mx.cpt = g.cpt;
+  for (int t0 = 0; t0 < g.ntile; t0 += chunk) {
+    const int nt = std::min(chunk, g.ntile - t0);
+    fx.tile0 = t0; iv.tile0 = t0;
+    launch_fwd(h, xf, fx, nt);
+    launch_mix(h, xf, mx, gin, gout, nt);
+    launch_inv(h, xf, iv, nt);
   }
   PCNN_CHECK_LAUNCH(h, "spectral convolution");
   return 0;
 }
 
 int pcnn_spectral_conv_wgrad(pcnn_handle h, const pcnn_conv_desc* d, const float* x, const float* dz, float* dw) {
-  const int Tg = pick_tile(h, d);
-  const int Vy = Tg - d->kh + 1, Vx = Tg - d->kw + 1;
-  const int tiles_y = pcnn_cdiv(d->Ho, Vy), tiles_x = pcnn_cdiv(d->Wo, Vx);
-  const int pack = Tg == 64 ? 1 : pack_for(d->Cin, d->Cout), cpt = 32 / pack, tgx = pcnn_cdiv(tiles_x, pack);
-  const int64_t ntile = (int64_t)d->N * tiles_y * tgx;
-  PCNN_REQUIRE(h, ntile < (1ll << 30), "spectral convolution: too many tiles");
-  const int gin = pcnn_cdiv(d->Cin, 32), S = wgrad_splits(Tg);
-  const int rows = Tg * Tg, nslot = rows / 2;
+  TileGrid g;
+  if (int rc = tile_grid(h, d, d->kh, d->kw, d->N, d->Ho, d->Wo, d->Cin, d->Cout, &g)) return rc;
+  const int gin = pcnn_cdiv(d->Cin, 32), S = wgrad_splits(g.T);
   // workspace: [C^ | x window spectra | dz tile spectra | partial sums]
-  const size_t csp_b = align256(sp_bytes((size_t)d->Cin, rows)), part_b = align256((size_t)S * nslot * gin * 4 * 1024 * 4);
-  auto xs_bytes = [&](int ch) { return align256(sp_bytes((size_t)ch * gin, rows)); };
-  auto zs_bytes = [&](int ch) { return align256(sp_bytes((size_t)ch, rows)); };
-  const int chunk = fit_chunk(h, (int)std::min<int64_t>(chunk_tiles(Tg) / gin, ntile), [&](int ch) { return csp_b + part_b + xs_bytes(ch) + zs_bytes(ch); });
-  const size_t xs_b = xs_bytes(chunk), zs_b = zs_bytes(chunk);
-  char* r;
-  if (int rc = ensure_workspace(h, csp_b + xs_b + zs_b + part_b, &r)) return rc;
-  const Geom gm = geom_of(h, Tg);
-  float* csp = reinterpret_cast<float*>(r); r += csp_b;
-  float* xs = reinterpret_cast<float*>(r); r += xs_b;
-  float* zs = reinterpret_cast<float*>(r); r += zs_b;
-  float* part = reinterpret_cast<float*>(r);
-  FwdParams fx;
-  fx.x = x; fx.sp = xs; fx.tab = gm.tab; fx.H = d->H; fx.W = d->W; fx.C = d->Cin; fx.ld = d->ldx; fx.groups = gin; fx.cstride = 32; fx.cvalid = 32;
-  fx.tiles_x = tiles_x; fx.tiles_y = tiles_y; fx.Vy = Vy; fx.Vx = Vx; fx.oy = d->pad_top; fx.ox = d->pad_left; fx.pad_mode = d->pad_mode;
-  fx.pad_value = d->pad_value; fx.ylim = Tg; fx.xlim = Tg; fx.ext_y = 1 << 30; fx.ext_x = 1 << 30;
-  fx.pack = pack; fx.cpt = cpt; fx.tgx = tgx;
-  if (pack > 1) { fx.cstride = cpt; fx.cvalid = cpt; }
-  FwdParams fz = fx;                                    // dz: the tile's own Vy x Vx outputs, zero elsewhere in the window
-  fz.x = dz; fz.sp = zs; fz.H = d->Ho; fz.W = d->Wo; fz.C = d->Cout; fz.ld = d->ldy; fz.groups = 1; fz.oy = 0; fz.ox = 0;
-  fz.pad_mode = PCNN_PAD_CONSTANT; fz.pad_value = 0.f; fz.ylim = Vy; fz.xlim = Vx;
+  int chunk = std::min(chunk_tiles(g.T) / gin, g.ntile);
+  float* ws[4];
+  if (int rc = carve_workspace(h, &chunk, [&](int ch) {
+        return std::array<size_t, 4>{sp_region((size_t)d->Cin, g.rows), sp_region((size_t)ch * gin, g.rows), sp_region((size_t)ch, g.rows), align256((size_t)S * g.nslot * gin * 4 * 1024 * 4)};
+      }, ws)) return rc;
+  float *csp = ws[0], *xs = ws[1], *zs = ws[2], *part = ws[3];
+  const Xform xf = xform_of(h, g.T);
+  FwdParams fx = image_fwd_params(g, x, xs, d->H, d->W, d->Cin, d->ldx, gin, d->pad_top, d->pad_left, d->pad_mode, d->pad_value);
+  FwdParams fz = image_fwd_params(g, dz, zs, d->Ho, d->Wo, d->Cout, d->ldy, 1, 0, 0, PCNN_PAD_CONSTANT, 0.f);
+  fz.ylim = g.Vy; fz.xlim = g.Vx;                        // dz: the tile's own Vy x Vx outputs, zero elsewhere in the window
   WMixParams wm;
-  wm.xs = xs; wm.ds = zs; wm.part = part; wm.slots = gm.slots; wm.gin = gin; wm.S = S / 4; wm.rows = rows; wm.nslot = nslot;
-  for (int64_t t0 = 0; t0 < ntile; t0 += chunk) {
-    const int nt = (int)std::min<int64_t>(chunk, ntile - t0);
-    fx.tile0 = (int)t0; fz.tile0 = (int)t0; wm.ntile = nt; wm.accumulate = t0 > 0;
-    launch_fwd(h, gm, fx, nt);
-    launch_fwd(h, gm, fz, nt);
-    hipLaunchKernelGGL(spec_wmix_kernel, dim3(nslot, S / 4, gin), dim3(256), 0, h->stream, wm);
+  wm.xs = xs; wm.ds = zs; wm.part = part; wm.slots = xf.slots; wm.gin = gin; wm.S = S / 4; wm.rows = g.rows; wm.nslot = g.nslot;
+  for (int t0 = 0; t0 < g.ntile; t0 += chunk) {
+    const int nt = std::min(chunk, g.ntile - t0);
+    fx.tile0 = t0; fz.tile0 = t0; wm.ntile = nt; wm.accumulate = t0 > 0;
+    launch_fwd(h, xf, fx, nt);
+    launch_fwd(h, xf, fz, nt);
+    hipLaunchKernelGGL(spec_wmix_kernel, dim3(g.nslot, S / 4, gin), dim3(256), 0, h->stream, wm);
   }
-  hipLaunchKernelGGL(spec_wcombine_kernel, dim3(nslot, gin), dim3(256), 0, h->stream, part, gm.slots, csp, S, gin, d->Cin, 1.0f, cpt, rows);
-  launch_inv(h, gm, taps_params(gm, csp, dw, d->kh, d->kw, d->Cin, d->Cout, 0), 1);
+  hipLaunchKernelGGL(spec_wcombine_kernel, dim3(g.nslot, gin), dim3(256), 0, h->stream, part, xf.slots, csp, S, gin, d->Cin, 1.0f, g.cpt, g.rows);
+  launch_inv(h, xf, taps_params(xf, csp, dw, d->kh, d->kw, d->Cin, d->Cout, 0), 1);
   PCNN_CHECK_LAUNCH(h, "spectral weight gradient");
   return 0;
 }
@@ -1257,26 +1256,24 @@ __global__ __launch_bounds__(256) void spec_canonical_rows_kernel(const float* _
     out[(size_t)item * rows * 32 + e] = sp[pcnn_spec::sp_item(item, rows) + pcnn_spec::sp_row_from_canonical(T, r, P) * RS + c];
   }
 }
-static int canonical_copy(pcnn_handle h, const float* sp, float* out, int T, int items) {
-  const int P = h->spectral_xform == PCNN_XFORM_FFT ? SP_P : 64;
-  hipLaunchKernelGGL(spec_canonical_rows_kernel, dim3(16, items), dim3(256), 0, h->stream, sp, out, T, T * T, P);
+static int canonical_copy(pcnn_handle h, const Xform& xf, const float* sp, float* out, int items) {
+  hipLaunchKernelGGL(spec_canonical_rows_kernel, dim3(16, items), dim3(256), 0, h->stream, sp, out, xf.T, xf.rows, xf.P);
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
 extern "C" int pcnn_debug_tile_spectrum64(pcnn_handle h, int H, int W, int C, const float* x, int ylim, int xlim, float* out) {
   PCNN_REQUIRE(h, h && x && out && H >= 1 && W >= 1 && C >= 1 && C <= 64, "pcnn_debug_tile_spectrum64: bad argument");
+  TileGrid g;
+  if (int rc = tile_grid_given(h, 64, 64, 64, 1, 1, 64, 64, &g)) return rc;       // the one window at the image origin
   const int groups = pcnn_cdiv(C, 32);
-  const size_t sp_b = align256(sp_bytes((size_t)groups, 4096));
   char* r;
-  if (int rc = ensure_workspace(h, sp_b, &r)) return rc;
-  const Geom gm = geom_of(h, 64);
-  FwdParams f;
-  f.x = x; f.sp = reinterpret_cast<float*>(r); f.tab = gm.tab; f.H = H; f.W = W; f.C = C; f.ld = C; f.groups = groups; f.cstride = 32; f.cvalid = 32;
-  f.tiles_x = 1; f.tiles_y = 1; f.tile0 = 0; f.Vy = 64; f.Vx = 64; f.oy = 0; f.ox = 0; f.pad_mode = PCNN_PAD_CONSTANT; f.pad_value = 0.f;
-  f.ylim = ylim; f.xlim = xlim; f.ext_y = 1 << 30; f.ext_x = 1 << 30; f.pack = 1; f.cpt = 32; f.tgx = 1;
-  launch_fwd(h, gm, f, 1);
+  if (int rc = ensure_workspace(h, sp_region((size_t)groups, g.rows), &r)) return rc;
+  const Xform xf = xform_of(h, g.T);
+  FwdParams f = image_fwd_params(g, x, reinterpret_cast<float*>(r), H, W, C, C, groups, 0, 0, PCNN_PAD_CONSTANT, 0.f);
+  f.ylim = ylim; f.xlim = xlim;
+  launch_fwd(h, xf, f, 1);
   PCNN_CHECK_LAUNCH(h, "pcnn_debug_tile_spectrum64");
-  if (canonical_copy(h, f.sp, out, 64, groups)) PCNN_FAIL(h, "pcnn_debug_tile_spectrum64: copy failed");
+  if (canonical_copy(h, xf, f.sp, out, groups)) PCNN_FAIL(h, "pcnn_debug_tile_spectrum64: copy failed");
   return 0;
 }
 
@@ -1289,21 +1286,18 @@ extern "C" int pcnn_debug_forward_spectrum32(pcnn_handle h, int H, int W, int C,
                                              int ylim, int xlim, int pack, float* out, size_t out_floats) {
   PCNN_REQUIRE(h, h && x && out && H >= 1 && W >= 1 && C >= 1 && C <= 64 && Vy >= 1 && Vy <= 32 && Vx >= 1 && Vx <= 32, "pcnn_debug_forward_spectrum32: bad argument");
   PCNN_REQUIRE(h, pack == 1 || ((pack == 2 || pack == 4 || pack == 8) && C <= 32 / pack), "pcnn_debug_forward_spectrum32: pack = %d with %d channels", pack, C);
-  const int tiles_y = pcnn_cdiv(H, Vy), tiles_x = pcnn_cdiv(W, Vx), tgx = pcnn_cdiv(tiles_x, pack), groups = pack > 1 ? 1 : pcnn_cdiv(C, 32);
-  const int ntile = tiles_y * tgx;
-  PCNN_REQUIRE(h, out_floats >= (size_t)ntile * groups * 1024 * 32, "pcnn_debug_forward_spectrum32: output holds %zu floats, %zu needed", out_floats, (size_t)ntile * groups * 1024 * 32);
-  const size_t sp_b = align256(sp_bytes((size_t)ntile * groups, 1024));
+  TileGrid g;
+  if (int rc = tile_grid_given(h, 32, Vy, Vx, pack, 1, H, W, &g)) return rc;
+  const int groups = pack > 1 ? 1 : pcnn_cdiv(C, 32);
+  PCNN_REQUIRE(h, out_floats >= (size_t)g.ntile * groups * 1024 * 32, "pcnn_debug_forward_spectrum32: output holds %zu floats, %zu needed", out_floats, (size_t)g.ntile * groups * 1024 * 32);
   char* r;
-  if (int rc = ensure_workspace(h, sp_b, &r)) return rc;
-  const Geom gm = geom_of(h, 32);
-  FwdParams f;
-  f.x = x; f.sp = reinterpret_cast<float*>(r); f.tab = gm.tab; f.H = H; f.W = W; f.C = C; f.ld = C; f.groups = groups; f.cstride = 32; f.cvalid = 32;
-  f.tiles_x = tiles_x; f.tiles_y = tiles_y; f.tile0 = 0; f.Vy = Vy; f.Vx = Vx; f.oy = oy; f.ox = ox; f.pad_mode = pad_mode; f.pad_value = pad_value;
-  f.ylim = ylim; f.xlim = xlim; f.ext_y = 1 << 30; f.ext_x = 1 << 30; f.pack = pack; f.cpt = 32 / pack; f.tgx = tgx;
-  if (pack > 1) { f.cstride = f.cpt; f.cvalid = f.cpt; }
-  launch_fwd(h, gm, f, ntile);
+  if (int rc = ensure_workspace(h, sp_region((size_t)g.ntile * groups, g.rows), &r)) return rc;
+  const Xform xf = xform_of(h, g.T);
+  FwdParams f = image_fwd_params(g, x, reinterpret_cast<float*>(r), H, W, C, C, groups, oy, ox, pad_mode, pad_value);
+  f.ylim = ylim; f.xlim = xlim;
+  launch_fwd(h, xf, f, g.ntile);
   PCNN_CHECK_LAUNCH(h, "pcnn_debug_forward_spectrum32");
-  if (canonical_copy(h, f.sp, out, 32, ntile * groups)) PCNN_FAIL(h, "pcnn_debug_forward_spectrum32: copy failed");
+  if (canonical_copy(h, xf, f.sp, out, g.ntile * groups)) PCNN_FAIL(h, "pcnn_debug_forward_spectrum32: copy failed");
   return 0;
 }
 
@@ -1349,77 +1343,52 @@ static int bwd_spectral_impl(pcnn_handle h, const pcnn_conv_desc* d, const pcnn_
   PCNN_REQUIRE(h, h && d && dg && x && dz && w_flipped && dx && dw, "pcnn_conv2d_bwd_spectral: null argument");
   PCNN_REQUIRE(h, pcnn_conv2d_bwd_spectral_eligible(h, d, dg), "pcnn_conv2d_bwd_spectral: layer is not eligible (ask pcnn_conv2d_bwd_spectral_eligible first)");
   PCNN_REQUIRE(h, dg->Cin == d->Cout && dg->Cout == d->Cin && dg->kh == d->kh && dg->kw == d->kw && dg->N == d->N, "pcnn_conv2d_bwd_spectral: descriptors do not match");
-  const int Tg = pick_tile(h, dg);
-  const int Vy = Tg - d->kh + 1, Vx = Tg - d->kw + 1;
-  const int tiles_y = pcnn_cdiv(dg->Ho, Vy), tiles_x = pcnn_cdiv(dg->Wo, Vx);
-  const int pack = Tg == 64 ? 1 : pack_for(d->Cin, d->Cout), cpt = 32 / pack, tgx = pcnn_cdiv(tiles_x, pack);
-  const int64_t ntile = (int64_t)d->N * tiles_y * tgx;
-  PCNN_REQUIRE(h, ntile < (1ll << 30), "spectral convolution: too many tiles");
-  const int gz = 1, gx = pcnn_cdiv(d->Cin, 32), S = wgrad_splits(Tg);       // channel groups of dz (<= 32 channels) and of x / dx
-  const int rows = Tg * Tg, nslot = rows / 2;
-  // workspace: [filter spectrum | dz spectra (gz) | dx spectra (gx) | x-tile spectra (gx) | partial sums]; C^ reuses the filter-spectrum slot
-  const size_t wsp_b = align256(sp_bytes((size_t)std::max(dg->Cin * gx, d->Cin), rows));
-  const size_t part_b = align256((size_t)S * nslot * gx * 4 * 1024 * 4);
-  auto zs_bytes = [&](int ch) { return align256(sp_bytes((size_t)ch * gz, rows)); };
-  auto ys_bytes = [&](int ch) { return align256(sp_bytes((size_t)pad32(ch) * gx, rows)); };
-  const int chunk = fit_chunk(h, (int)std::min<int64_t>(chunk_tiles(Tg) / gx, ntile), [&](int ch) { return wsp_b + part_b + 4096 + zs_bytes(ch) + 2 * ys_bytes(ch); });
-  const size_t zs_b = zs_bytes(chunk), ys_b = ys_bytes(chunk);
-  char* r;
-  const size_t bs_b = post ? (size_t)256 * 8 * 64 * 4 * sizeof(float) : 0;   // POST: one partial bias sum per (workgroup, wave, lane) - four at 64 points (a lane holds four channels)
-  if (int rc = ensure_workspace(h, wsp_b + zs_b + 2 * ys_b + part_b + bs_b + 4096, &r)) return rc;
-  const Geom gm = geom_of(h, Tg);
-  float* wsp = reinterpret_cast<float*>(r); r += wsp_b;
-  float* zs = reinterpret_cast<float*>(r); r += zs_b;
-  float* ys = reinterpret_cast<float*>(r); r += ys_b;
-  float* xs = reinterpret_cast<float*>(r); r += ys_b;
-  float* part = reinterpret_cast<float*>(r); r += part_b;
-  float* bsum = post ? reinterpret_cast<float*>(r) : nullptr;
+  TileGrid g;
+  if (int rc = tile_grid(h, dg, d->kh, d->kw, d->N, dg->Ho, dg->Wo, d->Cin, d->Cout, &g)) return rc;
+  const int gz = 1, gx = pcnn_cdiv(d->Cin, 32), S = wgrad_splits(g.T);       // channel groups of dz (<= 32 channels) and of x / dx
+  // workspace: [filter spectrum | dz spectra (gz) | dx spectra (gx) | x-tile spectra (gx) | partial sums | POST partial bias sums | 4 KB spare]; C^ reuses
+  // the filter-spectrum slot
+  const size_t bs_b = post ? (size_t)POST_SLOTS_MAX * 64 * sizeof(float) : 0;
+  int chunk = std::min(chunk_tiles(g.T) / gx, g.ntile);
+  float* ws[7];
+  if (int rc = carve_workspace(h, &chunk, [&](int ch) {
+        const size_t ys_b = sp_region((size_t)pad32(ch) * gx, g.rows);
+        return std::array<size_t, 7>{sp_region((size_t)std::max(dg->Cin * gx, d->Cin), g.rows), sp_region((size_t)ch * gz, g.rows), ys_b, ys_b,
+                                     align256((size_t)S * g.nslot * gx * 4 * 1024 * 4), bs_b, 4096};
+      }, ws)) return rc;
+  float *wsp = ws[0], *zs = ws[1], *ys = ws[2], *xs = ws[3], *part = ws[4], *bsum = ws[5];
+  const Xform xf = xform_of(h, g.T);
   // flipped filter spectrum -> mixing matrices of the data gradient (input groups: dz's, output groups: dx's)
   PCNN_REQUIRE(h, gx == 1 || dg->Cout == 64, "pcnn_conv2d_bwd_spectral: %d input channels unsupported (<= 32 or 64)", d->Cin);
-  const float* fsp = filter_spectrum(h, gm, w_flipped, wsp, d->kh, d->kw, dg->Cin, dg->Cout, gx);
+  const float* fsp = filter_spectrum(h, xf, w_flipped, wsp, d->kh, d->kw, dg->Cin, dg->Cout, gx);
   PCNN_CHECK_LAUNCH(h, "pcnn_conv2d_bwd_spectral (filter spectrum)");
-  FwdParams fz;                                          // dz windows with halo: the data gradient's input transform
-  fz.x = dz; fz.sp = zs; fz.tab = gm.tab; fz.H = dg->H; fz.W = dg->W; fz.C = dg->Cin; fz.ld = dg->ldx; fz.groups = gz; fz.cstride = 32; fz.cvalid = 32;
-  fz.tiles_x = tiles_x; fz.tiles_y = tiles_y; fz.Vy = Vy; fz.Vx = Vx; fz.oy = dg->pad_top; fz.ox = dg->pad_left; fz.pad_mode = dg->pad_mode;
-  fz.pad_value = dg->pad_value; fz.ylim = Tg; fz.xlim = Tg; fz.ext_y = 1 << 30; fz.ext_x = 1 << 30;
-  fz.pack = pack; fz.cpt = cpt; fz.tgx = tgx;
-  if (pack > 1) { fz.cstride = cpt; fz.cvalid = cpt; }
-  FwdParams fxm = fz;                                    // x tiles: own Vy x Vx values (boundary-condition padded where the grid is the padded domain)
+  // dz windows with halo: the data gradient's input transform
+  FwdParams fz = image_fwd_params(g, dz, zs, dg->H, dg->W, dg->Cin, dg->ldx, gz, dg->pad_top, dg->pad_left, dg->pad_mode, dg->pad_value);
+  // x tiles: own Vy x Vx values (boundary-condition padded where the grid is the padded domain), inside the data gradient's extent
   const bool padded_domain = d->pad_mode != PCNN_PAD_CONSTANT;
-  fxm.x = x; fxm.sp = xs; fxm.H = d->H; fxm.W = d->W; fxm.C = d->Cin; fxm.ld = d->ldx; fxm.groups = gx;
-  fxm.oy = padded_domain ? d->pad_top : 0; fxm.ox = padded_domain ? d->pad_left : 0; fxm.pad_mode = d->pad_mode; fxm.pad_value = 0.f;
-  fxm.ylim = Vy; fxm.xlim = Vx; fxm.ext_y = dg->Ho; fxm.ext_x = dg->Wo;
-  InvParams iv;
-  iv.sp = ys; iv.tab = gm.tab; iv.y = dx; iv.bias = nullptr; iv.bn_scale = nullptr; iv.bn_shift = nullptr; iv.res = residual; iv.act_out = nullptr; iv.absmax = nullptr;
-  iv.Ho = dg->Ho; iv.Wo = dg->Wo; iv.C = dg->Cout; iv.ldy = dg->ldy; iv.ld_res = dg->ld_res; iv.ld_act = 0; iv.groups = gx; iv.cstride = 32; iv.cvalid = 32;
-  iv.act = PCNN_ACT_LINEAR; iv.alpha = 0.f; iv.tiles_x = tiles_x; iv.tiles_y = tiles_y; iv.Vy = Vy; iv.Vx = Vx; iv.flip = 0;
-  iv.pack = pack; iv.cpt = cpt; iv.tgx = tgx;
-  if (pack > 1) { iv.cstride = cpt; iv.cvalid = cpt; }
+  FwdParams fxm = image_fwd_params(g, x, xs, d->H, d->W, d->Cin, d->ldx, gx, padded_domain ? d->pad_top : 0, padded_domain ? d->pad_left : 0, d->pad_mode, 0.f);
+  fxm.ylim = g.Vy; fxm.xlim = g.Vx; fxm.ext_y = dg->Ho; fxm.ext_x = dg->Wo;
+  InvParams iv = image_inv_params(g, ys, dx, dg->Ho, dg->Wo, dg->Cout, dg->ldy, gx, residual, dg->ld_res);
   if (post) {
     iv.gact = post->act_out; iv.ld_gact = post->ld_act_out; iv.gmode = post->act; iv.galpha = post->act_alpha;
     iv.y2 = post->raw_out; iv.ld_y2 = post->ld_raw; iv.bsum = post->dbias ? bsum : nullptr;
     if (iv.bsum && hipMemsetAsync(bsum, 0, bs_b, h->stream) != hipSuccess) PCNN_FAIL(h, "pcnn_conv2d_bwd_spectral_post: memset failed");
   }
   MixWParams mw;                                         // one pass over D^ for both gradients (spec_mixw_kernel)
-  mw.zs = zs; mw.xs = xs; mw.ys = ys; mw.part = part; mw.wsp = fsp; mw.slots = gm.slots; mw.gx = gx; mw.rows = rows; mw.nslot = nslot;
-  mw.Cz = dg->Cin; mw.cpt = cpt;
-  for (int64_t t0 = 0; t0 < ntile; t0 += chunk) {
-    const int nt = (int)std::min<int64_t>(chunk, ntile - t0);
-    fz.tile0 = (int)t0; fxm.tile0 = (int)t0; iv.tile0 = (int)t0; mw.ntile = nt; mw.accumulate = t0 > 0;
-    launch_fwd(h, gm, fz, nt);
-    launch_fwd(h, gm, fxm, nt);
-    hipLaunchKernelGGL(spec_mixw_kernel, dim3(nslot, S / 4, gx), dim3(256), 0, h->stream, mw);
-    launch_inv(h, gm, iv, nt);
+  mw.zs = zs; mw.xs = xs; mw.ys = ys; mw.part = part; mw.wsp = fsp; mw.slots = xf.slots; mw.gx = gx; mw.rows = g.rows; mw.nslot = g.nslot;
+  mw.Cz = dg->Cin; mw.cpt = g.cpt;
+  for (int t0 = 0; t0 < g.ntile; t0 += chunk) {
+    const int nt = std::min(chunk, g.ntile - t0);
+    fz.tile0 = t0; fxm.tile0 = t0; iv.tile0 = t0; mw.ntile = nt; mw.accumulate = t0 > 0;
+    launch_fwd(h, xf, fz, nt);
+    launch_fwd(h, xf, fxm, nt);
+    hipLaunchKernelGGL(spec_mixw_kernel, dim3(g.nslot, S / 4, gx), dim3(256), 0, h->stream, mw);
+    launch_inv(h, xf, iv, nt);
   }
-  if (post && post->dbias) {
-    if (Tg == 64 && h->spectral_xform == PCNN_XFORM_FFT) launch_post_bias_fft64(h, bsum, 256, dg->Cout, post->dbias);
-    else if (Tg == 64) launch_post_bias64(h, bsum, 256, dg->Cout, post->dbias);
-    else if (h->spectral_xform == PCNN_XFORM_FFT) launch_post_bias_fft32(h, bsum, pack, cpt, dg->Cout, post->dbias);
-    else hipLaunchKernelGGL(spec_post_bias_kernel, dim3((unsigned)dg->Cout), dim3(256), 0, h->stream, bsum, 256 * 8, pack, cpt, post->dbias);
-  }
+  if (post && post->dbias) xf.post_bias(h, bsum, g.pack, g.cpt, dg->Cout, post->dbias);
   float* csp = wsp;                                      // the workspace's filter-spectrum slot: every mixing launch above has read it (same stream), or the spectrum came from the cache
-  hipLaunchKernelGGL(spec_wcombine_kernel, dim3(nslot, gx), dim3(256), 0, h->stream, part, gm.slots, csp, S, gx, d->Cin, -1.0f, cpt, rows);
-  launch_inv(h, gm, taps_params(gm, csp, dw, d->kh, d->kw, d->Cin, d->Cout, 1), 1);
+  hipLaunchKernelGGL(spec_wcombine_kernel, dim3(g.nslot, gx), dim3(256), 0, h->stream, part, xf.slots, csp, S, gx, d->Cin, -1.0f, g.cpt, g.rows);
+  launch_inv(h, xf, taps_params(xf, csp, dw, d->kh, d->kw, d->Cin, d->Cout, 1), 1);
   PCNN_CHECK_LAUNCH(h, "pcnn_conv2d_bwd_spectral");
   return 0;
 }

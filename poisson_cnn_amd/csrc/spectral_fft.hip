@@ -982,33 +982,23 @@ __global__ __launch_bounds__(256) void fft64_post_bias_kernel(const float* __res
 }
 
 constexpr size_t LDS64_BYTES = LDS_BYTES + 128 * sizeof(float);       // + the twiddle table of the radix-4 step
-template <typename K>
-void set_lds(K kernel, size_t bytes = LDS_BYTES) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); }
-
-template <bool TANH, bool RES, bool POST>
-void launch_inv_t(pcnn_handle h, const InvParams& p, const dim3& grid) {
-  set_lds(fft32_inv_kernel<TANH, RES, POST>);
-  hipLaunchKernelGGL((fft32_inv_kernel<TANH, RES, POST>), grid, dim3(1024), LDS_BYTES, h->stream, p);
-}
-
-}  // namespace
 
 // persistent kernels: one 16-wave workgroup per CU (128 KB of LDS) walking the (tile, channel group) items
 void launch_fwd_fft32(pcnn_handle h, FwdParams p, int ntile) {
   p.ntile = ntile;
   const dim3 grid((unsigned)std::min(ntile * p.groups, 256));
   if (p.ylim < T || p.xlim < T) {
-    set_lds(fft32_fwd_kernel<true>);
+    set_lds(fft32_fwd_kernel<true>, LDS_BYTES);
     hipLaunchKernelGGL((fft32_fwd_kernel<true>), grid, dim3(1024), LDS_BYTES, h->stream, p);
   } else {
-    set_lds(fft32_fwd_kernel<false>);
+    set_lds(fft32_fwd_kernel<false>, LDS_BYTES);
     hipLaunchKernelGGL((fft32_fwd_kernel<false>), grid, dim3(1024), LDS_BYTES, h->stream, p);
   }
 }
 
 // `count` filters (table entries in device memory, ntile = 1 each) in one launch; max_items: the largest groups value among them
 void launch_fwd_fft32_multi(pcnn_handle h, const FwdParams* tab, int count, int max_items) {
-  set_lds(fft32_fwd_multi_kernel);
+  set_lds(fft32_fwd_multi_kernel, LDS_BYTES);
   hipLaunchKernelGGL(fft32_fwd_multi_kernel, dim3((unsigned)std::min(max_items, 64), (unsigned)count), dim3(1024), LDS_BYTES, h->stream, tab);
 }
 void launch_fwd_fft64_multi(pcnn_handle h, const FwdParams* tab, int count, int max_items) {
@@ -1017,9 +1007,11 @@ void launch_fwd_fft64_multi(pcnn_handle h, const FwdParams* tab, int count, int 
   hipLaunchKernelGGL(fft64_fwd_multi_kernel, dim3((unsigned)std::min((nvirt + 15) & ~15, 64), (unsigned)count), dim3(512), LDS64_BYTES, h->stream, tab);
 }
 
-// POST partial sums of the 32-point FFT inverse -> dbias
 void launch_post_bias_fft32(pcnn_handle h, const float* bsum, int pack, int cpt, int C, float* dbias) {
-  hipLaunchKernelGGL(fft32_post_bias_kernel, dim3((unsigned)C), dim3(256), 0, h->stream, bsum, 256 * FFT_WAVES, pack, cpt, dbias);
+  hipLaunchKernelGGL(fft32_post_bias_kernel, dim3((unsigned)C), dim3(256), 0, h->stream, bsum, XFORM_FFT32.post_slots, pack, cpt, dbias);
+}
+void launch_post_bias_fft64(pcnn_handle h, const float* bsum, int, int, int C, float* dbias) {
+  hipLaunchKernelGGL(fft64_post_bias_kernel, dim3((unsigned)C), dim3(256), 0, h->stream, bsum, POST_BLOCKS, dbias);
 }
 
 void launch_fwd_fft64(pcnn_handle h, FwdParams p, int ntile) {
@@ -1037,50 +1029,37 @@ void launch_fwd_fft64(pcnn_handle h, FwdParams p, int ntile) {
   }
 }
 
-template <bool TANH, bool RES, bool POST>
-static void launch_inv64_t(pcnn_handle h, const InvParams& p, const dim3& grid, int nvirt) {
-  set_lds(fft64_inv_kernel<TANH, RES, POST>, LDS64I_BYTES);
-  hipLaunchKernelGGL((fft64_inv_kernel<TANH, RES, POST>), grid, dim3(512), LDS64I_BYTES, h->stream, p, nvirt);
-}
-
 void launch_inv_fft64(pcnn_handle h, InvParams p, int ntile) {
   p.ntile = ntile;
   const int ntg = ntile * p.groups;
   const int nvirt = 2 * ((ntg + 7) & ~7);
   const dim3 grid((unsigned)std::min((nvirt + 15) & ~15, 256));
-  if (p.gact) {
-    p.alpha = 1.f;
-    p.galpha = p.gmode == PCNN_ACT_LINEAR ? 1.f : (p.gmode == PCNN_ACT_RELU ? 0.f : p.galpha);
-    if (p.res) launch_inv64_t<false, true, true>(h, p, grid, nvirt); else launch_inv64_t<false, false, true>(h, p, grid, nvirt);
-    return;
-  }
-  if (p.act == PCNN_ACT_TANH) {
-    if (p.res) launch_inv64_t<true, true, false>(h, p, grid, nvirt); else launch_inv64_t<true, false, false>(h, p, grid, nvirt);
-  } else {
-    p.alpha = p.act == PCNN_ACT_LINEAR ? 1.f : (p.act == PCNN_ACT_RELU ? 0.f : p.alpha);
-    if (p.res) launch_inv64_t<false, true, false>(h, p, grid, nvirt); else launch_inv64_t<false, false, false>(h, p, grid, nvirt);
-  }
-}
-
-void launch_post_bias_fft64(pcnn_handle h, const float* bsum, int nblocks, int C, float* dbias) {
-  hipLaunchKernelGGL(fft64_post_bias_kernel, dim3((unsigned)C), dim3(256), 0, h->stream, bsum, nblocks, dbias);
+  dispatch_epilogue(p, [&](auto TANH, auto RES, auto POST, const InvParams& q) {
+    constexpr auto kernel = fft64_inv_kernel<TANH.value, RES.value, POST.value>;
+    set_lds(kernel, LDS64I_BYTES);
+    hipLaunchKernelGGL(kernel, grid, dim3(512), LDS64I_BYTES, h->stream, q, nvirt);
+  });
 }
 
 void launch_inv_fft32(pcnn_handle h, InvParams p, int ntile) {
   p.ntile = ntile;
   const dim3 grid((unsigned)std::min(ntile * p.groups, 256));
-  if (p.gact) {                                                      // data gradient + the producer's activation backward (linear conv epilogue)
-    p.alpha = 1.f;
-    p.galpha = p.gmode == PCNN_ACT_LINEAR ? 1.f : (p.gmode == PCNN_ACT_RELU ? 0.f : p.galpha);
-    if (p.res) launch_inv_t<false, true, true>(h, p, grid); else launch_inv_t<false, false, true>(h, p, grid);
-    return;
-  }
-  if (p.act == PCNN_ACT_TANH) {
-    if (p.res) launch_inv_t<true, true, false>(h, p, grid); else launch_inv_t<true, false, false>(h, p, grid);
-  } else {
-    p.alpha = p.act == PCNN_ACT_LINEAR ? 1.f : (p.act == PCNN_ACT_RELU ? 0.f : p.alpha);     // slope of the negative side
-    if (p.res) launch_inv_t<false, true, false>(h, p, grid); else launch_inv_t<false, false, false>(h, p, grid);
-  }
+  dispatch_epilogue(p, [&](auto TANH, auto RES, auto POST, const InvParams& q) {
+    constexpr auto kernel = fft32_inv_kernel<TANH.value, RES.value, POST.value>;
+    set_lds(kernel, LDS_BYTES);
+    hipLaunchKernelGGL(kernel, grid, dim3(1024), LDS_BYTES, h->stream, q);
+  });
 }
+
+}  // namespace
+
+// the FFT family writes its rows in the interleaved order (block size SP_P); its workgroups have 16 waves (32 points) / 8 waves (64 points), one POST
+// slot per (workgroup, wave)
+#ifndef __HIP_DEVICE_COMPILE__       // host data (launcher addresses): not for the device pass
+const Xform XFORM_FFT32 = {PCNN_XFORM_FFT, T, ROWS, ROWS / 2, SP_P, O_TAB32, O_SLOTS32F, launch_fwd_fft32, launch_inv_fft32, launch_post_bias_fft32,
+                           launch_fwd_fft32_multi, POST_BLOCKS * 16, nullptr, nullptr};
+const Xform XFORM_FFT64 = {PCNN_XFORM_FFT, T64, ROWS64, ROWS64 / 2, SP_P, O_TAB64, O_SLOTS64F, launch_fwd_fft64, launch_inv_fft64, launch_post_bias_fft64,
+                           launch_fwd_fft64_multi, POST_BLOCKS * 8, nullptr, nullptr};
+#endif
 
 }  // namespace pcnn_spec
