@@ -445,6 +445,20 @@ int pcnn_spp_max_bwd(pcnn_handle h, int N, int H, int W, int C, int nb, const in
 /* Jacobi post-smoother (layers/JacobiIterationLayer.py:43-66), 3x3 second-order stencil, one sweep */
 int pcnn_jacobi_sweep(pcnn_handle h, int N, int H, int W, const float* u, const float* rhs, const float* dx /*N x 2*/, float* out);
 int pcnn_jacobi_sweep_bwd(pcnn_handle h, int N, int H, int W, const float* dout, const float* dx /*N x 2*/, float* du);
+/* The same smoother for any cross-shaped FD stencil (layers/JacobiIterationLayer.py:7-41: odd `stencil_sizes` per axis, any `orders`), n_sweeps sweeps
+ * per call (:57-66) with several sweeps fused into one launch by temporal blocking in LDS.  sy taps along H and sx along W, both
+ * odd in 3..9.  coef holds one row per sample as the layer composes its kernel (:43-46): the sy H-taps and the sx W-taps of (L+U) - centre entries
+ * zero - then 1 / diagonal.  One sweep: out = coef[sy+sx] * (rhs - taps . u) where sy/2 <= y < H - sy/2 and sx/2 <= x < W - sx/2, out = u on the ring
+ * (:48-52).  The result does not depend on how the sweeps are split into launches.  out must not alias u or rhs.  A call that needs more than one
+ * launch (n_sweeps > pcnn_jacobi_fused_max_sweeps) keeps one intermediate image in the handle's auxiliary scratch. */
+int pcnn_jacobi_fused_fwd(pcnn_handle h, int N, int H, int W, int sy, int sx, const float* coef /*N x (sy+sx+1)*/, const float* u, const float* rhs,
+                          int n_sweeps, float* out);
+/* adjoint of those n_sweeps sweeps w.r.t. u (the guess): du = J^T dout.  du must not alias dout. */
+int pcnn_jacobi_fused_bwd(pcnn_handle h, int N, int H, int W, int sy, int sx, const float* coef /*N x (sy+sx+1)*/, const float* dout, int n_sweeps,
+                          float* du);
+/* the edge of the square output tile one workgroup owns, and the most sweeps one launch fuses for an sy x sx stencil */
+int pcnn_jacobi_fused_tile(void);
+int pcnn_jacobi_fused_max_sweeps(int sy, int sx);
 
 /* ---- loss (losses/loss_wrapper.py:53-71, losses/integral_loss.py:126-179) --------------------------------------
  * per-sample partial sums: out[n] = {sum|p-t|, sum (p-t)^2, sum G*(p-t)^2, max|t|}; G is the (H,W) quadrature map.
@@ -471,6 +485,12 @@ int pcnn_loss_coefficients_p(pcnn_handle h, int N, int64_t hw, const float* part
 int pcnn_pi_loss_partials(pcnn_handle h, int N, int H, int W, int s, const float* pred, const float* rhs, const float* kern, float* out /*N*/);
 int pcnn_pi_loss_bwd(pcnn_handle h, int N, int H, int W, int s, const float* pred, const float* rhs, const float* kern,
                      const float* coef /*N*/, float* dpred);
+/* The same two for a rectangular stencil (losses/physics_informed_loss.py:6-50 takes any `stencil_sizes`): kern (N, sy, sx), the interior is
+ * sy/2 <= y < H - sy/2, sx/2 <= x < W - sx/2.  The entry points above are these with sy == sx == s. */
+int pcnn_pi_loss_partials_rect(pcnn_handle h, int N, int H, int W, int sy, int sx, const float* pred, const float* rhs, const float* kern,
+                               float* out /*N*/);
+int pcnn_pi_loss_bwd_rect(pcnn_handle h, int N, int H, int W, int sy, int sx, const float* pred, const float* rhs, const float* kern,
+                          const float* coef /*N*/, float* dpred);
 
 /* ---- optimizer: tf.keras.optimizers.Adam (train/utils.py:3-8), flat parameter bucket ---------------------------- */
 int pcnn_adam_step(pcnn_handle h, int64_t n, float* w, const float* g, float* m, float* v, float lr, float beta1, float beta2,

@@ -238,21 +238,21 @@ __global__ void loss_bwd_kernel(int N, int64_t hw, const float* __restrict__ pre
   }
 }
 
-// FD-Laplacian residual: out[n] = sum over interior of (rhs - sum_{ij} kern[n,i,j] pred[y+i-s/2, x+j-s/2])^2
-__global__ __launch_bounds__(1024) void pi_partials_kernel(int H, int W, int s, const float* __restrict__ pred, const float* __restrict__ rhs,
+// FD-Laplacian residual: out[n] = sum over interior of (rhs - sum_{ij} kern[n,i,j] pred[y+i-sy/2, x+j-sx/2])^2
+__global__ __launch_bounds__(1024) void pi_partials_kernel(int H, int W, int sy, int sx, const float* __restrict__ pred, const float* __restrict__ rhs,
                                                            const float* __restrict__ kern, float* __restrict__ out) {
   __shared__ float red[1024];
-  const int n = blockIdx.x, hs = s / 2, Hi = H - 2 * hs, Wi = W - 2 * hs;
-  const float* kn = kern + (int64_t)n * s * s;
+  const int n = blockIdx.x, hy = sy / 2, hx = sx / 2, Hi = H - 2 * hy, Wi = W - 2 * hx;
+  const float* kn = kern + (int64_t)n * sy * sx;
   const float* pn = pred + (int64_t)n * H * W;
   float acc = 0.f;
   for (int64_t q = threadIdx.x; q < (int64_t)Hi * Wi; q += blockDim.x) {
-    const int yy = q / Wi + hs, xx = q % Wi + hs;
+    const int yy = q / Wi + hy, xx = q % Wi + hx;
     float lap = 0.f;
-    for (int i = 0; i < s; ++i)
-      for (int j = 0; j < s; ++j) {
-        const float kv = kn[i * s + j];
-        if (kv != 0.f) lap = fmaf(kv, pn[(int64_t)(yy + i - hs) * W + xx + j - hs], lap);
+    for (int i = 0; i < sy; ++i)
+      for (int j = 0; j < sx; ++j) {
+        const float kv = kn[i * sx + j];
+        if (kv != 0.f) lap = fmaf(kv, pn[(int64_t)(yy + i - hy) * W + xx + j - hx], lap);
       }
     const float e = rhs[(int64_t)n * H * W + (int64_t)yy * W + xx] - lap;
     acc += e * e;
@@ -266,29 +266,29 @@ __global__ __launch_bounds__(1024) void pi_partials_kernel(int H, int W, int s, 
   if (threadIdx.x == 0) out[n] = red[0];
 }
 
-// dpred[n,y,x] += coef[n] * sum over interior cells (Y,X) touching (y,x): -2 e(Y,X) kern[n, y-Y+hs, x-X+hs]
-__global__ void pi_bwd_kernel(int N, int H, int W, int s, const float* __restrict__ pred, const float* __restrict__ rhs, const float* __restrict__ kern,
-                              const float* __restrict__ coef, float* __restrict__ dpred) {
-  const int hs = s / 2;
+// dpred[n,y,x] += coef[n] * sum over interior cells (Y,X) touching (y,x): -2 e(Y,X) kern[n, y-Y+hy, x-X+hx]
+__global__ void pi_bwd_kernel(int N, int H, int W, int sy, int sx, const float* __restrict__ pred, const float* __restrict__ rhs,
+                              const float* __restrict__ kern, const float* __restrict__ coef, float* __restrict__ dpred) {
+  const int hy = sy / 2, hx = sx / 2;
   const int64_t total = (int64_t)N * H * W;
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
     const int xx = idx % W; const int yy = (idx / W) % H; const int n = idx / ((int64_t)H * W);
-    const float* kn = kern + (int64_t)n * s * s;
+    const float* kn = kern + (int64_t)n * sy * sx;
     const float* pn = pred + (int64_t)n * H * W;
     float acc = 0.f;
-    for (int i = 0; i < s; ++i) {
-      const int Y = yy - (i - hs);
-      if (Y < hs || Y >= H - hs) continue;
-      for (int j = 0; j < s; ++j) {
-        const int X = xx - (j - hs);
-        if (X < hs || X >= W - hs) continue;
-        const float kv = kn[i * s + j];
+    for (int i = 0; i < sy; ++i) {
+      const int Y = yy - (i - hy);
+      if (Y < hy || Y >= H - hy) continue;
+      for (int j = 0; j < sx; ++j) {
+        const int X = xx - (j - hx);
+        if (X < hx || X >= W - hx) continue;
+        const float kv = kn[i * sx + j];
         if (kv == 0.f) continue;
         float lap = 0.f;
-        for (int a = 0; a < s; ++a)
-          for (int b = 0; b < s; ++b) {
-            const float k2 = kn[a * s + b];
-            if (k2 != 0.f) lap = fmaf(k2, pn[(int64_t)(Y + a - hs) * W + X + b - hs], lap);
+        for (int a = 0; a < sy; ++a)
+          for (int b = 0; b < sx; ++b) {
+            const float k2 = kn[a * sx + b];
+            if (k2 != 0.f) lap = fmaf(k2, pn[(int64_t)(Y + a - hy) * W + X + b - hx], lap);
           }
         const float e = rhs[(int64_t)n * H * W + (int64_t)Y * W + X] - lap;
         acc += -2.0f * e * kv;
@@ -438,19 +438,29 @@ extern "C" int pcnn_loss_bwd(pcnn_handle h, int N, int64_t hw, const float* pred
   return pcnn_loss_bwd_p(h, N, hw, pred, target, G, c_mae, c_mse, c_int, 2.0f, dpred);
 }
 
-extern "C" int pcnn_pi_loss_partials(pcnn_handle h, int N, int H, int W, int s, const float* pred, const float* rhs, const float* kern, float* out) {
-  PCNN_REQUIRE(h, h && pred && rhs && kern && out && s % 2 == 1 && H > s && W > s, "pcnn_pi_loss_partials: bad argument");
-  hipLaunchKernelGGL(pi_partials_kernel, dim3(N), dim3(1024), 0, h->stream, H, W, s, pred, rhs, kern, out);
+extern "C" int pcnn_pi_loss_partials_rect(pcnn_handle h, int N, int H, int W, int sy, int sx, const float* pred, const float* rhs, const float* kern,
+                                          float* out) {
+  PCNN_REQUIRE(h, h && pred && rhs && kern && out && sy >= 1 && sx >= 1 && sy % 2 == 1 && sx % 2 == 1 && H > sy && W > sx, "pcnn_pi_loss_partials: bad argument");
+  hipLaunchKernelGGL(pi_partials_kernel, dim3(N), dim3(1024), 0, h->stream, H, W, sy, sx, pred, rhs, kern, out);
   PCNN_CHECK_LAUNCH(h, "pcnn_pi_loss_partials");
+  return 0;
+}
+
+extern "C" int pcnn_pi_loss_partials(pcnn_handle h, int N, int H, int W, int s, const float* pred, const float* rhs, const float* kern, float* out) {
+  return pcnn_pi_loss_partials_rect(h, N, H, W, s, s, pred, rhs, kern, out);
+}
+
+extern "C" int pcnn_pi_loss_bwd_rect(pcnn_handle h, int N, int H, int W, int sy, int sx, const float* pred, const float* rhs, const float* kern,
+                                     const float* coef, float* dpred) {
+  PCNN_REQUIRE(h, h && pred && rhs && kern && coef && dpred && sy >= 1 && sx >= 1 && sy % 2 == 1 && sx % 2 == 1 && H > sy && W > sx, "pcnn_pi_loss_bwd: bad argument");
+  hipLaunchKernelGGL(pi_bwd_kernel, grid1d((int64_t)N * H * W), dim3(256), 0, h->stream, N, H, W, sy, sx, pred, rhs, kern, coef, dpred);
+  PCNN_CHECK_LAUNCH(h, "pcnn_pi_loss_bwd");
   return 0;
 }
 
 extern "C" int pcnn_pi_loss_bwd(pcnn_handle h, int N, int H, int W, int s, const float* pred, const float* rhs, const float* kern, const float* coef,
                                 float* dpred) {
-  PCNN_REQUIRE(h, h && pred && rhs && kern && coef && dpred && s % 2 == 1 && H > s && W > s, "pcnn_pi_loss_bwd: bad argument");
-  hipLaunchKernelGGL(pi_bwd_kernel, grid1d((int64_t)N * H * W), dim3(256), 0, h->stream, N, H, W, s, pred, rhs, kern, coef, dpred);
-  PCNN_CHECK_LAUNCH(h, "pcnn_pi_loss_bwd");
-  return 0;
+  return pcnn_pi_loss_bwd_rect(h, N, H, W, s, s, pred, rhs, kern, coef, dpred);
 }
 
 // ---- loss_wrapper bookkeeping (losses/loss_wrapper.py:45-71) on the N per-sample partial sums

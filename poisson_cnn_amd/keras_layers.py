@@ -505,16 +505,15 @@ class MergeWithAttention(_Layer):
 
 
 class JacobiIterationLayer(_Layer):
-    """layers/JacobiIterationLayer.py:7-66 for the model's second-order 3-point stencils: n_iterations weighted-Jacobi sweeps
-    new = D^-1 (rhs - (L+U) guess) on the interior, the boundary ring kept; call([guess, rhs, dx]), dx (N, 2) or (N, 1)."""
+    """layers/JacobiIterationLayer.py:7-66: n_iterations weighted-Jacobi sweeps new = D^-1 (rhs - (L+U) guess) on the interior of the FD operator
+    build_fd_coefficients(stencil_sizes, orders), the boundary ring of width stencil//2 kept; call([guess, rhs, dx]), dx (N, 2) or (N, 1).
+    stencil_sizes: odd, 3..9 per axis; orders: even, >= 2, below the axis's stencil size (layers.JacobiIterationLayer); an int means both axes."""
 
     def __init__(self, stencil_sizes, orders, ndims=None, data_format='channels_first', n_iterations=5, device=None):
         super().__init__(data_format, device)
-        ss = [stencil_sizes] * 2 if isinstance(stencil_sizes, int) else list(stencil_sizes)
-        od = [orders] * 2 if isinstance(orders, int) else list(orders)
-        if (ndims not in (None, 2)) or ss != [3, 3] or od != [2, 2]:
-            raise NotImplementedError('JacobiIterationLayer is implemented for stencil_sizes [3,3], orders [2,2] (models/Homogeneous_Poisson_NN_Legacy.py:104)')
-        self.layer = L.JacobiIterationLayer(n_iterations)
+        if ndims not in (None, 2):
+            raise NotImplementedError('JacobiIterationLayer: 2-D only')
+        self.layer = L.JacobiIterationLayer(n_iterations, stencil_sizes, orders)
         self.built = True
 
     def call(self, inputs, training=False):

@@ -759,20 +759,75 @@ class Scaling:
 
 
 class JacobiIterationLayer:
-    """layers/JacobiIterationLayer.py:7-66 for the model's ([3,3],[2,2]) stencil."""
+    """layers/JacobiIterationLayer.py:7-66: n_iterations weighted-Jacobi sweeps new = D^-1 (rhs - (L+U) guess) of the cross-shaped FD operator
+    build_fd_coefficients(stencil_sizes, orders) scaled per sample by (1/dx)**orders, the ring of width stencil//2 kept.
 
-    def __init__(self, n_iterations=5):
+    The model's stencil ([3,3],[2,2], models/Homogeneous_Poisson_NN_Legacy.py:104) with `fused` unset runs one launch per sweep, as it always has.
+    Any other stencil, or fused=True, runs csrc/stencil.hip: up to ops.jacobi_k_max(sy, sx) sweeps per launch, blocked in LDS.
+    Orders must be even, at least 2 and below that axis's stencil size: an odd order has a zero centre coefficient (the reference divides by it and
+    returns inf), and the Vandermonde system of get_fd_coefficients has no row for an order >= the stencil size."""
+
+    def __init__(self, n_iterations=5, stencil_sizes=(3, 3), orders=(2, 2), fused=None):
+        from .losses import get_fd_coefficients
         self.n = int(n_iterations)
+        ss = [stencil_sizes] * 2 if isinstance(stencil_sizes, (int, np.integer)) else list(stencil_sizes)
+        od = [orders] * 2 if isinstance(orders, (int, np.integer)) else list(orders)
+        if len(ss) != 2 or len(od) != 2:
+            raise ValueError('JacobiIterationLayer: 2-D only - stencil_sizes and orders take an int or two entries, got %r / %r' % (stencil_sizes, orders))
+        for d, (sz, o) in enumerate(zip(ss, od)):
+            if int(sz) != sz or int(o) != o:
+                raise ValueError('JacobiIterationLayer: stencil_sizes and orders must be integers, got %r / %r' % (stencil_sizes, orders))
+            if sz % 2 != 1 or not 3 <= sz <= 9:
+                raise ValueError('JacobiIterationLayer: stencil_sizes must be odd and in 3..9, got %r' % (ss,))
+            if o >= sz:
+                raise ValueError('JacobiIterationLayer: order %d needs a stencil of more than %d points along axis %d' % (o, sz, d))
+            if o < 2 or o % 2 != 0:
+                raise ValueError('JacobiIterationLayer: order %d along axis %d has a zero centre coefficient, the Jacobi diagonal would be singular '
+                                 '(orders must be even and >= 2)' % (o, d))
+        self.stencil_sizes, self.orders = [int(v) for v in ss], [int(v) for v in od]
+        self.fused = bool(fused) if fused is not None else (self.stencil_sizes != [3, 3] or self.orders != [2, 2])
+        if not self.fused and (self.stencil_sizes != [3, 3] or self.orders != [2, 2]):
+            raise ValueError('JacobiIterationLayer: fused=False exists for the ([3,3],[2,2]) stencil only')
+        # build_fd_coefficients is cross-shaped: axis d contributes one line of taps through the centre
+        lines = [get_fd_coefficients(list(range(-(sz // 2), sz // 2 + 1)), o) for sz, o in zip(self.stencil_sizes, self.orders)]
+        self._diag = np.array([ln[len(ln) // 2] for ln in lines], dtype=np.float32)
+        for ln in lines:
+            ln[len(ln) // 2] = 0.0
+        self._taps = [ln.astype(np.float32) for ln in lines]
+        self._consts = {}
+        self.dx2 = self.coef = None
+
+    def coefficient_rows(self, dx2):
+        """(N, sy+sx+1) float32 on dx2's device: per sample the H taps and the W taps of (L+U) - centres zero - then 1 / diagonal, composed as
+        layers/JacobiIterationLayer.py:43-46 does: (1/dx)**orders weights the axes' coefficient lines."""
+        key = str(dx2.device)
+        c = self._consts.get(key)
+        if c is None:
+            mk = lambda a: torch.tensor(np.asarray(a, dtype=np.float32), device=dx2.device)
+            c = self._consts[key] = (mk(self._taps[0]), mk(self._taps[1]), mk(self._diag), mk(self.orders))
+        ty, tx, diag, od = c
+        dxp = (1.0 / dx2.to(torch.float32)) ** od                                       # (N, 2)
+        dinv = 1.0 / (dxp * diag).sum(dim=1, keepdim=True)
+        return torch.cat([dxp[:, 0:1] * ty, dxp[:, 1:2] * tx, dinv], dim=1).contiguous()
 
     def forward(self, guess, rhs, dx2, training=True):
-        u = guess
-        for _ in range(self.n):
-            u = ops.jacobi_sweep(u, rhs, dx2)
-        self.dx2 = dx2
-        return u
+        if not self.fused:
+            u = guess
+            for _ in range(self.n):
+                u = ops.jacobi_sweep(u, rhs, dx2)
+            self.dx2 = dx2
+            return u
+        if self.n < 1:
+            return guess
+        self.coef = self.coefficient_rows(dx2)
+        return ops.jacobi_fused(guess, rhs, self.coef, self.stencil_sizes, self.n)
 
     def backward(self, dout):
-        d = dout
-        for _ in range(self.n):
-            d = ops.jacobi_sweep_bwd(d, self.dx2)
-        return d
+        if not self.fused:
+            d = dout
+            for _ in range(self.n):
+                d = ops.jacobi_sweep_bwd(d, self.dx2)
+            return d
+        if self.n < 1:
+            return dout
+        return ops.jacobi_fused_bwd(dout, self.coef, self.stencil_sizes, self.n)

@@ -103,8 +103,6 @@ class loss_wrapper:
         self.lp = float(self.integral_loss.Lp_norm_power)      # exponent of the integral term (integral_loss.py:153) and of its peak scaling (:68)
         pcfg = {k: v for k, v in physics_informed_loss_config.items() if k not in ('ndims', 'data_format')}
         self.pi_stencil = build_fd_coefficients(pcfg.get('stencil_sizes', 5), pcfg.get('orders', 2), ndims)
-        if self.pi_stencil.shape[1] != self.pi_stencil.shape[2]:
-            raise NotImplementedError('physics-informed loss: square stencils only')
         self.pi_normalize = bool(pcfg.get('normalize', False))
         self.pi_domain_norm = bool(pcfg.get('inputs_have_max_domain_size_squared_normalization', False))
         self._last = None
@@ -133,9 +131,9 @@ class loss_wrapper:
         if self.physics_informed_loss_weight != 0.0:
             rhs = rhs.to(device=dev, dtype=torch.float32).contiguous()
             kern = self._pi_kernels(dx.to(dev), H, W)
-            s = kern.shape[-1]
+            sy, sx = kern.shape[-2], kern.shape[-1]
             sums = ops.pi_loss_partials(y_pred, rhs, kern)
-            coef = torch.full((N,), self.physics_informed_loss_weight / float(N * (H - 2 * (s // 2)) * (W - 2 * (s // 2))), device=dev)
+            coef = torch.full((N,), self.physics_informed_loss_weight / float(N * (H - 2 * (sy // 2)) * (W - 2 * (sx // 2))), device=dev)
             if self.pi_normalize:
                 coef = coef / rhs.abs().amax(dim=(1, 2, 3)) ** 2
             extra = (coef * sums).sum().reshape(1)

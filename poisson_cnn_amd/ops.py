@@ -979,6 +979,41 @@ def jacobi_sweep_bwd(dout, dx2):
     return du
 
 
+def jacobi_tile():
+    """Edge of the output tile one workgroup of the fused smoother owns (csrc/stencil.hip)."""
+    return int(_lib.load().pcnn_jacobi_fused_tile())
+
+
+def jacobi_k_max(sy, sx):
+    """The most sweeps one launch of the fused smoother runs for an sy x sx stencil; more sweeps chain launches."""
+    return int(_lib.load().pcnn_jacobi_fused_max_sweeps(int(sy), int(sx)))
+
+
+def jacobi_fused(u, rhs, coef, stencil_sizes, n_sweeps):
+    """n_sweeps weighted-Jacobi sweeps of the cross-shaped stencil whose per-sample rows are `coef` (N, sy+sx+1): the H taps, the W taps (centres
+    zero), 1 / diagonal.  u, rhs (N,H,W,1)."""
+    N, H, W = u.shape[0], u.shape[1], u.shape[2]
+    sy, sx = int(stencil_sizes[0]), int(stencil_sizes[1])
+    if tuple(coef.shape) != (N, sy + sx + 1) or not coef.is_contiguous():
+        raise ValueError('jacobi_fused: coef must be a contiguous (%d, %d) tensor' % (N, sy + sx + 1))
+    u, rhs = u.contiguous(), rhs.contiguous()
+    out = torch.empty_like(u)
+    handle().call('pcnn_jacobi_fused_fwd', c_int(N), c_int(H), c_int(W), c_int(sy), c_int(sx), _p(coef), _p(u), _p(rhs), c_int(n_sweeps), _p(out))
+    return out
+
+
+def jacobi_fused_bwd(dout, coef, stencil_sizes, n_sweeps):
+    """The adjoint of jacobi_fused w.r.t. u."""
+    N, H, W = dout.shape[0], dout.shape[1], dout.shape[2]
+    sy, sx = int(stencil_sizes[0]), int(stencil_sizes[1])
+    if tuple(coef.shape) != (N, sy + sx + 1) or not coef.is_contiguous():
+        raise ValueError('jacobi_fused_bwd: coef must be a contiguous (%d, %d) tensor' % (N, sy + sx + 1))
+    dout = dout.contiguous()
+    du = torch.empty_like(dout)
+    handle().call('pcnn_jacobi_fused_bwd', c_int(N), c_int(H), c_int(W), c_int(sy), c_int(sx), _p(coef), _p(dout), c_int(n_sweeps), _p(du))
+    return du
+
+
 # ----------------------------------------------------------------------------- loss / optimizer
 def loss_partials(pred, target, G, lp_power=2.0):
     N = pred.shape[0]
@@ -996,15 +1031,17 @@ def loss_bwd(pred, target, G, c_mae, c_mse, c_int_, out=None, lp_power=2.0):
 
 
 def pi_loss_partials(pred, rhs, kern):
+    """kern (N, sy, sx): one stencil per sample, square or rectangular."""
     N, H, W = pred.shape[0], pred.shape[-2], pred.shape[-1]   # (N,1,H,W) or (N,H,W)
     out = empty((N,), pred.device)
-    handle().call('pcnn_pi_loss_partials', c_int(N), c_int(H), c_int(W), c_int(kern.shape[-1]), _p(pred), _p(rhs), _p(kern), _p(out))
+    handle().call('pcnn_pi_loss_partials_rect', c_int(N), c_int(H), c_int(W), c_int(kern.shape[-2]), c_int(kern.shape[-1]), _p(pred), _p(rhs), _p(kern), _p(out))
     return out
 
 
 def pi_loss_bwd(pred, rhs, kern, coef, dpred):
     N, H, W = pred.shape[0], pred.shape[-2], pred.shape[-1]   # (N,1,H,W) or (N,H,W)
-    handle().call('pcnn_pi_loss_bwd', c_int(N), c_int(H), c_int(W), c_int(kern.shape[-1]), _p(pred), _p(rhs), _p(kern), _p(coef), _p(dpred))
+    handle().call('pcnn_pi_loss_bwd_rect', c_int(N), c_int(H), c_int(W), c_int(kern.shape[-2]), c_int(kern.shape[-1]), _p(pred), _p(rhs), _p(kern), _p(coef),
+                  _p(dpred))
     return dpred
 
 
