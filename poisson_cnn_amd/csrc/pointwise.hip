@@ -787,7 +787,22 @@ extern "C" int pcnn_bn_fold_bwd(pcnn_handle h, int n, const float* s_dy_a, const
 }
 
 // ---- training-mode BatchNormalization (fused semantics: biased variance normalises, unbiased variance feeds the moving average)
+// The statistics are accumulated CENTRED: fp32 sums of a and a*a lose the variance to cancellation once |mean| >> std (a saturated tanh
+// channel sits near 0.99 +- 0.005), so the forward sums d = a - K_c and d*d about a pivot K_c read from the data (mean = K + E[d],
+// var = E[d*d] - E[d]^2: the cancellation is then between terms of the size of the variance itself), the backward sums dy * (a - mean_c)
+// with the saved mean, and y is formed as (a - mean) * scale + beta.
 namespace {
+// The pivot of channel c: the average of the channel's first 8 pixels (4, 2, 1 where there are fewer), added as a binary tree.  One sample would
+// do for the variance; the average keeps |K - mean| near std/3, and with it the rounding of sum d, which is what the mean of a centred channel
+// is made of.  A power of two and a tree, so that a constant channel gives K = the constant exactly.  Every thread that needs K forms the same value.
+__device__ __forceinline__ float bn_pivot(const float* __restrict__ a, int lda, int64_t npix, int c) {
+  const int n = npix >= 8 ? 8 : npix >= 4 ? 4 : npix >= 2 ? 2 : 1;
+  float v[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) v[i] = i < n ? a[(int64_t)i * lda + c] : 0.f;
+  return (((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]))) * (1.0f / (float)n);
+}
+
 __global__ void channel_affine_kernel(int64_t npix, int C, const float* __restrict__ x, int ldx, const float* __restrict__ scale,
                                       const float* __restrict__ shift, const float* __restrict__ res, int ld_res, float* __restrict__ y, int ldy) {
   const int64_t total = npix * C;
@@ -799,26 +814,107 @@ __global__ void channel_affine_kernel(int64_t npix, int C, const float* __restri
   }
 }
 
-__global__ void bn_train_finalize_kernel(int C, float inv_n, float unbias, const float* sum_a, const float* sum_a2, const float* gamma, const float* beta,
-                                         float eps, float momentum, float* moving_mean, float* moving_var, float* mean, float* inv_std, float* scale,
-                                         float* shift) {
+// y = (a - mean) * scale + beta (+ residual); y may alias the residual (each element is read before it is written, by the same thread)
+__global__ void bn_train_apply_kernel(int64_t npix, int C, const float* __restrict__ a, int lda, const float* __restrict__ mean,
+                                      const float* __restrict__ scale, const float* __restrict__ beta, const float* res, int ld_res, float* y, int ldy) {
+  const int64_t total = npix * C;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int c = i % C; const int64_t pix = i / C;
+    float v = (a[pix * lda + c] - mean[c]) * scale[c] + beta[c];
+    if (res) v += res[pix * ld_res + c];
+    y[pix * ldy + c] = v;
+  }
+}
+
+// Per-channel sums of d = a - k_c:   g == nullptr (forward statistics):  k_c = bn_pivot,  S1 = sum d*d,  S2 = sum d
+//                                    g != nullptr (backward):            k_c = shift[c],  S1 = sum g*d,  S2 = sum g
+// Thread layout, block partials ([gridDim][3][C]; slot 0 is not used and written as 0) and summation order of epilogue_bwd_kernel, so that
+// colsum_final_kernel finishes the sums: two stages, fixed order, no atomics.
+__global__ __launch_bounds__(CS_BLOCK) void bn_shifted_sums_kernel(int64_t npix, int C, int CP, const float* __restrict__ g, int ldg,
+                                                                   const float* __restrict__ a, int lda, const float* __restrict__ shift,
+                                                                   float* __restrict__ partial /*[gridDim][3][C]*/) {
+  __shared__ float red[2][CS_BLOCK];
+  const int tid = threadIdx.x, c = tid % CP, r = tid / CP, R = CS_BLOCK / CP;
+  float s1 = 0.f, s2 = 0.f;
+  if (c < C) {
+    const float k = g ? shift[c] : bn_pivot(a, lda, npix, c);
+    for (int64_t pix = (int64_t)blockIdx.x * R + r; pix < npix; pix += (int64_t)gridDim.x * R) {
+      const float d = a[pix * lda + c] - k;
+      const float gv = g ? g[pix * ldg + c] : d;
+      s1 += gv * d; s2 += gv;
+    }
+  }
+  red[0][tid] = s1; red[1][tid] = s2;
+  __syncthreads();
+  if (r == 0 && c < C) {
+    partial[((int64_t)blockIdx.x * 3 + 0) * C + c] = 0.f;
+    for (int k = 0; k < 2; ++k) {
+      float s = 0.f;
+      for (int q = 0; q < R; ++q) s += red[k][q * CP + c];
+      partial[((int64_t)blockIdx.x * 3 + 1 + k) * C + c] = s;
+    }
+  }
+}
+
+// float4 variant (C, the channel strides and the base pointers multiples of 4 floats): thread layout of epilogue_bwd_vec4_kernel
+__global__ __launch_bounds__(CS_BLOCK) void bn_shifted_sums_vec4_kernel(int64_t npix, int C, const float* __restrict__ g, int ldg,
+                                                                        const float* __restrict__ a, int lda, const float* __restrict__ shift,
+                                                                        float* __restrict__ partial /*[gridDim][3][C]*/) {
+  __shared__ float red[2][CS_BLOCK * 4];
+  const int GQ = C >> 2, R = CS_BLOCK / GQ;
+  const int tid = threadIdx.x, r = tid / GQ, q = tid - r * GQ, c = q << 2;
+  float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
+  if (r < R) {
+    float k[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) k[j] = g ? shift[c + j] : bn_pivot(a, lda, npix, c + j);
+    for (int64_t pix = (int64_t)blockIdx.x * R + r; pix < npix; pix += (int64_t)gridDim.x * R) {
+      const float4 a4 = *reinterpret_cast<const float4*>(a + pix * lda + c);
+      const float d[4] = {a4.x - k[0], a4.y - k[1], a4.z - k[2], a4.w - k[3]};
+      float gv[4] = {d[0], d[1], d[2], d[3]};
+      if (g) {
+        const float4 g4 = *reinterpret_cast<const float4*>(g + pix * ldg + c);
+        gv[0] = g4.x; gv[1] = g4.y; gv[2] = g4.z; gv[3] = g4.w;
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { s1[j] += gv[j] * d[j]; s2[j] += gv[j]; }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { red[0][tid * 4 + j] = s1[j]; red[1][tid * 4 + j] = s2[j]; }
+  __syncthreads();
+  if (tid < C) {                       // channel tid: entries (r * GQ + tid / 4) * 4 + tid % 4 = r * C + tid
+    partial[((int64_t)blockIdx.x * 3 + 0) * C + tid] = 0.f;
+    for (int k = 0; k < 2; ++k) {
+      float s = 0.f;
+      for (int rr = 0; rr < R; ++rr) s += red[k][rr * C + tid];
+      partial[((int64_t)blockIdx.x * 3 + 1 + k) * C + tid] = s;
+    }
+  }
+}
+
+// sum_d / sum_d2: the sums of (a - K) and (a - K)^2 about K = bn_pivot
+__global__ void bn_train_finalize_kernel(int C, int64_t npix, float inv_n, float unbias, const float* a, int lda, const float* sum_d, const float* sum_d2, const float* gamma,
+                                         float eps, float momentum, float* moving_mean, float* moving_var, float* mean, float* inv_std, float* scale) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  const float m = sum_a[c] * inv_n;
-  float v = sum_a2[c] * inv_n - m * m;
+  const float md = sum_d[c] * inv_n;
+  const float m = bn_pivot(a, lda, npix, c) + md;
+  float v = sum_d2[c] * inv_n - md * md;
   if (v < 0.f) v = 0.f;
   const float is = 1.0f / sqrtf(v + eps);
   mean[c] = m; inv_std[c] = is;
-  scale[c] = gamma[c] * is; shift[c] = beta[c] - m * gamma[c] * is;
+  scale[c] = gamma[c] * is;
   moving_mean[c] = moving_mean[c] * momentum + m * (1.0f - momentum);
   moving_var[c] = moving_var[c] * momentum + v * unbias * (1.0f - momentum);
 }
 
-__global__ void bn_train_bwd_finalize_kernel(int C, float inv_n, const float* s_dy_a, const float* s_dy, const float* mean, const float* inv_std,
+// s_dy_ac = sum dy * (a - mean)
+__global__ void bn_train_bwd_finalize_kernel(int C, float inv_n, const float* s_dy_ac, const float* s_dy, const float* inv_std,
                                              float* dgamma, float* dbeta, float* c1, float* c2) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  const float dg = inv_std[c] * (s_dy_a[c] - mean[c] * s_dy[c]);   // sum dy * xhat
+  const float dg = inv_std[c] * s_dy_ac[c];   // sum dy * xhat
   dgamma[c] = dg; dbeta[c] = s_dy[c];
   c1[c] = s_dy[c] * inv_n; c2[c] = dg * inv_n;
 }
@@ -833,6 +929,26 @@ __global__ void bn_train_bwd_kernel(int64_t npix, int C, const float* __restrict
     da[pix * ldda + c] = scale[c] * (dy[pix * lddy + c] - c1[c] - xh * c2[c]);
   }
 }
+
+// launches the shifted sums of a (npix, C) tensor into s1 / s2 (C floats each)
+static int bn_shifted_sums(pcnn_handle h, const char* what, int64_t npix, int C, const float* g, int ldg, const float* a, int lda, const float* shift,
+                           float* s1, float* s2, void* workspace, size_t workspace_bytes) {
+  PCNN_REQUIRE(h, C >= 1 && C <= CS_BLOCK, "%s: C=%d unsupported", what, C);
+  PCNN_REQUIRE(h, npix > 0 && lda >= C && (!g || ldg >= C), "%s: bad shape", what);
+  PCNN_REQUIRE(h, workspace_bytes >= pcnn_colsum_workspace(C), "%s: workspace too small", what);
+  const int CP = pow2_ge(C);
+  const int nb = colsum_blocks(npix, CP);
+  float* partial = static_cast<float*>(workspace);
+  const bool vec4 = C % 4 == 0 && lda % 4 == 0 && (!g || ldg % 4 == 0) && ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(a)) & 15) == 0;
+  if (vec4)
+    hipLaunchKernelGGL(bn_shifted_sums_vec4_kernel, dim3(nb), dim3(CS_BLOCK), 0, h->stream, npix, C, g, ldg, a, lda, shift, partial);
+  else
+    hipLaunchKernelGGL(bn_shifted_sums_kernel, dim3(nb), dim3(CS_BLOCK), 0, h->stream, npix, C, CP, g, ldg, a, lda, shift, partial);
+  PCNN_CHECK_LAUNCH(h, what);
+  hipLaunchKernelGGL(colsum_final_kernel, dim3(C), dim3(256), 0, h->stream, partial, nb, C, (float*)nullptr, s1, s2);
+  PCNN_CHECK_LAUNCH(h, what);
+  return 0;
+}
 }  // namespace
 
 extern "C" int pcnn_channel_affine(pcnn_handle h, int64_t npix, int C, const float* x, int ldx, const float* scale, const float* shift,
@@ -843,24 +959,31 @@ extern "C" int pcnn_channel_affine(pcnn_handle h, int64_t npix, int C, const flo
   return 0;
 }
 
-extern "C" int pcnn_bn_train_finalize(pcnn_handle h, int C, int64_t npix, const float* sum_a, const float* sum_a2, const float* gamma, const float* beta,
-                                      float eps, float momentum, float* moving_mean, float* moving_var, float* mean, float* inv_std, float* scale,
-                                      float* shift) {
-  PCNN_REQUIRE(h, h && sum_a && sum_a2 && gamma && beta && moving_mean && moving_var && mean && inv_std && scale && shift && npix > 0,
-               "pcnn_bn_train_finalize: bad argument");
+extern "C" int pcnn_bn_train_fwd(pcnn_handle h, int64_t npix, int C, const float* a, int lda, const float* gamma, const float* beta, float eps,
+                                 float momentum, float* moving_mean, float* moving_var, float* mean, float* inv_std, float* scale, float* scratch_2C,
+                                 const float* residual, int ld_res, float* y, int ldy, void* workspace, size_t workspace_bytes) {
+  PCNN_REQUIRE(h, h && a && gamma && beta && moving_mean && moving_var && mean && inv_std && scale && scratch_2C && y && workspace,
+               "pcnn_bn_train_fwd: null argument");
+  PCNN_REQUIRE(h, ldy >= C && (!residual || ld_res >= C), "pcnn_bn_train_fwd: bad stride");
+  float* sum_d2 = scratch_2C; float* sum_d = scratch_2C + C;
+  if (int rc = bn_shifted_sums(h, "pcnn_bn_train_fwd", npix, C, nullptr, 0, a, lda, nullptr, sum_d2, sum_d, workspace, workspace_bytes)) return rc;
   const float unbias = npix > 1 ? (float)((double)npix / (double)(npix - 1)) : 1.0f;
-  hipLaunchKernelGGL(bn_train_finalize_kernel, dim3(pcnn_cdiv(C, 64)), dim3(64), 0, h->stream, C, (float)(1.0 / (double)npix), unbias, sum_a, sum_a2, gamma,
-                     beta, eps, momentum, moving_mean, moving_var, mean, inv_std, scale, shift);
-  PCNN_CHECK_LAUNCH(h, "pcnn_bn_train_finalize");
+  hipLaunchKernelGGL(bn_train_finalize_kernel, dim3(pcnn_cdiv(C, 64)), dim3(64), 0, h->stream, C, npix, (float)(1.0 / (double)npix), unbias, a, lda, sum_d, sum_d2, gamma,
+                     eps, momentum, moving_mean, moving_var, mean, inv_std, scale);
+  PCNN_CHECK_LAUNCH(h, "pcnn_bn_train_fwd(finalize)");
+  hipLaunchKernelGGL(bn_train_apply_kernel, grid1d(npix * C), dim3(256), 0, h->stream, npix, C, a, lda, mean, scale, beta, residual, ld_res, y, ldy);
+  PCNN_CHECK_LAUNCH(h, "pcnn_bn_train_fwd(apply)");
   return 0;
 }
 
 extern "C" int pcnn_bn_train_bwd(pcnn_handle h, int64_t npix, int C, const float* dy, int lddy, const float* a, int lda, const float* scale,
-                                 const float* mean, const float* inv_std, const float* s_dy_a, const float* s_dy, float* dgamma, float* dbeta,
-                                 float* scratch_2C, float* da, int ldda) {
-  PCNN_REQUIRE(h, h && dy && a && scale && mean && inv_std && s_dy_a && s_dy && dgamma && dbeta && scratch_2C && da, "pcnn_bn_train_bwd: null argument");
-  float* c1 = scratch_2C; float* c2 = scratch_2C + C;
-  hipLaunchKernelGGL(bn_train_bwd_finalize_kernel, dim3(pcnn_cdiv(C, 64)), dim3(64), 0, h->stream, C, (float)(1.0 / (double)npix), s_dy_a, s_dy, mean, inv_std,
+                                 const float* mean, const float* inv_std, float* dgamma, float* dbeta, float* scratch_4C, float* da, int ldda,
+                                 void* workspace, size_t workspace_bytes) {
+  PCNN_REQUIRE(h, h && dy && a && scale && mean && inv_std && dgamma && dbeta && scratch_4C && da && workspace, "pcnn_bn_train_bwd: null argument");
+  PCNN_REQUIRE(h, ldda >= C, "pcnn_bn_train_bwd: bad stride");
+  float* s_dy_ac = scratch_4C; float* s_dy = scratch_4C + C; float* c1 = scratch_4C + 2 * C; float* c2 = scratch_4C + 3 * C;
+  if (int rc = bn_shifted_sums(h, "pcnn_bn_train_bwd", npix, C, dy, lddy, a, lda, mean, s_dy_ac, s_dy, workspace, workspace_bytes)) return rc;
+  hipLaunchKernelGGL(bn_train_bwd_finalize_kernel, dim3(pcnn_cdiv(C, 64)), dim3(64), 0, h->stream, C, (float)(1.0 / (double)npix), s_dy_ac, s_dy, inv_std,
                      dgamma, dbeta, c1, c2);
   PCNN_CHECK_LAUNCH(h, "pcnn_bn_train_bwd(finalize)");
   hipLaunchKernelGGL(bn_train_bwd_kernel, grid1d(npix * C), dim3(256), 0, h->stream, npix, C, dy, lddy, a, lda, scale, mean, inv_std, c1, c2, da, ldda);

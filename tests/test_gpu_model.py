@@ -195,6 +195,16 @@ def test_forward_matches_committed_golden_vectors():
 
 def test_training_mode_batchnorm_train_step():
     """batchnorm_training=True: batch statistics in the forward pass, their gradient in the backward pass, moving-average update."""
+    _bn_train_step(None)
+
+
+def test_training_mode_batchnorm_train_step_off_centre():
+    """The same step with pre/conv0/bias near +3: every channel of the first BatchNormalization's input is a saturated tanh, |mean|/std in the
+    hundreds.  Statistics summed as sum a, sum a*a lose that layer's variance and the whole-step gradient with it."""
+    _bn_train_step(3.0)
+
+
+def _bn_train_step(bias0):
     from poisson_cnn_amd.losses import loss_wrapper
     from poisson_cnn_amd.train import Adam
     full = configs.hpnn_tiny()
@@ -207,6 +217,8 @@ def test_training_mode_batchnorm_train_step():
     from poisson_cnn_amd.models import Homogeneous_Poisson_NN_Legacy
     model = Homogeneous_Poisson_NN_Legacy(batchnorm_training=True, **cfg)
     p = ohpnn.init_params(cfg, seed=51, gain=1.3, randomize_all=True)
+    if bias0 is not None:
+        p['pre/conv0/bias'] = (bias0 + 0.1 * np.random.default_rng(6).standard_normal(p['pre/conv0/bias'].shape)).astype(np.float32).astype(np.float64)
     model.set_weights(p)
     rhs, dx = make_inputs(3, 48, 40, 53)
     target = np.random.default_rng(4).standard_normal(rhs.shape).astype(np.float32).astype(np.float64) * 0.1
@@ -222,9 +234,13 @@ def test_training_mode_batchnorm_train_step():
     names = model.store.trainable_names()
     flat = np.concatenate([model.store.g[n].cpu().numpy().ravel() for n in names])
     flat_ref = np.concatenate([pt[n].grad.numpy().ravel() for n in names])
+    print('whole-step gradient rel-L2', rel(flat, flat_ref))
     assert rel(flat, flat_ref) < 5e-4
     for n in ('pre/bn0/gamma', 'pre/bn0/beta', 'deconv_f3/res0/bn1/gamma'):
-        assert rel(model.store.g[n].cpu().numpy(), pt[n].grad.numpy()) < 2e-3, n
+        print(n, rel(model.store.g[n].cpu().numpy(), pt[n].grad.numpy()))
+        if bias0 is None:
+            # measured on the MI355X with the centred statistics: 1.9e-6 / 1.1e-6 / 1.0e-6 (2e-3 was allowed while the sums were uncentred); at most 4x that
+            assert rel(model.store.g[n].cpu().numpy(), pt[n].grad.numpy()) < 7.5e-6, n
     # moving statistics moved towards the batch statistics with momentum 0.99
     w1 = dict(zip(model.weight_names, model.get_weights()))
     x0 = ohpnn.forward(np_ops, cfg, p, rhs, dx, bn_training=True, taps={})   # oracle batch stats of the first BN input
