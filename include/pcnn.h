@@ -509,6 +509,51 @@ int pcnn_sgd_step(pcnn_handle h, int64_t n, float* w, const float* g, float lr, 
 int pcnn_sgd_momentum_step(pcnn_handle h, int64_t n, float* w, const float* g, float* velocity, float lr, float momentum, int nesterov,
                            float grad_scale);
 
+/* ---- gradient clipping on the flat gradient bucket: clipnorm / global_clipnorm / clipvalue of tf.keras OptimizerV2 (TF 2.4) ----------
+ * train/utils.py:3-8 hands `optimizer_parameters` to tf.keras.optimizers.Adam / SGD, which accept these.  Restated from TF 2.4
+ * (OptimizerV2._clip_gradients, tf.clip_by_norm, tf.clip_by_global_norm, tf.clip_by_value); parity unpinned like the rest of the TF arithmetic.
+ * With g = grad_scale * (the bucket's contents) and a VARIABLE = one trainable entry of the bucket (a kernel, a bias, a BN gamma or beta vector):
+ *   clipnorm c          g_v <- g_v * c / max(||g_v||_2, c)      per variable; ||g_v|| <= c (0 included): scale exactly 1.0f, the variable keeps its bits
+ *   global_clipnorm c   G = sqrt(sum_v ||g_v||^2) over every variable of every participating bucket;  g <- g * c / max(G, c);
+ *                       G not finite: every g becomes NaN (tf.clip_by_global_norm)
+ *   clipvalue c         g <- min(max(g, -c), c), after either norm clip; a NaN stays a NaN
+ * (the fourth option, decay d: the step uses lr / (1 + d t), t = updates already applied - a host scalar, poisson_cnn_amd/train.py).
+ *
+ * The PLAN (host only, no handle): the bucket's variables, in their physical order and with sizes[v] floats each, are cut into items
+ * (item_var, item_start, item_len): item_len <= PCNN_GRAD_CLIP_CHUNK, consecutive items tile each variable once, none crosses a variable
+ * boundary; var_first_item[v] .. var_first_item[v+1] are variable v's items (n_vars + 1 entries).  pcnn_grad_clip_plan_items returns the
+ * item count (-1: bad argument); pcnn_grad_clip_plan fills the caller's arrays (non-zero: bad argument).  The device entry points take
+ * DEVICE copies of these arrays.
+ *
+ * Sums: one fp32 partial per item in a fixed order (per lane, then a wave butterfly, then four wave sums from LDS), the partials of a variable
+ * added in plan order in a double, the variables of a bucket and the buckets added in order in a double.  No float atomics: a result depends
+ * on the gradient and the plan only.
+ *
+ * pcnn_grad_clip_workspace: bytes of `workspace` (8-byte aligned) for a plan.
+ * pcnn_grad_clip_norms:  two launches.  sqnorm (n_vars floats, may be NULL) receives ||g_v||^2, *total (one double, may be NULL) the bucket's
+ *                        sum of them; the workspace keeps the per-variable sums in double for pcnn_grad_clip_scales.
+ * pcnn_grad_clip_scales: one launch.  mode PER_VARIABLE: scale[v], n_vars floats, from this bucket's workspace.  mode GLOBAL: scale[0] from
+ *                        totals[0 .. n_totals) - the `total` of every participating bucket, in the caller's fixed order: this is the one extra
+ *                        launch that combines several buckets, no host round trip.  global_norm (may be NULL; needs totals): sqrt(sum of totals)
+ *                        as one float, in any mode (mode NONE: that only).
+ * pcnn_grad_clip_apply:  one launch, in place: g <- clamp((grad_scale * g) * scale, -clipvalue, clipvalue); clipvalue < 0: no clamp; mode NONE:
+ *                        scale = 1.  An item whose scale is exactly 1.0f is skipped when there is no clamp and grad_scale == 1.  The optimizer step
+ *                        that follows runs with grad_scale = 1.
+ * All device entry points are asynchronous on the handle's stream; the caller owns every buffer. */
+#define PCNN_GRAD_CLIP_CHUNK 4096          /* floats per item: 4 rounds of 256 lanes x float4 */
+#define PCNN_GRAD_CLIP_NONE 0
+#define PCNN_GRAD_CLIP_PER_VARIABLE 1
+#define PCNN_GRAD_CLIP_GLOBAL 2
+int64_t pcnn_grad_clip_plan_items(int n_vars, const int64_t* sizes);
+int pcnn_grad_clip_plan(int n_vars, const int64_t* sizes, int32_t* item_var, int64_t* item_start, int32_t* item_len, int32_t* var_first_item);
+size_t pcnn_grad_clip_workspace(int64_t n_items, int n_vars);
+int pcnn_grad_clip_norms(pcnn_handle h, const float* g, int64_t n_items, const int64_t* item_start, const int32_t* item_len, int n_vars,
+                         const int32_t* var_first_item, float grad_scale, void* workspace, float* sqnorm, double* total);
+int pcnn_grad_clip_scales(pcnn_handle h, int mode, float c, int64_t n_items, int n_vars, const void* workspace, int n_totals,
+                          const double* totals, float* scale, float* global_norm);
+int pcnn_grad_clip_apply(pcnn_handle h, float* g, int64_t n_items, const int32_t* item_var, const int64_t* item_start, const int32_t* item_len,
+                         int mode, const float* scale, float grad_scale, float clipvalue);
+
 /* ---- dataset: reference-solution generators (poisson_CNN/dataset) ------------------------------------------- */
 /* Dirichlet 5-point FD Poisson solve by DST-I diagonalisation, fp64 on the f64 matrix cores; replaces
  * multigrid_poisson_solve + poisson_RHS (dataset/solvers/multigrid.py:98-150, dataset/solvers/cholesky.py:45-119):

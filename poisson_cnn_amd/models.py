@@ -245,8 +245,11 @@ class _ModelBase:
         return self._logs(loss, mse, extra)
 
     def _extra_logs(self):
-        """Further train_step entries, computed on the synchronised gradient in front of the update (UNetModel: its gradient norm)."""
-        return {}
+        """Further train_step entries, computed on the synchronised gradient in front of the update (UNetModel: its gradient norm).  With a clip
+        option of the optimizer set: 'grad_norm', the pre-clip global gradient norm - the optimizer's own device scalar, which the update that
+        follows on the same stream fills before anything reads it."""
+        opt = self.optimizer
+        return {'grad_norm': opt.global_norm} if getattr(opt, 'clips', False) else {}
 
     @property
     def stores(self):

@@ -1065,6 +1065,105 @@ def sgd_momentum_step(w, g, v, lr, momentum, nesterov, grad_scale=1.0):
     handle().call('pcnn_sgd_momentum_step', c_int64(w.numel()), _p(w), _p(g), _p(v), c_float(lr), c_float(momentum), c_int(1 if nesterov else 0), c_float(grad_scale))
 
 
+# ----------------------------------------------------------------------------- gradient clipping (csrc/grad_clip.hip; formulas: include/pcnn.h)
+GRAD_CLIP_MODES = {None: 0, 'none': 0, 'clipnorm': 1, 'global_clipnorm': 2}
+GRAD_CLIP_CHUNK = 4096            # PCNN_GRAD_CLIP_CHUNK
+
+
+class GradClipPlan:
+    """The item table of one gradient bucket (pcnn_grad_clip_plan): host arrays item_var / item_start / item_len / var_first_item, their device
+    copies and the bucket's workspace (made on first use on a device, kept), and the outputs of the last pass: sqnorm (n_vars floats), total (one
+    double), scale (n_vars floats; global mode uses scale[0])."""
+
+    def __init__(self, sizes):
+        self.sizes = np.ascontiguousarray(np.asarray(sizes, dtype=np.int64).reshape(-1))
+        lib = _lib.load()
+        nv = self.n_vars = int(self.sizes.size)
+        ptr = lambda a: a.ctypes.data_as(c_void_p)
+        self.n_items = int(lib.pcnn_grad_clip_plan_items(c_int(nv), ptr(self.sizes)))
+        if self.n_items < 0:
+            raise ValueError('grad_clip_plan: variable sizes must be >= 0')
+        self.item_var = np.zeros(max(self.n_items, 1), np.int32)
+        self.item_start = np.zeros(max(self.n_items, 1), np.int64)
+        self.item_len = np.zeros(max(self.n_items, 1), np.int32)
+        self.var_first_item = np.zeros(nv + 1, np.int32)
+        if lib.pcnn_grad_clip_plan(c_int(nv), ptr(self.sizes), ptr(self.item_var), ptr(self.item_start), ptr(self.item_len), ptr(self.var_first_item)) != 0:
+            raise ValueError('grad_clip_plan: pcnn_grad_clip_plan rejected the sizes')
+        self.item_var, self.item_start, self.item_len = self.item_var[:self.n_items], self.item_start[:self.n_items], self.item_len[:self.n_items]
+        self.numel = int(self.sizes.sum())
+        self.workspace_bytes = int(lib.pcnn_grad_clip_workspace(c_int64(self.n_items), c_int(nv)))
+        self.device = None
+
+    def to(self, device):
+        if self.device != device:
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a) if a.size else np.zeros(1, a.dtype)).to(device)
+            self.d_item_var, self.d_item_start, self.d_item_len, self.d_var_first_item = (up(a) for a in (self.item_var, self.item_start, self.item_len,
+                                                                                                           self.var_first_item))
+            self.workspace = torch.zeros(max(self.workspace_bytes // 8, 1), dtype=torch.float64, device=device)       # float64: 8-byte aligned
+            self.sqnorm = torch.zeros(max(self.n_vars, 1), dtype=torch.float32, device=device)
+            self.scale = torch.ones(max(self.n_vars, 1), dtype=torch.float32, device=device)
+            self.total = torch.zeros(1, dtype=torch.float64, device=device)
+            self.device = device
+        return self
+
+
+def grad_clip_plan(sizes):
+    """sizes: the variables' element counts in the bucket's physical order -> GradClipPlan."""
+    return GradClipPlan(sizes)
+
+
+def _grad_clip_check(g, plan):
+    if g.dtype != torch.float32 or not g.is_cuda or not g.is_contiguous() or g.numel() != plan.numel:
+        raise ValueError('the gradient bucket must be a contiguous CUDA float32 tensor of the plan\'s %d elements' % plan.numel)
+    return plan.to(g.device)
+
+
+def grad_sqnorms(g, plan, grad_scale=1.0, total=None):
+    """||grad_scale g_v||^2 of every variable of the bucket -> plan.sqnorm (n_vars floats, returned); the bucket's sum of them -> `total` (a one-element
+    float64 tensor; default plan.total).  Asynchronous."""
+    _grad_clip_check(g, plan)
+    total = plan.total if total is None else total
+    if total.dtype != torch.float64 or total.numel() != 1 or not total.is_cuda:
+        raise ValueError('total must be a one-element CUDA float64 tensor')
+    handle().call('pcnn_grad_clip_norms', _p(g), c_int64(plan.n_items), _p(plan.d_item_start), _p(plan.d_item_len), c_int(plan.n_vars),
+                  _p(plan.d_var_first_item), c_float(grad_scale), _p(plan.workspace), _p(plan.sqnorm), _p(total))
+    return plan.sqnorm[:plan.n_vars]
+
+
+def grad_clip_scales(plan, mode, c, totals=None, scale=None, global_norm=None):
+    """The scales of `mode` ('clipnorm': plan.scale[v] per variable; 'global_clipnorm': scale[0] from `totals`, the float64 tensor holding the
+    total of every participating bucket; None: only global_norm) from what grad_sqnorms left in the plan.  global_norm: a one-element float32
+    tensor that receives sqrt(sum(totals)).  Asynchronous; returns the scale tensor."""
+    m = GRAD_CLIP_MODES[mode]
+    totals = plan.total if totals is None else totals
+    scale = plan.scale if scale is None else scale
+    if totals.dtype != torch.float64 or not totals.is_contiguous() or scale.dtype != torch.float32 or scale.numel() < (plan.n_vars if m == 1 else 1):
+        raise ValueError('grad_clip_scales: totals must be float64, scale float32 with one entry per variable')
+    if global_norm is not None and (global_norm.dtype != torch.float32 or global_norm.numel() != 1):
+        raise ValueError('global_norm must be a one-element float32 tensor')
+    handle().call('pcnn_grad_clip_scales', c_int(m), c_float(c if m else 0.0), c_int64(plan.n_items), c_int(plan.n_vars), _p(plan.workspace),
+                  c_int(totals.numel()), _p(totals), _p(scale), _p(global_norm))
+    return scale
+
+
+def grad_clip_apply(g, plan, mode, scale=None, clipvalue=None, grad_scale=1.0):
+    """g <- clamp((grad_scale g) scale, -clipvalue, clipvalue) in place (clipvalue None: no clamp; mode None: scale 1)."""
+    _grad_clip_check(g, plan)
+    scale = plan.scale if scale is None else scale
+    handle().call('pcnn_grad_clip_apply', _p(g), c_int64(plan.n_items), _p(plan.d_item_var), _p(plan.d_item_start), _p(plan.d_item_len),
+                  c_int(GRAD_CLIP_MODES[mode]), _p(scale), c_float(grad_scale), c_float(-1.0 if clipvalue is None else clipvalue))
+    return g
+
+
+def grad_clip_(g, plan, mode, c=0.0, clipvalue=None, grad_scale=1.0):
+    """One bucket, the whole sequence: norms, scales, apply - tf.keras' clipnorm (mode 'clipnorm'), global_clipnorm over this bucket alone
+    ('global_clipnorm'), and / or clipvalue, on grad_scale * g, in place.  Several buckets under one global norm: train._Optimizer."""
+    if GRAD_CLIP_MODES[mode]:
+        grad_sqnorms(g, plan, grad_scale)
+        grad_clip_scales(plan, mode, c)
+    return grad_clip_apply(g, plan, mode, clipvalue=clipvalue, grad_scale=grad_scale)
+
+
 # ----------------------------------------------------------------------------- Dirichlet_BC_NN_Legacy_2 / Poisson_CNN_Legacy
 def dbc_assemble_input(bc_nl):
     """(N, L) boundary values -> (N, 1, L, 3) NHWC [bc, 1, cos(pi y/(L-1))] (models/Dirichlet_BC_NN_Legacy.py:136-139)."""

@@ -16,25 +16,97 @@ import torch
 from . import ops
 
 
+_CLIP_OPTIONS = ('clipnorm', 'global_clipnorm', 'clipvalue', 'decay')
+
+
 class _Optimizer:
+    """What Adam and SGD share: the parameter buckets they are bound to and the tf.keras OptimizerV2 options `clipnorm`, `global_clipnorm`,
+    `clipvalue`, `decay` (TF 2.4; formulas in include/pcnn.h, kernels in csrc/grad_clip.hip) and `lr` as an alias of `learning_rate`.
+
+    A clip option rewrites every bucket's gradient in place in front of the update (per bucket: squared norms, scales, apply), which then runs
+    with grad_scale = 1; with no option set apply_gradients launches exactly the update kernels.  `decay` changes only the learning rate handed
+    down: lr / (1 + decay * t), t = updates already applied; `learning_rate` stays the base value ReduceLROnPlateau reads and writes.
+    `global_norm`: a device scalar, the pre-clip global gradient norm of the last step while a clip option is set."""
+
+    def _init_options(self, who, learning_rate, kwargs):
+        kwargs = dict(kwargs)
+        if 'lr' in kwargs:
+            learning_rate = kwargs.pop('lr')
+        opts = {k: kwargs.pop(k, None) for k in _CLIP_OPTIONS}
+        _reject_unsupported_optimizer_kwargs(who, kwargs)
+        for k, v in opts.items():
+            if v is not None and not float(v) >= 0.0:
+                raise ValueError('%s: %s must be >= 0, got %r' % (who, k, v))
+        if opts['clipnorm'] is not None and opts['global_clipnorm'] is not None:
+            raise ValueError('%s: clipnorm and global_clipnorm cannot both be set' % who)
+        self.clipnorm, self.global_clipnorm, self.clipvalue = (None if opts[k] is None else float(opts[k]) for k in _CLIP_OPTIONS[:3])
+        self.decay = float(opts['decay'] or 0.0)
+        self.learning_rate = float(learning_rate)
+        self.iterations = 0
+        self.global_norm = None
+
+    @property
+    def clip_mode(self):
+        return 'clipnorm' if self.clipnorm is not None else 'global_clipnorm' if self.global_clipnorm is not None else None
+
+    @property
+    def clips(self):
+        return self.clip_mode is not None or self.clipvalue is not None
+
+    def decayed_learning_rate(self, t=None):
+        """The learning rate of the update after `t` applied ones (default: the next one)."""
+        t = self.iterations if t is None else t
+        return self.learning_rate / (1.0 + self.decay * t) if self.decay else self.learning_rate
+
     def bind(self, store):
         """store: one ParamStore or a list of them (a composite model such as Poisson_CNN_Legacy trains several buckets)."""
         self.stores = list(store) if isinstance(store, (list, tuple)) else [store]
         self.store = self.stores[0]
+        if self.clips:
+            self._plans = [ops.grad_clip_plan(store_variable_sizes(s)) for s in self.stores]
+            dev = self.store.flat_g.device
+            self._totals = torch.zeros(len(self.stores), dtype=torch.float64, device=dev)      # one squared norm per bucket, in binding order
+            self._global_scale = torch.ones(1, dtype=torch.float32, device=dev)
+            self.global_norm = torch.zeros((), dtype=torch.float32, device=dev)
         self._init_state()
 
     def _init_state(self):
         pass
 
+    def _clip_gradients(self, grad_scale):
+        """Norms of every bucket, then the scales (global mode: ONE launch over the buckets' totals, no host round trip), then the in-place clip."""
+        mode, pairs = self.clip_mode, list(zip(self.stores, self._plans))
+        for k, (s, plan) in enumerate(pairs):
+            ops.grad_sqnorms(s.flat_g, plan, grad_scale, total=self._totals[k:k + 1])
+        if mode == 'clipnorm':
+            for k, (s, plan) in enumerate(pairs):
+                ops.grad_clip_scales(plan, mode, self.clipnorm, totals=self._totals, global_norm=self.global_norm if k == 0 else None)
+        else:
+            ops.grad_clip_scales(self._plans[0], mode, self.global_clipnorm or 0.0, totals=self._totals, scale=self._global_scale, global_norm=self.global_norm)
+        for s, plan in pairs:
+            ops.grad_clip_apply(s.flat_g, plan, mode, scale=plan.scale if mode == 'clipnorm' else self._global_scale, clipvalue=self.clipvalue,
+                                grad_scale=grad_scale)
+
+    def apply_gradients(self, grad_scale=1.0):
+        lr = self.decayed_learning_rate()
+        if self.clips:
+            self._clip_gradients(grad_scale)
+            grad_scale = 1.0
+        self.iterations += 1
+        self._update(lr, grad_scale)
+
+
+def store_variable_sizes(store):
+    """Element counts of a ParamStore's trainable variables in the physical order of flat_g: the 'w' specs, then every BN gamma, then every BN beta
+    (layers.ParamStore.finalize).  Moving statistics are not variables."""
+    by_kind = {k: [int(np.prod(shape)) for _, shape, _, kind in store.specs if kind == k] for k in ('w', 'bn_gamma', 'bn_beta')}
+    return by_kind['w'] + by_kind['bn_gamma'] + by_kind['bn_beta']
+
 
 def _reject_unsupported_optimizer_kwargs(who, kwargs):
-    """tf.keras optimizers also take clipnorm / clipvalue / decay (/ lr as an alias): options that change the update must not be
-    swallowed silently - a config that sets them would train differently from the reference."""
+    """Whatever is left after the options _Optimizer implements: an option that would change the update must not be swallowed silently - a
+    config that sets it would train differently from the reference."""
     for k, v in kwargs.items():
-        if k in ('clipnorm', 'clipvalue', 'global_clipnorm') and v is None:
-            continue
-        if k == 'decay' and not v:
-            continue
         raise NotImplementedError('%s: optimizer option %r=%r is not implemented' % (who, k, v))
 
 
@@ -42,40 +114,35 @@ class Adam(_Optimizer):
     """tf.keras.optimizers.Adam defaults (train/utils.py:3-8; experiments/hpnn.json optimizer_parameters)."""
 
     def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, amsgrad=False, name='Adam', **kwargs):
-        _reject_unsupported_optimizer_kwargs('Adam', kwargs)
+        self._init_options('Adam', learning_rate, kwargs)
         self.amsgrad = bool(amsgrad)
-        self.learning_rate, self.beta_1, self.beta_2, self.epsilon = float(learning_rate), float(beta_1), float(beta_2), float(epsilon)
-        self.iterations = 0
+        self.beta_1, self.beta_2, self.epsilon = float(beta_1), float(beta_2), float(epsilon)
 
     def _init_state(self):
-        import torch
         self.ms = [torch.zeros_like(s.flat_w) for s in self.stores]
         self.vs = [torch.zeros_like(s.flat_w) for s in self.stores]
         self.vhats = [torch.zeros_like(s.flat_w) if self.amsgrad else None for s in self.stores]
         self.m, self.v = self.ms[0], self.vs[0]
 
-    def apply_gradients(self, grad_scale=1.0):
-        self.iterations += 1
+    def _update(self, lr, grad_scale):
         for s, m, v, vh in zip(self.stores, self.ms, self.vs, self.vhats):
-            ops.adam_step(s.flat_w, s.flat_g, m, v, self.learning_rate, self.beta_1, self.beta_2, self.epsilon, self.iterations, grad_scale, vhat=vh)
+            ops.adam_step(s.flat_w, s.flat_g, m, v, lr, self.beta_1, self.beta_2, self.epsilon, self.iterations, grad_scale, vhat=vh)
 
 
 class SGD(_Optimizer):
     def __init__(self, learning_rate=0.01, momentum=0.0, nesterov=False, name='SGD', **kwargs):
-        _reject_unsupported_optimizer_kwargs('SGD', kwargs)
-        self.learning_rate, self.momentum, self.nesterov = float(learning_rate), float(momentum), bool(nesterov)
-        self.iterations = 0
+        self._init_options('SGD', learning_rate, kwargs)
+        self.momentum, self.nesterov = float(momentum), bool(nesterov)
 
     def _init_state(self):
         self.vs = [torch.zeros_like(s.flat_w) for s in self.stores] if self.momentum != 0.0 else None
 
-    def apply_gradients(self, grad_scale=1.0):
-        self.iterations += 1
+    def _update(self, lr, grad_scale):
         for k, s in enumerate(self.stores):
             if self.momentum != 0.0:
-                ops.sgd_momentum_step(s.flat_w, s.flat_g, self.vs[k], self.learning_rate, self.momentum, self.nesterov, grad_scale)
+                ops.sgd_momentum_step(s.flat_w, s.flat_g, self.vs[k], lr, self.momentum, self.nesterov, grad_scale)
             else:
-                ops.sgd_step(s.flat_w, s.flat_g, self.learning_rate, grad_scale)
+                ops.sgd_step(s.flat_w, s.flat_g, lr, grad_scale)
 
 
 def choose_optimizer(name):

@@ -282,7 +282,7 @@ class UNetModel(_ModelBase):
         return sums.mean().sqrt().float()
 
     def _extra_logs(self):
-        return {'grad L2 norm': self.grad_l2_norm()}
+        return {'grad L2 norm': self.grad_l2_norm(), **super()._extra_logs()}
 
 
 def UNet(nx=None, ny=None, in_channels=1, out_channels=1, layer_depth=5, filters_root=64, kernel_size=3, pool_size=2, dropout_rate=0.5,
