@@ -236,19 +236,8 @@ extern "C" int pcnn_conv2d_fwd_absmax(pcnn_handle h, const pcnn_conv_desc* d, co
 extern "C" int pcnn_conv2d_fwd(pcnn_handle h, const pcnn_conv_desc* d, const float* x, const float* w, const float* bias,
                                const float* bn_scale, const float* bn_shift, const float* residual, float* y, float* act_out) {
   PCNN_REQUIRE(h, h && d && x && w && y, "pcnn_conv2d_fwd: null argument");
-  PCNN_REQUIRE(h, d->N > 0 && d->H > 0 && d->W > 0 && d->Ho > 0 && d->Wo > 0, "pcnn_conv2d_fwd: empty tensor");
-  PCNN_REQUIRE(h, d->Cin >= 1 && d->Cout >= 1 && d->Cout <= 64, "pcnn_conv2d_fwd: Cout=%d unsupported (1..64)", d->Cout);
-  PCNN_REQUIRE(h, d->kh >= 1 && d->kw >= 1 && d->kh <= 31 && d->kw <= 31, "pcnn_conv2d_fwd: kernel %dx%d unsupported", d->kh, d->kw);
-  PCNN_REQUIRE(h, d->ldx >= d->Cin && d->ldy >= d->Cout, "pcnn_conv2d_fwd: channel stride smaller than channel count");
-  PCNN_REQUIRE(h, d->pad_mode >= 0 && d->pad_mode <= 2, "pcnn_conv2d_fwd: bad pad_mode %d", d->pad_mode);
+  if (pcnn_check_conv_desc(h, "pcnn_conv2d_fwd", d, PCNN_ANY, 64, 31)) return 1;
   PCNN_REQUIRE(h, (bn_scale == nullptr) == (bn_shift == nullptr), "pcnn_conv2d_fwd: bn_scale and bn_shift go together");
-  // every read must resolve inside the image: the farthest tap of the last output must be within pad reach
-  if (d->pad_mode != PCNN_PAD_CONSTANT) {
-    const int lim_y = d->pad_mode == PCNN_PAD_SYMMETRIC ? d->H : d->H - 1, lim_x = d->pad_mode == PCNN_PAD_SYMMETRIC ? d->W : d->W - 1;
-    const int pb = d->Ho - 1 - d->pad_top + d->kh - 1 - (d->H - 1), pr = d->Wo - 1 - d->pad_left + d->kw - 1 - (d->W - 1);
-    PCNN_REQUIRE(h, d->pad_top <= lim_y && pb <= lim_y && d->pad_left <= lim_x && pr <= lim_x,
-                 "pcnn_conv2d_fwd: padding exceeds what tf.pad allows for a %dx%d image", d->H, d->W);
-  }
   if (pcnn_conv_fwd_takes_narrow_route(h, d)) return pcnn_conv_small_fwd(h, d, x, w, bias, bn_scale, bn_shift, residual, y, act_out);
   if (pcnn_spectral_eligible(h, d, false)) return pcnn_spectral_conv_fwd(h, d, x, w, bias, bn_scale, bn_shift, residual, y, act_out);
   if (h->math_mode == PCNN_MATH_SPLIT_F16) {
@@ -261,7 +250,7 @@ extern "C" int pcnn_conv2d_fwd(pcnn_handle h, const pcnn_conv_desc* d, const flo
   p.kh = d->kh; p.kw = d->kw; p.pt = d->pad_top; p.pl = d->pad_left; p.pad_mode = d->pad_mode; p.pad_value = d->pad_value;
   p.act = d->act; p.alpha = d->act_alpha; p.ld_res = d->ld_res; p.ld_act = d->ld_act_out;
   p.tiles_x = pcnn_cdiv(d->Wo, TW); p.tiles_y = pcnn_cdiv(d->Ho, TH);
-  p.vec_ok = (d->ldx % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
+  p.vec_ok = pcnn_quads_ok(x, d->ldx);
   const int cin_pad = (d->Cin + 7) & ~7;
   const int TR = TH + d->kh - 1, TC = TW + d->kw - 1;
   int CK = 8;
@@ -280,27 +269,21 @@ extern "C" int pcnn_conv2d_fwd(pcnn_handle h, const pcnn_conv_desc* d, const flo
     // + one full tap of spare K-steps: with several Cin chunks the last chunk's unconditional prefetch reads up to cin_pad / 8 - 1 steps past
     // the end (16 spare channels were only safe under the 4 MB minimum allocation)
     const size_t need = ((size_t)d->kh * d->kw * cin_pad + cin_pad + 16) * NTh * 32 * sizeof(float);
-    if (h->scratch_bytes < need) {
-      // grown on demand; stream-ordered reuse is safe because pack and conv run back to back on the handle's stream
-      if (h->scratch) { pcnn_release(h, h->scratch); h->scratch = nullptr; h->scratch_bytes = 0; }
-      size_t cap = need < (4u << 20) ? (4u << 20) : need;
-      if (hipMalloc(&h->scratch, cap) != hipSuccess) PCNN_FAIL(h, "pcnn_conv2d_fwd: cannot allocate %zu B of filter scratch", cap);
-      h->scratch_bytes = cap;
-    }
+    if (pcnn_reserve(h, h->scratch, need, PCNN_SCRATCH_FLOOR, "pcnn_conv2d_fwd")) return 1;
     const int64_t total = (int64_t)d->kh * d->kw * cin_pad * NTh * 32;
     hipLaunchKernelGGL(pack_weights_kernel, dim3((unsigned)std::min<int64_t>(pcnn_cdiv64(total, 256), 2048)), dim3(256), 0, h->stream, w,
-                       static_cast<float*>(h->scratch), d->kh * d->kw, d->Cin, d->Cout, cin_pad, NTh);
+                       static_cast<float*>(h->scratch.p), d->kh * d->kw, d->Cin, d->Cout, cin_pad, NTh);
     PCNN_CHECK_LAUNCH(h, "pcnn_conv2d_fwd(pack)");
-    p.wp = static_cast<const float*>(h->scratch);
+    p.wp = static_cast<const float*>(h->scratch.p);
   }
   const int64_t nblk = (int64_t)d->N * p.tiles_x * p.tiles_y;
   PCNN_REQUIRE(h, nblk < (1ll << 31), "pcnn_conv2d_fwd: grid too large");
   dim3 grid((unsigned)nblk), block(256);
   if (d->Cout <= 32) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fwd_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    set_lds(conv_fwd_kernel<1>, 160 * 1024);
     hipLaunchKernelGGL(conv_fwd_kernel<1>, grid, block, lds, h->stream, p);
   } else {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fwd_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    set_lds(conv_fwd_kernel<2>, 160 * 1024);
     hipLaunchKernelGGL(conv_fwd_kernel<2>, grid, block, lds, h->stream, p);
   }
   PCNN_CHECK_LAUNCH(h, "pcnn_conv2d_fwd");

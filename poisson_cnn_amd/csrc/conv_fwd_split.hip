@@ -264,14 +264,9 @@ int pcnn_conv2d_fwd_split(pcnn_handle h, const pcnn_conv_desc* d, const float* x
   if (TR * TC > 256 * max_pix(MTsel)) return -1;
   const int64_t plane_halfs = ((int64_t)ng * nT2 + 4) * 2 * NT * 32 * 8;       // + spare steps for the prefetch past the end
   const size_t need = 256 + (size_t)plane_halfs * 2 * sizeof(_Float16);
-  if (h->scratch_bytes < need) {
-    if (h->scratch) { pcnn_release(h, h->scratch); h->scratch = nullptr; h->scratch_bytes = 0; }
-    const size_t cap = need < (4u << 20) ? (4u << 20) : need;
-    if (hipMalloc(&h->scratch, cap) != hipSuccess) PCNN_FAIL(h, "pcnn_conv2d_fwd: cannot allocate %zu B of filter scratch", cap);
-    h->scratch_bytes = cap;
-  }
-  float* scale = static_cast<float*>(h->scratch);
-  _Float16* wp = reinterpret_cast<_Float16*>(static_cast<unsigned char*>(h->scratch) + 256);
+  if (pcnn_reserve(h, h->scratch, need, PCNN_SCRATCH_FLOOR, "pcnn_conv2d_fwd")) return 1;
+  float* scale = static_cast<float*>(h->scratch.p);
+  _Float16* wp = reinterpret_cast<_Float16*>(static_cast<unsigned char*>(h->scratch.p) + 256);
   const int64_t nw = (int64_t)T * d->Cin * d->Cout;
   hipLaunchKernelGGL(filter_scale_kernel, dim3(1), dim3(1024), 0, h->stream, w, nw, scale);
   const int64_t total = (int64_t)ng * nT2 * 2 * NT * 32 * 8;
@@ -285,20 +280,20 @@ int pcnn_conv2d_fwd_split(pcnn_handle h, const pcnn_conv_desc* d, const float* x
   p.kh = d->kh; p.kw = d->kw; p.pt = d->pad_top; p.pl = d->pad_left; p.pad_mode = d->pad_mode; p.pad_value = d->pad_value;
   p.act = d->act; p.alpha = d->act_alpha; p.ld_res = d->ld_res; p.ld_act = d->ld_act_out;
   p.tiles_x = pcnn_cdiv(d->Wo, TW); p.tiles_y = pcnn_cdiv(d->Ho, TH);
-  p.vec_ok = (d->ldx % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
+  p.vec_ok = pcnn_quads_ok(x, d->ldx);
   p.epi_vec = conv_epilogue_vec_ok(d->Cout, y, d->ldy, residual, d->ld_res, act_out, d->ld_act_out);
   p.y_absmax = reinterpret_cast<unsigned*>(h->y_absmax);
   const size_t lds = std::max((size_t)TR * TC * 32 + 64, conv_epilogue_lds_bytes(d->Cout));
   const int64_t nblk = (int64_t)d->N * p.tiles_x * p.tiles_y;
   if (nblk >= (1ll << 31)) return -1;
   if (NT == 1 && MTsel == 2) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fwd_split_kernel<1, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    set_lds(conv_fwd_split_kernel<1, 2>, 160 * 1024);
     hipLaunchKernelGGL((conv_fwd_split_kernel<1, 2>), dim3((unsigned)nblk), dim3(256), lds, h->stream, p);
   } else if (NT == 1) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fwd_split_kernel<1, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    set_lds(conv_fwd_split_kernel<1, 4>, 160 * 1024);
     hipLaunchKernelGGL((conv_fwd_split_kernel<1, 4>), dim3((unsigned)nblk), dim3(256), lds, h->stream, p);
   } else {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fwd_split_kernel<2, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    set_lds(conv_fwd_split_kernel<2, 4>, 160 * 1024);
     hipLaunchKernelGGL((conv_fwd_split_kernel<2, 4>), dim3((unsigned)nblk), dim3(256), lds, h->stream, p);
   }
   PCNN_CHECK_LAUNCH(h, "pcnn_conv2d_fwd(split)");

@@ -618,7 +618,7 @@ __global__ __launch_bounds__(256) void resnet3_stage_kernel(StageParams p) {
 template <int C, int TH>
 void launch_stage(pcnn_handle h, StageParams p) {
   constexpr size_t lds = ((size_t)(TH + 6) * (STW + 6) + (size_t)(TH + 4) * (STW + 4)) * C * sizeof(float);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(resnet3_stage_kernel<C, TH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  set_lds(resnet3_stage_kernel<C, TH>, lds);
   p.tiles_x = pcnn_cdiv(p.W, STW); p.tiles_y = pcnn_cdiv(p.H, TH);
   hipLaunchKernelGGL((resnet3_stage_kernel<C, TH>), dim3((unsigned)(p.N * p.tiles_x * p.tiles_y)), dim3(256), lds, h->stream, p);
 }
@@ -663,7 +663,7 @@ int pcnn_conv_small_fwd(pcnn_handle h, const pcnn_conv_desc* d, const float* x, 
 
 // The data gradient of a narrow layer with the activation backward of the layer that produced its input fused into the epilogue (include/pcnn.h
 // pcnn_conv2d_dgrad_post): eligible when the data-gradient convolution takes the narrow route and every tensor can be accessed in whole 16-byte channel quads.
-static bool quads_ok(const void* q, int ld) { return q == nullptr || ((reinterpret_cast<uintptr_t>(q) & 15) == 0 && ld % 4 == 0); }
+static bool quads_ok(const void* q, int ld) { return q == nullptr || pcnn_quads_ok(q, ld); }   // an optional tensor
 extern "C" int pcnn_conv2d_dgrad_post_eligible(pcnn_handle h, const pcnn_conv_desc* dg, const float* dz, const float* residual, const float* dx, const pcnn_post_desc* post) {
   if (!h || !dg || !post || !post->act_out) return 0;
   if (dg->pad_mode != PCNN_PAD_CONSTANT || dg->act != PCNN_ACT_LINEAR || dg->N < 1) return 0;
@@ -683,13 +683,8 @@ static int small_fwd_impl(pcnn_handle h, const pcnn_conv_desc* d, const float* x
                           const float* bn_shift, const float* residual, float* y, float* act_out, const pcnn_post_desc* post) {
   const int CI = pad4(d->Cin), CO = pad4(d->Cout), taps = d->kh * d->kw;
   const size_t need = (size_t)taps * CI * CO * sizeof(float);
-  if (h->scratch_bytes < need) {
-    if (h->scratch) { pcnn_release(h, h->scratch); h->scratch = nullptr; h->scratch_bytes = 0; }
-    const size_t cap = 4u << 20;
-    if (hipMalloc(&h->scratch, cap) != hipSuccess) PCNN_FAIL(h, "pcnn_conv2d_fwd: cannot allocate %zu B of filter scratch", cap);
-    h->scratch_bytes = cap;
-  }
-  float* wp = static_cast<float*>(h->scratch);
+  if (pcnn_reserve(h, h->scratch, need, PCNN_SCRATCH_FLOOR, "pcnn_conv2d_fwd")) return 1;
+  float* wp = static_cast<float*>(h->scratch.p);
   hipLaunchKernelGGL(pack_small_kernel, dim3(pcnn_cdiv(taps * CI * CO, 256)), dim3(256), 0, h->stream, w, wp, taps, d->Cin, d->Cout, CI, CO);
   SmallParams p;
   p.x = x; p.wp = wp; p.bias = bias; p.bn_scale = bn_scale; p.bn_shift = bn_shift; p.res = residual; p.y = y; p.act_out = act_out;
@@ -698,7 +693,7 @@ static int small_fwd_impl(pcnn_handle h, const pcnn_conv_desc* d, const float* x
   p.pt = d->pad_top; p.pl = d->pad_left; p.pad_mode = d->pad_mode; p.pad_value = d->pad_value; p.act = d->act; p.alpha = d->act_alpha;
   p.ld_res = d->ld_res; p.ld_act = d->ld_act_out;
   p.tiles_x = pcnn_cdiv(d->Wo, STW); p.tiles_y = pcnn_cdiv(d->Ho, STH);
-  p.vec_in = (d->ldx % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
+  p.vec_in = pcnn_quads_ok(x, d->ldx);
   p.vec_out = conv_epilogue_vec_ok(d->Cout, y, d->ldy, residual, d->ld_res, act_out, d->ld_act_out);
   const int64_t nblk = (int64_t)d->N * p.tiles_x * p.tiles_y;
   PCNN_REQUIRE(h, nblk < (1ll << 31), "pcnn_conv2d_fwd: grid too large");
@@ -706,13 +701,8 @@ static int small_fwd_impl(pcnn_handle h, const pcnn_conv_desc* d, const float* x
     p.gact = post->act_out; p.ld_gact = post->ld_act_out; p.y2 = post->raw_out; p.ld_y2 = post->ld_raw; p.gmode = post->act;
     p.galpha = post->act == PCNN_ACT_LINEAR ? 1.f : (post->act == PCNN_ACT_RELU ? 0.f : post->act_alpha);
     if (post->dbias) {                                           // the workgroups' partial sums: nblk x CO floats in the handle's auxiliary scratch
-      const size_t need = (size_t)nblk * CO * sizeof(float);
-      if (h->aux_ws_bytes < need) {
-        if (h->aux_ws) { pcnn_release(h, h->aux_ws); h->aux_ws = nullptr; h->aux_ws_bytes = 0; }
-        if (hipMalloc(&h->aux_ws, need) != hipSuccess) PCNN_FAIL(h, "pcnn_conv2d_dgrad_post: cannot allocate %zu B of scratch", need);
-        h->aux_ws_bytes = need;
-      }
-      p.bpart = static_cast<float*>(h->aux_ws);
+      if (pcnn_reserve(h, h->aux_ws, (size_t)nblk * CO * sizeof(float), 0, "pcnn_conv2d_dgrad_post")) return 1;
+      p.bpart = static_cast<float*>(h->aux_ws.p);
     }
   }
   const bool ok = d->kh == 3 ? dispatch_ci<3>(h, p, nblk, CI, CO) : dispatch_ci<5>(h, p, nblk, CI, CO);
@@ -733,8 +723,8 @@ int pcnn_conv_small_wgrad(pcnn_handle h, const pcnn_conv_desc* d, const float* x
   p.N = d->N; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.ldx = d->ldx; p.Ho = d->Ho; p.Wo = d->Wo; p.Cout = d->Cout; p.lddz = d->ldy;
   p.pt = d->pad_top; p.pl = d->pad_left; p.pad_mode = d->pad_mode; p.pad_value = d->pad_value;
   p.tiles_x = pcnn_cdiv(d->Wo, STW); p.tiles_y = pcnn_cdiv(d->Ho, STH); p.ntiles = d->N * p.tiles_x * p.tiles_y; p.S = wgrad_splits(d);
-  p.vec_in = (d->ldx % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
-  p.vec_dz = (d->ldy % 4 == 0) && ((reinterpret_cast<uintptr_t>(dz) & 15) == 0);
+  p.vec_in = pcnn_quads_ok(x, d->ldx);
+  p.vec_dz = pcnn_quads_ok(dz, d->ldy);
   const bool ok = d->kh == 3 ? wgrad_dispatch_ci<3>(h, p, CI, CO) : wgrad_dispatch_ci<5>(h, p, CI, CO);
   PCNN_REQUIRE(h, ok, "pcnn_conv2d_wgrad(small): no kernel for %d->%d", d->Cin, d->Cout);
   PCNN_CHECK_LAUNCH(h, "pcnn_conv2d_wgrad(small)");

@@ -321,7 +321,7 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ ws, float* __restr
 
 template <int NTC, int TAPS>
 void launch_wgrad(pcnn_handle h, const WgradParams& p, const WgradPlan& pl) {
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_kernel<NTC, TAPS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  set_lds(wgrad_kernel<NTC, TAPS>, 160 * 1024);
   hipLaunchKernelGGL((wgrad_kernel<NTC, TAPS>), dim3(8 * pcnn_cdiv(pl.S, 8) * p.kh * pl.gz), dim3(256), pl.lds, h->stream, p);
 }
 
@@ -670,7 +670,7 @@ __global__ __launch_bounds__(256, (TAPS >= 3 && XR == 2) ? 3 : 2) void wgrad_spl
 
 template <int TAPS, int XR>
 void launch_wgrad_split(pcnn_handle h, const WgradSplitParams& p, const WgradPlan& pl, size_t lds) {
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_split_kernel<TAPS, XR>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  set_lds(wgrad_split_kernel<TAPS, XR>, 160 * 1024);
   hipLaunchKernelGGL((wgrad_split_kernel<TAPS, XR>), dim3(8 * pcnn_cdiv(pl.S, 8) * p.b.kh * pl.gz), dim3(256), lds, h->stream, p);
 }
 
@@ -733,8 +733,7 @@ extern "C" int pcnn_conv2d_wgrad(pcnn_handle h, const pcnn_conv_desc* d, const f
 extern "C" int pcnn_conv2d_wgrad_hint(pcnn_handle h, const pcnn_conv_desc* d, const float* x, const float* dz, float* dw,
                                       void* workspace, size_t workspace_bytes, const float* x_absmax, const float* dz_absmax) {
   PCNN_REQUIRE(h, h && d && x && dz && dw && workspace, "pcnn_conv2d_wgrad: null argument");
-  PCNN_REQUIRE(h, d->Cin >= 1 && d->Cin <= 128 && d->Cout >= 1 && d->Cout <= 64, "pcnn_conv2d_wgrad: channels %d->%d unsupported (<=64)", d->Cin, d->Cout);
-  PCNN_REQUIRE(h, d->ldx >= d->Cin && d->ldy >= d->Cout, "pcnn_conv2d_wgrad: channel stride smaller than channel count");
+  if (pcnn_check_conv_desc(h, "pcnn_conv2d_wgrad", d, 128, 64, PCNN_ANY)) return 1;
   PCNN_REQUIRE(h, workspace_bytes >= pcnn_conv2d_wgrad_workspace(d), "pcnn_conv2d_wgrad: workspace too small");
   if (pcnn_conv_small_wgrad_eligible(d)) return pcnn_conv_small_wgrad(h, d, x, dz, dw, workspace, workspace_bytes);
   if (pcnn_spectral_eligible(h, d, true)) return pcnn_spectral_conv_wgrad(h, d, x, dz, dw);
@@ -749,8 +748,8 @@ extern "C" int pcnn_conv2d_wgrad_hint(pcnn_handle h, const pcnn_conv_desc* d, co
   p.N = d->N; p.H = d->H; p.W = d->W; p.Cin = ud->Cin; p.ldx = d->ldx; p.Ho = d->Ho; p.Wo = d->Wo; p.Cout = ud->Cout; p.lddz = d->ldy;
   p.kh = d->kh; p.kw = d->kw; p.pt = d->pad_top; p.pl = d->pad_left; p.pad_mode = d->pad_mode; p.pad_value = d->pad_value;
   p.tiles_x = pl.tiles_x; p.tiles_y = pl.tiles_y; p.ntiles = pl.ntiles; p.S = pl.S; p.KWG = pl.KWG; p.lg = pl.lg; p.gz = pl.gz;
-  p.vecx = (d->Cin % 4 == 0) && (d->ldx % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
-  p.vecdz = (d->Cout % 4 == 0) && (d->ldy % 4 == 0) && ((reinterpret_cast<uintptr_t>(dz) & 15) == 0);
+  p.vecx = d->Cin % 4 == 0 && pcnn_quads_ok(x, d->ldx);
+  p.vecdz = d->Cout % 4 == 0 && pcnn_quads_ok(dz, d->ldy);
   const int xr = split_xr(&pd, pls);
   if (split_ok) {
     char* base = static_cast<char*>(workspace) + partials_bytes(&pd, pl);

@@ -320,7 +320,7 @@ __global__ void wide_reduce_splits(const float* part, int splits, long long coun
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 int launch_rows(pcnn_handle_s* h, RowArgs& a, const char* name) {
-  a.vecx = (a.ldx % 4 == 0 && a.Cx % 4 == 0 && aligned16(a.x)) ? 1 : 0;
+  a.vecx = (a.Cx % 4 == 0 && pcnn_quads_ok(a.x, a.ldx)) ? 1 : 0;
   a.vecw = (!a.transb && a.Ncol % 4 == 0 && aligned16(a.w)) ? 1 : 0;
   if (a.M <= 0 || a.Ncol <= 0) return 0;
   if (a.Ncol <= 64) {
@@ -359,7 +359,7 @@ int launch_pix(pcnn_handle_s* h, PixArgs& a, const PixPlan& q, float* dw, float*
   a.Mrows = q.Mrows;
   a.tiles_per_split = q.per;
   a.ktiles = q.ktiles;
-  a.vecb = (a.ldb % 4 == 0 && a.Ncol % 4 == 0 && aligned16(a.b)) ? 1 : 0;
+  a.vecb = (a.Ncol % 4 == 0 && pcnn_quads_ok(a.b, a.ldb)) ? 1 : 0;
   if (q.wide) {
     dim3 g((unsigned)pcnn_cdiv(q.Mrows, 128), (unsigned)pcnn_cdiv(a.Ncol, 128), (unsigned)q.splits);
     hipLaunchKernelGGL((wide_gemm_pix<2, 2>), g, dim3(NT), 0, h->stream, a);

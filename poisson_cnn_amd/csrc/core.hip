@@ -20,12 +20,11 @@ extern "C" int pcnn_create(int device, void* hip_stream, pcnn_handle* out) {
 }
 
 extern "C" int pcnn_destroy(pcnn_handle h) {
-  if (h && h->scratch) (void)hipFree(h->scratch);
-  if (h && h->spec_ws) (void)hipFree(h->spec_ws);
-  if (h && h->aux_ws) (void)hipFree(h->aux_ws);
-  if (h) for (void* p : h->retired) (void)hipFree(p);
-  if (h && h->comm) pcnn_comm_release(h);
-  if (h) pcnn_filter_cache_free(h);
+  if (!h) return 0;
+  for (pcnn_buffer* b : {&h->scratch, &h->spec_ws, &h->aux_ws}) (void)hipFree(b->p);
+  for (void* p : h->retired) (void)hipFree(p);
+  if (h->comm) pcnn_comm_release(h);
+  pcnn_filter_cache_free(h);
   delete h;
   return 0;
 }

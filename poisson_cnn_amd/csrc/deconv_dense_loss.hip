@@ -408,13 +408,8 @@ extern "C" int pcnn_loss_partials_p(pcnn_handle h, int N, int64_t hw, const floa
   PCNN_REQUIRE(h, h && pred && target && out, "pcnn_loss_partials: null argument");
   // scratch for the split sums: N * 64 * 4 floats from the handle's filter scratch (stream-ordered with every other user of it)
   const size_t need = (size_t)N * LOSS_SPLITS * 4 * sizeof(float);
-  if (h->scratch_bytes < need) {
-    if (h->scratch) { pcnn_release(h, h->scratch); h->scratch = nullptr; h->scratch_bytes = 0; }
-    const size_t cap = need < (4u << 20) ? (4u << 20) : need;
-    if (hipMalloc(&h->scratch, cap) != hipSuccess) PCNN_FAIL(h, "pcnn_loss_partials: cannot allocate %zu B of scratch", cap);
-    h->scratch_bytes = cap;
-  }
-  float* part = static_cast<float*>(h->scratch);
+  if (pcnn_reserve(h, h->scratch, need, PCNN_SCRATCH_FLOOR, "pcnn_loss_partials")) return 1;
+  float* part = static_cast<float*>(h->scratch.p);
   hipLaunchKernelGGL(loss_partials_kernel, dim3(LOSS_SPLITS, N), dim3(1024), 0, h->stream, hw, pred, target, G, lp_power, part);
   hipLaunchKernelGGL(loss_partials_final_kernel, dim3(N), dim3(64), 0, h->stream, part, out);
   PCNN_CHECK_LAUNCH(h, "pcnn_loss_partials");

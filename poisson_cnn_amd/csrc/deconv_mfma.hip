@@ -246,34 +246,23 @@ __global__ __launch_bounds__(256) void deconv_bwd_filter_mfma_kernel(DeconvParam
   }
 }
 
-static bool ensure_scratch(pcnn_handle h, size_t need) {
-  if (h->scratch_bytes >= need) return true;
-  if (h->scratch) { pcnn_release(h, h->scratch); h->scratch = nullptr; h->scratch_bytes = 0; }
-  const size_t cap = need < (4u << 20) ? (4u << 20) : need;
-  if (hipMalloc(&h->scratch, cap) != hipSuccess) return false;
-  h->scratch_bytes = cap;
-  return true;
-}
-
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 // Returns 0 on success, -1 if the shape is outside what the MFMA path covers (caller falls back), >0 on error.
 int pcnn_deconv_fwd_mfma(pcnn_handle h, int N, int hc, int wc, int Cin, int H, int W, int Cout, int f, const float* x, int ldx, const float* k,
                          const float* bias, float alpha, float beta, float* y, int ldy) {
-  if (Cin > 32 || Cout > 32 || Cin % 4 || ldx % 4 || !aligned16(x)) return -1;
+  if (Cin > 32 || Cout > 32 || Cin % 4 || !pcnn_quads_ok(x, ldx)) return -1;
   const int ng = (Cin + 7) >> 3;
   const size_t need = (size_t)f * f * ng * 64 * 4 * sizeof(float);                 // packed filter, then 64 dummy floats (deconv_fwd_mfma_kernel)
-  if (!ensure_scratch(h, need + 64 * sizeof(float))) PCNN_FAIL(h, "pcnn_deconv_fwd: cannot allocate filter scratch");
+  if (pcnn_reserve(h, h->scratch, need + 64 * sizeof(float), PCNN_SCRATCH_FLOOR, "pcnn_deconv_fwd")) return 1;
   const int64_t tot = (int64_t)f * f * ng * 64 * 4;
   hipLaunchKernelGGL(pack_deconv_fwd_kernel, dim3((unsigned)std::min<int64_t>(pcnn_cdiv64(tot, 256), 1024)), dim3(256), 0, h->stream, k,
-                     static_cast<float*>(h->scratch), f * f, Cin, Cout, ng);
+                     static_cast<float*>(h->scratch.p), f * f, Cin, Cout, ng);
   DeconvParams p{};
   p.N = N; p.hc = hc; p.wc = wc; p.Cin = Cin; p.H = H; p.W = W; p.Cout = Cout; p.f = f; p.py = (hc * f - H) / 2; p.px = (wc * f - W) / 2;
-  p.x = x; p.ldx = ldx; p.wp = static_cast<const float*>(h->scratch); p.bias = bias; p.alpha = alpha; p.beta = beta; p.y = y; p.ldy = ldy;
+  p.x = x; p.ldx = ldx; p.wp = static_cast<const float*>(h->scratch.p); p.bias = bias; p.alpha = alpha; p.beta = beta; p.y = y; p.ldy = ldy;
   p.tiles_x = pcnn_cdiv(wc, 32);
-  p.dummy = static_cast<float*>(h->scratch) + need / sizeof(float);
+  p.dummy = static_cast<float*>(h->scratch.p) + need / sizeof(float);
   const int64_t waves = (int64_t)N * hc * p.tiles_x * f;
   if (beta != 0.f) hipLaunchKernelGGL(deconv_fwd_mfma_kernel<true>, dim3((unsigned)pcnn_cdiv64(waves, 4)), dim3(256), 0, h->stream, p);
   else hipLaunchKernelGGL(deconv_fwd_mfma_kernel<false>, dim3((unsigned)pcnn_cdiv64(waves, 4)), dim3(256), 0, h->stream, p);
@@ -283,16 +272,16 @@ int pcnn_deconv_fwd_mfma(pcnn_handle h, int N, int hc, int wc, int Cin, int H, i
 
 int pcnn_deconv_bwd_data_mfma(pcnn_handle h, int N, int hc, int wc, int Cin, int H, int W, int Cout, int f, const float* dy, int lddy, const float* k,
                               float alpha, float* dx, int lddx) {
-  if (Cin > 32 || Cout > 32 || Cout % 4 || lddy % 4 || !aligned16(dy)) return -1;
+  if (Cin > 32 || Cout > 32 || Cout % 4 || !pcnn_quads_ok(dy, lddy)) return -1;
   const int ng = (Cout + 7) >> 3;
   const size_t need = (size_t)f * f * ng * 64 * 4 * sizeof(float);
-  if (!ensure_scratch(h, need)) PCNN_FAIL(h, "pcnn_deconv_bwd_data: cannot allocate filter scratch");
+  if (pcnn_reserve(h, h->scratch, need, PCNN_SCRATCH_FLOOR, "pcnn_deconv_bwd_data")) return 1;
   const int64_t tot = (int64_t)f * f * ng * 64 * 4;
   hipLaunchKernelGGL(pack_deconv_bwd_kernel, dim3((unsigned)std::min<int64_t>(pcnn_cdiv64(tot, 256), 1024)), dim3(256), 0, h->stream, k,
-                     static_cast<float*>(h->scratch), f * f, Cin, Cout, ng);
+                     static_cast<float*>(h->scratch.p), f * f, Cin, Cout, ng);
   DeconvParams p{};
   p.N = N; p.hc = hc; p.wc = wc; p.Cin = Cin; p.H = H; p.W = W; p.Cout = Cout; p.f = f; p.py = (hc * f - H) / 2; p.px = (wc * f - W) / 2;
-  p.dy = dy; p.lddy = lddy; p.wp = static_cast<const float*>(h->scratch); p.alpha = alpha; p.dx = dx; p.lddx = lddx;
+  p.dy = dy; p.lddy = lddy; p.wp = static_cast<const float*>(h->scratch.p); p.alpha = alpha; p.dx = dx; p.lddx = lddx;
   p.tiles_x = pcnn_cdiv(wc, 32);
   const int64_t groups = (int64_t)N * hc * p.tiles_x;            // one workgroup (four waves sharing the taps) per 32 coarse pixels of a row
   hipLaunchKernelGGL(deconv_bwd_data_mfma_kernel, dim3((unsigned)groups), dim3(256), 0, h->stream, p);

@@ -547,9 +547,9 @@ extern "C" int pcnn_grouped_conv2d_uses_mfma(const pcnn_conv_desc* d, int what) 
 template <int CP>
 static void gm_fwd_launch(int CO4, dim3 grid, size_t lds, hipStream_t st, const GmFwdParams& p) {
   if (lds > 64 * 1024) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gm_fwd_kernel<CP, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gm_fwd_kernel<CP, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gm_fwd_kernel<CP, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    set_lds(gm_fwd_kernel<CP, 1>, lds);
+    set_lds(gm_fwd_kernel<CP, 2>, lds);
+    set_lds(gm_fwd_kernel<CP, 4>, lds);
   }
   if (CO4 == 1) hipLaunchKernelGGL((gm_fwd_kernel<CP, 1>), grid, dim3(256), lds, st, p);
   else if (CO4 == 2) hipLaunchKernelGGL((gm_fwd_kernel<CP, 2>), grid, dim3(256), lds, st, p);
@@ -559,18 +559,13 @@ static void gm_fwd_launch(int CO4, dim3 grid, size_t lds, hipStream_t st, const 
 extern "C" int pcnn_grouped_conv2d_fwd(pcnn_handle h, const pcnn_conv_desc* d, const float* x, const float* w, long long w_sample_stride, const float* bias,
                                        long long bias_sample_stride, int flip_transpose, float* y) {
   PCNN_REQUIRE(h, h && d && x && w && y, "pcnn_grouped_conv2d_fwd: null argument");
-  PCNN_REQUIRE(h, d->Cout >= 1 && d->Cout <= 32 && d->Cin >= 1 && d->kh >= 1 && d->kw >= 1 && d->kh <= 31 && d->kw <= 31,
-               "pcnn_grouped_conv2d_fwd: %d -> %d channels, %d x %d taps unsupported (<= 32 output channels, <= 31 taps)", d->Cin, d->Cout, d->kh, d->kw);
+  if (pcnn_check_conv_desc(h, "pcnn_grouped_conv2d_fwd", d, PCNN_ANY, 32, 31)) return 1;
   const GmFwdPlan q = gm_fwd_plan(d);
   if (q.ok) {                                                        // grouped implicit GEMM on the matrix cores
     const size_t need = (size_t)d->N * d->kh * q.MV * q.CO4 * 64 * sizeof(float);
-    if (h->scratch_bytes < need) {
-      if (h->scratch) { pcnn_release(h, h->scratch); h->scratch = nullptr; h->scratch_bytes = 0; }
-      if (hipMalloc(&h->scratch, need) != hipSuccess) PCNN_FAIL(h, "pcnn_grouped_conv2d_fwd: cannot allocate %zu B of filter scratch", need);
-      h->scratch_bytes = need;
-    }
+    if (pcnn_reserve(h, h->scratch, need, 0, "pcnn_grouped_conv2d_fwd")) return 1;
     GmPackParams k;
-    k.w = w; k.wp = static_cast<float*>(h->scratch); k.w_stride = w_sample_stride; k.N = d->N; k.kh = d->kh; k.kw = d->kw; k.Cin = d->Cin; k.Cout = d->Cout;
+    k.w = w; k.wp = static_cast<float*>(h->scratch.p); k.w_stride = w_sample_stride; k.N = d->N; k.kh = d->kh; k.kw = d->kw; k.Cin = d->Cin; k.Cout = d->Cout;
     k.C = q.C; k.MV = q.MV; k.CO4 = q.CO4; k.flip = flip_transpose ? 1 : 0;
     hipLaunchKernelGGL(gm_pack_kernel, dim3((unsigned)std::min<int64_t>(pcnn_cdiv64((int64_t)need / 4, 256), 2048)), dim3(256), 0, h->stream, k);
     GmFwdParams g;
@@ -607,6 +602,7 @@ extern "C" int pcnn_grouped_conv2d_fwd(pcnn_handle h, const pcnn_conv_desc* d, c
 
 extern "C" int pcnn_grouped_conv2d_wgrad(pcnn_handle h, const pcnn_conv_desc* d, const float* x, const float* dz, float* dw, long long dw_sample_stride, void* workspace) {
   PCNN_REQUIRE(h, h && d && x && dz && dw && workspace, "pcnn_grouped_conv2d_wgrad: null argument");
+  if (pcnn_check_conv_desc(h, "pcnn_grouped_conv2d_wgrad", d, PCNN_ANY, PCNN_ANY, PCNN_ANY)) return 1;
   const int nout = d->kw * d->Cin * d->Cout;
   const GmWgradPlan q = gm_wgrad_plan(d);
   if (q.ok) {                                                        // matrix-core route
@@ -618,7 +614,7 @@ extern "C" int pcnn_grouped_conv2d_wgrad(pcnn_handle h, const pcnn_conv_desc* d,
     const dim3 grid((unsigned)q.S, (unsigned)d->N);
 #define GM_WLAUNCH(NIv, MCv, COv)                                                                                                \
     do {                                                                                                                         \
-      if (q.lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gm_wgrad_kernel<NIv, MCv, COv>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)q.lds); \
+      if (q.lds > 64 * 1024) set_lds(gm_wgrad_kernel<NIv, MCv, COv>, q.lds);                                                    \
       hipLaunchKernelGGL((gm_wgrad_kernel<NIv, MCv, COv>), grid, dim3(256), q.lds, h->stream, g);                                \
     } while (0)
 #define GM_WLAUNCH_MC(NIv, MCv)                                                   \
@@ -709,12 +705,8 @@ extern "C" int pcnn_grouped_deconv_bwd_filter(pcnn_handle h, int N, int H, int W
   p.S = std::max(1, std::min(32, H / 2)); p.rows_per_strip = pcnn_cdiv(H, p.S); p.S = pcnn_cdiv(H, p.rows_per_strip);
   const int64_t rec = (int64_t)f * f * Cout * Cin + Cout;
   const size_t need = (size_t)N * p.S * rec * sizeof(float);
-  if (h->aux_ws_bytes < need) {                              // handle-owned scratch (shared with the two-pass resize; one stream per handle)
-    if (h->aux_ws) { pcnn_release(h, h->aux_ws); h->aux_ws = nullptr; h->aux_ws_bytes = 0; }
-    if (hipMalloc(&h->aux_ws, need) != hipSuccess) PCNN_FAIL(h, "pcnn_grouped_deconv_bwd_filter: cannot allocate %zu B of scratch", need);
-    h->aux_ws_bytes = need;
-  }
-  p.part = static_cast<float*>(h->aux_ws);
+  if (pcnn_reserve(h, h->aux_ws, need, 0, "pcnn_grouped_deconv_bwd_filter")) return 1;
+  p.part = static_cast<float*>(h->aux_ws.p);
   hipLaunchKernelGGL(grouped_deconv_bwd_filter_kernel, dim3((unsigned)(f * f), (unsigned)p.S, (unsigned)N), dim3(256), 0, h->stream, p);
   hipLaunchKernelGGL(grouped_deconv_filter_reduce_kernel, dim3((unsigned)std::min<int64_t>(pcnn_cdiv64((int64_t)N * rec, 256), 1024)), dim3(256), 0, h->stream, p);
   PCNN_CHECK_LAUNCH(h, "pcnn_grouped_deconv_bwd_filter");

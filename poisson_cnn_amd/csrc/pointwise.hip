@@ -695,13 +695,8 @@ extern "C" int pcnn_sample_scale_fwd(pcnn_handle h, int N, int64_t per, const fl
 extern "C" int pcnn_sample_scale_bwd(pcnn_handle h, int N, int64_t per, const float* x, const float* g, const float* dy, float* dx, float* dg) {
   PCNN_REQUIRE(h, h && x && g && dy && dx && dg, "pcnn_sample_scale_bwd: null argument");
   const size_t need = (size_t)N * SS_SPLIT * sizeof(float);
-  if (h->aux_ws_bytes < need) {                              // handle-owned scratch (shared with the two-pass resize; one stream per handle)
-    if (h->aux_ws) { pcnn_release(h, h->aux_ws); h->aux_ws = nullptr; h->aux_ws_bytes = 0; }
-    const size_t cap = need < (1u << 20) ? (1u << 20) : need;
-    if (hipMalloc(&h->aux_ws, cap) != hipSuccess) PCNN_FAIL(h, "pcnn_sample_scale_bwd: cannot allocate %zu B of scratch", cap);
-    h->aux_ws_bytes = cap;
-  }
-  float* part = static_cast<float*>(h->aux_ws);
+  if (pcnn_reserve(h, h->aux_ws, need, (size_t)1 << 20, "pcnn_sample_scale_bwd")) return 1;
+  float* part = static_cast<float*>(h->aux_ws.p);
   hipLaunchKernelGGL(sample_scale_bwd_kernel, dim3(SS_SPLIT, N), dim3(256), 0, h->stream, per, x, g, dy, dx, part);
   hipLaunchKernelGGL(sample_scale_final_kernel, dim3((N + 63) / 64), dim3(64), 0, h->stream, N, part, dg);
   PCNN_CHECK_LAUNCH(h, "pcnn_sample_scale_bwd");

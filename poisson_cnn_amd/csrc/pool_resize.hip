@@ -554,12 +554,8 @@ extern "C" int pcnn_resize_fwd(pcnn_handle h, int N, int hc, int wc, int C, int 
   if (vec4_ok(C, x, ldx, y, ldy) && (int64_t)N * ((Ho + RESIZE_RPB - 1) / RESIZE_RPB) < 65536) {
     // two passes: x interpolation of the hc coarse rows into the handle's scratch, then the row-uniform y pass
     const size_t need = (size_t)N * hc * Wo * C * sizeof(float);
-    if (h->aux_ws_bytes < need) {
-      if (h->aux_ws) { pcnn_release(h, h->aux_ws); h->aux_ws = nullptr; h->aux_ws_bytes = 0; }
-      if (hipMalloc(&h->aux_ws, need) != hipSuccess) PCNN_FAIL(h, "pcnn_resize_fwd: cannot allocate %zu B of scratch", need);
-      h->aux_ws_bytes = need;
-    }
-    float* t = static_cast<float*>(h->aux_ws);
+    if (pcnn_reserve(h, h->aux_ws, need, 0, "pcnn_resize_fwd")) return 1;
+    float* t = static_cast<float*>(h->aux_ws.p);
     hipLaunchKernelGGL(resize_x_kernel, grid1d((int64_t)N * hc * Wo * (C / 4)), dim3(256), 0, h->stream, (int64_t)N * hc, wc, C, Wo, x, ldx, idx_x, wt_x, t);
     hipLaunchKernelGGL(resize_fwd_y_kernel, dim3((unsigned)((Wo * (C / 4) + 255) / 256), (unsigned)(N * ((Ho + RESIZE_RPB - 1) / RESIZE_RPB))), dim3(256), 0, h->stream,
                        N, hc, C, Ho, Wo, t, idx_y, wt_y, alpha, beta, y, ldy);
@@ -587,14 +583,10 @@ extern "C" int pcnn_resize_fwd_multi(pcnn_handle h, int N, int C, int Ho, int Wo
   PCNN_REQUIRE(h, h && pcnn_resize_fwd_multi_eligible(N, C, Ho, Wo, nsrc, src, y, ldy), "pcnn_resize_fwd_multi: not eligible (ask pcnn_resize_fwd_multi_eligible first)");
   size_t off[4] = {0, 0, 0, 0};
   for (int k = 0; k < nsrc; ++k) off[k + 1] = off[k] + (((size_t)N * src[k].hc * Wo * C * sizeof(float) + 255) & ~(size_t)255);
-  if (h->aux_ws_bytes < off[nsrc]) {
-    if (h->aux_ws) { pcnn_release(h, h->aux_ws); h->aux_ws = nullptr; h->aux_ws_bytes = 0; }
-    if (hipMalloc(&h->aux_ws, off[nsrc]) != hipSuccess) PCNN_FAIL(h, "pcnn_resize_fwd_multi: cannot allocate %zu B of scratch", off[nsrc]);
-    h->aux_ws_bytes = off[nsrc];
-  }
+  if (pcnn_reserve(h, h->aux_ws, off[nsrc], 0, "pcnn_resize_fwd_multi")) return 1;
   ResizeYSrc ys[3] = {};
   for (int k = 0; k < nsrc; ++k) {
-    float* t = reinterpret_cast<float*>(static_cast<char*>(h->aux_ws) + off[k]);
+    float* t = reinterpret_cast<float*>(static_cast<char*>(h->aux_ws.p) + off[k]);
     hipLaunchKernelGGL(resize_x_kernel, grid1d((int64_t)N * src[k].hc * Wo * (C / 4)), dim3(256), 0, h->stream, (int64_t)N * src[k].hc, src[k].wc, C, Wo, src[k].x, src[k].ldx,
                        src[k].idx_x, src[k].wt_x, t);
     ys[k] = ResizeYSrc{t, src[k].idx_y, src[k].wt_y, src[k].hc};

@@ -134,10 +134,6 @@ struct Xform {
 };
 extern const Xform XFORM_MFMA32, XFORM_MFMA64, XFORM_FFT32, XFORM_FFT64;
 
-// dynamic LDS beyond 64 KB has to be allowed per kernel before its first launch
-template <typename K>
-void set_lds(K kernel, size_t bytes) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); }
-
 // The epilogue variants of an inverse kernel, chosen once for all four back ends: launch(flag<TANH>, flag<RES>, flag<POST>, params) starts the
 // instantiation <TANH, RES, POST> with the back end's own launch geometry.  alpha / galpha arrive at the kernel as the slope of the negative side
 // (1 linear, 0 relu, the given slope for leaky relu); tanh has its own instantiation, and POST implies a linear convolution epilogue.

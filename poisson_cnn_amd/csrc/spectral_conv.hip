@@ -805,12 +805,11 @@ int ensure_workspace(pcnn_handle h, size_t bytes_after_tables, char** rest) {
   const size_t need = O_REST + bytes_after_tables;
   if (h->spec_ws_limit && need > h->spec_ws_limit)
     PCNN_FAIL(h, "spectral convolution: %zu B of workspace needed, the caller allows %zu B (pcnn_set_workspace_limit)", need, h->spec_ws_limit);
-  if (h->spec_ws_bytes < need) {
-    if (h->spec_ws) { pcnn_release(h, h->spec_ws); h->spec_ws = nullptr; h->spec_ws_bytes = 0; }
-    size_t cap = need + need / 8;
-    if (h->spec_ws_limit && cap > h->spec_ws_limit) cap = h->spec_ws_limit;
-    if (hipMalloc(&h->spec_ws, cap) != hipSuccess) PCNN_FAIL(h, "spectral convolution: cannot allocate %zu B of workspace", cap);
-    h->spec_ws_bytes = cap;
+  size_t cap = need + need / 8;                                // some headroom: layers of nearly the same size do not grow it one by one
+  if (h->spec_ws_limit && cap > h->spec_ws_limit) cap = h->spec_ws_limit;
+  bool grew;
+  if (pcnn_reserve(h, h->spec_ws, need, cap, "spectral convolution", &grew)) return 1;
+  if (grew) {
     static std::vector<float> tab, tab64; static std::vector<int> slots, slots64, slots32f, slots64f;   // static: the async copies below read them after this call returns
     if (tab.empty()) {
       build_tables(tab, slots);
@@ -820,7 +819,7 @@ int ensure_workspace(pcnn_handle h, size_t bytes_after_tables, char** rest) {
       pcnn_spec::sp_build_slots(32, SP_P, slots32f.data());
       pcnn_spec::sp_build_slots(64, SP_P, slots64f.data());
     }
-    char* b = static_cast<char*>(h->spec_ws);
+    char* b = static_cast<char*>(h->spec_ws.p);
     if (hipMemcpyAsync(b + O_TAB32, tab.data(), TAB_FLOATS * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
         hipMemcpyAsync(b + O_SLOTS32, slots.data(), NSLOT * 16, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
         hipMemcpyAsync(b + O_TAB64, tab64.data(), TAB64_FLOATS * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
@@ -829,7 +828,7 @@ int ensure_workspace(pcnn_handle h, size_t bytes_after_tables, char** rest) {
         hipMemcpyAsync(b + O_SLOTS64F, slots64f.data(), 2048 * 16, hipMemcpyHostToDevice, h->stream) != hipSuccess)
       PCNN_FAIL(h, "spectral convolution: table upload failed");
   }
-  *rest = static_cast<char*>(h->spec_ws) + O_REST;
+  *rest = static_cast<char*>(h->spec_ws.p) + O_REST;
   return 0;
 }
 
@@ -856,7 +855,7 @@ const Xform& xform_record(int family, int Tg) {
 }
 Xform xform_at(pcnn_handle h, const Xform& rec) {
   Xform xf = rec;
-  char* b = static_cast<char*>(h->spec_ws);
+  char* b = static_cast<char*>(h->spec_ws.p);
   xf.tab = reinterpret_cast<const float*>(b + rec.tab_off); xf.slots = reinterpret_cast<const int4*>(b + rec.slots_off);
   return xf;
 }
@@ -977,10 +976,7 @@ const Xform pcnn_spec::XFORM_MFMA32 = {PCNN_XFORM_MFMA, T, ROWS, NSLOT, 64, O_TA
 extern "C" int pcnn_set_workspace_limit(pcnn_handle h, size_t bytes) {
   if (!h) return 1;
   h->spec_ws_limit = bytes;
-  if (bytes && h->spec_ws && h->spec_ws_bytes > bytes) {       // what the handle already holds beyond the new cap goes back to the caller's pool
-    pcnn_release(h, h->spec_ws);
-    h->spec_ws = nullptr; h->spec_ws_bytes = 0;
-  }
+  if (bytes && h->spec_ws.bytes > bytes) pcnn_drop(h, h->spec_ws);   // what the handle already holds beyond the new cap goes back to the caller's pool
   return 0;
 }
 
@@ -1341,6 +1337,7 @@ extern "C" int pcnn_conv2d_bwd_spectral_post(pcnn_handle h, const pcnn_conv_desc
 static int bwd_spectral_impl(pcnn_handle h, const pcnn_conv_desc* d, const pcnn_conv_desc* dg, const float* x, const float* dz, const float* w_flipped,
                              const float* residual, float* dx, float* dw, const pcnn_post_desc* post) {
   PCNN_REQUIRE(h, h && d && dg && x && dz && w_flipped && dx && dw, "pcnn_conv2d_bwd_spectral: null argument");
+  if (pcnn_check_conv_desc(h, "pcnn_conv2d_bwd_spectral", d, 64, 32, PCNN_ANY) || pcnn_check_conv_desc(h, "pcnn_conv2d_bwd_spectral (dg)", dg, 32, 64, PCNN_ANY)) return 1;
   PCNN_REQUIRE(h, pcnn_conv2d_bwd_spectral_eligible(h, d, dg), "pcnn_conv2d_bwd_spectral: layer is not eligible (ask pcnn_conv2d_bwd_spectral_eligible first)");
   PCNN_REQUIRE(h, dg->Cin == d->Cout && dg->Cout == d->Cin && dg->kh == d->kh && dg->kw == d->kw && dg->N == d->N, "pcnn_conv2d_bwd_spectral: descriptors do not match");
   TileGrid g;

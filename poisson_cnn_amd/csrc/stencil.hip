@@ -117,7 +117,7 @@ int jacobi_launch(pcnn_handle_s* h, int N, int H, int W, int sy, int sx, int k, 
   const dim3 grid((unsigned)pcnn_cdiv(W, JAC_TILE), (unsigned)pcnn_cdiv(H, JAC_TILE), (unsigned)N);
   const size_t lds = (size_t)(BWD ? 2 : 3) * (JAC_TILE + 2 * k * ry) * (JAC_TILE + 2 * k * rx) * sizeof(float);
   auto go = [&](auto kernel) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    set_lds(kernel, lds);
     hipLaunchKernelGGL(kernel, grid, dim3(JAC_THREADS), lds, h->stream, H, W, k, coef, u, rhs, out);
   };
 #define JAC_CASE(A, B) \
@@ -142,13 +142,8 @@ int jacobi_chain(pcnn_handle_s* h, const char* name, int N, int H, int W, int sy
   const int launches = pcnn_cdiv(n_sweeps, kmax);
   float* tmp = nullptr;
   if (launches > 1) {
-    const size_t need = (size_t)N * H * W * sizeof(float);
-    if (h->aux_ws_bytes < need) {                              // handle-owned scratch (shared with the two-pass resize; one stream per handle)
-      if (h->aux_ws) { pcnn_release(h, h->aux_ws); h->aux_ws = nullptr; h->aux_ws_bytes = 0; }
-      if (hipMalloc(&h->aux_ws, need) != hipSuccess) PCNN_FAIL(h, "%s: cannot allocate %zu B of scratch", name, need);
-      h->aux_ws_bytes = need;
-    }
-    tmp = static_cast<float*>(h->aux_ws);
+    if (pcnn_reserve(h, h->aux_ws, (size_t)N * H * W * sizeof(float), 0, name)) return 1;
+    tmp = static_cast<float*>(h->aux_ws.p);
   }
   const float* in = u;
   int left = n_sweeps;
