@@ -443,6 +443,14 @@ int pcnn_sample_scale_bwd(pcnn_handle h, int N, int64_t per, const float* x, con
 /* BC ring (models/..Legacy.py:251): Dirichlet -> ring = 0 ; Neumann -> ring = adjacent interior.  1 channel. */
 int pcnn_bc_ring_fwd(pcnn_handle h, int N, int H, int W, int neumann, const float* x, float* y);
 int pcnn_bc_ring_bwd(pcnn_handle h, int N, int H, int W, int neumann, const float* dy, float* dx);
+/* The ring with a boundary type per edge (extension: the reference's bc_type is model-wide).  Edges are named as the dataset names them: on an
+ * (N,1,H,W) tensor left is y = 0, right y = H-1, bottom x = 0, top x = W-1.  neumann_mask bit 0/1/2/3 set: the left/right/bottom/top edge is Neumann,
+ * clear: Dirichlet (the order of pcnn_fd_poisson_mixed).  y = E_m x: interior points are copied; a ring point on any Dirichlet edge is 0 - at a corner a
+ * Dirichlet edge wins - and any other ring point is x[clamp(y,1,H-2), clamp(x,1,W-2)], the first-order mirror u_0 = u_1 of tf.pad SYMMETRIC (a
+ * Neumann/Neumann corner takes its diagonal neighbour).  bwd is E_m^T as a gather: no atomics, deterministic.  Mask 0 and mask 15 give the bits of
+ * pcnn_bc_ring_fwd/bwd with neumann = 0 and 1.  H, W >= 3. */
+int pcnn_bc_ring_edges_fwd(pcnn_handle h, int N, int H, int W, int neumann_mask, const float* x, float* y);
+int pcnn_bc_ring_edges_bwd(pcnn_handle h, int N, int H, int W, int neumann_mask, const float* dy, float* dx);
 /* Spatial pyramid max-pool over channels and spatial bins (layers/SpatialPyramidPool.py:35-66).
  * bins: nb x 4 int32 (y0,y1,x0,x1) on device; out (N, nb); argmax (N, nb) int32 flat index into (H,W,C) for bwd */
 int pcnn_spp_max_fwd(pcnn_handle h, int N, int H, int W, int C, int nb, const int32_t* bins, const float* x, float* out, int32_t* argmax);
@@ -464,6 +472,18 @@ int pcnn_jacobi_fused_bwd(pcnn_handle h, int N, int H, int W, int sy, int sx, co
 /* the edge of the square output tile one workgroup owns, and the most sweeps one launch fuses for an sy x sx stencil */
 int pcnn_jacobi_fused_tile(void);
 int pcnn_jacobi_fused_max_sweeps(int sy, int sx);
+/* The fused smoother with the model's boundary types (neumann_mask as for pcnn_bc_ring_edges_fwd).  One sweep is R_m o J: J the sweep above, R_m a
+ * refresh of the frozen band.  With ry = sy/2, rx = sx/2 a point is in the left band where y < ry, the right band where y >= H-ry, the bottom band where
+ * x < rx and the top band where x >= W-rx.  A point in no band keeps J(u); a point in any band on a Dirichlet edge keeps its value (frozen, as above);
+ * any other band point takes J(u) at (my, mx), my = 2 ry - 1 - y in the left band, 2 (H-ry) - 1 - y in the right band, y otherwise, mx likewise: the
+ * SYMMETRIC reflection of the updated interior, which for the 3 x 3 stencil is the ring of pcnn_bc_ring_edges_fwd on its Neumann edges.  n sweeps are
+ * (R_m J)^n; bwd is du = (J^T R_m^T)^n dout, a gather.  Needs H >= 3 ry where the mask has a left or right bit and W >= 3 rx where it has a bottom or
+ * top bit (mirror sources are interior points).  Mask 0 gives the bits of pcnn_jacobi_fused_fwd/bwd; the result does not depend on how the sweeps are
+ * split into launches, and pcnn_jacobi_fused_max_sweeps is the fused depth here too.  The same aliasing rules and scratch. */
+int pcnn_jacobi_fused_bc_fwd(pcnn_handle h, int N, int H, int W, int sy, int sx, const float* coef /*N x (sy+sx+1)*/, const float* u, const float* rhs,
+                             int n_sweeps, int neumann_mask, float* out);
+int pcnn_jacobi_fused_bc_bwd(pcnn_handle h, int N, int H, int W, int sy, int sx, const float* coef /*N x (sy+sx+1)*/, const float* dout, int n_sweeps,
+                             int neumann_mask, float* du);
 
 /* ---- loss (losses/loss_wrapper.py:53-71, losses/integral_loss.py:126-179) --------------------------------------
  * per-sample partial sums: out[n] = {sum|p-t|, sum (p-t)^2, sum G*(p-t)^2, max|t|}; G is the (H,W) quadrature map.

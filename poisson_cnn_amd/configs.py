@@ -62,6 +62,19 @@ def hpnn_neumann():
     return cfg
 
 
+def hpnn_mixed(boundary_types):
+    """hpnn() with a boundary type per edge (extension; BASELINE configs[2]): boundary_types maps 'left' | 'right' | 'bottom' | 'top' to
+    'dirichlet' | 'neumann' (a missing edge is Dirichlet).  Train it on the numerical generator, whose mixed solver gives the ground truth; the
+    keys the analytic generators alone read are dropped as in hpnn_neumann()."""
+    from .dataset import _neumann_flags
+    flags = _neumann_flags(boundary_types)
+    cfg = hpnn()
+    cfg['model']['bc_type'] = {e: 'neumann' if f else 'dirichlet' for e, f in zip(('left', 'right', 'bottom', 'top'), flags)}
+    for k in ('taylor_degree_range', 'homogeneous_bc', 'return_boundaries'):
+        cfg['dataset'].pop(k)
+    return cfg
+
+
 def hpnn_tiny():
     """A reduced-width model with the same topology, for fast CPU-side tests of host logic."""
     cfg = hpnn()

@@ -8,10 +8,17 @@
 // to memory.  rhs is needed from the first sweep's region on: a halo of (k - 1) radii.  The arithmetic per point (the H taps top to bottom,
 // then the W taps left to right, one fmaf each into one accumulator; then dinv * (rhs - acc)) does not depend on k or on where the tile lies,
 // so any split of n sweeps into launches gives the same bits.
+//
+// BC == true (pcnn_jacobi_fused_bc_*): one sweep is R_m o J.  R_m refreshes the frozen band where every edge that contains the point is Neumann
+// (neumann_mask, include/pcnn.h): the point takes J(u) at its SYMMETRIC mirror image in the interior; a band point on a Dirichlet edge stays
+// frozen.  A refreshed point depends on J(u) up to 2r - 1 points away, so the regions follow a recurrence (jac_range) instead of the plain
+// (k - s) radii: each sweep's computed region includes the mirror sources of the band points it has to deliver, and the adjoint's includes the
+// band points that mirror into it.  The refresh reads values other threads wrote in the same sweep and has a barrier of its own; a sweep whose
+// region meets no Neumann band (workgroup-uniform) takes the BC == false path.  The BC == false instantiations are the code they were.
 #include "pcnn_internal.h"
 
 #define JAC_TILE 64        // output tile edge
-#define JAC_HALO_MAX 8     // k * max(ry, rx) <= JAC_HALO_MAX: the LDS region is at most (64 + 16)^2 floats per buffer
+#define JAC_HALO_MAX 8     // k * max(ry, rx) <= JAC_HALO_MAX: the LDS region is at most (64 + 16)^2 floats per buffer (BC adjoint: up to 2r - 1 more per axis)
 #define JAC_THREADS 512
 
 namespace {
@@ -28,20 +35,65 @@ __device__ __forceinline__ void for_points(int tid, int y0, int x0, int h, int w
   }
 }
 
+// One axis of the boundary-aware regions.  [t0, t1) is the tile, L the image extent, r the radius, lo / hi whether the low / high edge is Neumann.
+// Forward: d = D_s, what sweep s has to deliver (D_k the tile, D_0 what is loaded); c = C_s, what sweep s computes: D_s and the mirror sources of
+// its band points.  D_(s-1) is C_s grown by r.   Adjoint: d = D_s, what sweep s delivers; c = G_s, where R^T of its input is needed: D_s grown by
+// r; D_(s-1) is G_s and the band points that mirror into it.  Everything is clipped to the image.  Called with s == 0 for the loaded region (c unused).
+template <bool BWD>
+__host__ __device__ __forceinline__ void jac_range(int t0, int t1, int L, int r, int k, int s, bool lo, bool hi, int& d0, int& d1, int& c0, int& c1) {
+  d0 = t0; d1 = t1;
+  for (int j = k;; --j) {
+    if (!BWD) {
+      c0 = d0; c1 = d1;
+      if (lo && d0 < r && 2 * r - d0 > c1) c1 = 2 * r - d0;                      // sources 2r-1-y of the band points y in [d0, r)
+      if (hi && d1 > L - r && 2 * (L - r) - d1 < c0) c0 = 2 * (L - r) - d1;      // sources 2(L-r)-1-y of y in [L-r, d1)
+    } else {
+      c0 = d0 - r < 0 ? 0 : d0 - r; c1 = d1 + r > L ? L : d1 + r;
+    }
+    if (j <= s) return;
+    if (!BWD) {
+      d0 = c0 - r < 0 ? 0 : c0 - r; d1 = c1 + r > L ? L : c1 + r;
+    } else {
+      d0 = c0; d1 = c1;
+      if (lo && c0 < 2 * r && c1 > r) { const int e = c1 < 2 * r ? 2 * r - c1 : 0; if (e < d0) d0 = e; }             // band points 2r-1-y of y in [r, 2r)
+      if (hi && c1 > L - 2 * r && c0 < L - r) { const int e = 2 * (L - r) - (c0 > L - 2 * r ? c0 : L - 2 * r); if (e > d1) d1 = e; }
+    }
+  }
+}
+
+// R_m at (y, x): false where the point keeps its own value (no band, or a band on a Dirichlet edge), else (my, mx) is the interior point it mirrors.
+template <int RY, int RX>
+__device__ __forceinline__ bool jac_refreshed(int y, int x, int H, int W, int mask, int& my, int& mx) {
+  bool any = false, frozen = false;
+  my = y; mx = x;
+  if (y < RY) { any = true; if (mask & 1) my = 2 * RY - 1 - y; else frozen = true; }
+  else if (y >= H - RY) { any = true; if (mask & 2) my = 2 * (H - RY) - 1 - y; else frozen = true; }
+  if (x < RX) { any = true; if (mask & 4) mx = 2 * RX - 1 - x; else frozen = true; }
+  else if (x >= W - RX) { any = true; if (mask & 8) mx = 2 * (W - RX) - 1 - x; else frozen = true; }
+  return any && !frozen;
+}
+
 // BWD == false: u -> k sweeps -> out.   BWD == true: u is d(out), out is d(guess), rhs unused.
-template <int RY, int RX, bool BWD>
+// BC == false: mask and S_bc are not read.   BC == true: S_bc is the floats per LDS buffer as the host sized them from jac_range.
+template <int RY, int RX, bool BWD, bool BC>
 __global__ __launch_bounds__(JAC_THREADS) void jacobi_fused_kernel(int H, int W, int k, const float* __restrict__ coef, const float* __restrict__ u,
-                                                                   const float* __restrict__ rhs, float* __restrict__ out) {
+                                                                   const float* __restrict__ rhs, float* __restrict__ out, int mask, int S_bc) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int SY = 2 * RY + 1, SX = 2 * RX + 1;
   const int n = blockIdx.z, tid = threadIdx.x;
   const int ty0 = blockIdx.y * JAC_TILE, tx0 = blockIdx.x * JAC_TILE;
   const int ty1 = min(ty0 + JAC_TILE, H), tx1 = min(tx0 + JAC_TILE, W);
-  // the region held in LDS: the tile grown by k radii, clipped to the image
-  const int ly0 = max(ty0 - k * RY, 0), ly1 = min(ty1 + k * RY, H);
-  const int lx0 = max(tx0 - k * RX, 0), lx1 = min(tx1 + k * RX, W);
+  // the region held in LDS: the tile grown by k radii, clipped to the image (BC: D_0 of jac_range)
+  int ly0 = max(ty0 - k * RY, 0), ly1 = min(ty1 + k * RY, H);
+  int lx0 = max(tx0 - k * RX, 0), lx1 = min(tx1 + k * RX, W);
+  int S = (JAC_TILE + 2 * k * RY) * (JAC_TILE + 2 * k * RX);         // floats per buffer as the host sized them
+  if (BC) {
+    int c0, c1;
+    jac_range<BWD>(ty0, ty1, H, RY, k, 0, mask & 1, mask & 2, ly0, ly1, c0, c1);
+    jac_range<BWD>(tx0, tx1, W, RX, k, 0, mask & 4, mask & 8, lx0, lx1, c0, c1);
+    S = S_bc;
+  }
   const int LW = lx1 - lx0;
-  const int S = (JAC_TILE + 2 * k * RY) * (JAC_TILE + 2 * k * RX);   // floats per buffer as the host sized them
   float* src = lds;
   float* dst = lds + S;
   float* rb = lds + 2 * S;                                            // forward only
@@ -57,52 +109,125 @@ __global__ __launch_bounds__(JAC_THREADS) void jacobi_fused_kernel(int H, int W,
   const int64_t img = (int64_t)n * H * W;
   for_points(tid, ly0, lx0, ly1 - ly0, LW, [&](int y, int x) { src[(y - ly0) * LW + (x - lx0)] = u[img + (int64_t)y * W + x]; });
   if (!BWD) {
-    const int ry0 = max(ty0 - (k - 1) * RY, 0), ry1 = min(ty1 + (k - 1) * RY, H);
-    const int rx0 = max(tx0 - (k - 1) * RX, 0), rx1 = min(tx1 + (k - 1) * RX, W);
+    int ry0 = max(ty0 - (k - 1) * RY, 0), ry1 = min(ty1 + (k - 1) * RY, H);
+    int rx0 = max(tx0 - (k - 1) * RX, 0), rx1 = min(tx1 + (k - 1) * RX, W);
+    if (BC) {                                                         // the first sweep's computed region C_1; every later one lies inside it
+      int d0, d1;
+      jac_range<false>(ty0, ty1, H, RY, k, 1, mask & 1, mask & 2, d0, d1, ry0, ry1);
+      jac_range<false>(tx0, tx1, W, RX, k, 1, mask & 4, mask & 8, d0, d1, rx0, rx1);
+    }
     for_points(tid, ry0, rx0, ry1 - ry0, rx1 - rx0, [&](int y, int x) { rb[(y - ly0) * LW + (x - lx0)] = rhs[img + (int64_t)y * W + x]; });
   }
   __syncthreads();
 
+  // J (or J^T) at one point, read from `in`
+  auto point = [&](const float* in, int c, int y, int x) -> float {
+    const bool in_x = x >= RX && x < W - RX, in_y = y >= RY && y < H - RY;
+    float v;
+    if (!BWD) {
+      if (in_x && in_y) {
+        float acc = 0.f;
+#pragma unroll
+        for (int i = 0; i < SY; ++i)
+          if (i != RY) acc = fmaf(cy[i], in[c + (i - RY) * LW], acc);
+#pragma unroll
+        for (int j = 0; j < SX; ++j)
+          if (j != RX) acc = fmaf(cx[j], in[c + (j - RX)], acc);
+        v = dinv * (rb[c] - acc);
+      } else {
+        v = in[c];
+      }
+    } else {
+      // adjoint: gather from the interior points q = p - t whose stencil reached p with tap t
+      float acc = 0.f;
+      if (in_x) {
+#pragma unroll
+        for (int i = 0; i < SY; ++i) {
+          const int qy = y - (i - RY);
+          if (i != RY && qy >= RY && qy < H - RY) acc = fmaf(cy[i], in[c - (i - RY) * LW], acc);
+        }
+      }
+      if (in_y) {
+#pragma unroll
+        for (int j = 0; j < SX; ++j) {
+          const int qx = x - (j - RX);
+          if (j != RX && qx >= RX && qx < W - RX) acc = fmaf(cx[j], in[c - (j - RX)], acc);
+        }
+      }
+      v = ((in_x && in_y) ? 0.f : in[c]) - dinv * acc;
+    }
+    return v;
+  };
+
   for (int s = 1; s <= k; ++s) {
     const int g = k - s;                                              // radii this sweep's region still extends past the tile
-    const int y0 = max(ty0 - g * RY, 0), y1 = min(ty1 + g * RY, H);
-    const int x0 = max(tx0 - g * RX, 0), x1 = min(tx1 + g * RX, W);
-    for_points(tid, y0, x0, y1 - y0, x1 - x0, [&](int y, int x) {
-      const int c = (y - ly0) * LW + (x - lx0);
-      const bool in_x = x >= RX && x < W - RX, in_y = y >= RY && y < H - RY;
-      float v;
+    int y0 = max(ty0 - g * RY, 0), y1 = min(ty1 + g * RY, H);
+    int x0 = max(tx0 - g * RX, 0), x1 = min(tx1 + g * RX, W);
+    if (BC) {
+      int cy0, cy1, cx0, cx1;                                         // forward: C_s; adjoint: G_s
+      jac_range<BWD>(ty0, ty1, H, RY, k, s, mask & 1, mask & 2, y0, y1, cy0, cy1);
+      jac_range<BWD>(tx0, tx1, W, RX, k, s, mask & 4, mask & 8, x0, x1, cx0, cx1);
       if (!BWD) {
-        if (in_x && in_y) {
-          float acc = 0.f;
-#pragma unroll
-          for (int i = 0; i < SY; ++i)
-            if (i != RY) acc = fmaf(cy[i], src[c + (i - RY) * LW], acc);
-#pragma unroll
-          for (int j = 0; j < SX; ++j)
-            if (j != RX) acc = fmaf(cx[j], src[c + (j - RX)], acc);
-          v = dinv * (rb[c] - acc);
-        } else {
-          v = src[c];
+        // does what this sweep delivers meet a Neumann band?  (the same for every thread of the workgroup)
+        const bool touch = ((mask & 1) && y0 < RY) || ((mask & 2) && y1 > H - RY) || ((mask & 4) && x0 < RX) || ((mask & 8) && x1 > W - RX);
+        if (touch) {
+          for_points(tid, cy0, cx0, cy1 - cy0, cx1 - cx0, [&](int y, int x) {
+            const int c = (y - ly0) * LW + (x - lx0);
+            dst[c] = point(src, c, y, x);
+          });
+          __syncthreads();                                            // the refresh reads this sweep's J(u) as other threads wrote it
+          for_points(tid, y0, x0, y1 - y0, x1 - x0, [&](int y, int x) {
+            const int c = (y - ly0) * LW + (x - lx0);
+            int my, mx;
+            const bool r = jac_refreshed<RY, RX>(y, x, H, W, mask, my, mx);   // sources are interior points: no refresh writes what another reads
+            const int m = (my - ly0) * LW + (mx - lx0);
+            if (s == k) out[img + (int64_t)y * W + x] = dst[r ? m : c];
+            else if (r) dst[c] = dst[m];
+          });
+          __syncthreads();
+          float* t = src; src = dst; dst = t;
+          continue;
         }
       } else {
-        // adjoint: gather from the interior points q = p - t whose stencil reached p with tap t
-        float acc = 0.f;
-        if (in_x) {
-#pragma unroll
-          for (int i = 0; i < SY; ++i) {
-            const int qy = y - (i - RY);
-            if (i != RY && qy >= RY && qy < H - RY) acc = fmaf(cy[i], src[c - (i - RY) * LW], acc);
-          }
+        // does R_m^T act on the region its output is gathered from?
+        const bool touch = ((mask & 1) && cy0 < 2 * RY) || ((mask & 2) && cy1 > H - 2 * RY) || ((mask & 4) && cx0 < 2 * RX) || ((mask & 8) && cx1 > W - 2 * RX);
+        if (touch) {
+          // R_m^T as a gather: a point that kept its own value passes its gradient on, and an interior point collects those of the band points
+          // that mirrored it - along y, along x, and across a Neumann/Neumann corner - in this fixed order
+          for_points(tid, cy0, cx0, cy1 - cy0, cx1 - cx0, [&](int y, int x) {
+            const int c = (y - ly0) * LW + (x - lx0);
+            int my, mx;
+            float v = jac_refreshed<RY, RX>(y, x, H, W, mask, my, mx) ? 0.f : src[c];
+            const bool in_x = x >= RX && x < W - RX, in_y = y >= RY && y < H - RY;
+            const bool yl = (mask & 1) && y >= RY && y < 2 * RY, yh = (mask & 2) && y >= H - 2 * RY && y < H - RY;
+            const bool xl = (mask & 4) && x >= RX && x < 2 * RX, xh = (mask & 8) && x >= W - 2 * RX && x < W - RX;
+            const int oyl = (2 * RY - 1 - 2 * y) * LW, oyh = (2 * (H - RY) - 1 - 2 * y) * LW;
+            const int oxl = 2 * RX - 1 - 2 * x, oxh = 2 * (W - RX) - 1 - 2 * x;
+            if (in_x && yl) v += src[c + oyl];
+            if (in_x && yh) v += src[c + oyh];
+            if (in_y && xl) v += src[c + oxl];
+            if (in_y && xh) v += src[c + oxh];
+            if (yl && xl) v += src[c + oyl + oxl];
+            if (yl && xh) v += src[c + oyl + oxh];
+            if (yh && xl) v += src[c + oyh + oxl];
+            if (yh && xh) v += src[c + oyh + oxh];
+            dst[c] = v;
+          });
+          __syncthreads();
+          for_points(tid, y0, x0, y1 - y0, x1 - x0, [&](int y, int x) {
+            const int c = (y - ly0) * LW + (x - lx0);
+            const float v = point(dst, c, y, x);
+            if (s == k) out[img + (int64_t)y * W + x] = v;
+            else src[c] = v;                                          // all of src was read before the barrier: the result returns to it, no exchange
+          });
+          __syncthreads();
+          continue;
         }
-        if (in_y) {
-#pragma unroll
-          for (int j = 0; j < SX; ++j) {
-            const int qx = x - (j - RX);
-            if (j != RX && qx >= RX && qx < W - RX) acc = fmaf(cx[j], src[c - (j - RX)], acc);
-          }
-        }
-        v = ((in_x && in_y) ? 0.f : src[c]) - dinv * acc;
       }
+    }
+    for_points(tid, y0, x0, y1 - y0, x1 - x0, [&](int y, int x) {
+      const int c = (y - ly0) * LW + (x - lx0);
+      const float v = point(src, c, y, x);
       if (s == k) out[img + (int64_t)y * W + x] = v;                 // the last sweep's region is the tile itself
       else dst[c] = v;
     });
@@ -111,17 +236,37 @@ __global__ __launch_bounds__(JAC_THREADS) void jacobi_fused_kernel(int H, int W,
   }
 }
 
+// mask < 0: the frozen-band kernels.  mask >= 0: the boundary-aware ones (with mask 0 they compute the same bits - no sweep ever refreshes - but the
+// entry points send mask 0 to the frozen-band kernels, which are faster).
 template <bool BWD>
-int jacobi_launch(pcnn_handle_s* h, int N, int H, int W, int sy, int sx, int k, const float* coef, const float* u, const float* rhs, float* out) {
+int jacobi_launch(pcnn_handle_s* h, int N, int H, int W, int sy, int sx, int k, const float* coef, const float* u, const float* rhs, float* out, int mask) {
   const int ry = sy / 2, rx = sx / 2;
   const dim3 grid((unsigned)pcnn_cdiv(W, JAC_TILE), (unsigned)pcnn_cdiv(H, JAC_TILE), (unsigned)N);
-  const size_t lds = (size_t)(BWD ? 2 : 3) * (JAC_TILE + 2 * k * ry) * (JAC_TILE + 2 * k * rx) * sizeof(float);
+  size_t per = (size_t)(JAC_TILE + 2 * k * ry) * (JAC_TILE + 2 * k * rx);
+  if (mask >= 0) {
+    // the largest loaded region over the tiles of each axis, from the recurrence the kernel itself evaluates
+    int mh = 0, mw = 0, d0, d1, c0, c1;
+    for (int t = 0; t < H; t += JAC_TILE) {
+      jac_range<BWD>(t, t + JAC_TILE < H ? t + JAC_TILE : H, H, ry, k, 0, mask & 1, mask & 2, d0, d1, c0, c1);
+      mh = d1 - d0 > mh ? d1 - d0 : mh;
+    }
+    for (int t = 0; t < W; t += JAC_TILE) {
+      jac_range<BWD>(t, t + JAC_TILE < W ? t + JAC_TILE : W, W, rx, k, 0, mask & 4, mask & 8, d0, d1, c0, c1);
+      mw = d1 - d0 > mw ? d1 - d0 : mw;
+    }
+    per = (size_t)mh * mw;
+  }
+  const size_t lds = (size_t)(BWD ? 2 : 3) * per * sizeof(float);
+  PCNN_REQUIRE(h, lds <= 160u * 1024u, "pcnn_jacobi_fused: %zu bytes of LDS for %d fused sweeps of a %d x %d stencil", lds, k, sy, sx);
   auto go = [&](auto kernel) {
     set_lds(kernel, lds);
-    hipLaunchKernelGGL(kernel, grid, dim3(JAC_THREADS), lds, h->stream, H, W, k, coef, u, rhs, out);
+    hipLaunchKernelGGL(kernel, grid, dim3(JAC_THREADS), lds, h->stream, H, W, k, coef, u, rhs, out, mask, (int)per);
   };
-#define JAC_CASE(A, B) \
-  case A * 8 + B: go(jacobi_fused_kernel<A, B, BWD>); break;
+#define JAC_CASE(A, B)                                        \
+  case A * 8 + B:                                             \
+    if (mask >= 0) go(jacobi_fused_kernel<A, B, BWD, true>);  \
+    else go(jacobi_fused_kernel<A, B, BWD, false>);           \
+    break;
   switch (ry * 8 + rx) {
     JAC_CASE(1, 1) JAC_CASE(1, 2) JAC_CASE(1, 3) JAC_CASE(1, 4)
     JAC_CASE(2, 1) JAC_CASE(2, 2) JAC_CASE(2, 3) JAC_CASE(2, 4)
@@ -137,7 +282,7 @@ int jacobi_launch(pcnn_handle_s* h, int N, int H, int W, int sy, int sx, int k, 
 // that the last launch writes `out` and no launch reads what it writes.
 template <bool BWD>
 int jacobi_chain(pcnn_handle_s* h, const char* name, int N, int H, int W, int sy, int sx, const float* coef, const float* u, const float* rhs,
-                 int n_sweeps, float* out) {
+                 int n_sweeps, float* out, int mask = -1) {
   const int kmax = pcnn_jacobi_fused_max_sweeps(sy, sx);
   const int launches = pcnn_cdiv(n_sweeps, kmax);
   float* tmp = nullptr;
@@ -150,7 +295,7 @@ int jacobi_chain(pcnn_handle_s* h, const char* name, int N, int H, int W, int sy
   for (int l = 0; l < launches; ++l) {
     const int k = pcnn_cdiv(left, launches - l);
     float* to = ((launches - 1 - l) % 2 == 0) ? out : tmp;
-    const int rc = jacobi_launch<BWD>(h, N, H, W, sy, sx, k, coef, in, rhs, to);
+    const int rc = jacobi_launch<BWD>(h, N, H, W, sy, sx, k, coef, in, rhs, to, mask);
     if (rc) return rc;
     in = to;
     left -= k;
@@ -161,6 +306,11 @@ int jacobi_chain(pcnn_handle_s* h, const char* name, int N, int H, int W, int sy
 
 bool jacobi_shape_ok(int N, int H, int W, int sy, int sx, int n_sweeps) {
   return N >= 1 && N <= 65535 && sy % 2 == 1 && sx % 2 == 1 && sy >= 3 && sy <= 9 && sx >= 3 && sx <= 9 && H > 2 * (sy / 2) && W > 2 * (sx / 2) && n_sweeps >= 1;
+}
+
+// a Neumann edge's mirror sources must be interior points: three radii along every axis the mask touches
+bool jacobi_mask_ok(int H, int W, int sy, int sx, int mask) {
+  return mask >= 0 && mask < 16 && (!(mask & 3) || H >= 3 * (sy / 2)) && (!(mask & 12) || W >= 3 * (sx / 2));
 }
 
 }  // namespace
@@ -189,4 +339,31 @@ extern "C" int pcnn_jacobi_fused_bwd(pcnn_handle h, int N, int H, int W, int sy,
                H, W, n_sweeps);
   PCNN_REQUIRE(h, du != dout, "pcnn_jacobi_fused_bwd: du must not alias dout");
   return jacobi_chain<true>(h, "pcnn_jacobi_fused_bwd", N, H, W, sy, sx, coef, dout, nullptr, n_sweeps, du);
+}
+
+extern "C" int pcnn_jacobi_fused_bc_fwd(pcnn_handle h, int N, int H, int W, int sy, int sx, const float* coef, const float* u, const float* rhs, int n_sweeps,
+                                        int neumann_mask, float* out) {
+  PCNN_REQUIRE(h, h && coef && u && rhs && out, "pcnn_jacobi_fused_bc_fwd: null argument");
+  PCNN_REQUIRE(h, jacobi_shape_ok(N, H, W, sy, sx, n_sweeps),
+               "pcnn_jacobi_fused_bc_fwd: needs odd stencil sizes in 3..9, H > 2*(sy/2), W > 2*(sx/2), n_sweeps >= 1 (got %d x %d stencil, %d x %d image, %d sweeps)", sy,
+               sx, H, W, n_sweeps);
+  PCNN_REQUIRE(h, jacobi_mask_ok(H, W, sy, sx, neumann_mask),
+               "pcnn_jacobi_fused_bc_fwd: needs neumann_mask in 0..15, H >= 3*(sy/2) with a left or right Neumann edge, W >= 3*(sx/2) with a bottom or top one (got mask %d, "
+               "%d x %d stencil, %d x %d image)", neumann_mask, sy, sx, H, W);
+  PCNN_REQUIRE(h, out != u && out != rhs, "pcnn_jacobi_fused_bc_fwd: out must not alias u or rhs");
+  // mask 0 runs the frozen-band kernels: the same bits, and measurably faster than the boundary-aware ones with nothing to refresh
+  return jacobi_chain<false>(h, "pcnn_jacobi_fused_bc_fwd", N, H, W, sy, sx, coef, u, rhs, n_sweeps, out, neumann_mask ? neumann_mask : -1);
+}
+
+extern "C" int pcnn_jacobi_fused_bc_bwd(pcnn_handle h, int N, int H, int W, int sy, int sx, const float* coef, const float* dout, int n_sweeps, int neumann_mask,
+                                        float* du) {
+  PCNN_REQUIRE(h, h && coef && dout && du, "pcnn_jacobi_fused_bc_bwd: null argument");
+  PCNN_REQUIRE(h, jacobi_shape_ok(N, H, W, sy, sx, n_sweeps),
+               "pcnn_jacobi_fused_bc_bwd: needs odd stencil sizes in 3..9, H > 2*(sy/2), W > 2*(sx/2), n_sweeps >= 1 (got %d x %d stencil, %d x %d image, %d sweeps)", sy,
+               sx, H, W, n_sweeps);
+  PCNN_REQUIRE(h, jacobi_mask_ok(H, W, sy, sx, neumann_mask),
+               "pcnn_jacobi_fused_bc_bwd: needs neumann_mask in 0..15, H >= 3*(sy/2) with a left or right Neumann edge, W >= 3*(sx/2) with a bottom or top one (got mask %d, "
+               "%d x %d stencil, %d x %d image)", neumann_mask, sy, sx, H, W);
+  PCNN_REQUIRE(h, du != dout, "pcnn_jacobi_fused_bc_bwd: du must not alias dout");
+  return jacobi_chain<true>(h, "pcnn_jacobi_fused_bc_bwd", N, H, W, sy, sx, coef, dout, nullptr, n_sweeps, du, neumann_mask ? neumann_mask : -1);
 }

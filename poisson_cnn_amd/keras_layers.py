@@ -507,13 +507,14 @@ class MergeWithAttention(_Layer):
 class JacobiIterationLayer(_Layer):
     """layers/JacobiIterationLayer.py:7-66: n_iterations weighted-Jacobi sweeps new = D^-1 (rhs - (L+U) guess) on the interior of the FD operator
     build_fd_coefficients(stencil_sizes, orders), the boundary ring of width stencil//2 kept; call([guess, rhs, dx]), dx (N, 2) or (N, 1).
-    stencil_sizes: odd, 3..9 per axis; orders: even, >= 2, below the axis's stencil size (layers.JacobiIterationLayer); an int means both axes."""
+    stencil_sizes: odd, 3..9 per axis; orders: even, >= 2, below the axis's stencil size (layers.JacobiIterationLayer); an int means both axes.
+    boundary_types (extension): a dict edge -> 'dirichlet' | 'neumann' re-imposes the Neumann edges after every sweep (layers.JacobiIterationLayer)."""
 
-    def __init__(self, stencil_sizes, orders, ndims=None, data_format='channels_first', n_iterations=5, device=None):
+    def __init__(self, stencil_sizes, orders, ndims=None, data_format='channels_first', n_iterations=5, device=None, boundary_types=None):
         super().__init__(data_format, device)
         if ndims not in (None, 2):
             raise NotImplementedError('JacobiIterationLayer: 2-D only')
-        self.layer = L.JacobiIterationLayer(n_iterations, stencil_sizes, orders)
+        self.layer = L.JacobiIterationLayer(n_iterations, stencil_sizes, orders, boundary_types=boundary_types)
         self.built = True
 
     def call(self, inputs, training=False):

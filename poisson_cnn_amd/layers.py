@@ -765,11 +765,24 @@ class JacobiIterationLayer:
     The model's stencil ([3,3],[2,2], models/Homogeneous_Poisson_NN_Legacy.py:104) with `fused` unset runs one launch per sweep, as it always has.
     Any other stencil, or fused=True, runs csrc/stencil.hip: up to ops.jacobi_k_max(sy, sx) sweeps per launch, blocked in LDS.
     Orders must be even, at least 2 and below that axis's stencil size: an odd order has a zero centre coefficient (the reference divides by it and
-    returns inf), and the Vandermonde system of get_fd_coefficients has no row for an order >= the stencil size."""
+    returns inf), and the Vandermonde system of get_fd_coefficients has no row for an order >= the stencil size.
 
-    def __init__(self, n_iterations=5, stencil_sizes=(3, 3), orders=(2, 2), fused=None):
+    boundary_types (extension): None keeps the ring frozen, as the reference does.  A dict edge -> 'dirichlet' | 'neumann' (dataset._neumann_flags)
+    runs the fused route for every stencil and re-imposes the Neumann edges after every sweep: their band takes the mirror image of the updated
+    interior (first order, u_0 = u_1, as the model's SYMMETRIC ring), forward and adjoint; Dirichlet edges stay frozen."""
+
+    def __init__(self, n_iterations=5, stencil_sizes=(3, 3), orders=(2, 2), fused=None, boundary_types=None):
         from .losses import get_fd_coefficients
         self.n = int(n_iterations)
+        self.neumann_mask = None
+        if boundary_types is not None:
+            from .dataset import _neumann_flags
+            if not isinstance(boundary_types, dict):
+                raise ValueError("JacobiIterationLayer: boundary_types is None or a dict edge -> 'dirichlet' | 'neumann', got %r" % (boundary_types,))
+            if fused is not None and not fused:
+                raise ValueError('JacobiIterationLayer: boundary_types runs on the fused kernels only (fused=False given)')
+            self.neumann_mask = sum(1 << i for i, f in enumerate(_neumann_flags(boundary_types)) if f)
+            fused = True
         ss = [stencil_sizes] * 2 if isinstance(stencil_sizes, (int, np.integer)) else list(stencil_sizes)
         od = [orders] * 2 if isinstance(orders, (int, np.integer)) else list(orders)
         if len(ss) != 2 or len(od) != 2:
@@ -820,7 +833,7 @@ class JacobiIterationLayer:
         if self.n < 1:
             return guess
         self.coef = self.coefficient_rows(dx2)
-        return ops.jacobi_fused(guess, rhs, self.coef, self.stencil_sizes, self.n)
+        return ops.jacobi_fused(guess, rhs, self.coef, self.stencil_sizes, self.n, self.neumann_mask or 0)
 
     def backward(self, dout):
         if not self.fused:
@@ -830,4 +843,4 @@ class JacobiIterationLayer:
             return d
         if self.n < 1:
             return dout
-        return ops.jacobi_fused_bwd(dout, self.coef, self.stencil_sizes, self.n)
+        return ops.jacobi_fused_bwd(dout, self.coef, self.stencil_sizes, self.n, self.neumann_mask or 0)

@@ -359,7 +359,14 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
     def __init__(self, data_format='channels_first', final_convolutions_config=None, pre_bottleneck_convolutions_config=None,
                  bottleneck_deconv_config=None, bottleneck_multilinear_config=None, input_normalization=None, output_scaling=None,
                  use_batchnorm=False, postsmoother_iterations=5, use_scaling=False, use_positional_embeddings=True, scaling_config=None,
-                 gradient_accumulation_steps=None, bc_type='dirichlet', device=None, seed=0, batchnorm_training=False):
+                 gradient_accumulation_steps=None, bc_type='dirichlet', device=None, seed=0, batchnorm_training=False, smoother_boundaries='frozen'):
+        """bc_type: 'dirichlet' or 'neumann' for all four edges (the reference), or - an extension - a dict 'left' | 'right' | 'bottom' | 'top' ->
+        'dirichlet' | 'neumann' with the dataset's edge names (left: y = 0, right: y = H-1, bottom: x = 0, top: x = W-1 of the (N,1,H,W) output; a missing
+        edge is Dirichlet, at a corner a Dirichlet edge wins).  A Neumann edge is enforced as the reference's SYMMETRIC ring does, to first order:
+        u_0 = u_1.
+        smoother_boundaries: 'frozen' - the post-smoother keeps the ring it is given, as the reference's does, so its sweeps move the interior away
+        from a Neumann edge's mirror values; 'enforce' - the smoother re-imposes the model's Neumann edges after every sweep
+        (layers.JacobiIterationLayer(boundary_types=...)); with no Neumann edge there is nothing to enforce and the two are the same."""
         if data_format not in ('channels_first', 'channels_last'):
             raise ValueError('data_format must be channels_first or channels_last')
         if pre_bottleneck_convolutions_config is None:
@@ -368,8 +375,15 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
             raise ValueError('Provide a config for bottleneck blocks')
         if final_convolutions_config is None:
             raise ValueError('Provide a config for final convolutions')
-        if bc_type.lower() not in ('dirichlet', 'neumann'):
+        if isinstance(bc_type, dict):
+            from .dataset import _neumann_flags
+            flags = _neumann_flags(bc_type)
+        elif not isinstance(bc_type, str) or bc_type.lower() not in ('dirichlet', 'neumann'):
             raise ValueError('bc_type can only be neumann or dirichlet.')
+        else:
+            flags = (bc_type.lower() == 'neumann',) * 4
+        if smoother_boundaries not in ('frozen', 'enforce'):
+            raise ValueError("smoother_boundaries can only be 'frozen' or 'enforce'.")
         self._init_device(device, _CPU_NOTE_RAISES)
         self.ndims = 2
         self.data_format = data_format
@@ -378,7 +392,9 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
         self.output_scaling = process_output_scaling_modes(output_scaling)
         self.use_batchnorm = use_batchnorm
         self.use_positional_embeddings = use_positional_embeddings
-        self.neumann = bc_type.lower() == 'neumann'
+        self.neumann = all(flags)
+        self.neumann_mask = sum(1 << i for i, f in enumerate(flags) if f)
+        self.per_edge_bc = isinstance(bc_type, dict)              # a dict runs the per-edge ring kernels, a string the reference's two modes as before
         self.store = S = L.ParamStore()
         # BatchNormalization mode inside train_step: False = moving statistics (what the reference's train_step most likely does,
         # SURVEY.md row H4), True = batch statistics + moving-average update (Keras training=True semantics, per replica)
@@ -445,7 +461,10 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
         for i, (u, a) in enumerate(zip(units, acts)):
             self.dx_dense_layers.append(L.Dense(S, 'dx_dense%d' % i, din, u, a))
             din = u
-        self.postsmoother = L.JacobiIterationLayer(postsmoother_iterations) if postsmoother_iterations > 0 else None
+        enforce = None
+        if smoother_boundaries == 'enforce' and self.neumann_mask:
+            enforce = {e: 'neumann' if f else 'dirichlet' for e, f in zip(('left', 'right', 'bottom', 'top'), flags)}
+        self.postsmoother = L.JacobiIterationLayer(postsmoother_iterations, boundary_types=enforce) if postsmoother_iterations > 0 else None
         self.scaling = L.Scaling(S, C, 'scaling', **scaling_config) if use_scaling else None
         S.finalize(self.device)
         S.initialize(seed)
@@ -562,7 +581,7 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
             hint = lyr.out_absmax
         if self.scaling is not None:
             x = self.scaling.forward(x, rhs_hw.view(N, H, W, 1), training=training)
-        x = ops.bc_ring_fwd(x, self.neumann)                      # :251
+        x = ops.bc_ring_edges_fwd(x, self.neumann_mask) if self.per_edge_bc else ops.bc_ring_fwd(x, self.neumann)     # :251
         if self.postsmoother is not None:
             x = self.postsmoother.forward(x, rhs_hw.view(N, H, W, 1), _dx_pair(dx), training=training)
         return x.view(N, 1, H, W)
@@ -577,7 +596,7 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
         d = dpred.contiguous().view(N, H, W, 1)
         if self.postsmoother is not None:
             d = self.postsmoother.backward(d)
-        d = ops.bc_ring_bwd(d, self.neumann)
+        d = ops.bc_ring_edges_bwd(d, self.neumann_mask) if self.per_edge_bc else ops.bc_ring_bwd(d, self.neumann)
         if self.scaling is not None:
             d = self.scaling.backward(d)
         ready = False                                              # the gradient arriving at a layer already went through its activation backward

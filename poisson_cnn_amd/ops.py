@@ -969,6 +969,22 @@ def bc_ring_bwd(dy, neumann):
     return dx
 
 
+def bc_ring_edges_fwd(x, mask):
+    """The ring with a boundary type per edge: mask bit 0 / 1 / 2 / 3 set = the left (y = 0) / right (y = H-1) / bottom (x = 0) / top (x = W-1) edge is
+    Neumann, clear = Dirichlet; at a corner a Dirichlet edge wins.  x (N,H,W,1)."""
+    N, H, W = x.shape[0], x.shape[1], x.shape[2]
+    y = torch.empty_like(x)
+    handle().call('pcnn_bc_ring_edges_fwd', c_int(N), c_int(H), c_int(W), c_int(int(mask)), _p(x), _p(y))
+    return y
+
+
+def bc_ring_edges_bwd(dy, mask):
+    N, H, W = dy.shape[0], dy.shape[1], dy.shape[2]
+    dx = torch.empty_like(dy)
+    handle().call('pcnn_bc_ring_edges_bwd', c_int(N), c_int(H), c_int(W), c_int(int(mask)), _p(dy), _p(dx))
+    return dx
+
+
 def jacobi_sweep(u, rhs, dx2):
     N, H, W = u.shape[0], u.shape[1], u.shape[2]
     out = torch.empty_like(u)
@@ -993,20 +1009,25 @@ def jacobi_k_max(sy, sx):
     return int(_lib.load().pcnn_jacobi_fused_max_sweeps(int(sy), int(sx)))
 
 
-def jacobi_fused(u, rhs, coef, stencil_sizes, n_sweeps):
+def jacobi_fused(u, rhs, coef, stencil_sizes, n_sweeps, neumann_mask=0):
     """n_sweeps weighted-Jacobi sweeps of the cross-shaped stencil whose per-sample rows are `coef` (N, sy+sx+1): the H taps, the W taps (centres
-    zero), 1 / diagonal.  u, rhs (N,H,W,1)."""
+    zero), 1 / diagonal.  u, rhs (N,H,W,1).  neumann_mask (bits as in bc_ring_edges_fwd) non-zero: after every sweep the frozen band is refreshed on
+    its Neumann edges with the mirror image of the updated interior (pcnn_jacobi_fused_bc_fwd); 0: the band stays frozen, today's entry point."""
     N, H, W = u.shape[0], u.shape[1], u.shape[2]
     sy, sx = int(stencil_sizes[0]), int(stencil_sizes[1])
     if tuple(coef.shape) != (N, sy + sx + 1) or not coef.is_contiguous():
         raise ValueError('jacobi_fused: coef must be a contiguous (%d, %d) tensor' % (N, sy + sx + 1))
     u, rhs = u.contiguous(), rhs.contiguous()
     out = torch.empty_like(u)
+    if neumann_mask:
+        handle().call('pcnn_jacobi_fused_bc_fwd', c_int(N), c_int(H), c_int(W), c_int(sy), c_int(sx), _p(coef), _p(u), _p(rhs), c_int(n_sweeps),
+                      c_int(int(neumann_mask)), _p(out))
+        return out
     handle().call('pcnn_jacobi_fused_fwd', c_int(N), c_int(H), c_int(W), c_int(sy), c_int(sx), _p(coef), _p(u), _p(rhs), c_int(n_sweeps), _p(out))
     return out
 
 
-def jacobi_fused_bwd(dout, coef, stencil_sizes, n_sweeps):
+def jacobi_fused_bwd(dout, coef, stencil_sizes, n_sweeps, neumann_mask=0):
     """The adjoint of jacobi_fused w.r.t. u."""
     N, H, W = dout.shape[0], dout.shape[1], dout.shape[2]
     sy, sx = int(stencil_sizes[0]), int(stencil_sizes[1])
@@ -1014,6 +1035,10 @@ def jacobi_fused_bwd(dout, coef, stencil_sizes, n_sweeps):
         raise ValueError('jacobi_fused_bwd: coef must be a contiguous (%d, %d) tensor' % (N, sy + sx + 1))
     dout = dout.contiguous()
     du = torch.empty_like(dout)
+    if neumann_mask:
+        handle().call('pcnn_jacobi_fused_bc_bwd', c_int(N), c_int(H), c_int(W), c_int(sy), c_int(sx), _p(coef), _p(dout), c_int(n_sweeps),
+                      c_int(int(neumann_mask)), _p(du))
+        return du
     handle().call('pcnn_jacobi_fused_bwd', c_int(N), c_int(H), c_int(W), c_int(sy), c_int(sx), _p(coef), _p(dout), c_int(n_sweeps), _p(du))
     return du
 

@@ -300,8 +300,19 @@ def main(argv=None):
         dataset = reverse_poisson_dataset_generator(**dcfg)
         model = classes[model_type](**mcfg)
     else:
-        neumann = config['model'].get('bc_type', 'dirichlet').lower() == 'neumann'
-        if args.dataset_type == 'numerical':
+        bc_type = config['model'].get('bc_type', 'dirichlet')
+        if isinstance(bc_type, dict):                # per-edge boundary types (extension): the numerical generator's mixed Dirichlet/Neumann solve
+            from .dataset import _neumann_flags
+            flags = _neumann_flags(bc_type)
+            if args.dataset_type != 'numerical' and any(flags) and not all(flags):
+                raise ValueError('there is no analytic mixed Dirichlet/Neumann generator: a per-edge bc_type needs --dataset_type numerical (got %r)' % (bc_type,))
+            neumann = all(flags)
+        else:
+            neumann = bc_type.lower() == 'neumann'
+        if args.dataset_type == 'numerical' and isinstance(bc_type, dict):
+            # homogeneous data on every edge (any boundaries string but 'random' is zero data): the mixed solver's ground truth for the model's edge types
+            dataset = numerical_dataset_generator(**dict(dcfg, boundary_types=bc_type, boundaries='zero'))
+        elif args.dataset_type == 'numerical':
             dataset = numerical_dataset_generator(**dcfg)
         elif neumann:
             dataset = reverse_poisson_dataset_generator_homogeneous_neumann(**dcfg)

@@ -14,6 +14,12 @@ synchronise; the spread reported is (max - min) / median over the repeats' per-c
 result on the same inputs (rel-L2) before anything is timed.  No threshold is applied.
 
     python tools/bench_jacobi.py [--calls 20] [--repeats 7] [--warmup 3] [--out profiles/jacobi_bench.json]
+
+With `--neumann-mask M[,M...]` it measures the boundary-aware entry points instead (pcnn_jacobi_fused_bc_fwd/bwd, called through the handle so that
+mask 0 runs them too) against the frozen-band ones (pcnn_jacobi_fused_fwd/bwd) in the same process: 5 sweeps, stencils [3,3] and [9,9], both shapes,
+forward and adjoint, the routes alternated and timed in the same way.
+
+    python tools/bench_jacobi.py --neumann-mask 0,15 [--out profiles/jacobi_bc_bench.json]
 """
 import argparse
 import json
@@ -44,18 +50,81 @@ def model_bytes_per_px(n, ss, T, kmax):
     return b
 
 
+def bench_bc(args, masks):
+    from ctypes import c_int
+    import torch
+    from poisson_cnn_amd import ops
+    from poisson_cnn_amd.layers import JacobiIterationLayer
+    n = 5
+    res = {'device': torch.cuda.get_device_name(0), 'n_sweeps': n, 'calls_per_timing': args.calls, 'repeats': args.repeats, 'cases': []}
+    h = ops.handle()
+    for (N, S) in ((8, 1024), (32, 512)):
+        g = torch.Generator(device='cuda').manual_seed(S)
+        u = torch.randn(N, S, S, 1, device='cuda', generator=g)
+        rhs = torch.randn(N, S, S, 1, device='cuda', generator=g)
+        dx2 = torch.rand(N, 2, device='cuda', generator=g) * 0.045 + 0.005
+        out = torch.empty_like(u)
+        dims = (c_int(N), c_int(S), c_int(S))
+        for ss in ((3, 3), (9, 9)):
+            coef = JacobiIterationLayer(n, ss, (2, 2), fused=True).coefficient_rows(dx2)
+            sz = (c_int(ss[0]), c_int(ss[1]))
+            for direction in ('fwd', 'bwd'):
+                def frozen():
+                    if direction == 'fwd':
+                        h.call('pcnn_jacobi_fused_fwd', *dims, *sz, ops._p(coef), ops._p(u), ops._p(rhs), c_int(n), ops._p(out))
+                    else:
+                        h.call('pcnn_jacobi_fused_bwd', *dims, *sz, ops._p(coef), ops._p(u), c_int(n), ops._p(out))
+
+                def aware(m):
+                    if direction == 'fwd':
+                        h.call('pcnn_jacobi_fused_bc_fwd', *dims, *sz, ops._p(coef), ops._p(u), ops._p(rhs), c_int(n), c_int(m), ops._p(out))
+                    else:
+                        h.call('pcnn_jacobi_fused_bc_bwd', *dims, *sz, ops._p(coef), ops._p(u), c_int(n), c_int(m), ops._p(out))
+                routes = [('frozen', frozen)] + [('mask_%d' % m, (lambda m=m: aware(m))) for m in masks]
+                for _, fn in routes:
+                    for _ in range(args.warmup):
+                        fn()
+                torch.cuda.synchronize()
+                times = [[] for _ in routes]
+                for _ in range(args.repeats):
+                    for i, (_, fn) in enumerate(routes):
+                        t0 = time.perf_counter()
+                        for _ in range(args.calls):
+                            fn()
+                        torch.cuda.synchronize()
+                        times[i].append((time.perf_counter() - t0) * 1e3 / args.calls)
+                case = {'N': N, 'H': S, 'W': S, 'stencil': list(ss), 'direction': direction, 'routes': []}
+                for (name, _), t in zip(routes, times):
+                    t = sorted(t)
+                    med = t[len(t) // 2]
+                    case['routes'].append({'route': name, 'median_ms': med, 'min_ms': t[0], 'max_ms': t[-1], 'spread': (t[-1] - t[0]) / med})
+                base = case['routes'][0]['median_ms']
+                for r in case['routes']:
+                    r['vs_frozen'] = r['median_ms'] / base
+                res['cases'].append(case)
+                print('%dx%dx%d %s %s n=%d: ' % (N, S, S, list(ss), direction, n) + ' | '.join('%s %.3f ms (x%.3f, spread %.1f%%)' % (r['route'], r['median_ms'],
+                      r['vs_frozen'], 100 * r['spread']) for r in case['routes']), flush=True)
+    if args.out:
+        with open(args.out, 'w') as f:
+            json.dump(res, f, indent=1)
+    print(json.dumps({'jacobi_bc_bench': 'done', 'cases': len(res['cases'])}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--calls', type=int, default=20)
     ap.add_argument('--repeats', type=int, default=7)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--neumann-mask', default=None, help='comma-separated masks: time the boundary-aware entry points against the frozen-band ones')
     args = ap.parse_args()
     import torch
     from poisson_cnn_amd import ops
     from poisson_cnn_amd.layers import JacobiIterationLayer
     if not torch.cuda.is_available():
         raise SystemExit('bench_jacobi.py measures on the GPU; none found')
+    if args.neumann_mask is not None:
+        return bench_bc(args, [int(m, 0) for m in args.neumann_mask.split(',')])
     T = ops.jacobi_tile()
     res = {'device': torch.cuda.get_device_name(0), 'tile': T, 'algorithmic_bytes_per_px': 12, 'calls_per_timing': args.calls, 'repeats': args.repeats, 'cases': []}
     for (N, S) in ((8, 1024), (32, 512)):
