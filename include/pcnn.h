@@ -516,6 +516,14 @@ int pcnn_pi_loss_partials_rect(pcnn_handle h, int N, int H, int W, int sy, int s
                                float* out /*N*/);
 int pcnn_pi_loss_bwd_rect(pcnn_handle h, int N, int H, int W, int sy, int sx, const float* pred, const float* rhs, const float* kern,
                           const float* coef /*N*/, float* dpred);
+/* Error statistics of a prediction in one pass over the three fields (evaluate / predict / validation).  Per sample n, out[8n..8n+7] =
+ * {sum|e|, sum e^2, max|e|, sum t^2, max|t|, sum r^2, max|r|, sum f^2}: e = pred - target and t = target over all H W points;
+ * r = (p[i-1,j] - 2 p[i,j] + p[i+1,j]) / dx0^2 + (p[i,j-1] - 2 p[i,j] + p[i,j+1]) / dx1^2 - rhs[i,j] and f = rhs[i,j] over the (H-2)(W-2)
+ * interior points, dx as for pcnn_jacobi_sweep (column 0: the H axis).  target == NULL: the first five entries are 0; rhs == NULL: the last
+ * three are 0 and dx is not read; rhs needs dx and H, W >= 3.  Two launches, no atomics: a fixed number of workgroups per sample write
+ * partials into the handle's scratch and a second kernel combines them in a fixed order, so equal inputs give equal bits. */
+int pcnn_error_stats(pcnn_handle h, int N, int H, int W, const float* pred, const float* target /* may be NULL */,
+                     const float* rhs /* may be NULL */, const float* dx /* N x 2; required with rhs */, float* out /* N x 8 */);
 
 /* ---- optimizer: tf.keras.optimizers.Adam (train/utils.py:3-8), flat parameter bucket ---------------------------- */
 int pcnn_adam_step(pcnn_handle h, int64_t n, float* w, const float* g, float* m, float* v, float lr, float beta1, float beta2,

@@ -179,6 +179,9 @@ class Dirichlet_BC_NN_Metalearning(_BoundaryTables, _ModelBase):
         self.ctx.join()
         self.store.finish_bn_grads()
 
+    _loss_dx = staticmethod(_dx_tiled)           # evaluation hands the loss what _forward_backward does
+    _call_takes_loss_dx = True
+
     def _forward_backward(self, data):
         """reference :185-205: dx tiled to both axes (:192), the loss sees rhs = 0."""
         (bc, dx), y_true = data

@@ -114,6 +114,9 @@ class _ChainModel(_ModelBase):
         self.ctx.join()
         self.store.finish_bn_grads()
 
+    _loss_dx = staticmethod(_dx_tiled)           # evaluation hands the loss what _forward_backward does
+    _call_takes_loss_dx = True
+
     def _forward_backward(self, data):
         """reference :279-309: loss_fn(y_true, y_pred, rhs, dx) and its gradients."""
         (rhs, dx), y_true = data

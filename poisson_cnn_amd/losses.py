@@ -161,6 +161,11 @@ class loss_wrapper:
         """(loss scalar tensor, dL/dy_pred) - what tape.gradient(loss, y_pred) would give."""
         return self._evaluate(y_true, y_pred, rhs, dx, True)
 
+    def value(self, y_true, y_pred, rhs, dx):
+        """The loss scalar of channels-first tensors without the gradient pass (test_step / evaluate); rhs may be None when the
+        physics-informed weight is zero."""
+        return self._evaluate(y_true, y_pred, rhs, dx, False)[0]
+
     def mse_metric(self, y_true, y_pred):
         """tf.reduce_mean((pred - ground_truth)**2) of the last evaluated (micro-)batch (train_step :291)."""
         return self._last['mse'][0]

@@ -297,24 +297,208 @@ class _ModelBase:
             loss, mse = self.metric_sync(loss, mse)
         return {'loss': loss, 'mse': mse, **extra, 'lr': self.optimizer.learning_rate}
 
-    def fit(self, dataset, epochs=1, callbacks=(), verbose=1, steps_per_epoch=None):
+    # ------------------------------------------------------------------ evaluation: test_step / evaluate / predict
+    eval_sync = None     # set by parallel.DataParallel.attach: (totals vector, maximum) of this rank -> of all ranks (global_eval_totals)
+
+    @staticmethod
+    def _loss_dx(dx):
+        """The user's dx -> the (N,2) per-axis spacings this model's training step hands to the loss (and evaluation to ops.error_stats)."""
+        return _dx_pair(_dx_column(dx))
+
+    _call_takes_loss_dx = False
+
+    def _eval_inputs(self, inputs, y_true):
+        """A channels-first input list -> (what call() takes, rhs (N,1,H,W) or None, dx (N,2)).  The three input lists of the package:
+        [rhs, dx] (homogeneous models, UNet), [bc, dx] / [bc, dx, x_output_resolution] (boundary models: no right-hand side, the resolution
+        comes from the target when it is not given) and Poisson_CNN_Legacy's [rhs, left, top, right, bottom, dx]."""
+        dev = self.device
+        if len(inputs) == 6:
+            rhs, dx = _as_device(inputs[0], dev), _as_device(inputs[5], dev)
+            return [rhs] + list(inputs[1:5]) + [dx], rhs, self._loss_dx(dx).contiguous()
+        if len(inputs) not in (2, 3):
+            raise ValueError('%s: cannot evaluate an input list of %d entries' % (self.model_name, len(inputs)))
+        first, dx = _as_device(inputs[0], dev), _as_device(inputs[1], dev)
+        dx2 = self._loss_dx(dx).contiguous()
+        if self._call_takes_loss_dx:                                 # the metalearning family's call() works on the per-axis spacings themselves
+            dx = dx2
+        if first.dim() == 4 and len(inputs) == 2:
+            return [first, dx], first, dx2
+        if len(inputs) == 2 and y_true is None:
+            raise ValueError('%s: without a target the input list needs the x_output_resolution as its third entry' % self.model_name)
+        return [first, dx, int(inputs[2]) if len(inputs) == 3 else int(y_true.shape[2])], None, dx2
+
+    def _eval_call(self, call_inputs):
+        return self.call(call_inputs, training=False)
+
+    def _eval_forward(self, inputs, y_true=None):
+        """The inference-mode forward of one batch of user tensors -> (pred, y_true, rhs, dx), channels-first on the device."""
+        inputs = [self._cf(v) for v in inputs]
+        if y_true is not None:
+            y_true = _as_device(self._cf(y_true), self.device)
+        call_inputs, rhs, dx = self._eval_inputs(inputs, y_true)
+        return self._eval_call(call_inputs), y_true, rhs, dx
+
+    @staticmethod
+    def _error_stats(pred, y_true, rhs, dx):
+        """ops.error_stats of a channels-first batch -> ((N, 8) rows, points per sample as (H, W)).  A model with several output channels
+        (UNet(out_channels > 1)) gets the error columns over all its channels and no residual."""
+        N, C, H, W = pred.shape
+        if C != 1:
+            return ops.error_stats(pred.reshape(N, C * H, W), None if y_true is None else y_true.reshape(N, C * H, W)), (C * H, W)
+        if rhs is not None and (H < 3 or W < 3):
+            rhs = None
+        return ops.error_stats(pred, y_true, rhs, dx), (H, W)
+
+    def test_step(self, data):
+        """One batch (inputs, target) in inference mode: forward with training=False, the compiled loss and ops.error_stats - no backward pass, no
+        optimizer step, no BatchNormalization update; weights, gradients, statistics and optimizer state keep their bits.  Returns device
+        tensors: 'loss' (the compiled loss of this batch, i.e. divided by the loss's global_batch_size), 'mse', and 'stats', the (N, 8) rows of
+        ops.error_stats (columns ops.ERROR_STATS; the residual columns are zero for a model without a right-hand side input)."""
+        if self.loss_fn is None:
+            raise RuntimeError('test_step() / evaluate() need compile(loss, optimizer) first')
+        inputs, y_true = data
+        pred, y_true, rhs, dx = self._eval_forward(inputs, y_true)
+        loss_rhs = rhs
+        if loss_rhs is None and getattr(self.loss_fn, 'physics_informed_loss_weight', 1.0) != 0.0:
+            loss_rhs = torch.zeros_like(y_true)                      # the boundary models' training steps: the loss sees rhs = 0
+        value = self.loss_fn.value if hasattr(self.loss_fn, 'value') else self.loss_fn
+        loss = value(y_true, pred, loss_rhs, dx)
+        stats, (H, W) = self._error_stats(pred, y_true, rhs, dx)
+        return {'loss': loss, 'mse': stats[:, 1].sum() / float(stats.shape[0] * H * W), 'stats': stats, 'H': H, 'W': W}
+
+    def _batches(self, x, y, batch_size, steps):
+        from . import evaluation as E
+        if E.is_sequence(x):
+            if y is not None:
+                raise ValueError('a Sequence-style dataset provides its own targets: y must be None')
+            data = x
+        else:
+            data = E.ArrayBatches(x, y, batch_size)
+        n = len(data)
+        return data, (n if steps is None else min(int(steps), n))
+
+    def evaluate(self, x=None, y=None, batch_size=None, steps=None, return_dict=False, per_sample=False, verbose=0, **unsupported):
+        """Keras' Model.evaluate on the one-pass error kernel.  x: a Sequence-style dataset (`__len__`, `__getitem__` -> (inputs, target); the grid
+        shape may change from batch to batch), or an input list with `y` the targets, cut into chunks of `batch_size` (default 32) samples.
+        One host round trip per batch.  Over all evaluated samples:
+          loss: mean per-sample compiled loss          mse, mae: sums over all points / number of points
+          rel_l2: mean of sqrt(sum e^2 / sum t^2)      mae_over_peak: mean of (mean|e|) / max|t|          max_abs_error: maximum
+          rel_residual: mean of sqrt(sum r^2 / sum f^2), r the 3 x 3 FD residual of the prediction, f the right-hand side
+        Samples with a zero target (right-hand side) are left out of the relative means and counted under skipped_rel_l2
+        (skipped_rel_residual).  A model without a right-hand side among its inputs (the Dirichlet boundary models) has no residual: rel_residual
+        is NaN and every sample counts as skipped.  Returns [loss, mse], or the whole dict with return_dict=True; per_sample=True adds 'stats'
+        (the (samples, 8) float64 rows of ops.error_stats) and 'H', 'W' per sample.  Under data parallelism every rank evaluates its own
+        batches and the totals are combined (parallel.DataParallel.global_eval_totals), so all ranks return the same figures; 'stats' stays
+        this rank's.  sample_weight and class_weight are not implemented."""
+        from . import evaluation as E
+        E.reject_unsupported('evaluate', unsupported)
+        data, n = self._batches(x, y, batch_size, steps)
+        totals, worst = np.zeros(len(E.TOTALS)), 0.0
+        rows, hs, ws = [], [], []
+        gbs = getattr(self.loss_fn, 'global_batch_size', None)
+        fetch = _Prefetcher(data, self.device)
+        try:
+            if n > 0:
+                fetch.request(0)
+            for step in range(n):
+                inp, tar = fetch.take()
+                out = self.test_step((list(inp), tar))
+                if step + 1 < n:
+                    fetch.request(step + 1)
+                flat = torch.cat([out['loss'].reshape(1).float(), out['stats'].reshape(-1)]).tolist()       # the batch's one host round trip
+                stats = np.asarray(flat[1:], dtype=np.float64).reshape(-1, 8)
+                t, m = E.batch_totals(stats, out['H'], out['W'], flat[0], gbs)
+                totals += t
+                worst = max(worst, m)
+                if per_sample:
+                    rows.append(stats)
+                    hs += [out['H']] * stats.shape[0]
+                    ws += [out['W']] * stats.shape[0]
+                if verbose:
+                    print('evaluate %d/%d - loss: %.6g' % (step + 1, n, flat[0] * (gbs or stats.shape[0]) / stats.shape[0]), flush=True)
+        finally:
+            fetch.close()
+        if self.eval_sync is not None:
+            totals, worst = self.eval_sync(totals, worst)
+        res = E.finish(totals, worst)
+        if per_sample:
+            res.update(stats=np.concatenate(rows) if rows else np.zeros((0, 8)), H=np.asarray(hs, dtype=np.int64), W=np.asarray(ws, dtype=np.int64))
+            return res
+        return res if return_dict else [res['loss'], res['mse']]
+
+    def predict(self, x, batch_size=None, steps=None, verbose=0, return_stats=False):
+        """Keras' Model.predict.  x: an input list, cut into chunks of `batch_size` (default 32) samples, or a Sequence-style dataset whose
+        targets - if it has any - are ignored (a boundary model then takes its x_output_resolution from the target's shape).  Returns ONE numpy
+        array in the model's data_format when all batches share a grid shape, otherwise a LIST of per-batch arrays.  return_stats=True also
+        returns the residual columns of ops.error_stats per sample - a (samples, 3) float64 array [sum r^2, max|r|, sum f^2] - which measure
+        the solution's quality without a ground truth; it needs rhs and dx among the inputs.  Nothing in the model changes: no BatchNormalization
+        update, no gradient, no optimizer state."""
+        from . import evaluation as E
+        if E.is_sequence(x):
+            data = x
+        else:
+            data = E.ArrayBatches(x, None, batch_size)
+        n = len(data) if steps is None else min(int(steps), len(data))
+        preds, res = [], []
+        for step in range(n):
+            item = data[step]
+            inp, tar = item if (isinstance(item, tuple) and len(item) == 2 and isinstance(item[0], (list, tuple))) else (item, None)
+            pred, _, rhs, dx = self._eval_forward(list(inp), tar)
+            if return_stats:
+                if rhs is None:
+                    raise ValueError('predict(return_stats=True) needs rhs and dx among the inputs')
+                res.append(self._error_stats(pred, None, rhs, dx)[0][:, 5:])
+            preds.append(self._cl(pred).cpu().numpy())
+            if verbose:
+                print('predict %d/%d' % (step + 1, n), flush=True)
+        out = preds
+        if preds and all(p.shape[1:] == preds[0].shape[1:] for p in preds):
+            out = np.concatenate(preds, 0)
+        if return_stats:
+            return out, (torch.cat(res).cpu().numpy().astype(np.float64) if res else np.zeros((0, 3)))
+        return out
+
+    _VAL_KEYS = ('loss', 'mse', 'rel_l2', 'rel_residual')     # evaluate()'s entries that fit() reports as val_<key>
+
+    def fit(self, dataset, epochs=1, callbacks=(), verbose=1, steps_per_epoch=None, validation_data=None, validation_steps=None, validation_freq=1,
+            validation_batch_size=None, **unsupported):
         """Minimal Keras-style loop over a Sequence-like dataset (`__len__`, `__getitem__` -> ([rhs, dx], soln)).
 
         Keras semantics for a custom train_step that returns plain values (models/Homogeneous_Poisson_NN_Legacy.py:291): the dict handed
         to on_epoch_end / History is the LAST batch's (tf.keras Model.fit: `epoch_logs = copy.copy(logs)`), not an epoch average - so that
         is what ReduceLROnPlateau and ModelCheckpoint monitor here too.  The epoch means are added under `loss_epoch_mean` / `mse_epoch_mean`.
-        Under data parallelism the values are global (see _logs), so every rank's callbacks decide alike."""
+        Under data parallelism the values are global (see _logs), so every rank's callbacks decide alike.
+
+        validation_data: a Sequence-style dataset or a tuple (inputs, targets).  After the training steps of every validation_freq-th epoch
+        evaluate() runs on it (validation_steps batches; validation_batch_size for the tuple form) and val_loss, val_mse, val_rel_l2 and
+        val_rel_residual join that epoch's logs - before the callbacks see them - and the history; an epoch without a validation run has
+        none of them, as in Keras.  Without validation_data nothing changes.  validation_split, sample_weight and class_weight are not
+        implemented."""
+        from . import evaluation as E
+        E.reject_unsupported('fit', unsupported)
         history = {'loss': [], 'mse': [], 'lr': [], 'loss_epoch_mean': [], 'mse_epoch_mean': []}
+        validation = None
+        if validation_data is not None:
+            if int(validation_freq) < 1:
+                raise ValueError('validation_freq must be >= 1')
+            if E.is_sequence(validation_data):
+                validation = dict(x=validation_data, steps=validation_steps)
+            elif isinstance(validation_data, (tuple, list)) and len(validation_data) == 2:
+                validation = dict(x=validation_data[0], y=validation_data[1], batch_size=validation_batch_size, steps=validation_steps)
+            else:
+                raise ValueError('validation_data must be a Sequence-style dataset or a tuple (inputs, targets)')
+            validation['freq'] = int(validation_freq)
+            history.update({'val_' + k: [] for k in self._VAL_KEYS})
         self.stop_training = False
         for cb in callbacks:
             cb.set_model(self)
         fetch = _Prefetcher(dataset, self.device)             # one producer stream (and one libpcnn handle on it) per fit() call
         try:
-            return self._fit_epochs(dataset, epochs, callbacks, verbose, steps_per_epoch, history, fetch)
+            return self._fit_epochs(dataset, epochs, callbacks, verbose, steps_per_epoch, history, fetch, validation)
         finally:
             fetch.close()
 
-    def _fit_epochs(self, dataset, epochs, callbacks, verbose, steps_per_epoch, history, fetch):
+    def _fit_epochs(self, dataset, epochs, callbacks, verbose, steps_per_epoch, history, fetch, validation=None):
         for epoch in range(epochs):
             n = steps_per_epoch if steps_per_epoch is not None else len(dataset)
             agg = {'loss': 0.0, 'mse': 0.0}
@@ -336,11 +520,16 @@ class _ModelBase:
                     break
             logs = {'loss': logs['loss'], 'mse': logs['mse'], 'lr': self.optimizer.learning_rate,
                     'loss_epoch_mean': agg['loss'] / max(step + 1, 1), 'mse_epoch_mean': agg['mse'] / max(step + 1, 1)}
-            for k in history:
+            val_line = ''
+            if validation is not None and (epoch + 1) % validation['freq'] == 0:
+                res = self.evaluate(return_dict=True, **{k: v for k, v in validation.items() if k != 'freq'})
+                logs.update({'val_' + k: res[k] for k in self._VAL_KEYS})
+                val_line = ''.join(' - val_%s: %.6g' % (k, res[k]) for k in self._VAL_KEYS)
+            for k in logs:
                 history[k].append(logs[k])
             if verbose:
-                print('Epoch %d/%d - loss: %.6g - mse: %.6g - lr: %.3g (epoch mean loss %.6g)'
-                      % (epoch + 1, epochs, logs['loss'], logs['mse'], logs['lr'], logs['loss_epoch_mean']), flush=True)
+                print('Epoch %d/%d - loss: %.6g - mse: %.6g - lr: %.3g (epoch mean loss %.6g)%s'
+                      % (epoch + 1, epochs, logs['loss'], logs['mse'], logs['lr'], logs['loss_epoch_mean'], val_line), flush=True)
             for cb in callbacks:
                 cb.on_epoch_end(epoch, logs)
             if hasattr(dataset, 'on_epoch_end'):

@@ -1074,6 +1074,42 @@ def pi_loss_bwd(pred, rhs, kern, coef, dpred):
     return dpred
 
 
+ERROR_STATS = ('sum_abs_e', 'sum_e2', 'max_abs_e', 'sum_t2', 'max_abs_t', 'sum_r2', 'max_abs_r', 'sum_f2')       # the columns of error_stats
+
+
+def error_stats(pred, target=None, rhs=None, dx=None):
+    """(N, 8) per-sample statistics of a one-channel prediction (N,1,H,W) / (N,H,W) / (N,H,W,1) in one pass (pcnn_error_stats; columns: ERROR_STATS).
+    e = pred - target, t = target over all points; r = 3 x 3 FD Laplacian of pred minus rhs, f = rhs over the interior, dx (N, 2) per axis.
+    Without `target` the first five columns are 0, without `rhs` the last three."""
+    shape = [int(s) for s in pred.shape]
+    if len(shape) == 4:
+        if shape[1] != 1 and shape[3] != 1:
+            raise ValueError('error_stats takes one-channel fields, got shape %s' % (tuple(shape),))
+        shape = [shape[0]] + (shape[2:] if shape[1] == 1 else shape[1:3])
+    if len(shape) != 3:
+        raise ValueError('error_stats: pred must be (N,1,H,W), (N,H,W,1) or (N,H,W), got %s' % (tuple(pred.shape),))
+    N, H, W = shape
+    fields = {'pred': pred, 'target': target, 'rhs': rhs}
+    for name, t in fields.items():
+        if t is None:
+            continue
+        if t.dtype != torch.float32 or not t.is_cuda or t.numel() != N * H * W:
+            raise ValueError('error_stats: %s must be a CUDA float32 tensor with the %d x %d x %d points of pred' % (name, N, H, W))
+        fields[name] = t.contiguous()
+    if rhs is not None:
+        if dx is None:
+            raise ValueError('error_stats: rhs needs dx')
+        dx = dx.to(device=pred.device, dtype=torch.float32).reshape(N, -1)
+        if dx.shape[1] != 2:
+            raise ValueError('error_stats: dx must be (N, 2), one spacing per axis')
+        dx = dx.contiguous()
+    else:
+        dx = None
+    out = empty((N, 8), pred.device)
+    handle().call('pcnn_error_stats', c_int(N), c_int(H), c_int(W), _p(fields['pred']), _p(fields['target']), _p(fields['rhs']), _p(dx), _p(out))
+    return out
+
+
 def adam_step(w, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0, vhat=None):
     weights_changed()                                                 # a raw-pointer write torch does not count: cached filter spectra go stale
     handle().call('pcnn_adam_amsgrad_step', c_int64(w.numel()), _p(w), _p(g), _p(m), _p(v), _p(vhat), c_float(lr), c_float(beta1), c_float(beta2),

@@ -122,6 +122,7 @@ class DataParallel:
             return flat_g
         model.grad_sync = grad_sync
         model.metric_sync = self.global_metrics
+        model.eval_sync = self.global_eval_totals
         return model
 
     def sync_bn_stats(self, store):
@@ -147,6 +148,22 @@ class DataParallel:
         t = torch.stack([torch.as_tensor(loss, dtype=torch.float32).reshape(()), torch.as_tensor(mse, dtype=torch.float32).reshape(()) / self.world_size])
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         return t[0], t[1]
+
+    def global_eval_totals(self, totals, max_abs_error):
+        """evaluate() under data parallelism: each rank has evaluated its own batches; this rank's vector of sums (evaluation.TOTALS:
+        [sum loss n, n, sum e^2, sum|e|, sum HW, sum rel_l2, ...]) and its maximum error -> those over all ranks, on every rank: one
+        all-reduce(SUM) of the float64 vector and one all-reduce(MAX) of the scalar.  Validation figures and the callbacks that act on them
+        (EarlyStopping, ReduceLROnPlateau(monitor='val_loss')) are then the same everywhere.  -> (numpy float64 vector, float)"""
+        import numpy as np
+        totals = np.asarray(totals, dtype=np.float64)
+        if self.world_size == 1:
+            return totals, float(max_abs_error)
+        dev = 'cuda' if self.backend == 'nccl' else 'cpu'
+        t = torch.tensor(totals, dtype=torch.float64, device=dev)
+        m = torch.tensor([float(max_abs_error)], dtype=torch.float64, device=dev)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+        dist.all_reduce(m, op=dist.ReduceOp.MAX)
+        return t.cpu().numpy(), float(m.item())
 
     def collective_name(self):
         """The collective actually in use, for reports: backend "nccl" is RCCL on ROCm."""

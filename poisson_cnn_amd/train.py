@@ -213,6 +213,62 @@ class ReduceLROnPlateau(Callback):
                     self.wait = 0
 
 
+class EarlyStopping(Callback):
+    """tf.keras.callbacks.EarlyStopping (same arguments, Keras' order).  An epoch improves when monitor < best - min_delta (mode 'min'; 'auto'
+    is 'max' for a monitor with 'acc' in its name, else 'min') or monitor > best + min_delta ('max'); `best` starts at `baseline` when given.
+    Once `wait`, the number of epochs without improvement since the last one, reaches `patience` (checked from the first non-improving
+    epoch on, so patience=0 stops like patience=1), model.stop_training is set.  An epoch whose logs lack the
+    monitored key (validation_freq > 1) is skipped.
+    restore_best_weights keeps a device copy of every store's flat_w (and flat_stats) of the best epoch and, when it stops the training,
+    writes them back and calls ops.weights_changed().  A new fit() (set_model) starts the bookkeeping afresh."""
+
+    def __init__(self, monitor='val_loss', min_delta=0, patience=0, verbose=0, mode='auto', baseline=None, restore_best_weights=False):
+        if mode not in ('auto', 'min', 'max'):
+            raise ValueError("EarlyStopping mode must be 'auto', 'min' or 'max', got %r" % (mode,))
+        if mode == 'auto':
+            mode = 'max' if 'acc' in monitor else 'min'
+        self.monitor, self.patience, self.verbose, self.mode, self.baseline = monitor, int(patience), verbose, mode, baseline
+        self.min_delta = abs(float(min_delta))
+        self.restore_best_weights = bool(restore_best_weights)
+        self._reset()
+
+    def _reset(self):
+        self.wait, self.stopped_epoch, self.best_weights = 0, 0, None
+        self.best = self.baseline if self.baseline is not None else (math.inf if self.mode == 'min' else -math.inf)
+
+    def set_model(self, model):
+        self.model = model
+        self._reset()
+
+    def _improved(self, current):
+        return current + self.min_delta < self.best if self.mode == 'min' else current - self.min_delta > self.best
+
+    def _stores(self):
+        return list(self.model.stores) if hasattr(self.model, 'stores') else [self.model.store]
+
+    def on_epoch_end(self, epoch, logs):
+        current = logs.get(self.monitor)
+        if current is None:
+            return
+        if self._improved(current):
+            self.best, self.wait = current, 0
+            if self.restore_best_weights:
+                self.best_weights = [(s.flat_w.clone(), s.flat_stats.clone() if getattr(s, 'flat_stats', None) is not None else None) for s in self._stores()]
+            return
+        self.wait += 1
+        if self.wait >= self.patience:
+            self.stopped_epoch = epoch
+            self.model.stop_training = True
+            if self.verbose:
+                print('Epoch %d: early stopping' % (epoch + 1))
+            if self.restore_best_weights and self.best_weights is not None:
+                for s, (w, stats) in zip(self._stores(), self.best_weights):
+                    s.flat_w.copy_(w)
+                    if stats is not None:
+                        s.flat_stats.copy_(stats)
+                ops.weights_changed()
+
+
 class TerminateOnNaN(Callback):
     def on_batch_end(self, batch, logs):
         if not math.isfinite(logs['loss']):

@@ -276,6 +276,10 @@ class UNetModel(_ModelBase):
         self.backward(dpred, need_dx=False)
         return loss, y_true, pred
 
+    def _eval_call(self, call_inputs):
+        """evaluate / predict: the input list is [rhs, dx] as in the training data, the network takes the right-hand side alone."""
+        return self.call(call_inputs[0], training=False)
+
     def grad_l2_norm(self):
         """'grad L2 norm' of UNetModel.train_step (:178): sqrt(mean over the trainable variables of sum(g^2)) - a device scalar."""
         sums = torch.stack([self.store.g[n].double().square().sum() for n in self.store.trainable_names()])
