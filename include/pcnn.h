@@ -620,6 +620,15 @@ int pcnn_batched_gemm_f64(pcnn_handle h, int batch, int M, int Nn, int K, const 
 /* Separable series synthesis out[n,a,b] (+)= sum_{A<ka,B<kb} c[n,A,B] f((A+1) x_a) f((B+1) y_b), x = linspace(0,pi,H),
  * y = linspace(0,pi,W), f = sin (trig 0) or cos (trig 1) (dataset/utils/generate_smooth_function.py:45-62). */
 int pcnn_series_synthesis(pcnn_handle h, int N, int H, int W, int ka, int kb, const float* coef, int trig, int accumulate, float* out);
+/* A (solution, right-hand side) pair of one separable series in one launch, on the same grid x = linspace(0,pi,H), y = linspace(0,pi,W):
+ *   soln[n,a,b] = sum_{A<ka,B<kb} c[n,A,B] phi_A(x_a) psi_B(y_b)
+ *   rhs[n,a,b]  = sum_{A<ka,B<kb} c[n,A,B] (lam_a[n,A] + lam_b[n,B]) phi_A(x_a) psi_B(y_b)
+ * coef (N,ka,kb), lam_a (N,ka), lam_b (N,kb), soln and rhs (N,H,W).  basis_a / basis_b choose phi / psi for the mode A = 1..k:
+ *   0: sin(A t)   1: cos(A t)   2: sin((A - 1/2) t)   3: cos((A - 1/2) t)
+ * - the eigenfunctions of -d2/dt2 on [0,pi] with (Dirichlet, Dirichlet), (Neumann, Neumann), (Dirichlet, Neumann) and (Neumann, Dirichlet)
+ * ends.  ka, kb <= 16; any W (the grid is tiled in both directions). */
+int pcnn_series_pair_synthesis(pcnn_handle h, int N, int H, int W, int ka, int kb, const float* coef, const float* lam_a, const float* lam_b,
+                               int basis_a, int basis_b, float* soln, float* rhs);
 /* out[n,a,b] (+)= sum_{r<R} U[n,r,a] V[n,r,b]: the Taylor component X(x)Y(y), X''Y + XY'' (dataset/generators/reverse.py:231-256) */
 int pcnn_separable_sum(pcnn_handle h, int N, int H, int W, int R, const float* U, const float* V, int accumulate, float* out);
 /* x[n,:] *= target[n] / max|x[n,:]| (dataset/utils/set_max_magnitude.py:14-50); factors (optional) receives the scale */

@@ -64,8 +64,9 @@ def hpnn_neumann():
 
 def hpnn_mixed(boundary_types):
     """hpnn() with a boundary type per edge (extension; BASELINE configs[2]): boundary_types maps 'left' | 'right' | 'bottom' | 'top' to
-    'dirichlet' | 'neumann' (a missing edge is Dirichlet).  Train it on the numerical generator, whose mixed solver gives the ground truth; the
-    keys the analytic generators alone read are dropped as in hpnn_neumann()."""
+    'dirichlet' | 'neumann' (a missing edge is Dirichlet).  Its dataset section feeds reverse_poisson_dataset_generator_mixed (train.py
+    --dataset_type analytical_mixed, which takes boundary_types from the model's bc_type); the numerical generator's mixed solver is the other
+    ground truth.  The keys the Dirichlet analytic generator alone reads are dropped as in hpnn_neumann()."""
     from .dataset import _neumann_flags
     flags = _neumann_flags(boundary_types)
     cfg = hpnn()

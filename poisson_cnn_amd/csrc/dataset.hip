@@ -209,6 +209,79 @@ __global__ __launch_bounds__(256) void series_kernel(int H, int W, int ka, int k
   }
 }
 
+// ---------------------------------------------------------------- series pair synthesis
+// soln = sum_{A,B} c[A,B] phi_A(x_a) psi_B(y_b) and rhs = sum_{A,B} c[A,B] (lam_a[A] + lam_b[B]) phi_A(x_a) psi_B(y_b) in one launch.
+// One block owns a PAIR_ROWS x PAIR_COLS tile of one sample, so its LDS does not depend on W:
+//   1. the two trig tables of the tile, each entry evaluated once:   P[B][col] = psi_B(y_b),  F[A][r] = phi_A(x_a)
+//   2. per column, the sums over B (the two halves of the block take alternate A):
+//        T[A][col] = sum_B c[A,B] P[B][col],   T'= sum_B c[A,B] lam_b[B] P[B][col],   G[A][col] = lam_a[A] T + T'
+//   3. per pixel soln = sum_A F[A][r] T[A][col], rhs = sum_A F[A][r] G[A][col]: a thread keeps one column of 16 rows, so T and G are read once
+//      per A and F as a broadcast; a wave's 64 lanes store 64 consecutive floats of a row.
+// mode k+1 of basis 0..3: sin(w t), cos(w t) with w = k+1 (0, 1) or k+1/2 (2, 3); the frequency is formed first, so 0 and 1 evaluate
+// series_kernel's arguments.
+constexpr int PAIR_ROWS = 32, PAIR_COLS = 128, PAIR_THREADS = 256, PAIR_RPT = PAIR_ROWS / (PAIR_THREADS / PAIR_COLS);   // RPT: rows per thread
+static_assert(PAIR_THREADS % PAIR_COLS == 0 && PAIR_COLS % 64 == 0 && PAIR_RPT % 4 == 0, "a wave owns one row half; rows are read four at a time");
+__device__ __forceinline__ float series_basis(int basis, int k, float t) {
+  const float w = (float)(k + 1) - ((basis & 2) ? 0.5f : 0.f);
+  return (basis & 1) ? cosf(w * t) : sinf(w * t);
+}
+
+__global__ __launch_bounds__(PAIR_THREADS) void series_pair_kernel(int H, int W, int ka, int kb, const float* __restrict__ coef,
+                                                                   const float* __restrict__ lam_a, const float* __restrict__ lam_b, int basis_a,
+                                                                   int basis_b, float* __restrict__ soln, float* __restrict__ rhs) {
+  __shared__ float P[SYN_MAXK * PAIR_COLS], T[SYN_MAXK * PAIR_COLS], G[SYN_MAXK * PAIR_COLS];
+  __shared__ __attribute__((aligned(16))) float F[SYN_MAXK * PAIR_ROWS];
+  const int n = blockIdx.z, a0 = blockIdx.y * PAIR_ROWS, b0 = blockIdx.x * PAIR_COLS;
+  const int tid = threadIdx.x, col = tid % PAIR_COLS, half = tid / PAIR_COLS;     // half is uniform over a wave
+  const float pi = 3.14159265358979323846f;
+  const float dy = W > 1 ? pi / (float)(W - 1) : 0.f, dxs = H > 1 ? pi / (float)(H - 1) : 0.f;
+  const float* c = coef + (int64_t)n * ka * kb;
+  const float* la = lam_a + (int64_t)n * ka;
+  const float* lb = lam_b + (int64_t)n * kb;
+  for (int e = tid; e < kb * PAIR_COLS; e += PAIR_THREADS) P[e] = series_basis(basis_b, e / PAIR_COLS, (float)(b0 + e % PAIR_COLS) * dy);
+  for (int e = tid; e < ka * PAIR_ROWS; e += PAIR_THREADS) F[e] = series_basis(basis_a, e / PAIR_ROWS, (float)(a0 + e % PAIR_ROWS) * dxs);
+  __syncthreads();
+  for (int A = half; A < ka; A += PAIR_THREADS / PAIR_COLS) {
+    float s = 0.f, t = 0.f;
+    for (int B = 0; B < kb; ++B) {
+      const float p = P[B * PAIR_COLS + col], cv = c[A * kb + B];
+      s = fmaf(cv, p, s);
+      t = fmaf(cv * lb[B], p, t);
+    }
+    T[A * PAIR_COLS + col] = s;
+    G[A * PAIR_COLS + col] = fmaf(la[A], s, t);
+  }
+  __syncthreads();
+  const int b = b0 + col, r0 = half * PAIR_RPT;
+  if (b >= W || a0 + r0 >= H) return;
+  float u[PAIR_RPT], f[PAIR_RPT];
+#pragma unroll
+  for (int r = 0; r < PAIR_RPT; ++r) u[r] = f[r] = 0.f;
+  for (int A = 0; A < ka; ++A) {
+    const float t = T[A * PAIR_COLS + col], g = G[A * PAIR_COLS + col];
+    const float4* Fr = reinterpret_cast<const float4*>(&F[A * PAIR_ROWS + r0]);
+#pragma unroll
+    for (int r4 = 0; r4 < PAIR_RPT / 4; ++r4) {
+      const float4 ph = Fr[r4];
+      const float v[4] = {ph.x, ph.y, ph.z, ph.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        u[r4 * 4 + k] = fmaf(v[k], t, u[r4 * 4 + k]);
+        f[r4 * 4 + k] = fmaf(v[k], g, f[r4 * 4 + k]);
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < PAIR_RPT; ++r) {
+    const int a = a0 + r0 + r;
+    if (a < H) {
+      const int64_t o = ((int64_t)n * H + a) * W + b;
+      soln[o] = u[r];
+      rhs[o] = f[r];
+    }
+  }
+}
+
 // out[n,a,b] (+)= sum_r U[n,r,a] V[n,r,b]
 __global__ void separable_sum_kernel(int N, int H, int W, int R, const float* __restrict__ U, const float* __restrict__ V, int accumulate,
                                      float* __restrict__ out) {
@@ -465,6 +538,19 @@ extern "C" int pcnn_series_synthesis(pcnn_handle h, int N, int H, int W, int ka,
   PCNN_REQUIRE(h, lds <= 64 * 1024, "pcnn_series_synthesis: W=%d too wide for %d modes", W, ka);
   hipLaunchKernelGGL(series_kernel, dim3(pcnn_cdiv(H, SYN_ROWS), N), dim3(256), lds, h->stream, H, W, ka, kb, coef, trig, accumulate, out);
   PCNN_CHECK_LAUNCH(h, "pcnn_series_synthesis");
+  return 0;
+}
+
+extern "C" int pcnn_series_pair_synthesis(pcnn_handle h, int N, int H, int W, int ka, int kb, const float* coef, const float* lam_a, const float* lam_b,
+                                          int basis_a, int basis_b, float* soln, float* rhs) {
+  PCNN_REQUIRE(h, h && coef && lam_a && lam_b && soln && rhs, "pcnn_series_pair_synthesis: null argument");
+  PCNN_REQUIRE(h, N >= 1 && H >= 1 && W >= 1, "pcnn_series_pair_synthesis: bad shape %d x %d x %d", N, H, W);
+  PCNN_REQUIRE(h, ka >= 1 && kb >= 1 && ka <= SYN_MAXK && kb <= SYN_MAXK, "pcnn_series_pair_synthesis: %dx%d coefficients unsupported (<=%d)", ka, kb, SYN_MAXK);
+  PCNN_REQUIRE(h, basis_a >= 0 && basis_a <= 3 && basis_b >= 0 && basis_b <= 3, "pcnn_series_pair_synthesis: basis %d, %d not in 0..3", basis_a, basis_b);
+  PCNN_REQUIRE(h, N <= 65535 && pcnn_cdiv(H, PAIR_ROWS) <= 65535, "pcnn_series_pair_synthesis: %d samples of %d rows exceed the launch grid", N, H);
+  hipLaunchKernelGGL(series_pair_kernel, dim3(pcnn_cdiv(W, PAIR_COLS), pcnn_cdiv(H, PAIR_ROWS), N), dim3(PAIR_THREADS), 0, h->stream, H, W, ka, kb, coef,
+                     lam_a, lam_b, basis_a, basis_b, soln, rhs);
+  PCNN_CHECK_LAUNCH(h, "pcnn_series_pair_synthesis");
   return 0;
 }
 

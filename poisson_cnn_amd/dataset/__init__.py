@@ -199,7 +199,9 @@ class reverse_poisson_dataset_generator:
             tabs.append((P, D))
         return tabs
 
-    def __getitem__(self, idx=0):
+    def _draw_series(self):
+        """The host draws every analytic generator starts a batch with, in this order: mode counts per sample, the grid shape and spacings, the
+        series coefficients (zero beyond a sample's own mode counts).  -> ncoef (N,2), H, W, dx (N,2), domain_sizes (N,2), coef (N,ka,kb)."""
         N = self.batch_size
         ncoef = np.stack([self._grid_sizes(self.fourier_coeff_grid_size_range) for _ in range(N)])       # (N,2)
         shape, dx = self._shape_and_spacings()
@@ -209,6 +211,12 @@ class reverse_poisson_dataset_generator:
         for b in range(N):
             coef[b, :ncoef[b, 0], :ncoef[b, 1]] = 2 * self.rng.uniform(size=(ncoef[b, 0], ncoef[b, 1])) - 1
         domain_sizes = dx * np.array([H, W], dtype=np.float64)[None]     # L = dx * n (reverse.py:203), not dx*(n-1)
+        return ncoef, H, W, dx, domain_sizes, coef
+
+    def __getitem__(self, idx=0):
+        N = self.batch_size
+        ncoef, H, W, dx, domain_sizes, coef = self._draw_series()
+        ka, kb = coef.shape[1:]
         A, B = np.arange(1, ka + 1, dtype=np.float64), np.arange(1, kb + 1, dtype=np.float64)
         adj = -((math.pi * A[None, :, None] / domain_sizes[:, 0, None, None]) ** 2 + (math.pi * B[None, None, :] / domain_sizes[:, 1, None, None]) ** 2)
         trig = 1 if self.neumann else 0
@@ -230,6 +238,11 @@ class reverse_poisson_dataset_generator:
             K.scale_samples(soln_t, s)
             ops.axpby(1.0, rhs_t.view(N, H, W, 1), 1.0, rhs.view(N, H, W, 1))
             ops.axpby(1.0, soln_t.view(N, H, W, 1), 1.0, soln.view(N, H, W, 1))
+        return self._normalize_and_pack(rhs, soln, dx, domain_sizes)
+
+    def _normalize_and_pack(self, rhs, soln, dx, domain_sizes):
+        """rhs, soln (N,H,W) -> the normalised batch ([rhs, (boundaries...), dx], soln)."""
+        N, H, W = rhs.shape
         nz = self.normalizations
         if nz['rhs_max_magnitude'] is not False:                             # reverse.py:287-290
             f = K.set_max_magnitude(rhs, torch.full((N,), float(nz['rhs_max_magnitude']), device=self.device))
@@ -258,6 +271,41 @@ class reverse_poisson_dataset_generator_homogeneous_neumann(reverse_poisson_data
                          homogeneous_bc=False, return_rhses=return_rhses, return_boundaries=False, return_dx=return_dx, normalizations=normalizations,
                          uniform_grid_spacing=uniform_grid_spacing, seed=seed, device=device, shard=shard)
         self.neumann = True
+
+
+def _axis_basis(neumann_lo, neumann_hi):
+    """The series_pair_synthesis basis of an axis from the types of its two ends and the offset of its frequencies (omega = A - offset, A = 1..k):
+    (D,D) sin(A t), (N,N) cos(A t), (D,N) sin((A-1/2) t), (N,D) cos((A-1/2) t) - the eigenfunctions of -d2/dt2 on [0, pi] with u = 0 at a
+    Dirichlet end and u' = 0 at a Neumann end."""
+    mixed = bool(neumann_lo) != bool(neumann_hi)
+    return (1 if neumann_lo else 0) | (2 if mixed else 0), (0.5 if mixed else 0.0)
+
+
+class reverse_poisson_dataset_generator_mixed(reverse_poisson_dataset_generator):
+    """Analytic pairs with a boundary type per edge and homogeneous data on every edge (u = 0 on a Dirichlet edge, du/dn = 0 on a Neumann one):
+    the tensor product of the per-axis eigenfunction families of _axis_basis, (left, right) choosing the family along axis -2 and (bottom, top)
+    the one along axis -1.  All-Dirichlet / all-Neumann flags give the sine / cosine series of the two generators above; the reference has no
+    mixed analytic generator.  The host draws are the parent's (same seed, same coefficients); soln and rhs come from ONE launch
+    (K.series_pair_synthesis) with the eigenvalues lam = -(pi omega / L)^2, L = dx * n as in the parent (reverse.py:203)."""
+
+    def __init__(self, batch_size, batches_per_epoch, random_output_shape_range, fourier_coeff_grid_size_range, boundary_types, grid_spacings_range=None,
+                 ndims=None, return_rhses=True, return_dx=True, normalizations=None, uniform_grid_spacing=False, seed=0, device=None, shard=None):
+        super().__init__(batch_size, batches_per_epoch, random_output_shape_range, fourier_coeff_grid_size_range, None, grid_spacings_range, ndims,
+                         homogeneous_bc=True, return_rhses=return_rhses, return_boundaries=False, return_dx=return_dx, normalizations=normalizations,
+                         uniform_grid_spacing=uniform_grid_spacing, seed=seed, device=device, shard=shard)
+        self.neumann_flags = _neumann_flags(boundary_types)              # (left, right, bottom, top)
+
+    def __getitem__(self, idx=0):
+        _, H, W, dx, domain_sizes, coef = self._draw_series()
+        nl, nr, nb, nt = self.neumann_flags
+        lams, bases = [], []
+        for axis, (lo, hi) in enumerate(((nl, nr), (nb, nt))):
+            basis, offset = _axis_basis(lo, hi)
+            omega = np.arange(1, coef.shape[1 + axis] + 1, dtype=np.float64) - offset
+            lams.append(-(math.pi * omega[None, :] / domain_sizes[:, axis, None]) ** 2)
+            bases.append(basis)
+        soln, rhs = K.series_pair_synthesis(self._dev(coef), self._dev(lams[0]), self._dev(lams[1]), H, W, bases[0], bases[1])
+        return self._normalize_and_pack(rhs, soln, dx, domain_sizes)
 
 
 # ----------------------------------------------------------------------------- numerical (FD) generator

@@ -118,6 +118,24 @@ def series_synthesis(coef, H, W, trig, out=None, accumulate=False):
     return out
 
 
+SERIES_PAIR_TILE = (32, 128)     # rows x columns one block of series_pair_kernel writes (PAIR_ROWS, PAIR_COLS in csrc/dataset.hip)
+
+def series_pair_synthesis(coef, lam_a, lam_b, H, W, basis_a, basis_b):
+    """coef (N,ka,kb), lam_a (N,ka), lam_b (N,kb) -> (soln, rhs), each (N,H,W), in one launch: soln = sum c[A,B] phi_A(x) psi_B(y) and
+    rhs = sum c[A,B] (lam_a[A] + lam_b[B]) phi_A(x) psi_B(y).  basis 0: sin(A t), 1: cos(A t), 2: sin((A-1/2) t), 3: cos((A-1/2) t)."""
+    N, ka, kb = coef.shape
+    if tuple(lam_a.shape) != (N, ka) or tuple(lam_b.shape) != (N, kb):
+        raise ValueError('lam_a (N,ka) and lam_b (N,kb) must match coef (N,ka,kb): got %r, %r, %r' % (tuple(lam_a.shape), tuple(lam_b.shape), tuple(coef.shape)))
+    for t in (coef, lam_a, lam_b):
+        if t.dtype != torch.float32 or not t.is_cuda:
+            raise ValueError('series_pair_synthesis takes CUDA float32 tensors')
+    soln = torch.empty((N, H, W), dtype=torch.float32, device=coef.device)
+    rhs = torch.empty_like(soln)
+    handle().call('pcnn_series_pair_synthesis', c_int(N), c_int(H), c_int(W), c_int(ka), c_int(kb), _p(coef.contiguous()), _p(lam_a.contiguous()),
+                  _p(lam_b.contiguous()), c_int(basis_a), c_int(basis_b), _p(soln), _p(rhs))
+    return soln, rhs
+
+
 def separable_sum(U, V, out=None, accumulate=False):
     """U (N,R,H), V (N,R,W) -> (N,H,W)"""
     N, R, H = U.shape

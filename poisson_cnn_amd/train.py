@@ -1,9 +1,10 @@
 """Optimizers, callbacks and the training entry point (drop-in for poisson_CNN/train/hpnn_legacy_train.py and train/utils.py).
 
-python -m poisson_cnn_amd.train config.json [--checkpoint_dir D] [--continue_from_checkpoint D] [--dataset_type analytical|numerical]
+python -m poisson_cnn_amd.train config.json [--checkpoint_dir D] [--continue_from_checkpoint D] [--dataset_type analytical|analytical_mixed|numerical]
                                             [--learning_rate X|from_json]
 Under `torchrun` (WORLD_SIZE > 1) the batch is sharded over ranks and gradients are all-reduced over RCCL
 (parallel.DataParallel), replacing the reference's tf.distribute.MirroredStrategy (train/hpnn_legacy_train.py:37-38).
+`analytical_mixed` (extension): the analytic generator with a boundary type per edge, for a Homogeneous_Poisson_NN_Legacy whose bc_type is a dict.
 """
 import argparse
 import json
@@ -303,7 +304,8 @@ def main(argv=None):
     from .utils import convert_tf_object_names
     from .models import Homogeneous_Poisson_NN_Legacy, Dirichlet_BC_NN_Legacy_2, Poisson_CNN_Legacy
     from .losses import loss_wrapper
-    from .dataset import numerical_dataset_generator, reverse_poisson_dataset_generator, reverse_poisson_dataset_generator_homogeneous_neumann
+    from .dataset import (numerical_dataset_generator, reverse_poisson_dataset_generator, reverse_poisson_dataset_generator_homogeneous_neumann,
+                          reverse_poisson_dataset_generator_mixed)
     from . import parallel
     p = argparse.ArgumentParser(description='Train the Homogeneous Poisson NN')
     p.add_argument('config', type=str)
@@ -316,9 +318,13 @@ def main(argv=None):
                    help='hpnn: train/hpnn_legacy_train.py (train/hpnn_train.py when the model section carries model_type); dbcnn: train/dbcnn_legacy_train.py; '
                         'pcnn: train/pcnn_end_to_end.py; unet: train/UNet.py; dbcnn_rnn: train/dbcnn_rnn_train.py')
     args = p.parse_args(argv)
-    if args.dataset_type not in ('numerical', 'analytical'):
+    if args.dataset_type not in ('numerical', 'analytical', 'analytical_mixed'):
         raise ValueError('Invalid dataset type. Received: ' + args.dataset_type)
     config = convert_tf_object_names(configs.load_config(args.config))
+    if args.dataset_type == 'analytical_mixed' and (args.model != 'hpnn' or 'model_type' in config['model']
+                                                    or not isinstance(config['model'].get('bc_type'), dict)):
+        raise ValueError('--dataset_type analytical_mixed is the per-edge analytic generator of Homogeneous_Poisson_NN_Legacy: it needs --model hpnn and '
+                         'a model bc_type that is a dict over left/right/bottom/top (got --model %s, bc_type %r)' % (args.model, config['model'].get('bc_type')))
     if config['training'].get('precision', 'float32') != 'float32':
         raise NotImplementedError('the HIP kernels compute in float32')
     dp = parallel.DataParallel.from_env()
@@ -360,12 +366,15 @@ def main(argv=None):
         if isinstance(bc_type, dict):                # per-edge boundary types (extension): the numerical generator's mixed Dirichlet/Neumann solve
             from .dataset import _neumann_flags
             flags = _neumann_flags(bc_type)
-            if args.dataset_type != 'numerical' and any(flags) and not all(flags):
-                raise ValueError('there is no analytic mixed Dirichlet/Neumann generator: a per-edge bc_type needs --dataset_type numerical (got %r)' % (bc_type,))
+            if args.dataset_type == 'analytical' and any(flags) and not all(flags):
+                raise ValueError('there is no analytic mixed Dirichlet/Neumann generator behind --dataset_type analytical: a per-edge bc_type needs '
+                                 '--dataset_type analytical_mixed or numerical (got %r)' % (bc_type,))
             neumann = all(flags)
         else:
             neumann = bc_type.lower() == 'neumann'
-        if args.dataset_type == 'numerical' and isinstance(bc_type, dict):
+        if args.dataset_type == 'analytical_mixed':        # the quarter-wave / whole-wave series of the model's own edge types, homogeneous data
+            dataset = reverse_poisson_dataset_generator_mixed(**dict(dcfg, boundary_types=bc_type))
+        elif args.dataset_type == 'numerical' and isinstance(bc_type, dict):
             # homogeneous data on every edge (any boundaries string but 'random' is zero data): the mixed solver's ground truth for the model's edge types
             dataset = numerical_dataset_generator(**dict(dcfg, boundary_types=bc_type, boundaries='zero'))
         elif args.dataset_type == 'numerical':
