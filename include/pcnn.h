@@ -636,6 +636,37 @@ int pcnn_set_max_magnitude(pcnn_handle h, int N, int64_t per, const float* targe
 /* x[n,:] *= s[n] */
 int pcnn_scale_samples(pcnn_handle h, int N, int64_t per, const float* s, float* x);
 
+/* ---- dataset: variable-density problem div((1/rho) grad u) = f (csrc/varcoef.hip) ------ */
+/* Same vertex-centred grid, one spacing per sample (dy = dx), Dirichlet data on all four edges, rho (N,H,W) fp32 on every node.  Flux form with
+ * the face coefficients beta = 2 / (rho_a + rho_b) of the two nodes a face separates (the first matrix of dataset/generators/variable_density):
+ *   (A u)[i,j] = sum over the four neighbours of beta_face (u[i,j] - u[neighbour]) / dx^2   on the (H-2) x (W-2) interior nodes,
+ * A symmetric positive definite, A u = b with b = -f + (Dirichlet neighbours' values times their face coefficient / dx^2).  fp64 throughout,
+ * no atomics, every reduction in a fixed order per sample: a sample's result does not depend on the batch it is solved in.
+ * q = A p for p, q (N,H-2,W-2) fp64 with zero Dirichlet data, and pq[n] = p[n].q[n] from the same pass. */
+int pcnn_varcoef_apply(pcnn_handle h, int N, int H, int W, const float* rho, const float* dx, const double* p, double* q, double* pq);
+/* Conjugate gradients on A u = b, preconditioned by the constant-coefficient DST solve z = S_h ((S_h r S_w) ./ (lam_h + lam_w)) S_w (S, lam: device
+ * copies of pcnn_dst_setup output; four pcnn_batched_gemm_f64 products per iteration).  State lives on the device: `workspace`
+ * (pcnn_varcoef_pcg_workspace bytes), scal (N x 8 doubles per sample: b.b, r.r, p.q, r.z (two slots), min rho, 2 unused) and flags (N ints).
+ *   setup:   b, x = interior of the initial guess x0 ((N,H,W) fp64, NULL: 0), r = b - A x, first direction; scal[n][5] = min rho[n], a NaN counting as
+ *            -inf (the caller refuses anything but a positive minimum); flags[n] = 1 where ||r|| <= tol ||b|| already.  The workspace, scal and
+ *            flags need no initialisation: setup writes every value before it is read, whatever the memory held.
+ *   iterate: `iterations` iterations numbered from first_iteration (the count of iterations done before), no host round trip in between:
+ *            alpha = r.z / p.q and beta = r.z_new / r.z_old are formed inside the update kernels from scal; flags[n] is raised when
+ *            ||r|| <= tol ||b||, and a flagged sample's alpha and beta are 0 from then on - its x is frozen bit for bit.
+ *   finish:  soln (N,H,W) fp32: interior from x, edges from the boundary arrays with the corner convention of pcnn_fd_poisson_dst. */
+size_t pcnn_varcoef_pcg_workspace(int N, int H, int W);
+int pcnn_varcoef_pcg_setup(pcnn_handle h, int N, int H, int W, const float* rho, const float* rhs, const float* left, const float* right,
+                           const float* bottom, const float* top, const float* dx, const double* x0, double tol, const double* S_h,
+                           const double* lam_h, const double* S_w, const double* lam_w, void* workspace, size_t workspace_bytes, double* scal,
+                           int* flags);
+int pcnn_varcoef_pcg_iterate(pcnn_handle h, int N, int H, int W, const float* rho, const float* dx, double tol, int first_iteration, int iterations,
+                             const double* S_h, const double* lam_h, const double* S_w, const double* lam_w, void* workspace, size_t workspace_bytes,
+                             double* scal, int* flags);
+int pcnn_varcoef_pcg_finish(pcnn_handle h, int N, int H, int W, const void* workspace, const float* left, const float* right, const float* bottom,
+                            const float* top, float* soln);
+/* g[i] = lo + (hi - lo) min(|g[i]|, 1): a density field from a smooth function scaled to max|g| = 1 (the reference takes 1e-7 + |g|) */
+int pcnn_varcoef_density(pcnn_handle h, int64_t total, float lo, float hi, float* g);
+
 /* tf.keras.layers.LayerNormalization() over the last axis of an (N, F) matrix (epsilon 1e-3 in Keras): the optional final layer of the
  * metalearning hyper-networks (layers/metalearning_conv.py:128-129).  fwd also returns the per-row mean and 1/sqrt(var + eps) for bwd. */
 int pcnn_layernorm_fwd(pcnn_handle h, int N, int F, const float* x, const float* gamma, const float* beta, float eps, float* y, float* mean, float* rstd);

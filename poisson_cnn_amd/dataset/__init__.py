@@ -499,3 +499,159 @@ def mixed_bc_poisson_solve(rhses, boundaries, dx, boundary_types, device=None):
     d = d.expand(N).contiguous() if d.numel() == 1 else d.reshape(N, -1)[:, 0].contiguous()
     out = K.fd_poisson_mixed(r.contiguous(), b['left'], b['right'], b['bottom'], b['top'], d, _neumann_flags(boundary_types))
     return out.view(N, 1, H, W)
+
+
+# ----------------------------------------------------------------------------- variable-density problem (dataset/generators/variable_density)
+def _host_array(a):
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def _per_sample_spacing(v, N):
+    """One spacing, (N,), (N,1) or (N,2) -> (N,): the first column, as multigrid_poisson_solve reads it."""
+    return np.full((N,), float(v.reshape(-1)[0])) if v.size == 1 else v.reshape(N, -1)[:, 0]
+
+
+def _lead_shape(a, name, dims):
+    s = tuple(a.shape)
+    if len(s) == dims + 1 and s[1] == 1:
+        s = s[:1] + s[2:]
+    if len(s) != dims:
+        raise ValueError('%s must have %d dimensions (a singleton channel axis is allowed), got shape %r' % (name, dims, tuple(a.shape)))
+    return s
+
+
+def variable_density_poisson_solve(rho, rhses, boundaries, dx, dy=None, tol=1e-10, max_iterations=500, initial_guesses=None, check_every=8,
+                                   return_info=False, device=None):
+    """Solves div((1/rho) grad u) = f with Dirichlet data on the four edges, on the vertex-centred grid of multigrid_poisson_solve (same shapes
+    and edge names: rhses (N,1,H,W) or (N,H,W); boundaries: dict with 'left'/'right' (N,W) and 'bottom'/'top' (N,H); dx one spacing per sample).
+    rho (N,H,W) or (N,1,H,W) is given on every node, boundary nodes included, and must be positive.
+
+    Discretisation: the conservative (flux) form with the face coefficients beta = 2 / (rho_a + rho_b) of the two nodes a face separates - the
+    first matrix of the reference's dataset/generators/variable_density, c = 2 / (dx^2 (rho_c + rho_neighbour)).  With A = -L this is a symmetric
+    positive definite system A u = b on the (H-2) x (W-2) interior nodes; rho = c everywhere gives the system of multigrid_poisson_solve with
+    f replaced by c f.  The reference's third matrix - the non-conservative form (1/rho) lap u + grad(1/rho).grad u with identity rows for the
+    boundary nodes - is nonsymmetric and is NOT reproduced.  Only dy = dx is supported: a dy that differs from dx raises NotImplementedError.
+
+    Solver: conjugate gradients in fp64 on the GPU, preconditioned by the constant-coefficient DST solve (condition number at most
+    max(beta) / min(beta), whatever the grid size).  A sample stops changing once ||r|| <= tol ||b||; the host looks at the convergence flags
+    every `check_every` iterations, so max_iterations is rounded up to a multiple of check_every.  initial_guesses: optional (N,H,W) or
+    (N,1,H,W) start values (read in fp64; only the interior is used).  A sample that has not converged when the iterations run out raises a
+    RuntimeWarning and is reported as converged = False.
+
+    Returns soln (N,1,H,W) fp32; with return_info also a dict of per-sample numpy arrays `iterations` (a multiple of check_every), `converged`
+    and `relative_residual` (||r|| / ||b|| of the recurrence)."""
+    import warnings
+    # everything that can be refused without a device is refused first
+    rs = _lead_shape(rhses, 'rhses', 3)
+    if _lead_shape(rho, 'rho', 3) != rs:
+        raise ValueError('rho %r and rhses %r must have the same (N,H,W)' % (tuple(rho.shape), tuple(rhses.shape)))
+    N, H, W = rs
+    if H < 3 or W < 3:
+        raise ValueError('the grid needs at least 3 points per axis, got %d x %d' % (H, W))
+    two_columns = len(tuple(np.shape(dx))) == 2 and np.shape(dx)[1] == 2           # (N,2): dx and dy side by side, as the generators hand them out
+    if dy is not None or two_columns:
+        hx = _host_array(dx).astype(np.float64)
+        hy = hx[:, 1] if dy is None else _host_array(dy).astype(np.float64)
+        if not np.array_equal(_per_sample_spacing(hx, N), _per_sample_spacing(hy, N)):
+            raise NotImplementedError('variable_density_poisson_solve: anisotropic spacing (dy != dx) is not supported')
+    if not (float(tol) > 0.0):
+        raise ValueError('tol must be positive')
+    if int(max_iterations) < 1 or int(check_every) < 1:
+        raise ValueError('max_iterations and check_every must be at least 1')
+    missing = [k for k in _BOUNDARY_KEYS if k not in boundaries]
+    if missing:
+        raise ValueError('boundaries lacks %r' % (missing,))
+    if initial_guesses is not None and _lead_shape(initial_guesses, 'initial_guesses', 3) != rs:
+        raise ValueError('initial_guesses %r must match rhses %r' % (tuple(initial_guesses.shape), tuple(rhses.shape)))
+    if not (isinstance(rho, torch.Tensor) and rho.is_cuda) and not np.all(_host_array(rho) > 0):
+        raise ValueError('rho must be positive everywhere')
+    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+    t = lambda a: (a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))).to(device=dev, dtype=torch.float32)
+    r = t(rhses).reshape(N, H, W).contiguous()
+    dens = t(rho).reshape(N, H, W).contiguous()
+    b = {k: t(boundaries[k]).reshape(-1, W if k in ('left', 'right') else H).expand(N, -1).contiguous() for k in _BOUNDARY_KEYS}
+    d = t(dx).reshape(-1)
+    d = d.expand(N).contiguous() if d.numel() == 1 else d.reshape(N, -1)[:, 0].contiguous()
+    x0 = None
+    if initial_guesses is not None:
+        g = initial_guesses if isinstance(initial_guesses, torch.Tensor) else torch.as_tensor(np.asarray(initial_guesses))
+        x0 = g.to(device=dev, dtype=torch.float64).reshape(N, H, W).contiguous()
+    soln, info = K.varcoef_pcg_solve(dens, r, b['left'], b['right'], b['bottom'], b['top'], d, tol=float(tol), max_iterations=int(max_iterations), x0=x0,
+                                     check_every=int(check_every))
+    if not info['converged'].all():           # (a rho <= 0 or NaN on the device was refused inside, straight after the setup kernel's minimum)
+        bad = np.flatnonzero(~info['converged'])
+        warnings.warn('variable_density_poisson_solve: sample(s) %r not converged to tol = %g after %d iterations (relative residual %r)'
+                      % (bad.tolist(), tol, int(info['iterations'].max()), info['relative_residual'][bad].tolist()), RuntimeWarning, stacklevel=2)
+    soln = soln.view(N, 1, H, W)
+    if return_info:
+        return soln, {k: info[k] for k in ('iterations', 'converged', 'relative_residual')}
+    return soln
+
+
+def compressible_poisson_solve(rho, rhses, boundaries, dx, dy=None, system_matrix=None):
+    """The reference's name and argument order (dataset/generators/variable_density: compressible_poisson_solve).  system_matrix is accepted and
+    ignored: no matrix is assembled."""
+    return variable_density_poisson_solve(rho, rhses, boundaries, dx, dy=dy)
+
+
+class variable_density_dataset_generator(numerical_dataset_generator):
+    """Random smooth right-hand side F and density rho -> the variable-density solve: generate_dataset of the reference's
+    dataset/generators/variable_density, which returns (soln, stack([F, rho], axis=1)).  Keras order here (return_keras_style):
+    ([stack([rhs, rho], axis=1), dx], soln), with the four boundary arrays (left, top, right, bottom, each (N,1,len)) between the stack and dx
+    when boundaries = 'random'; otherwise the reference's pair (soln, stack).  Feeding a network with the two-channel input is out of scope.
+
+    rho = lo + (hi - lo) |g| / max|g| with g a smooth random field (the bicubic up-sampling of random control points the numerical generator
+    uses) and (lo, hi) = density_range: the reference takes 1e-7 + |g|, whose ratio max/min is unbounded; density_range bounds the condition
+    number of the preconditioned system by hi / lo.  One grid shape per batch (output_shape, or drawn from random_output_shape_range), one
+    spacing per sample from random_dx_range."""
+
+    def __init__(self, batch_size=1, batches_per_epoch=1, output_shape=None, random_output_shape_range=((64, 85), (64, 85)), density_range=(1.0, 10.0),
+                 rhs_smoothness_range=(5, 20), density_smoothness_range=(5, 20), boundaries='zero', random_dx_range=(0.005, 0.05), rhs_max_magnitude=1.0,
+                 boundary_max_magnitude=1.0, tol=1e-10, max_iterations=500, seed=0, device=None, return_keras_style=True):
+        super().__init__(batch_size=batch_size, batches_per_epoch=batches_per_epoch, return_keras_style=return_keras_style, seed=seed, device=device)
+        lo, hi = float(density_range[0]), float(density_range[1])
+        if not 0.0 < lo <= hi:
+            raise ValueError('density_range = (lo, hi) needs 0 < lo <= hi, got %r' % (density_range,))
+        if boundaries not in ('zero', 'random'):
+            raise ValueError("boundaries must be 'zero' or 'random'")
+        for name, rg in (('rhs_smoothness_range', rhs_smoothness_range), ('density_smoothness_range', density_smoothness_range)):
+            if not 2 <= int(rg[0]) <= int(rg[1]):
+                raise ValueError('%s = (lo, hi) needs 2 <= lo <= hi control points, got %r' % (name, rg))
+        self.output_shape = None if output_shape is None else (int(output_shape[0]), int(output_shape[1]))
+        self.random_output_shape_range = np.asarray(random_output_shape_range, dtype=np.int64).reshape(2, 2)
+        self.density_range = (lo, hi)
+        self.rhs_smoothness_range, self.density_smoothness_range = tuple(rhs_smoothness_range), tuple(density_smoothness_range)
+        self.boundaries, self.random_dx_range = boundaries, (float(random_dx_range[0]), float(random_dx_range[1]))
+        self.rhs_max_magnitude, self.boundary_max_magnitude = float(rhs_max_magnitude), float(boundary_max_magnitude)
+        self.tol, self.max_iterations = float(tol), int(max_iterations)
+        self.last_info = None          # iterations / converged / relative_residual of the latest batch
+
+    def __getitem__(self, idx=0):
+        N, rng = self.batch_size, self.rng
+        if self.output_shape is not None:
+            H, W = self.output_shape
+        else:
+            H, W = [int(self.shape_rng.integers(r[0], r[1] + 1)) for r in self.random_output_shape_range]
+        dx = rng.uniform(size=(N, 1)) * (self.random_dx_range[1] - self.random_dx_range[0]) + self.random_dx_range[0]
+        ctrl = lambda rg: [int(rng.integers(rg[0], rg[1] + 1)) for _ in range(2)]
+        nf, nr = ctrl(self.rhs_smoothness_range), ctrl(self.density_smoothness_range)
+        rhs = self._smooth_field(2 * rng.uniform(size=(N, nf[0], nf[1])) - 1, (H, W), self.rhs_max_magnitude)
+        rho = K.varcoef_density(self._smooth_field(2 * rng.uniform(size=(N, nr[0], nr[1])) - 1, (H, W), 1.0), *self.density_range)
+        lengths = {'left': W, 'right': W, 'top': H, 'bottom': H}
+        bc = {}
+        for k in _BOUNDARY_KEYS:
+            if self.boundaries == 'random':
+                nb = int(rng.integers(self.rhs_smoothness_range[0], self.rhs_smoothness_range[1] + 1))
+                bc[k] = self._smooth_field((2 * rng.uniform(size=(N, nb)) - 1)[:, None, :], (1, lengths[k]), self.boundary_max_magnitude).view(N, lengths[k])
+            else:
+                bc[k] = torch.zeros((N, lengths[k]), dtype=torch.float32, device=self.device)
+        d = self._dev(dx)
+        soln, self.last_info = variable_density_poisson_solve(rho, rhs, bc, d, tol=self.tol, max_iterations=self.max_iterations, return_info=True,
+                                                              device=self.device)
+        frho = torch.stack([rhs, rho], dim=1)
+        if not self.return_keras_style:
+            return soln, frho
+        inp = [frho]
+        if self.boundaries == 'random':
+            inp += [bc[k].view(N, 1, -1) for k in _BOUNDARY_KEYS]
+        return inp + [d], soln

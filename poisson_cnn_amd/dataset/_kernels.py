@@ -107,6 +107,87 @@ def fd_poisson_mixed(rhs, left, right, bottom, top, dx, neumann=(False, False, F
     return soln
 
 
+def _chk_varcoef(t, name, shape, dtype=torch.float32):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError('%s must be a contiguous CUDA %s tensor of shape %r' % (name, str(dtype).replace('torch.', ''), tuple(shape)))
+    return t
+
+
+def varcoef_apply(rho, dx, p):
+    """q = A p of the variable-density flux-form operator (include/pcnn.h, pcnn_varcoef_apply) with zero Dirichlet data, and the per-sample p.q
+    of the same pass.  rho (N,H,W) fp32, dx (N,) fp32, p (N,H-2,W-2) fp64 -> q (N,H-2,W-2) fp64, pq (N,) fp64."""
+    if rho.dim() != 3:
+        raise ValueError('rho must be (N,H,W)')
+    N, H, W = rho.shape
+    _chk_varcoef(rho, 'rho', (N, H, W))
+    _chk_varcoef(dx, 'dx', (N,))
+    _chk_varcoef(p, 'p', (N, H - 2, W - 2), torch.float64)
+    q = torch.empty_like(p)
+    pq = torch.empty((N,), dtype=torch.float64, device=p.device)
+    handle().call('pcnn_varcoef_apply', c_int(N), c_int(H), c_int(W), _p(rho), _p(dx), _p(p), _p(q), _p(pq))
+    return q, pq
+
+
+VARCOEF_SCALARS = {'bb': 0, 'rr': 1, 'pq': 2, 'rho_min': 5}      # columns of the per-sample scalar table of pcnn_varcoef_pcg_* (8 doubles per sample)
+
+
+def varcoef_pcg_solve(rho, rhs, left, right, bottom, top, dx, tol=1e-10, max_iterations=500, x0=None, check_every=8):
+    """Preconditioned conjugate gradients on the variable-density system (pcnn_varcoef_pcg_setup / _iterate / _finish).  rho, rhs (N,H,W),
+    left/right (N,W), bottom/top (N,H), dx (N,): fp32 CUDA tensors; x0: optional (N,H,W) fp64 initial guess (its interior is used).
+    The device runs check_every iterations per call; the host reads the N convergence flags between calls and nothing else.
+    -> soln (N,H,W) fp32 and a dict of host arrays: iterations (the multiple of check_every at which the sample's flag was seen; for a sample that
+    did not converge, all that were run), converged, relative_residual = ||r|| / ||b|| of the recurrence, rho_min.
+    A rho that is not positive everywhere (NaN included) raises ValueError straight after the setup launch."""
+    from ctypes import c_double, c_size_t
+    N, H, W = rho.shape
+    for name, t, shape in (('rho', rho, (N, H, W)), ('rhs', rhs, (N, H, W)), ('left', left, (N, W)), ('right', right, (N, W)), ('bottom', bottom, (N, H)),
+                           ('top', top, (N, H)), ('dx', dx, (N,))):
+        _chk_varcoef(t, name, shape)
+    if x0 is not None:
+        _chk_varcoef(x0, 'x0', (N, H, W), torch.float64)
+    if not (tol > 0 and max_iterations >= 1 and check_every >= 1):
+        raise ValueError('tol must be positive, max_iterations and check_every at least 1')
+    dev = rho.device
+    Sh, lh = dst_matrices(H, dev)
+    Sw, lw = dst_matrices(W, dev)
+    nbytes = int(_lib.load().pcnn_varcoef_pcg_workspace(c_int(N), c_int(H), c_int(W)))
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+    scal = torch.empty((N, 8), dtype=torch.float64, device=dev)
+    flags = torch.empty((N,), dtype=torch.int32, device=dev)
+    h = handle()
+    h.call('pcnn_varcoef_pcg_setup', c_int(N), c_int(H), c_int(W), _p(rho), _p(rhs), _p(left), _p(right), _p(bottom), _p(top), _p(dx), _p(x0), c_double(tol),
+           _p(Sh), _p(lh), _p(Sw), _p(lw), _p(ws), c_size_t(nbytes), _p(scal), _p(flags))
+    rho_min = scal[:, VARCOEF_SCALARS['rho_min']].cpu().numpy()
+    if not np.all(rho_min > 0):                                         # the setup kernel's minimum counts a NaN as -inf; nothing more is launched
+        raise ValueError('rho must be positive everywhere (minimum per sample: %r)' % (rho_min.tolist(),))
+    iterations = np.zeros(N, dtype=np.int64)
+    done = np.zeros(N, dtype=bool)
+    it = 0
+    while it < max_iterations and not done.all():
+        h.call('pcnn_varcoef_pcg_iterate', c_int(N), c_int(H), c_int(W), _p(rho), _p(dx), c_double(tol), c_int(it), c_int(check_every), _p(Sh), _p(lh),
+               _p(Sw), _p(lw), _p(ws), c_size_t(nbytes), _p(scal), _p(flags))
+        it += check_every
+        f = flags.cpu().numpy() != 0                                    # the one host read per check_every iterations
+        iterations[f & ~done] = it
+        done |= f
+    iterations[~done] = it
+    soln = torch.empty((N, H, W), dtype=torch.float32, device=dev)
+    h.call('pcnn_varcoef_pcg_finish', c_int(N), c_int(H), c_int(W), _p(ws), _p(left), _p(right), _p(bottom), _p(top), _p(soln))
+    s = scal.cpu().numpy()
+    bb, rr = s[:, VARCOEF_SCALARS['bb']], s[:, VARCOEF_SCALARS['rr']]
+    with np.errstate(divide='ignore', invalid='ignore'):
+        rel = np.where(bb > 0, np.sqrt(rr / np.where(bb > 0, bb, 1.0)), 0.0)
+    return soln, {'iterations': iterations, 'converged': done, 'relative_residual': rel, 'rho_min': rho_min}
+
+
+def varcoef_density(g, lo, hi):
+    """In place: g -> lo + (hi - lo) min(|g|, 1) (pcnn_varcoef_density); g: a smooth fp32 field scaled to max|g| = 1."""
+    if g.dtype != torch.float32 or not g.is_cuda or not g.is_contiguous():
+        raise ValueError('varcoef_density takes a contiguous CUDA float32 tensor')
+    handle().call('pcnn_varcoef_density', c_int64(g.numel()), c_float(lo), c_float(hi), _p(g))
+    return g
+
+
 def series_synthesis(coef, H, W, trig, out=None, accumulate=False):
     """coef (N,ka,kb) -> (N,H,W): sum c[A,B] f((A+1)x) f((B+1)y), f = sin (trig=0) / cos (trig=1)."""
     N, ka, kb = coef.shape
