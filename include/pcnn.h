@@ -589,7 +589,9 @@ int pcnn_grad_clip_apply(pcnn_handle h, float* g, int64_t n_items, const int32_t
  * rhs (N,H,W) fp32; left/right (N,W) are the values on axis -2 index 0 / -1, bottom/top (N,H) those on axis -1 index
  * 0 / -1 (multigrid.py:145-148); dx (N).  S_h ((H-2)^2), lam_h (H-2), S_w, lam_w: device copies of pcnn_dst_setup output.
  * tmp: 2*N*(H-2)*(W-2) doubles.  soln (N,H,W) fp32 (fp64 solve, fp32 I/O like the reference's cast at
- * dataset/generators/numerical.py:131). */
+ * dataset/generators/numerical.py:131); at a corner it holds the left / right value (the write order of multigrid.py:145-148).
+ * This is the neumann_mask = 0 case of pcnn_fd_poisson_mixed's pipeline with S for V, V^-1 and their transposes (S is symmetric and its own
+ * inverse): one build kernel, one division, one ring / interior writer (write_soln, csrc/dataset.hip) serve every FD solve of this header. */
 int pcnn_dst_setup(int n, double* S /* (n-2)^2, host */, double* lam /* n-2, host */);
 int pcnn_fd_poisson_dst(pcnn_handle h, int N, int H, int W, const float* rhs, const float* left, const float* right,
                         const float* bottom, const float* top, const float* dx, const double* S_h, const double* lam_h,
@@ -653,7 +655,8 @@ int pcnn_varcoef_apply(pcnn_handle h, int N, int H, int W, const float* rho, con
  *   iterate: `iterations` iterations numbered from first_iteration (the count of iterations done before), no host round trip in between:
  *            alpha = r.z / p.q and beta = r.z_new / r.z_old are formed inside the update kernels from scal; flags[n] is raised when
  *            ||r|| <= tol ||b||, and a flagged sample's alpha and beta are 0 from then on - its x is frozen bit for bit.
- *   finish:  soln (N,H,W) fp32: interior from x, edges from the boundary arrays with the corner convention of pcnn_fd_poisson_dst. */
+ *   finish:  soln (N,H,W) fp32: interior from x, edges from the boundary arrays, through the one writer of every FD solve here (write_soln in
+ *            csrc/dataset.hip: rows 0 / H-1, i.e. left / right, win the corners). */
 size_t pcnn_varcoef_pcg_workspace(int N, int H, int W);
 int pcnn_varcoef_pcg_setup(pcnn_handle h, int N, int H, int W, const float* rho, const float* rhs, const float* left, const float* right,
                            const float* bottom, const float* top, const float* dx, const double* x0, double tol, const double* S_h,

@@ -68,83 +68,49 @@ __global__ __launch_bounds__(256) void gemm_f64_kernel(int M, int Nn, int K, con
       }
 }
 
-// ---------------------------------------------------------------- DST Poisson solve pieces
-// B[n,i,j] = -dx^2 f[i+1,j+1] + boundary values folded onto the first interior ring (dataset/solvers/cholesky.py:85,114-117)
-__global__ void dst_build_rhs_kernel(int N, int H, int W, const float* __restrict__ rhs, const float* __restrict__ left, const float* __restrict__ right,
-                                     const float* __restrict__ bottom, const float* __restrict__ top, const float* __restrict__ dx, double* __restrict__ Bm) {
-  const int nh = H - 2, nw = W - 2;
-  const int64_t total = (int64_t)N * nh * nw;
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-    const int j = idx % nw; const int i = (idx / nw) % nh; const int n = idx / ((int64_t)nh * nw);
-    const double h = (double)dx[n];
-    double v = -h * h * (double)rhs[((int64_t)n * H + i + 1) * W + j + 1];
-    if (j == 0) v += (double)bottom[(int64_t)n * H + i + 1];       // F[..., 1:-1, 1]  += bottom
-    if (j == nw - 1) v += (double)top[(int64_t)n * H + i + 1];     // F[..., 1:-1, -2] += top
-    if (i == 0) v += (double)left[(int64_t)n * W + j + 1];         // F[..., 1, 1:-1]  += left
-    if (i == nh - 1) v += (double)right[(int64_t)n * W + j + 1];   // F[..., -2, 1:-1] += right
-    Bm[idx] = v;
-  }
-}
-
-__global__ void dst_divide_kernel(int N, int nh, int nw, const double* __restrict__ lam_h, const double* __restrict__ lam_w, double* __restrict__ T) {
-  const int64_t total = (int64_t)N * nh * nw;
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-    const int j = idx % nw; const int i = (idx / nw) % nh;
-    T[idx] /= (lam_h[i] + lam_w[j]);
-  }
-}
-
-// interior from U, then [:, -1]=top, [:, 0]=bottom, [0, :]=left, [-1, :]=right in that order (dataset/solvers/multigrid.py:145-148)
-__global__ void dst_write_soln_kernel(int N, int H, int W, const double* __restrict__ U, const float* __restrict__ left, const float* __restrict__ right,
-                                      const float* __restrict__ bottom, const float* __restrict__ top, float* __restrict__ soln) {
-  const int nh = H - 2, nw = W - 2;
-  const int64_t total = (int64_t)N * H * W;
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-    const int j = idx % W; const int i = (idx / W) % H; const int n = idx / ((int64_t)H * W);
-    float v;
-    if (i == 0) v = left[(int64_t)n * W + j];
-    else if (i == H - 1) v = right[(int64_t)n * W + j];
-    else if (j == 0) v = bottom[(int64_t)n * H + i];
-    else if (j == W - 1) v = top[(int64_t)n * H + i];
-    else v = (float)U[((int64_t)n * nh + i - 1) * nw + j - 1];
-    soln[idx] = v;
-  }
-}
-
-// ---------------------------------------------------------------- mixed Dirichlet / Neumann 5-point solve
-// Vertex-centred grid as above; an edge is Dirichlet (its nodes are given) or Neumann (du/dn = g along the outward normal; its nodes are
-// unknowns, closed by the second-order ghost node u_ghost = u_inner + 2 dx g).  The unknowns are rows i0..i1 x columns j0..j1:
+// ---------------------------------------------------------------- 5-point FD Poisson solve pieces (Dirichlet and mixed Dirichlet / Neumann)
+// Vertex-centred grid; an edge is Dirichlet (its nodes are given) or Neumann (du/dn = g along the outward normal; its nodes are unknowns,
+// closed by the second-order ghost node u_ghost = u_inner + 2 dx g: SURVEY 8f rank 4).  types bit 0/1/2/3 = left / right / bottom / top is
+// Neumann; 0 is the all-Dirichlet system of dataset/solvers/cholesky.py:85,114-117.  The unknowns are rows i0..i1 x columns j0..j1:
 //   4 u_ij - [neighbours] = -dx^2 f_ij + (Dirichlet neighbours' values) + 2 dx g on Neumann edges, the mirrored neighbour counted twice.
-// types bit 0/1/2/3 = left / right / bottom / top is Neumann.
-__global__ void mixed_build_rhs_kernel(int N, int H, int W, int types, const float* __restrict__ rhs, const float* __restrict__ left,
-                                       const float* __restrict__ right, const float* __restrict__ bottom, const float* __restrict__ top,
-                                       const float* __restrict__ dx, double* __restrict__ Bm) {
-  const int i0 = (types & 1) ? 0 : 1, i1 = (types & 2) ? H - 1 : H - 2, j0 = (types & 4) ? 0 : 1, j1 = (types & 8) ? W - 1 : W - 2;
-  const int mh = i1 - i0 + 1, mw = j1 - j0 + 1;
-  const int64_t total = (int64_t)N * mh * mw;
+struct FdUnknowns { int i0, i1, j0, j1, mh, mw; };
+__host__ __device__ inline FdUnknowns fd_unknowns(int H, int W, int types) {
+  FdUnknowns u;
+  u.i0 = (types & 1) ? 0 : 1; u.i1 = (types & 2) ? H - 1 : H - 2; u.j0 = (types & 4) ? 0 : 1; u.j1 = (types & 8) ? W - 1 : W - 2;
+  u.mh = u.i1 - u.i0 + 1; u.mw = u.j1 - u.j0 + 1;
+  return u;
+}
+
+// The edge terms are added in the order bottom, top, left, right (F[..., 1:-1, 1] += bottom, F[..., 1:-1, -2] += top, F[..., 1, 1:-1] += left,
+// F[..., -2, 1:-1] += right) on every route: fp64 addition is not associative, and an unknown next to a row edge and a column edge gets both.
+__global__ void fd_build_rhs_kernel(int N, int H, int W, int types, const float* __restrict__ rhs, const float* __restrict__ left,
+                                    const float* __restrict__ right, const float* __restrict__ bottom, const float* __restrict__ top,
+                                    const float* __restrict__ dx, double* __restrict__ Bm) {
+  const FdUnknowns u = fd_unknowns(H, W, types);
+  const int64_t total = (int64_t)N * u.mh * u.mw;
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-    const int jj = idx % mw; const int ii = (idx / mw) % mh; const int n = idx / ((int64_t)mh * mw);
-    const int i = i0 + ii, j = j0 + jj;
+    const int jj = idx % u.mw; const int ii = (idx / u.mw) % u.mh; const int n = idx / ((int64_t)u.mh * u.mw);
+    const int i = u.i0 + ii, j = u.j0 + jj;
     const double h = (double)dx[n];
     double v = -h * h * (double)rhs[((int64_t)n * H + i) * W + j];
-    // axis -2 (index i): left edge i = 0, right edge i = H-1; their values are indexed by j
-    if (i == 0) v += 2.0 * h * (double)left[(int64_t)n * W + j];                       // Neumann node on the left edge
-    else if (i == 1 && !(types & 1)) v += (double)left[(int64_t)n * W + j];            // Dirichlet neighbour
-    if (i == H - 1) v += 2.0 * h * (double)right[(int64_t)n * W + j];
-    else if (i == H - 2 && !(types & 2)) v += (double)right[(int64_t)n * W + j];
-    // axis -1 (index j): bottom edge j = 0, top edge j = W-1; values indexed by i.  A Dirichlet corner takes the left / right value
-    // (the write order of dataset/solvers/multigrid.py:145-148 lets left / right overwrite bottom / top there)
-    if (j == 0) v += 2.0 * h * (double)bottom[(int64_t)n * H + i];
-    else if (j == 1 && !(types & 4)) v += (double)bottom[(int64_t)n * H + i];
+    // axis -1 (index j): bottom edge j = 0, top edge j = W-1; their values are indexed by i
+    if (j == 0) v += 2.0 * h * (double)bottom[(int64_t)n * H + i];                     // Neumann node on the bottom edge
+    else if (j == 1 && !(types & 4)) v += (double)bottom[(int64_t)n * H + i];          // Dirichlet neighbour
     if (j == W - 1) v += 2.0 * h * (double)top[(int64_t)n * H + i];
     else if (j == W - 2 && !(types & 8)) v += (double)top[(int64_t)n * H + i];
+    // axis -2 (index i): left edge i = 0, right edge i = H-1; values indexed by j.  A Dirichlet corner holds the left / right value (write_soln)
+    if (i == 0) v += 2.0 * h * (double)left[(int64_t)n * W + j];
+    else if (i == 1 && !(types & 1)) v += (double)left[(int64_t)n * W + j];
+    if (i == H - 1) v += 2.0 * h * (double)right[(int64_t)n * W + j];
+    else if (i == H - 2 && !(types & 2)) v += (double)right[(int64_t)n * W + j];
     Bm[idx] = v;
   }
 }
 
 // coefficient / (lam_h + lam_w); the null mode of the all-Neumann problem (lam = 0) is dropped, which is the solution whose
-// trapezoidal integral vanishes - the zero-integral constraint Navier_Stokes_2D/solvers.py:258-259 imposes with a Lagrange multiplier
-__global__ void mixed_divide_kernel(int N, int mh, int mw, const double* __restrict__ lam_h, const double* __restrict__ lam_w, double* __restrict__ T) {
+// trapezoidal integral vanishes - the zero-integral constraint Navier_Stokes_2D/solvers.py:258-259 imposes with a Lagrange multiplier.
+// With a Dirichlet end on either axis the sum is at least about (pi / n)^2 and the guard never fires.
+__global__ void fd_divide_kernel(int N, int mh, int mw, const double* __restrict__ lam_h, const double* __restrict__ lam_w, double* __restrict__ T) {
   const int64_t total = (int64_t)N * mh * mw;
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
     const int j = idx % mw; const int i = (idx / mw) % mh;
@@ -153,22 +119,30 @@ __global__ void mixed_divide_kernel(int N, int mh, int mw, const double* __restr
   }
 }
 
-__global__ void mixed_write_soln_kernel(int N, int H, int W, int types, const double* __restrict__ U, const float* __restrict__ left,
-                                        const float* __restrict__ right, const float* __restrict__ bottom, const float* __restrict__ top,
-                                        float* __restrict__ soln) {
-  const int i0 = (types & 1) ? 0 : 1, i1 = (types & 2) ? H - 1 : H - 2, j0 = (types & 4) ? 0 : 1, j1 = (types & 8) ? W - 1 : W - 2;
-  const int mh = i1 - i0 + 1, mw = j1 - j0 + 1;
+// THE ring / interior rule of every solver: soln[n][i][j] is unknown(n, i - i0, j - j0) inside the unknowns' range and the edge array's value
+// outside it, rows 0 / H-1 (left / right) winning over columns 0 / W-1 (bottom / top) at a Dirichlet corner - the write order [:, -1] = top,
+// [:, 0] = bottom, [0, :] = left, [-1, :] = right of dataset/solvers/multigrid.py:145-148.
+template <typename Unknown>
+__device__ __forceinline__ void write_soln(int N, int H, int W, int types, const float* __restrict__ left, const float* __restrict__ right,
+                                           const float* __restrict__ bottom, const float* __restrict__ top, float* __restrict__ soln, Unknown unknown) {
+  const FdUnknowns u = fd_unknowns(H, W, types);
   const int64_t total = (int64_t)N * H * W;
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
     const int j = idx % W; const int i = (idx / W) % H; const int n = idx / ((int64_t)H * W);
     float v;
-    if (i < i0) v = left[(int64_t)n * W + j];
-    else if (i > i1) v = right[(int64_t)n * W + j];
-    else if (j < j0) v = bottom[(int64_t)n * H + i];
-    else if (j > j1) v = top[(int64_t)n * H + i];
-    else v = (float)U[((int64_t)n * mh + (i - i0)) * mw + (j - j0)];
+    if (i < u.i0) v = left[(int64_t)n * W + j];
+    else if (i > u.i1) v = right[(int64_t)n * W + j];
+    else if (j < u.j0) v = bottom[(int64_t)n * H + i];
+    else if (j > u.j1) v = top[(int64_t)n * H + i];
+    else v = (float)unknown(n, i - u.i0, j - u.j0);
     soln[idx] = v;
   }
+}
+__global__ void fd_write_soln_kernel(int N, int H, int W, int types, const double* __restrict__ U, const float* __restrict__ left,
+                                     const float* __restrict__ right, const float* __restrict__ bottom, const float* __restrict__ top,
+                                     float* __restrict__ soln) {
+  const FdUnknowns u = fd_unknowns(H, W, types);
+  write_soln(N, H, W, types, left, right, bottom, top, soln, [&](int n, int ii, int jj) { return U[((int64_t)n * u.mh + ii) * u.mw + jj]; });
 }
 
 // ---------------------------------------------------------------- series synthesis
@@ -343,26 +317,57 @@ extern "C" int pcnn_dst_setup(int n, double* S, double* lam) {
   return 0;
 }
 
+// dst = A_h src A_w per sample (A_h mh x mh and A_w mw x mw, shared by the batch): mid = A_h src, then dst = mid A_w.  dst may be src.
+int pcnn_two_sided_gemm_f64(pcnn_handle h, int N, int mh, int mw, const double* A_h, const double* src, const double* A_w, double* mid, double* dst) {
+  const int64_t per = (int64_t)mh * mw;
+  if (int rc = pcnn_batched_gemm_f64(h, N, mh, mw, mh, A_h, 0, mh, src, per, mw, mid, per, mw)) return rc;
+  return pcnn_batched_gemm_f64(h, N, mh, mw, mw, mid, per, mw, A_w, 0, mw, dst, per, mw);
+}
+
+// launches the fp64 instantiation of write_soln on the handle's stream; the caller checks the launch under its own name
+void pcnn_fd_write_soln(pcnn_handle h, int N, int H, int W, int types, const double* U, const float* left, const float* right, const float* bottom,
+                        const float* top, float* soln) {
+  hipLaunchKernelGGL(fd_write_soln_kernel, grid1d((int64_t)N * H * W), dim3(256), 0, h->stream, N, H, W, types, U, left, right, bottom, top, soln);
+}
+
+// The GEMM pipeline of both entry points below: per axis the eigen-decomposition M = V diag(lam) V^-1 of the 1-D operator on that axis'
+// unknowns - Vinv_h (mh x mh), V_h, lam_h, and for the second axis the TRANSPOSED matrices VinvT_w, VT_w (applied from the right):
+//   u = V_h ((Vinv_h B VinvT_w) ./ (lam_h + lam_w)) VT_w.     tmp: 2 N mh mw doubles (B / coefficients / u, and the GEMM intermediate).
+static int fd_poisson_gemm(pcnn_handle h, const char* who, int N, int H, int W, int types, const float* rhs, const float* left, const float* right,
+                           const float* bottom, const float* top, const float* dx, const double* Vinv_h, const double* V_h, const double* lam_h,
+                           const double* VinvT_w, const double* VT_w, const double* lam_w, double* tmp, float* soln) {
+  const FdUnknowns u = fd_unknowns(H, W, types);
+  const int64_t per = (int64_t)u.mh * u.mw;
+  double* Bm = tmp; double* T = tmp + (int64_t)N * per;
+  hipLaunchKernelGGL(fd_build_rhs_kernel, grid1d(N * per), dim3(256), 0, h->stream, N, H, W, types, rhs, left, right, bottom, top, dx, Bm);
+  PCNN_CHECK_LAUNCH(h, (std::string(who) + "(build)").c_str());
+  if (int rc = pcnn_two_sided_gemm_f64(h, N, u.mh, u.mw, Vinv_h, Bm, VinvT_w, T, Bm)) return rc;     // spectral coefficients
+  hipLaunchKernelGGL(fd_divide_kernel, grid1d(N * per), dim3(256), 0, h->stream, N, u.mh, u.mw, lam_h, lam_w, Bm);
+  PCNN_CHECK_LAUNCH(h, (std::string(who) + "(divide)").c_str());
+  if (int rc = pcnn_two_sided_gemm_f64(h, N, u.mh, u.mw, V_h, Bm, VT_w, T, Bm)) return rc;            // u
+  pcnn_fd_write_soln(h, N, H, W, types, Bm, left, right, bottom, top, soln);
+  PCNN_CHECK_LAUNCH(h, (std::string(who) + "(write)").c_str());
+  return 0;
+}
+
+// All four edges Dirichlet: the orthonormal DST-I matrix of pcnn_dst_setup is symmetric and its own inverse, so it serves as V, V^-1 and both transposes
 extern "C" int pcnn_fd_poisson_dst(pcnn_handle h, int N, int H, int W, const float* rhs, const float* left, const float* right, const float* bottom,
                                    const float* top, const float* dx, const double* S_h, const double* lam_h, const double* S_w, const double* lam_w,
                                    double* tmp, float* soln) {
   PCNN_REQUIRE(h, h && rhs && left && right && bottom && top && dx && S_h && lam_h && S_w && lam_w && tmp && soln, "pcnn_fd_poisson_dst: null argument");
   PCNN_REQUIRE(h, H >= 3 && W >= 3 && N >= 1, "pcnn_fd_poisson_dst: grid %dx%d too small", H, W);
-  const int nh = H - 2, nw = W - 2;
-  const int64_t per = (int64_t)nh * nw;
-  double* Bm = tmp; double* T = tmp + (int64_t)N * per;
-  hipLaunchKernelGGL(dst_build_rhs_kernel, grid1d(N * per), dim3(256), 0, h->stream, N, H, W, rhs, left, right, bottom, top, dx, Bm);
-  PCNN_CHECK_LAUNCH(h, "pcnn_fd_poisson_dst(build)");
-  int rc;
-  if ((rc = pcnn_batched_gemm_f64(h, N, nh, nw, nh, S_h, 0, nh, Bm, per, nw, T, per, nw))) return rc;     // T  = S_h B
-  if ((rc = pcnn_batched_gemm_f64(h, N, nh, nw, nw, T, per, nw, S_w, 0, nw, Bm, per, nw))) return rc;     // Bm = T S_w   (spectral coefficients)
-  hipLaunchKernelGGL(dst_divide_kernel, grid1d(N * per), dim3(256), 0, h->stream, N, nh, nw, lam_h, lam_w, Bm);
-  PCNN_CHECK_LAUNCH(h, "pcnn_fd_poisson_dst(divide)");
-  if ((rc = pcnn_batched_gemm_f64(h, N, nh, nw, nh, S_h, 0, nh, Bm, per, nw, T, per, nw))) return rc;     // T  = S_h (.)
-  if ((rc = pcnn_batched_gemm_f64(h, N, nh, nw, nw, T, per, nw, S_w, 0, nw, Bm, per, nw))) return rc;     // Bm = T S_w = u
-  hipLaunchKernelGGL(dst_write_soln_kernel, grid1d((int64_t)N * H * W), dim3(256), 0, h->stream, N, H, W, Bm, left, right, bottom, top, soln);
-  PCNN_CHECK_LAUNCH(h, "pcnn_fd_poisson_dst(write)");
-  return 0;
+  return fd_poisson_gemm(h, "pcnn_fd_poisson_dst", N, H, W, 0, rhs, left, right, bottom, top, dx, S_h, S_h, lam_h, S_w, S_w, lam_w, tmp, soln);
+}
+
+// Per-edge Dirichlet / Neumann: the host supplies the decompositions (dataset/_kernels.py axis_decomposition)
+extern "C" int pcnn_fd_poisson_mixed(pcnn_handle h, int N, int H, int W, int neumann_mask, const float* rhs, const float* left, const float* right,
+                                     const float* bottom, const float* top, const float* dx, const double* Vinv_h, const double* V_h,
+                                     const double* lam_h, const double* VinvT_w, const double* VT_w, const double* lam_w, double* tmp, float* soln) {
+  PCNN_REQUIRE(h, h && rhs && left && right && bottom && top && dx && Vinv_h && V_h && lam_h && VinvT_w && VT_w && lam_w && tmp && soln,
+               "pcnn_fd_poisson_mixed: null argument");
+  PCNN_REQUIRE(h, H >= 3 && W >= 3 && N >= 1 && neumann_mask >= 0 && neumann_mask < 16, "pcnn_fd_poisson_mixed: bad shape or mask");
+  return fd_poisson_gemm(h, "pcnn_fd_poisson_mixed", N, H, W, neumann_mask, rhs, left, right, bottom, top, dx, Vinv_h, V_h, lam_h, VinvT_w, VT_w, lam_w, tmp,
+                         soln);
 }
 
 // ------------------------------------------------------------------------------------------------------------------ rocFFT route
@@ -482,21 +487,12 @@ __global__ void dst_extend_coeff_kernel(int N, int nh, int nw, const double2* __
     return -0.25 * Eh[((int64_t)n * Lh + a + 1) * Cw + b + 1].x / (lam_h[a] + lam_w[b]);
   });
 }
+// u[ii][jj] = -Re Ehat[ii+1][jj+1] / 4 c_h c_w of the second transform
 __global__ void dst_fft_write_soln_kernel(int N, int H, int W, const double2* __restrict__ Eh, const float* __restrict__ left, const float* __restrict__ right,
                                           const float* __restrict__ bottom, const float* __restrict__ top, float* __restrict__ soln) {
   const int nh = H - 2, nw = W - 2, Lh = 2 * (nh + 1), Cw = nw + 2;
   const double scale = -0.25 * (2.0 / (nh + 1)) * (2.0 / (nw + 1));
-  const int64_t total = (int64_t)N * H * W;
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-    const int j = idx % W; const int i = (idx / W) % H; const int n = idx / ((int64_t)H * W);
-    float v;
-    if (i == 0) v = left[(int64_t)n * W + j];
-    else if (i == H - 1) v = right[(int64_t)n * W + j];
-    else if (j == 0) v = bottom[(int64_t)n * H + i];
-    else if (j == W - 1) v = top[(int64_t)n * H + i];
-    else v = (float)(scale * Eh[((int64_t)n * Lh + i) * Cw + j].x);     // u[i-1][j-1] sits at Ehat[i][j]
-    soln[idx] = v;
-  }
+  write_soln(N, H, W, 0, left, right, bottom, top, soln, [&](int n, int ii, int jj) { return scale * Eh[((int64_t)n * Lh + ii + 1) * Cw + jj + 1].x; });
 }
 
 }  // namespace
@@ -518,7 +514,7 @@ extern "C" int pcnn_fd_poisson_fft(pcnn_handle h, int N, int H, int W, const flo
   double* Bm = static_cast<double*>(workspace);
   double* E = Bm + (int64_t)N * nh * nw;
   double2* Eh = reinterpret_cast<double2*>(E + (int64_t)N * Lh * Lw);
-  hipLaunchKernelGGL(dst_build_rhs_kernel, grid1d((int64_t)N * nh * nw), dim3(256), 0, h->stream, N, H, W, rhs, left, right, bottom, top, dx, Bm);
+  hipLaunchKernelGGL(fd_build_rhs_kernel, grid1d((int64_t)N * nh * nw), dim3(256), 0, h->stream, N, H, W, 0, rhs, left, right, bottom, top, dx, Bm);
   hipLaunchKernelGGL(dst_extend_rhs_kernel, grid1d((int64_t)N * Lh * Lw), dim3(256), 0, h->stream, N, nh, nw, Bm, E);
   PCNN_CHECK_LAUNCH(h, "pcnn_fd_poisson_fft(extend)");
   void* in[1] = {E}; void* out[1] = {Eh};
@@ -572,31 +568,5 @@ extern "C" int pcnn_scale_samples(pcnn_handle h, int N, int64_t per, const float
   PCNN_REQUIRE(h, h && s && x, "pcnn_scale_samples: null argument");
   hipLaunchKernelGGL(scale_samples_kernel, grid1d((int64_t)N * per), dim3(256), 0, h->stream, N, per, s, x);
   PCNN_CHECK_LAUNCH(h, "pcnn_scale_samples");
-  return 0;
-}
-
-// Mixed Dirichlet / Neumann solve.  Per axis the host supplies the eigen-decomposition of the 1-D operator on that axis' unknowns
-// (M = V diag(lam) V^-1: dataset/__init__.py axis_decomposition): Vinv_h (mh x mh), V_h, lam_h, and for the second axis the TRANSPOSED
-// matrices VinvT_w, VT_w (applied from the right).  u = V_h ((Vinv_h B VinvT_w) ./ (lam_h + lam_w)) VT_w.
-extern "C" int pcnn_fd_poisson_mixed(pcnn_handle h, int N, int H, int W, int neumann_mask, const float* rhs, const float* left, const float* right,
-                                     const float* bottom, const float* top, const float* dx, const double* Vinv_h, const double* V_h,
-                                     const double* lam_h, const double* VinvT_w, const double* VT_w, const double* lam_w, double* tmp, float* soln) {
-  PCNN_REQUIRE(h, h && rhs && left && right && bottom && top && dx && Vinv_h && V_h && lam_h && VinvT_w && VT_w && lam_w && tmp && soln,
-               "pcnn_fd_poisson_mixed: null argument");
-  PCNN_REQUIRE(h, H >= 3 && W >= 3 && N >= 1 && neumann_mask >= 0 && neumann_mask < 16, "pcnn_fd_poisson_mixed: bad shape or mask");
-  const int mh = H - 2 + (neumann_mask & 1) + ((neumann_mask >> 1) & 1), mw = W - 2 + ((neumann_mask >> 2) & 1) + ((neumann_mask >> 3) & 1);
-  const int64_t per = (int64_t)mh * mw;
-  double* Bm = tmp; double* T = tmp + (int64_t)N * per;
-  hipLaunchKernelGGL(mixed_build_rhs_kernel, grid1d(N * per), dim3(256), 0, h->stream, N, H, W, neumann_mask, rhs, left, right, bottom, top, dx, Bm);
-  PCNN_CHECK_LAUNCH(h, "pcnn_fd_poisson_mixed(build)");
-  int rc;
-  if ((rc = pcnn_batched_gemm_f64(h, N, mh, mw, mh, Vinv_h, 0, mh, Bm, per, mw, T, per, mw))) return rc;
-  if ((rc = pcnn_batched_gemm_f64(h, N, mh, mw, mw, T, per, mw, VinvT_w, 0, mw, Bm, per, mw))) return rc;
-  hipLaunchKernelGGL(mixed_divide_kernel, grid1d(N * per), dim3(256), 0, h->stream, N, mh, mw, lam_h, lam_w, Bm);
-  PCNN_CHECK_LAUNCH(h, "pcnn_fd_poisson_mixed(divide)");
-  if ((rc = pcnn_batched_gemm_f64(h, N, mh, mw, mh, V_h, 0, mh, Bm, per, mw, T, per, mw))) return rc;
-  if ((rc = pcnn_batched_gemm_f64(h, N, mh, mw, mw, T, per, mw, VT_w, 0, mw, Bm, per, mw))) return rc;
-  hipLaunchKernelGGL(mixed_write_soln_kernel, grid1d((int64_t)N * H * W), dim3(256), 0, h->stream, N, H, W, neumann_mask, Bm, left, right, bottom, top, soln);
-  PCNN_CHECK_LAUNCH(h, "pcnn_fd_poisson_mixed(write)");
   return 0;
 }

@@ -6,6 +6,14 @@
 void pcnn_comm_release(pcnn_handle_s* h);   // collective.hip
 void pcnn_filter_cache_free(pcnn_handle_s* h);   // spectral_conv.hip
 
+// dataset.hip: the two steps of the FD Poisson pipeline that varcoef.hip runs too.
+// dst = A_h src A_w per sample (A_h mh x mh and A_w mw x mw, shared by the batch) as two pcnn_batched_gemm_f64: mid = A_h src, dst = mid A_w; dst may be src
+int pcnn_two_sided_gemm_f64(pcnn_handle h, int N, int mh, int mw, const double* A_h, const double* src, const double* A_w, double* mid, double* dst);
+// soln (N,H,W) fp32 <- the unknowns U (fp64; rows / columns of a Neumann edge included, types bit 0/1/2/3 = left / right / bottom / top is Neumann) and
+// the Dirichlet ring from the edge arrays; rows 0 / H-1 (left / right) win at the corners.  Launch only: the caller checks it.
+void pcnn_fd_write_soln(pcnn_handle h, int N, int H, int W, int types, const double* U, const float* left, const float* right, const float* bottom,
+                        const float* top, float* soln);
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 

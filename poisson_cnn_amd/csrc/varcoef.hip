@@ -259,23 +259,6 @@ __global__ __launch_bounds__(EW_THREADS) void varcoef_update_p_kernel(int64_t pe
     p[base + k] = beta != 0.0 ? z[base + k] + beta * p[base + k] : z[base + k];
 }
 
-// interior from x, then the edges with the corner convention of the DST solve: rows 0 / H-1 (left / right) win over columns 0 / W-1 (bottom / top)
-__global__ void varcoef_write_soln_kernel(int N, int H, int W, const double* __restrict__ x, const float* __restrict__ left, const float* __restrict__ right,
-                                          const float* __restrict__ bottom, const float* __restrict__ top, float* __restrict__ soln) {
-  const int nh = H - 2, nw = W - 2;
-  const int64_t total = (int64_t)N * H * W;
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-    const int j = idx % W; const int i = (idx / W) % H; const int n = idx / ((int64_t)H * W);
-    float v;
-    if (i == 0) v = left[(int64_t)n * W + j];
-    else if (i == H - 1) v = right[(int64_t)n * W + j];
-    else if (j == 0) v = bottom[(int64_t)n * H + i];
-    else if (j == W - 1) v = top[(int64_t)n * H + i];
-    else v = (float)x[((int64_t)n * nh + i - 1) * nw + j - 1];
-    soln[idx] = v;
-  }
-}
-
 // g -> lo + (hi - lo) |g|: a density field from a smooth function already scaled to max|g| = 1
 __global__ void varcoef_density_kernel(int64_t total, float lo, float hi, float* __restrict__ g) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) g[i] = lo + (hi - lo) * fminf(fabsf(g[i]), 1.f);
@@ -295,15 +278,11 @@ static int vc_precondition(pcnn_handle h, int N, int H, int W, const VcWs& w, co
   const int nh = H - 2, nw = W - 2;
   const int64_t per = (int64_t)nh * nw;
   const int eb = vc_ew_blocks(per);
-  int rc;
-  if ((rc = pcnn_batched_gemm_f64(h, N, nh, nw, nh, S_h, 0, nh, w.r, per, nw, w.q, per, nw))) return rc;
-  if ((rc = pcnn_batched_gemm_f64(h, N, nh, nw, nw, w.q, per, nw, S_w, 0, nw, w.z, per, nw))) return rc;
+  if (int rc = pcnn_two_sided_gemm_f64(h, N, nh, nw, S_h, w.r, S_w, w.q, w.z)) return rc;
   hipLaunchKernelGGL(varcoef_divide_kernel, dim3(eb, N), dim3(EW_THREADS), 0, h->stream, nh, nw, w.cap, lam_h, lam_w, w.z, w.part);
   hipLaunchKernelGGL(varcoef_reduce_kernel<0>, dim3(N), dim3(EW_THREADS), 0, h->stream, eb, w.cap, w.part, scal, (int)VS_STRIDE, slot, 0, 0.0, (int*)nullptr);
   PCNN_CHECK_LAUNCH(h, "pcnn_varcoef_pcg(divide)");
-  if ((rc = pcnn_batched_gemm_f64(h, N, nh, nw, nh, S_h, 0, nh, w.z, per, nw, w.q, per, nw))) return rc;
-  if ((rc = pcnn_batched_gemm_f64(h, N, nh, nw, nw, w.q, per, nw, S_w, 0, nw, w.z, per, nw))) return rc;
-  return 0;
+  return pcnn_two_sided_gemm_f64(h, N, nh, nw, S_h, w.z, S_w, w.q, w.z);
 }
 
 }  // namespace
@@ -383,9 +362,7 @@ extern "C" int pcnn_varcoef_pcg_finish(pcnn_handle h, int N, int H, int W, const
   PCNN_REQUIRE(h, h && workspace && left && right && bottom && top && soln, "pcnn_varcoef_pcg_finish: null argument");
   if (int rc = vc_check_shape(h, "pcnn_varcoef_pcg_finish", N, H, W)) return rc;
   const VcWs w = vc_layout(const_cast<void*>(workspace), N, H, W);
-  int64_t blocks = pcnn_cdiv64((int64_t)N * H * W, 256);
-  if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(varcoef_write_soln_kernel, dim3((unsigned)blocks), dim3(256), 0, h->stream, N, H, W, w.x, left, right, bottom, top, soln);
+  pcnn_fd_write_soln(h, N, H, W, 0, w.x, left, right, bottom, top, soln);     // interior from x, the ring as every FD solve here writes it
   PCNN_CHECK_LAUNCH(h, "pcnn_varcoef_pcg_finish");
   return 0;
 }

@@ -122,8 +122,36 @@ def _streams(seed, shard):
     return np.random.default_rng(seed + rank), np.random.default_rng([int(seed), 0x5AFE]), (rank, world)
 
 
+_BOUNDARY_KEYS = ('left', 'top', 'right', 'bottom')
+
+
+def _neumann_flags(boundary_types):
+    bt = {k: 'dirichlet' for k in _BOUNDARY_KEYS}
+    for k, v in (boundary_types or {}).items():
+        if k not in bt or str(v).lower() not in ('dirichlet', 'neumann'):
+            raise ValueError("boundary_types maps 'left'/'right'/'bottom'/'top' to 'dirichlet' or 'neumann' (got %r: %r)" % (k, v))
+        bt[k] = str(v).lower()
+    return tuple(bt[k] == 'neumann' for k in ('left', 'right', 'bottom', 'top'))
+
+
+class _generator:
+    """What every generator family shares: the Keras Sequence length and the upload of host draws to self.device."""
+
+    def __len__(self):
+        return self.batches_per_epoch
+
+    def _dev(self, a):
+        """host array -> float32 device tensor through a pinned staging buffer and an asynchronous copy on the current stream: a pageable upload
+        (torch.tensor(..., device=...)) synchronises the stream, ten times per batch (profiles/r06_train_shipped.txt); torch's pinned-memory cache
+        keeps the staging buffer alive until the copy has run."""
+        t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+        if self.device.type != 'cuda':
+            return t.to(self.device)
+        return t.pin_memory().to(self.device, non_blocking=True)
+
+
 # ----------------------------------------------------------------------------- analytic ("reverse") generators
-class reverse_poisson_dataset_generator:
+class reverse_poisson_dataset_generator(_generator):
     def __init__(self, batch_size, batches_per_epoch, random_output_shape_range, fourier_coeff_grid_size_range, taylor_degree_range=None,
                  grid_spacings_range=None, ndims=None, homogeneous_bc=False, return_rhses=True, return_boundaries=True, return_dx=True,
                  normalizations=None, uniform_grid_spacing=False, seed=0, device=None, shard=None):
@@ -144,9 +172,6 @@ class reverse_poisson_dataset_generator:
         self.neumann = False
         self.fixed_output_shape = None     # set to (H, W) to pin the grid (benchmarks / data-parallel ranks sharing one shape)
 
-    def __len__(self):
-        return self.batches_per_epoch
-
     # -- host-side draws
     def _grid_sizes(self, rng_range):
         """generate_grid_sizes (reverse.py:164-171)."""
@@ -166,15 +191,6 @@ class reverse_poisson_dataset_generator:
         if self.fixed_output_shape is not None:
             shape = np.asarray(self.fixed_output_shape, dtype=np.int64)
         return shape, dx
-
-    def _dev(self, a):
-        """host array -> float32 device tensor through a pinned staging buffer and an asynchronous copy on the current stream: a pageable upload
-        (torch.tensor(..., device=...)) synchronises the stream, ten times per batch (profiles/r06_train_shipped.txt); torch's pinned-memory cache
-        keeps the staging buffer alive until the copy has run."""
-        t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
-        if self.device.type != 'cuda':
-            return t.to(self.device)
-        return t.pin_memory().to(self.device, non_blocking=True)
 
     def _taylor_tables(self, H, W, domain_sizes):
         """1-D tables of generate_soln_and_rhs_taylor (reverse.py:231-256): X, X'', Y, Y'' per sample."""
@@ -309,10 +325,7 @@ class reverse_poisson_dataset_generator_mixed(reverse_poisson_dataset_generator)
 
 
 # ----------------------------------------------------------------------------- numerical (FD) generator
-_BOUNDARY_KEYS = ('left', 'top', 'right', 'bottom')
-
-
-class numerical_dataset_generator:
+class numerical_dataset_generator(_generator):
     """Random smooth RHS / Dirichlet BCs (bicubic up-sampling of random control points) -> 5-point FD solve on the GPU (DST-I).
     Output order with return_keras_style: [rhs, left, top, right, bottom, dx] (dataset/generators/numerical.py:204-216)."""
 
@@ -333,18 +346,6 @@ class numerical_dataset_generator:
         self.rng, self.shape_rng, self.shard = _streams(seed, shard)
         self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
 
-    def __len__(self):
-        return self.batches_per_epoch
-
-    def _dev(self, a):
-        """host array -> float32 device tensor through a pinned staging buffer and an asynchronous copy on the current stream: a pageable upload
-        (torch.tensor(..., device=...)) synchronises the stream, ten times per batch (profiles/r06_train_shipped.txt); torch's pinned-memory cache
-        keeps the staging buffer alive until the copy has run."""
-        t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
-        if self.device.type != 'cuda':
-            return t.to(self.device)
-        return t.pin_memory().to(self.device, non_blocking=True)
-
     def _smooth_field(self, ctrl, out_hw, max_magnitude):
         """generate_random_RHS / generate_random_boundaries core (numerical.py:10-72): control points -> legacy bicubic
         (align_corners) up-sampling -> per-sample max-magnitude scaling."""
@@ -354,6 +355,12 @@ class numerical_dataset_generator:
         if max_magnitude != np.inf:
             K.set_max_magnitude(y, torch.full((N,), float(max_magnitude), device=self.device))
         return y
+
+    def _edge(self, ctrl, length, max_magnitude):
+        """One edge array (N, length): the smooth function through the already drawn control values ctrl (N, k), or zeros when ctrl is None."""
+        if ctrl is None:
+            return torch.zeros((self.batch_size, length), dtype=torch.float32, device=self.device)
+        return self._smooth_field(ctrl[:, None, :], (1, length), max_magnitude).view(self.batch_size, length)
 
     def numerical_dataset(self, output_shape='random', dx='random', boundaries='random', rhses='random', rhs_smoothness=None, boundary_smoothness=None,
                           rhs_max_magnitude=1.0, boundary_max_magnitude=None, nonzero_boundaries=_BOUNDARY_KEYS, solver_method='multigrid',
@@ -403,12 +410,7 @@ class numerical_dataset_generator:
                 sm = {k: sm for k in _BOUNDARY_KEYS}
             elif sm is None:
                 sm = {k: int(rng.integers(5, int(lengths[k] // 1.5))) for k in _BOUNDARY_KEYS}
-            bc = {}
-            for k in _BOUNDARY_KEYS:
-                if k in nonzero:
-                    bc[k] = self._smooth_field((2 * rng.uniform(size=(N, sm[k])) - 1)[:, None, :], (1, lengths[k]), boundary_max_magnitude[k]).view(N, lengths[k])
-                else:
-                    bc[k] = torch.zeros((N, lengths[k]), dtype=torch.float32, device=self.device)
+            bc = {k: self._edge(2 * rng.uniform(size=(N, sm[k])) - 1 if k in nonzero else None, lengths[k], boundary_max_magnitude[k]) for k in _BOUNDARY_KEYS}
         else:
             bc = {k: self._dev(np.asarray(boundaries[k])).view(N, lengths[k]) for k in _BOUNDARY_KEYS}
         if boundary_types is not None and any(str(v).lower() == 'neumann' for v in boundary_types.values()):
@@ -448,33 +450,34 @@ class numerical_dataset_generator:
         return inp, out
 
 
-def _neumann_flags(boundary_types):
-    bt = {k: 'dirichlet' for k in _BOUNDARY_KEYS}
-    for k, v in (boundary_types or {}).items():
-        if k not in bt or str(v).lower() not in ('dirichlet', 'neumann'):
-            raise ValueError("boundary_types maps 'left'/'right'/'bottom'/'top' to 'dirichlet' or 'neumann' (got %r: %r)" % (k, v))
-        bt[k] = str(v).lower()
-    return tuple(bt[k] == 'neumann' for k in ('left', 'right', 'bottom', 'top'))
-
-
 # ----------------------------------------------------------------------------- solver entry points (dataset/solvers)
+def _f32(a, device):
+    return (a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))).to(device=device, dtype=torch.float32)
+
+
+def _solver_args(rhses, boundaries, dx, device=None):
+    """What every solver entry point accepts -> (rhs (N,H,W), edges dict, dx (N,), device), all fp32, contiguous and on `device` (default: the
+    current CUDA device).  rhses (N,1,H,W) or (N,H,W), numpy or torch; boundaries: 'left'/'right' (N,W) and 'bottom'/'top' (N,H), extra
+    singleton dims allowed, a batch of 1 is broadcast to N; dx: one number, (N,), (N,1) or (N,2) - the first column."""
+    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+    r = _f32(rhses, dev)
+    if r.dim() == 4:
+        r = r[:, 0]
+    N, H, W = r.shape
+    b = {k: _f32(boundaries[k], dev).reshape(-1, W if k in ('left', 'right') else H).expand(N, -1).contiguous() for k in _BOUNDARY_KEYS}
+    d = _f32(dx, dev).reshape(-1)
+    d = d.expand(N).contiguous() if d.numel() == 1 else d.reshape(N, -1)[:, 0].contiguous()
+    return r.contiguous(), b, d, dev
+
+
 def multigrid_poisson_solve(rhses, boundaries, dx, dy=None, system_matrix=None, tol=1e-10, solver_init_parameters=None, solver_run_parameters=None,
                             use_pyamgx=False, initial_guesses=None, device=None):
     """Drop-in for dataset/solvers/multigrid.py:98-150: solves pyamg.gallery.poisson((H-2, W-2)) u = poisson_RHS(rhses, boundaries, dx)
     and writes the Dirichlet values - by the direct DST-I diagonalisation on the GPU instead of Ruge-Stuben V-cycles / AMGX
     (tol, solver parameters and initial guesses are accepted and irrelevant for a direct solve; like the reference only `dx` is used).
     rhses (N,1,H,W) or (N,H,W); boundaries: dict with 'left'/'right' (N,W) and 'bottom'/'top' (N,H) (extra singleton dims allowed)."""
-    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
-    t = lambda a: (a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))).to(device=dev, dtype=torch.float32)
-    r = t(rhses)
-    if r.dim() == 4:
-        r = r[:, 0]
-    N, H, W = r.shape
-    b = {k: t(boundaries[k]).reshape(-1, W if k in ('left', 'right') else H).expand(N, -1).contiguous() for k in _BOUNDARY_KEYS}
-    d = t(dx).reshape(-1)
-    d = d.expand(N).contiguous() if d.numel() == 1 else d.reshape(N, -1)[:, 0].contiguous()   # (N,), (N,1) or (N,2): first column
-    out = K.fd_poisson_dst(r.contiguous(), b['left'], b['right'], b['bottom'], b['top'], d)
-    return out.view(N, 1, H, W)
+    r, b, d, _ = _solver_args(rhses, boundaries, dx, device)
+    return K.fd_poisson_dst(r, b['left'], b['right'], b['bottom'], b['top'], d).unsqueeze(1)
 
 
 def cholesky_poisson_solve(rhses, boundaries, h, system_matrix=None, system_matrix_is_decomposed=False, device=None):
@@ -488,17 +491,8 @@ def mixed_bc_poisson_solve(rhses, boundaries, dx, boundary_types, device=None):
     cosine series (dataset/generators/reverse_neumann.py) - but its Navier-Stokes projection step solves exactly this system
     (Navier_Stokes_2D/solvers.py:225-335, zero-integral constraint for the singular all-Neumann case, :258-259).
     boundary_types: dict edge -> 'dirichlet' | 'neumann'; a Neumann edge's array holds du/dn along the outward normal."""
-    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
-    t = lambda a: (a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))).to(device=dev, dtype=torch.float32)
-    r = t(rhses)
-    if r.dim() == 4:
-        r = r[:, 0]
-    N, H, W = r.shape
-    b = {k: t(boundaries[k]).reshape(-1, W if k in ('left', 'right') else H).expand(N, -1).contiguous() for k in _BOUNDARY_KEYS}
-    d = t(dx).reshape(-1)
-    d = d.expand(N).contiguous() if d.numel() == 1 else d.reshape(N, -1)[:, 0].contiguous()
-    out = K.fd_poisson_mixed(r.contiguous(), b['left'], b['right'], b['bottom'], b['top'], d, _neumann_flags(boundary_types))
-    return out.view(N, 1, H, W)
+    r, b, d, _ = _solver_args(rhses, boundaries, dx, device)
+    return K.fd_poisson_mixed(r, b['left'], b['right'], b['bottom'], b['top'], d, _neumann_flags(boundary_types)).unsqueeze(1)
 
 
 # ----------------------------------------------------------------------------- variable-density problem (dataset/generators/variable_density)
@@ -565,13 +559,8 @@ def variable_density_poisson_solve(rho, rhses, boundaries, dx, dy=None, tol=1e-1
         raise ValueError('initial_guesses %r must match rhses %r' % (tuple(initial_guesses.shape), tuple(rhses.shape)))
     if not (isinstance(rho, torch.Tensor) and rho.is_cuda) and not np.all(_host_array(rho) > 0):
         raise ValueError('rho must be positive everywhere')
-    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
-    t = lambda a: (a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))).to(device=dev, dtype=torch.float32)
-    r = t(rhses).reshape(N, H, W).contiguous()
-    dens = t(rho).reshape(N, H, W).contiguous()
-    b = {k: t(boundaries[k]).reshape(-1, W if k in ('left', 'right') else H).expand(N, -1).contiguous() for k in _BOUNDARY_KEYS}
-    d = t(dx).reshape(-1)
-    d = d.expand(N).contiguous() if d.numel() == 1 else d.reshape(N, -1)[:, 0].contiguous()
+    r, b, d, dev = _solver_args(rhses, boundaries, dx, device)
+    dens = _f32(rho, dev).reshape(N, H, W).contiguous()
     x0 = None
     if initial_guesses is not None:
         g = initial_guesses if isinstance(initial_guesses, torch.Tensor) else torch.as_tensor(np.asarray(initial_guesses))
@@ -640,11 +629,11 @@ class variable_density_dataset_generator(numerical_dataset_generator):
         lengths = {'left': W, 'right': W, 'top': H, 'bottom': H}
         bc = {}
         for k in _BOUNDARY_KEYS:
-            if self.boundaries == 'random':
+            ctrl = None
+            if self.boundaries == 'random':                                # count, then values, edge by edge
                 nb = int(rng.integers(self.rhs_smoothness_range[0], self.rhs_smoothness_range[1] + 1))
-                bc[k] = self._smooth_field((2 * rng.uniform(size=(N, nb)) - 1)[:, None, :], (1, lengths[k]), self.boundary_max_magnitude).view(N, lengths[k])
-            else:
-                bc[k] = torch.zeros((N, lengths[k]), dtype=torch.float32, device=self.device)
+                ctrl = 2 * rng.uniform(size=(N, nb)) - 1
+            bc[k] = self._edge(ctrl, lengths[k], self.boundary_max_magnitude)
         d = self._dev(dx)
         soln, self.last_info = variable_density_poisson_solve(rho, rhs, bc, d, tol=self.tol, max_iterations=self.max_iterations, return_info=True,
                                                               device=self.device)

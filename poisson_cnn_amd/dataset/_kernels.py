@@ -1,5 +1,6 @@
 """ctypes wrappers of the dataset kernels of libpcnn (include/pcnn.h, "dataset" section)."""
-from ctypes import c_float, c_int, c_int64, c_void_p
+import os
+from ctypes import c_double, c_float, c_int, c_int64, c_size_t, c_void_p
 
 import numpy as np
 import torch
@@ -32,8 +33,6 @@ def fd_poisson_dst(rhs, left, right, bottom, top, dx, solver='auto'):
     """rhs (N,H,W); left/right (N,W); bottom/top (N,H); dx (N,) -> soln (N,H,W), all fp32 CUDA tensors.
     solver: 'gemm' (DST-I as fp64 matrix-core GEMMs, pcnn_fd_poisson_dst), 'fft' (rocFFT, pcnn_fd_poisson_fft) or 'auto' (fft from FFT_FROM
     points per axis; environment PCNN_FD_SOLVER overrides)."""
-    import os
-    from ctypes import c_size_t
     N, H, W = rhs.shape
     Sh, lh = dst_matrices(H, rhs.device)
     Sw, lw = dst_matrices(W, rhs.device)
@@ -41,9 +40,7 @@ def fd_poisson_dst(rhs, left, right, bottom, top, dx, solver='auto'):
     if solver not in ('auto', 'gemm', 'fft'):
         raise ValueError("solver must be 'auto', 'gemm' or 'fft'")
     if solver == 'fft' or (solver == 'auto' and min(H, W) >= FFT_FROM):
-        lib = _lib.load()
-        lib.pcnn_fd_poisson_fft_workspace.restype = c_size_t
-        ws = torch.empty((lib.pcnn_fd_poisson_fft_workspace(c_int(N), c_int(H), c_int(W)) + 7) // 8, dtype=torch.float64, device=rhs.device)
+        ws = torch.empty((_lib.load().pcnn_fd_poisson_fft_workspace(c_int(N), c_int(H), c_int(W)) + 7) // 8, dtype=torch.float64, device=rhs.device)
         soln = torch.empty_like(rhs)
         handle().call('pcnn_fd_poisson_fft', c_int(N), c_int(H), c_int(W), _p(rhs), _p(left), _p(right), _p(bottom), _p(top), _p(dx), _p(lh), _p(lw), _p(ws), _p(soln))
         return soln
@@ -138,7 +135,6 @@ def varcoef_pcg_solve(rho, rhs, left, right, bottom, top, dx, tol=1e-10, max_ite
     -> soln (N,H,W) fp32 and a dict of host arrays: iterations (the multiple of check_every at which the sample's flag was seen; for a sample that
     did not converge, all that were run), converged, relative_residual = ||r|| / ||b|| of the recurrence, rho_min.
     A rho that is not positive everywhere (NaN included) raises ValueError straight after the setup launch."""
-    from ctypes import c_double, c_size_t
     N, H, W = rho.shape
     for name, t, shape in (('rho', rho, (N, H, W)), ('rhs', rhs, (N, H, W)), ('left', left, (N, W)), ('right', right, (N, W)), ('bottom', bottom, (N, H)),
                            ('top', top, (N, H)), ('dx', dx, (N,))):

@@ -296,3 +296,49 @@ def test_host_logs_and_inline_prefetcher_on_cpu():
         f.take()
     f.close()
     assert s.calls == [0, 1, 2]
+
+
+def _solver_args_as_the_entry_points_spelled_them(rhses, boundaries, dx, device):
+    """The eight lines multigrid_poisson_solve, mixed_bc_poisson_solve and variable_density_poisson_solve each carried before _solver_args, as they stood."""
+    import torch
+    _BOUNDARY_KEYS = ('left', 'top', 'right', 'bottom')
+    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+    t = lambda a: (a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))).to(device=dev, dtype=torch.float32)
+    r = t(rhses)
+    if r.dim() == 4:
+        r = r[:, 0]
+    N, H, W = r.shape
+    b = {k: t(boundaries[k]).reshape(-1, W if k in ('left', 'right') else H).expand(N, -1).contiguous() for k in _BOUNDARY_KEYS}
+    d = t(dx).reshape(-1)
+    d = d.expand(N).contiguous() if d.numel() == 1 else d.reshape(N, -1)[:, 0].contiguous()
+    return r.contiguous(), b, d, dev
+
+
+@pytest.mark.parametrize('as_torch', [False, True], ids=['numpy', 'torch'])
+@pytest.mark.parametrize('channel_axis', [False, True], ids=['NHW', 'N1HW'])
+@pytest.mark.parametrize('edge_form', ['N_len', 'N_1_len', '1_len'])
+@pytest.mark.parametrize('dx_form', ['number', 'N', 'N_1', 'N_2'])
+def test_solver_args_normalisation(dx_form, edge_form, channel_axis, as_torch):
+    """dataset._solver_args - the one place the three solver entry points normalise their arguments - against a literal transcription of the lines
+    it replaced: rhs (N,H,W) or (N,1,H,W); edge arrays (N,len), (N,1,len) or a batch of 1 broadcast to N; dx as one number, (N,), (N,1) or
+    (N,2) (first column); numpy (fp64) and torch inputs.  Everything comes back fp32, contiguous and on the device asked for."""
+    import torch
+    from poisson_cnn_amd.dataset import _solver_args
+    rng = np.random.default_rng(7)
+    N, H, W = 3, 5, 4
+    rhs = rng.standard_normal((N, 1, H, W) if channel_axis else (N, H, W))
+    lead = {'N_len': (N,), 'N_1_len': (N, 1), '1_len': (1,)}[edge_form]
+    bc = {k: rng.standard_normal(lead + ((W,) if k in ('left', 'right') else (H,))) for k in ('left', 'right', 'bottom', 'top')}
+    dx = {'number': 0.02, 'N': rng.uniform(0.01, 0.05, N), 'N_1': rng.uniform(0.01, 0.05, (N, 1)), 'N_2': rng.uniform(0.01, 0.05, (N, 2))}[dx_form]
+    if as_torch:
+        rhs, bc = torch.from_numpy(rhs), {k: torch.from_numpy(v) for k, v in bc.items()}
+        dx = torch.as_tensor(dx)
+    want = _solver_args_as_the_entry_points_spelled_them(rhs, bc, dx, 'cpu')
+    got = _solver_args(rhs, bc, dx, 'cpu')
+    assert got[3] == want[3] == torch.device('cpu')
+    for a, b in [(got[0], want[0]), (got[2], want[2])] + [(got[1][k], want[1][k]) for k in ('left', 'right', 'bottom', 'top')]:
+        assert a.dtype == torch.float32 and a.is_contiguous() and a.shape == b.shape and torch.equal(a, b)
+    assert set(got[1]) == set(want[1]) and tuple(got[0].shape) == (N, H, W) and tuple(got[2].shape) == (N,)
+    assert tuple(got[1]['left'].shape) == (N, W) and tuple(got[1]['top'].shape) == (N, H)
+    first = np.asarray(dx, dtype=np.float64).reshape(-1)[0] if dx_form == 'number' else np.asarray(dx, dtype=np.float64).reshape(N, -1)[:, 0]
+    assert np.array_equal(got[2].numpy(), np.broadcast_to(np.float32(first), (N,)))
