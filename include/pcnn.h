@@ -670,6 +670,28 @@ int pcnn_varcoef_pcg_finish(pcnn_handle h, int N, int H, int W, const void* work
 /* g[i] = lo + (hi - lo) min(|g[i]|, 1): a density field from a smooth function scaled to max|g| = 1 (the reference takes 1e-7 + |g|) */
 int pcnn_varcoef_density(pcnn_handle h, int64_t total, float lo, float hi, float* g);
 
+/* ---- training on the variable-density problem (csrc/varcoef_train.hip) ------------------- */
+/* fp32 on one-channel (N,H,W) fields, dx (N) one spacing per sample, rho (N,H,W) read on every node; the discretisation above:
+ *   (L u)[i,j] = sum over the four faces of beta_face (u[neighbour] - u[i,j]) / dx^2 = -(A u)[i,j]  on the interior nodes,
+ * with the ring of u part of the field.  No atomics; a sample's result does not depend on the batch it sits in; equal inputs give equal bits.
+ * out[n] = sum over the interior of (L pred - rhs)^2 (per-tile partials in the handle's auxiliary scratch, then one block per sample). */
+int pcnn_varcoef_pi_loss_partials(pcnn_handle h, int N, int H, int W, const float* pred, const float* rho, const float* rhs, const float* dx,
+                                  float* out /*N*/);
+/* dpred += coef[n] * d(out[n]) / d(pred) on ALL nodes (the ring is read by L and receives gradient); rho and rhs are data.  dpred aliases no input. */
+int pcnn_varcoef_pi_loss_bwd(pcnn_handle h, int N, int H, int W, const float* pred, const float* rho, const float* rhs, const float* dx,
+                             const float* coef /*N*/, float* dpred);
+/* n_sweeps Jacobi sweeps of L u = rhs: u'[i,j] = (sum over the four faces of beta_face u[neighbour] - dx^2 rhs[i,j]) / (sum of the four beta_face)
+ * on interior nodes, the ring frozen.  Up to pcnn_varcoef_jacobi_max_sweeps sweeps are fused per launch in LDS; more sweeps chain launches
+ * (one intermediate image in the handle's auxiliary scratch) and the result does not depend on the split.  out aliases no input. */
+int pcnn_varcoef_jacobi_fwd(pcnn_handle h, int N, int H, int W, const float* rho, const float* u, const float* rhs, const float* dx, int n_sweeps,
+                            float* out);
+/* the adjoint of those sweeps w.r.t. u: du = J^T dout (rho and rhs get no gradient).  du aliases no input. */
+int pcnn_varcoef_jacobi_bwd(pcnn_handle h, int N, int H, int W, const float* rho, const float* dx, const float* dout, int n_sweeps, float* du);
+int pcnn_varcoef_jacobi_max_sweeps(void);
+/* out[n,y,x,0:2] = {stack[n,0,y,x], stack[n,1,y,x]} of the generator's (N,2,H,W) stack [rhs, rho], followed - use_pos - by the two positional
+ * channels of pcnn_assemble_input; ldo >= 2 (4 with use_pos). */
+int pcnn_assemble_density_input(pcnn_handle h, int N, int H, int W, const float* stack, int use_pos, float* out, int ldo);
+
 /* tf.keras.layers.LayerNormalization() over the last axis of an (N, F) matrix (epsilon 1e-3 in Keras): the optional final layer of the
  * metalearning hyper-networks (layers/metalearning_conv.py:128-129).  fwd also returns the per-row mean and 1/sqrt(var + eps) for bwd. */
 int pcnn_layernorm_fwd(pcnn_handle h, int N, int F, const float* x, const float* gamma, const float* beta, float eps, float* y, float* mean, float* rstd);

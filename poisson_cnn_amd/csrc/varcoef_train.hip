@@ -1,0 +1,339 @@
+// Training-side operators of the variable-density problem div((1/rho) grad u) = f: the flux-form residual loss with its
+// gradient, and the Jacobi sweep of the same operator with its adjoint.  fp32 on one-channel (N,H,W) fields, one spacing per sample (dy = dx),
+// rho on every node.  The discretisation is that of csrc/varcoef.hip (section 16):
+//   beta_face = 2 / (rho_a + rho_b),   (L u)[i,j] = sum over the four faces of beta_face (u[neighbour] - u[i,j]) / dx^2 = -(A u)[i,j]
+// on the (H-2) x (W-2) interior nodes; here the ring of u is part of the field (the model predicts it), so L maps all H W nodes to the interior.
+// The face coefficients are never stored: every kernel builds them from an LDS tile of rho.  No atomics: the loss sums are per-tile partials
+// (fixed tree) added per sample by a second one-block stage in a fixed order.  A sample's blocks read nothing of another sample.
+#include <math.h>
+#include "pcnn_internal.h"
+
+#define VJ_TILE 64         // output tile edge of the sweeps
+#define VJ_HALO_MAX 8      // fused sweeps per launch: four LDS buffers of at most (64 + 2 * 8 + 2)^2 floats (107.6 KB)
+#define VJ_THREADS 512
+
+namespace {
+
+constexpr int PT_ROWS = 16, PT_COLS = 64, PT_THREADS = 256, PT_RPT = PT_ROWS / (PT_THREADS / PT_COLS);   // loss kernels: the tile of varcoef_apply_kernel
+constexpr int RED_THREADS = 256;
+
+__device__ __forceinline__ float beta_face(float a, float b) { return 2.f / (a + b); }
+
+// (L u - rhs) at an interior node: uc / rc the node's u / rho, (u?, r?) its four neighbours towards i-1, i+1, j-1, j+1
+__device__ __forceinline__ float flux_residual(float uc, float rc, float u0, float r0, float u1, float r1, float u2, float r2, float u3, float r3, float inv_h2,
+                                               float f) {
+  const float s = (beta_face(rc, r0) * (u0 - uc) + beta_face(rc, r1) * (u1 - uc)) + (beta_face(rc, r2) * (u2 - uc) + beta_face(rc, r3) * (u3 - uc));
+  return s * inv_h2 - f;
+}
+
+// nodes (I0 .. I0+LR-1) x (J0 .. J0+LC-1) of one sample's field into LDS; nodes outside the grid read `fill`
+template <int LR, int LC>
+__device__ __forceinline__ void load_nodes(float (*t)[LC], const float* __restrict__ src, int H, int W, int I0, int J0, float fill) {
+  for (int e = threadIdx.x; e < LR * LC; e += PT_THREADS) {
+    const int r = e / LC, c = e % LC, i = I0 + r, j = J0 + c;
+    t[r][c] = (i >= 0 && i < H && j >= 0 && j < W) ? src[(int64_t)i * W + j] : fill;
+  }
+}
+
+// part[n][tile] = the tile's sum of (L pred - rhs)^2.  grid (column tiles, row tiles, N) over the interior
+__global__ __launch_bounds__(PT_THREADS) void vc_pi_partials_kernel(int H, int W, int tiles, const float* __restrict__ pred, const float* __restrict__ rho,
+                                                                    const float* __restrict__ rhs, const float* __restrict__ dx, float* __restrict__ part) {
+  constexpr int LR = PT_ROWS + 2, LC = PT_COLS + 2;
+  __shared__ float us[LR][LC];
+  __shared__ float rs[LR][LC];
+  __shared__ float red[PT_THREADS];
+  const int nh = H - 2, nw = W - 2, n = blockIdx.z, I0 = blockIdx.y * PT_ROWS, J0 = blockIdx.x * PT_COLS;   // LDS (r, c) is node (I0 + r, J0 + c)
+  const int64_t img = (int64_t)n * H * W;
+  load_nodes<LR, LC>(us, pred + img, H, W, I0, J0, 0.f);
+  load_nodes<LR, LC>(rs, rho + img, H, W, I0, J0, 1.f);
+  __syncthreads();
+  const float h = dx[n], inv_h2 = 1.f / (h * h);
+  const int c = threadIdx.x % PT_COLS, r0 = (threadIdx.x / PT_COLS) * PT_RPT;
+  float s = 0.f;
+  if (J0 + c < nw) {
+#pragma unroll
+    for (int k = 0; k < PT_RPT; ++k) {
+      const int r = r0 + k;
+      if (I0 + r < nh) {
+        const int a = r + 1, b = c + 1;
+        const float e = flux_residual(us[a][b], rs[a][b], us[a - 1][b], rs[a - 1][b], us[a + 1][b], rs[a + 1][b], us[a][b - 1], rs[a][b - 1], us[a][b + 1],
+                                      rs[a][b + 1], inv_h2, rhs[img + (int64_t)(I0 + a) * W + J0 + b]);
+        s += e * e;
+      }
+    }
+  }
+  red[threadIdx.x] = s;
+  __syncthreads();
+#pragma unroll
+  for (int w = PT_THREADS / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) part[(int64_t)n * tiles + blockIdx.y * gridDim.x + blockIdx.x] = red[0];
+}
+
+// out[n] = the sample's partials added in a fixed order (in fp64: the second stage costs nothing and adds no rounding of its own)
+__global__ __launch_bounds__(RED_THREADS) void vc_pi_reduce_kernel(int tiles, const float* __restrict__ part, float* __restrict__ out) {
+  __shared__ double red[RED_THREADS];
+  const int n = blockIdx.x, t = threadIdx.x;
+  double v = 0.0;
+  for (int k = t; k < tiles; k += RED_THREADS) v += (double)part[(int64_t)n * tiles + k];
+  red[t] = v;
+  __syncthreads();
+#pragma unroll
+  for (int w = RED_THREADS / 2; w > 0; w >>= 1) {
+    if (t < w) red[t] += red[t + w];
+    __syncthreads();
+  }
+  if (t == 0) out[n] = (float)red[0];
+}
+
+// dpred += coef[n] * 2 L^T e, e = L pred - rhs.  Gather form: e on the tile's nodes and a one-node halo (zero outside the interior), then
+// (L^T e)[p] = sum over the faces of p of beta_face (e[neighbour] - e[p]) / dx^2 - the operator is symmetric, and on a ring node, where e[p] = 0,
+// the same expression is the sum of beta_face e[interior neighbour].  grid (column tiles, row tiles, N) over ALL nodes
+__global__ __launch_bounds__(PT_THREADS) void vc_pi_bwd_kernel(int H, int W, const float* __restrict__ pred, const float* __restrict__ rho,
+                                                               const float* __restrict__ rhs, const float* __restrict__ dx, const float* __restrict__ coef,
+                                                               float* __restrict__ dpred) {
+  constexpr int LR = PT_ROWS + 4, LC = PT_COLS + 4, ER = PT_ROWS + 2, EC = PT_COLS + 2;
+  __shared__ float us[LR][LC];
+  __shared__ float rs[LR][LC];
+  __shared__ float es[ER][EC];
+  const int n = blockIdx.z, I0 = blockIdx.y * PT_ROWS, J0 = blockIdx.x * PT_COLS;     // us / rs (r, c) is node (I0 - 2 + r, J0 - 2 + c); es: (I0 - 1 + r, J0 - 1 + c)
+  const int64_t img = (int64_t)n * H * W;
+  load_nodes<LR, LC>(us, pred + img, H, W, I0 - 2, J0 - 2, 0.f);
+  load_nodes<LR, LC>(rs, rho + img, H, W, I0 - 2, J0 - 2, 1.f);
+  __syncthreads();
+  const float h = dx[n], inv_h2 = 1.f / (h * h);
+  for (int e = threadIdx.x; e < ER * EC; e += PT_THREADS) {
+    const int r = e / EC, c = e % EC, i = I0 - 1 + r, j = J0 - 1 + c;
+    float v = 0.f;
+    if (i >= 1 && i < H - 1 && j >= 1 && j < W - 1) {
+      const int a = r + 1, b = c + 1;
+      v = flux_residual(us[a][b], rs[a][b], us[a - 1][b], rs[a - 1][b], us[a + 1][b], rs[a + 1][b], us[a][b - 1], rs[a][b - 1], us[a][b + 1], rs[a][b + 1],
+                        inv_h2, rhs[img + (int64_t)i * W + j]);
+    }
+    es[r][c] = v;
+  }
+  __syncthreads();
+  const float scale = 2.f * coef[n] * inv_h2;
+  const int c = threadIdx.x % PT_COLS, r0 = (threadIdx.x / PT_COLS) * PT_RPT;
+  if (J0 + c < W) {
+#pragma unroll
+    for (int k = 0; k < PT_RPT; ++k) {
+      const int r = r0 + k;
+      if (I0 + r < H) {
+        const int a = r + 1, b = c + 1;                  // in es; rs is one further in
+        const float ec = es[a][b], rc = rs[a + 1][b + 1];
+        const float g = (beta_face(rc, rs[a][b + 1]) * (es[a - 1][b] - ec) + beta_face(rc, rs[a + 2][b + 1]) * (es[a + 1][b] - ec)) +
+                        (beta_face(rc, rs[a + 1][b]) * (es[a][b - 1] - ec) + beta_face(rc, rs[a + 1][b + 2]) * (es[a][b + 1] - ec));
+        dpred[img + (int64_t)(I0 + r) * W + J0 + c] += scale * g;
+      }
+    }
+  }
+}
+
+// Walks the rectangle (y0, x0, h, w) with the workgroup's threads in row-major order, without a division per point (as csrc/stencil.hip).
+template <class F>
+__device__ __forceinline__ void vj_points(int tid, int y0, int x0, int h, int w, F body) {
+  int q = tid / w, r = tid - q * w;
+  const int dq = VJ_THREADS / w, dr = VJ_THREADS - dq * w;
+  while (q < h) {
+    body(y0 + q, x0 + r);
+    q += dq; r += dr;
+    if (r >= w) { r -= w; ++q; }
+  }
+}
+
+// k sweeps in one launch by temporal blocking (DESIGN.md sections 11 and 17).  A workgroup owns a VJ_TILE^2 tile of one sample; after k sweeps the
+// tile depends on u within k nodes of it, clipped to the image where the frozen ring ends the dependence.  Sweep s of k computes the tile grown by
+// k - s nodes, ping-ponging between two LDS buffers; the last one stores the tile.  The arithmetic of a point does not depend on k or on the tile,
+// so any split of n sweeps into launches gives the same bits.
+//   BWD == false: u -> out; fb holds dx^2 rhs.
+//   BWD == true:  u is d(out), out is d(u); fb holds 1 / (sum of the node's four face coefficients) on interior nodes - the adjoint's gather
+//                 needs the diagonal of its NEIGHBOURS, so rho is held one node further out than u.
+template <bool BWD>
+__global__ __launch_bounds__(VJ_THREADS) void vc_jacobi_kernel(int H, int W, int k, const float* __restrict__ rho, const float* __restrict__ u,
+                                                               const float* __restrict__ rhs, const float* __restrict__ dx, float* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int n = blockIdx.z, tid = threadIdx.x, g0 = k + (BWD ? 1 : 0);
+  const int ty0 = blockIdx.y * VJ_TILE, tx0 = blockIdx.x * VJ_TILE;
+  const int ty1 = min(ty0 + VJ_TILE, H), tx1 = min(tx0 + VJ_TILE, W);
+  // the LDS frame: the tile grown by g0 nodes, clipped to the image
+  const int ly0 = max(ty0 - g0, 0), ly1 = min(ty1 + g0, H), lx0 = max(tx0 - g0, 0), lx1 = min(tx1 + g0, W);
+  const int LW = lx1 - lx0;
+  const int S = (VJ_TILE + 2 * g0) * (VJ_TILE + 2 * g0);              // floats per buffer as the host sized them
+  float* src = lds;
+  float* dst = lds + S;
+  float* fb = lds + 2 * S;
+  float* rb = lds + 3 * S;
+  const int64_t img = (int64_t)n * H * W;
+  const float h = dx[n], h2 = h * h;
+  auto at = [&](int y, int x) { return (y - ly0) * LW + (x - lx0); };
+
+  vj_points(tid, ly0, lx0, ly1 - ly0, LW, [&](int y, int x) { rb[at(y, x)] = rho[img + (int64_t)y * W + x]; });
+  {
+    const int y0 = max(ty0 - k, 0), y1 = min(ty1 + k, H), x0 = max(tx0 - k, 0), x1 = min(tx1 + k, W);
+    vj_points(tid, y0, x0, y1 - y0, x1 - x0, [&](int y, int x) { src[at(y, x)] = u[img + (int64_t)y * W + x]; });
+    if (BWD) {
+      __syncthreads();
+      vj_points(tid, y0, x0, y1 - y0, x1 - x0, [&](int y, int x) {
+        const int c = at(y, x);
+        float v = 0.f;
+        if (y >= 1 && y < H - 1 && x >= 1 && x < W - 1) {
+          const float rc = rb[c];
+          v = 1.f / ((beta_face(rc, rb[c - LW]) + beta_face(rc, rb[c + LW])) + (beta_face(rc, rb[c - 1]) + beta_face(rc, rb[c + 1])));
+        }
+        fb[c] = v;
+      });
+    } else {
+      const int ry0 = max(ty0 - (k - 1), 0), ry1 = min(ty1 + (k - 1), H), rx0 = max(tx0 - (k - 1), 0), rx1 = min(tx1 + (k - 1), W);
+      vj_points(tid, ry0, rx0, ry1 - ry0, rx1 - rx0, [&](int y, int x) { fb[at(y, x)] = h2 * rhs[img + (int64_t)y * W + x]; });
+    }
+  }
+  __syncthreads();
+
+  auto point = [&](const float* in, int c, int y, int x) -> float {
+    const bool interior = y >= 1 && y < H - 1 && x >= 1 && x < W - 1;
+    const float rc = rb[c];
+    if (!BWD) {
+      if (!interior) return in[c];
+      const float b0 = beta_face(rc, rb[c - LW]), b1 = beta_face(rc, rb[c + LW]), b2 = beta_face(rc, rb[c - 1]), b3 = beta_face(rc, rb[c + 1]);
+      const float num = (b0 * in[c - LW] + b1 * in[c + LW]) + (b2 * in[c - 1] + b3 * in[c + 1]);
+      return (num - fb[c]) / ((b0 + b1) + (b2 + b3));
+    }
+    // adjoint: gather from the interior neighbours p, each of which read this node with weight beta_face / diagonal(p)
+    const bool in_x = x >= 1 && x < W - 1, in_y = y >= 1 && y < H - 1;
+    float acc = 0.f;
+    if (in_x) {
+      if (y - 1 >= 1 && y - 1 < H - 1) acc += beta_face(rc, rb[c - LW]) * (fb[c - LW] * in[c - LW]);
+      if (y + 1 >= 1 && y + 1 < H - 1) acc += beta_face(rc, rb[c + LW]) * (fb[c + LW] * in[c + LW]);
+    }
+    if (in_y) {
+      if (x - 1 >= 1 && x - 1 < W - 1) acc += beta_face(rc, rb[c - 1]) * (fb[c - 1] * in[c - 1]);
+      if (x + 1 >= 1 && x + 1 < W - 1) acc += beta_face(rc, rb[c + 1]) * (fb[c + 1] * in[c + 1]);
+    }
+    return (interior ? 0.f : in[c]) + acc;
+  };
+
+  for (int s = 1; s <= k; ++s) {
+    const int g = k - s;
+    const int y0 = max(ty0 - g, 0), y1 = min(ty1 + g, H), x0 = max(tx0 - g, 0), x1 = min(tx1 + g, W);
+    vj_points(tid, y0, x0, y1 - y0, x1 - x0, [&](int y, int x) {
+      const int c = at(y, x);
+      const float v = point(src, c, y, x);
+      if (s == k) out[img + (int64_t)y * W + x] = v;
+      else dst[c] = v;
+    });
+    __syncthreads();
+    float* t = src; src = dst; dst = t;
+  }
+}
+
+template <bool BWD>
+int vj_launch(pcnn_handle_s* h, int N, int H, int W, int k, const float* rho, const float* u, const float* rhs, const float* dx, float* out) {
+  const dim3 grid((unsigned)pcnn_cdiv(W, VJ_TILE), (unsigned)pcnn_cdiv(H, VJ_TILE), (unsigned)N);
+  const int e = VJ_TILE + 2 * (k + (BWD ? 1 : 0));
+  const size_t lds = (size_t)4 * e * e * sizeof(float);
+  PCNN_REQUIRE(h, lds <= 160u * 1024u, "pcnn_varcoef_jacobi: %zu bytes of LDS for %d fused sweeps", lds, k);
+  set_lds(vc_jacobi_kernel<BWD>, lds);
+  hipLaunchKernelGGL(vc_jacobi_kernel<BWD>, grid, dim3(VJ_THREADS), lds, h->stream, H, W, k, rho, u, rhs, dx, out);
+  return 0;
+}
+
+// n sweeps as ceil(n / k_max) launches of near-equal depth; intermediates alternate between `out` and one handle-owned scratch image so that the
+// last launch writes `out` and no launch reads what it writes (jacobi_chain of csrc/stencil.hip).
+template <bool BWD>
+int vj_chain(pcnn_handle_s* h, const char* name, int N, int H, int W, const float* rho, const float* u, const float* rhs, const float* dx, int n_sweeps,
+             float* out) {
+  const int launches = pcnn_cdiv(n_sweeps, VJ_HALO_MAX);
+  float* tmp = nullptr;
+  if (launches > 1) {
+    if (pcnn_reserve(h, h->aux_ws, (size_t)N * H * W * sizeof(float), 0, name)) return 1;
+    tmp = static_cast<float*>(h->aux_ws.p);
+  }
+  const float* in = u;
+  int left = n_sweeps;
+  for (int l = 0; l < launches; ++l) {
+    const int k = pcnn_cdiv(left, launches - l);
+    float* to = ((launches - 1 - l) % 2 == 0) ? out : tmp;
+    if (int rc = vj_launch<BWD>(h, N, H, W, k, rho, in, rhs, dx, to)) return rc;
+    in = to;
+    left -= k;
+  }
+  PCNN_CHECK_LAUNCH(h, name);
+  return 0;
+}
+
+__global__ void assemble_density_input_kernel(int N, int H, int W, const float* __restrict__ stack, int use_pos, float* __restrict__ out, int ldo) {
+  const int64_t hw = (int64_t)H * W, total = (int64_t)N * hw;
+  const float pi = 3.14159265358979323846f;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t n = i / hw, p = i - n * hw;
+    const int x = p % W; const int y = p / W;
+    out[i * ldo] = stack[2 * n * hw + p];
+    out[i * ldo + 1] = stack[(2 * n + 1) * hw + p];
+    if (use_pos) {                                       // the two channels of pcnn_assemble_input, same arithmetic
+      const float ly = H > 1 ? (float)y * (1.0f / (float)(H - 1)) : 0.f;
+      const float lx = W > 1 ? (float)x * (1.0f / (float)(W - 1)) : 0.f;
+      out[i * ldo + 2] = cosf(pi * ly);
+      out[i * ldo + 3] = cosf(pi * lx);
+    }
+  }
+}
+
+bool vt_shape_ok(int N, int H, int W) { return N >= 1 && N <= 65535 && H >= 3 && W >= 3 && pcnn_cdiv(H, PT_ROWS) <= 65535; }
+
+}  // namespace
+
+extern "C" int pcnn_varcoef_pi_loss_partials(pcnn_handle h, int N, int H, int W, const float* pred, const float* rho, const float* rhs, const float* dx,
+                                             float* out) {
+  PCNN_REQUIRE(h, h && pred && rho && rhs && dx && out, "pcnn_varcoef_pi_loss_partials: null argument");
+  PCNN_REQUIRE(h, vt_shape_ok(N, H, W), "pcnn_varcoef_pi_loss_partials: batch %d of %d x %d grids unsupported", N, H, W);
+  const dim3 grid(pcnn_cdiv(W - 2, PT_COLS), pcnn_cdiv(H - 2, PT_ROWS), N);
+  const int tiles = (int)(grid.x * grid.y);
+  if (int rc = pcnn_reserve(h, h->aux_ws, (size_t)N * tiles * sizeof(float), 0, "pcnn_varcoef_pi_loss_partials")) return rc;
+  float* part = static_cast<float*>(h->aux_ws.p);
+  hipLaunchKernelGGL(vc_pi_partials_kernel, grid, dim3(PT_THREADS), 0, h->stream, H, W, tiles, pred, rho, rhs, dx, part);
+  hipLaunchKernelGGL(vc_pi_reduce_kernel, dim3(N), dim3(RED_THREADS), 0, h->stream, tiles, part, out);
+  PCNN_CHECK_LAUNCH(h, "pcnn_varcoef_pi_loss_partials");
+  return 0;
+}
+
+extern "C" int pcnn_varcoef_pi_loss_bwd(pcnn_handle h, int N, int H, int W, const float* pred, const float* rho, const float* rhs, const float* dx,
+                                        const float* coef, float* dpred) {
+  PCNN_REQUIRE(h, h && pred && rho && rhs && dx && coef && dpred, "pcnn_varcoef_pi_loss_bwd: null argument");
+  PCNN_REQUIRE(h, vt_shape_ok(N, H, W), "pcnn_varcoef_pi_loss_bwd: batch %d of %d x %d grids unsupported", N, H, W);
+  PCNN_REQUIRE(h, dpred != pred && dpred != rho && dpred != rhs, "pcnn_varcoef_pi_loss_bwd: dpred must not alias an input");
+  const dim3 grid(pcnn_cdiv(W, PT_COLS), pcnn_cdiv(H, PT_ROWS), N);
+  hipLaunchKernelGGL(vc_pi_bwd_kernel, grid, dim3(PT_THREADS), 0, h->stream, H, W, pred, rho, rhs, dx, coef, dpred);
+  PCNN_CHECK_LAUNCH(h, "pcnn_varcoef_pi_loss_bwd");
+  return 0;
+}
+
+extern "C" int pcnn_varcoef_jacobi_max_sweeps(void) { return VJ_HALO_MAX; }
+
+extern "C" int pcnn_varcoef_jacobi_fwd(pcnn_handle h, int N, int H, int W, const float* rho, const float* u, const float* rhs, const float* dx, int n_sweeps,
+                                       float* out) {
+  PCNN_REQUIRE(h, h && rho && u && rhs && dx && out, "pcnn_varcoef_jacobi_fwd: null argument");
+  PCNN_REQUIRE(h, vt_shape_ok(N, H, W) && n_sweeps >= 1, "pcnn_varcoef_jacobi_fwd: needs N in 1..65535, H, W >= 3, n_sweeps >= 1 (got %d, %d x %d, %d sweeps)", N, H,
+               W, n_sweeps);
+  PCNN_REQUIRE(h, out != u && out != rhs && out != rho, "pcnn_varcoef_jacobi_fwd: out must not alias an input");
+  return vj_chain<false>(h, "pcnn_varcoef_jacobi_fwd", N, H, W, rho, u, rhs, dx, n_sweeps, out);
+}
+
+extern "C" int pcnn_varcoef_jacobi_bwd(pcnn_handle h, int N, int H, int W, const float* rho, const float* dx, const float* dout, int n_sweeps, float* du) {
+  PCNN_REQUIRE(h, h && rho && dx && dout && du, "pcnn_varcoef_jacobi_bwd: null argument");
+  PCNN_REQUIRE(h, vt_shape_ok(N, H, W) && n_sweeps >= 1, "pcnn_varcoef_jacobi_bwd: needs N in 1..65535, H, W >= 3, n_sweeps >= 1 (got %d, %d x %d, %d sweeps)", N, H,
+               W, n_sweeps);
+  PCNN_REQUIRE(h, du != dout && du != rho, "pcnn_varcoef_jacobi_bwd: du must not alias an input");
+  return vj_chain<true>(h, "pcnn_varcoef_jacobi_bwd", N, H, W, rho, dout, nullptr, dx, n_sweeps, du);
+}
+
+extern "C" int pcnn_assemble_density_input(pcnn_handle h, int N, int H, int W, const float* stack, int use_pos, float* out, int ldo) {
+  PCNN_REQUIRE(h, h && stack && out && N >= 1 && H >= 1 && W >= 1 && ldo >= (use_pos ? 4 : 2), "pcnn_assemble_density_input: bad argument");
+  int64_t blocks = pcnn_cdiv64((int64_t)N * H * W, 256);
+  if (blocks > 16384) blocks = 16384;
+  hipLaunchKernelGGL(assemble_density_input_kernel, dim3((unsigned)blocks), dim3(256), 0, h->stream, N, H, W, stack, use_pos, out, ldo);
+  PCNN_CHECK_LAUNCH(h, "pcnn_assemble_density_input");
+  return 0;
+}

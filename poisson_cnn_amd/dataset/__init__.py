@@ -587,7 +587,8 @@ class variable_density_dataset_generator(numerical_dataset_generator):
     """Random smooth right-hand side F and density rho -> the variable-density solve: generate_dataset of the reference's
     dataset/generators/variable_density, which returns (soln, stack([F, rho], axis=1)).  Keras order here (return_keras_style):
     ([stack([rhs, rho], axis=1), dx], soln), with the four boundary arrays (left, top, right, bottom, each (N,1,len)) between the stack and dx
-    when boundaries = 'random'; otherwise the reference's pair (soln, stack).  Feeding a network with the two-channel input is out of scope.
+    when boundaries = 'random'; otherwise the reference's pair (soln, stack).  Homogeneous_Poisson_NN_Legacy(density_input=True) reads the
+    two-channel input (boundaries = 'zero'; train.py --dataset_type variable_density).
 
     rho = lo + (hi - lo) |g| / max|g| with g a smooth random field (the bicubic up-sampling of random control points the numerical generator
     uses) and (lo, hi) = density_range: the reference takes 1e-7 + |g|, whose ratio max/min is unbounded; density_range bounds the condition
@@ -596,8 +597,9 @@ class variable_density_dataset_generator(numerical_dataset_generator):
 
     def __init__(self, batch_size=1, batches_per_epoch=1, output_shape=None, random_output_shape_range=((64, 85), (64, 85)), density_range=(1.0, 10.0),
                  rhs_smoothness_range=(5, 20), density_smoothness_range=(5, 20), boundaries='zero', random_dx_range=(0.005, 0.05), rhs_max_magnitude=1.0,
-                 boundary_max_magnitude=1.0, tol=1e-10, max_iterations=500, seed=0, device=None, return_keras_style=True):
-        super().__init__(batch_size=batch_size, batches_per_epoch=batches_per_epoch, return_keras_style=return_keras_style, seed=seed, device=device)
+                 boundary_max_magnitude=1.0, tol=1e-10, max_iterations=500, seed=0, device=None, return_keras_style=True, shard=None):
+        super().__init__(batch_size=batch_size, batches_per_epoch=batches_per_epoch, return_keras_style=return_keras_style, seed=seed, device=device,
+                         shard=shard)
         lo, hi = float(density_range[0]), float(density_range[1])
         if not 0.0 < lo <= hi:
             raise ValueError('density_range = (lo, hi) needs 0 < lo <= hi, got %r' % (density_range,))

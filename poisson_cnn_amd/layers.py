@@ -844,3 +844,31 @@ class JacobiIterationLayer:
         if self.n < 1:
             return dout
         return ops.jacobi_fused_bwd(dout, self.coef, self.stencil_sizes, self.n, self.neumann_mask or 0)
+
+
+class VariableDensityJacobiLayer:
+    """n_iterations Jacobi sweeps of the variable-density problem div((1/rho) grad u) = rhs in the flux form of DESIGN.md sections 16 and 17:
+    u' = (sum over the four faces of beta_face * neighbour - dx^2 rhs) / (sum of beta_face) on interior nodes, beta_face = 2 / (rho_a + rho_b), the
+    ring frozen.  With rho = c everywhere this is JacobiIterationLayer's ([3,3],[2,2]) sweep with rhs replaced by c * rhs.  Up to
+    ops.varcoef_jacobi_k_max() sweeps run per launch (csrc/varcoef_train.hip).  backward is the adjoint w.r.t. the guess; rho and rhs are data.
+    Dirichlet (frozen) edges and one spacing per sample only."""
+
+    def __init__(self, n_iterations=5):
+        self.n = int(n_iterations)
+        self.saved = None
+
+    def forward(self, guess, rhs, rho, dx, training=True):
+        """guess, rhs, rho (N,H,W,1); dx (N,) or (N,1)."""
+        if self.n < 1:
+            return guess
+        dx = dx.reshape(-1).contiguous()
+        rho = rho.contiguous()
+        self.saved = (rho, dx) if training else None
+        return ops.varcoef_jacobi(guess.contiguous(), rho, rhs.contiguous(), dx, self.n)
+
+    def backward(self, dout):
+        if self.n < 1:
+            return dout
+        rho, dx = self.saved
+        self.saved = None
+        return ops.varcoef_jacobi_bwd(dout.contiguous(), rho, dx, self.n)

@@ -102,10 +102,13 @@ class loss_wrapper:
         self.integral_loss = integral_loss(ndims=ndims, reduce_results=True, **icfg)
         self.lp = float(self.integral_loss.Lp_norm_power)      # exponent of the integral term (integral_loss.py:153) and of its peak scaling (:68)
         pcfg = {k: v for k, v in physics_informed_loss_config.items() if k not in ('ndims', 'data_format')}
-        self.pi_stencil = build_fd_coefficients(pcfg.get('stencil_sizes', 5), pcfg.get('orders', 2), ndims)
+        self._init_physics_informed(pcfg, ndims)
         self.pi_normalize = bool(pcfg.get('normalize', False))
-        self.pi_domain_norm = bool(pcfg.get('inputs_have_max_domain_size_squared_normalization', False))
         self._last = None
+
+    def _init_physics_informed(self, pcfg, ndims):
+        self.pi_stencil = build_fd_coefficients(pcfg.get('stencil_sizes', 5), pcfg.get('orders', 2), ndims)
+        self.pi_domain_norm = bool(pcfg.get('inputs_have_max_domain_size_squared_normalization', False))
 
     # -- helpers
     def _pi_kernels(self, dx, H, W):
@@ -129,15 +132,11 @@ class loss_wrapper:
         extra = None
         pi = None
         if self.physics_informed_loss_weight != 0.0:
-            rhs = rhs.to(device=dev, dtype=torch.float32).contiguous()
-            kern = self._pi_kernels(dx.to(dev), H, W)
-            sy, sx = kern.shape[-2], kern.shape[-1]
-            sums = ops.pi_loss_partials(y_pred, rhs, kern)
-            coef = torch.full((N,), self.physics_informed_loss_weight / float(N * (H - 2 * (sy // 2)) * (W - 2 * (sx // 2))), device=dev)
+            sums, points, peak, pi = self._pi_partials(y_pred, rhs, dx, H, W)
+            coef = torch.full((N,), self.physics_informed_loss_weight / float(N * points), device=dev)
             if self.pi_normalize:
-                coef = coef / rhs.abs().amax(dim=(1, 2, 3)) ** 2
+                coef = coef / peak() ** 2
             extra = (coef * sums).sum().reshape(1)
-            pi = (rhs, kern, coef)
         out = ops.empty((3 * N + 2,), dev)
         loss, mse = out[0:1], out[1:2]
         c_mae, c_mse, c_int = out[2:2 + N], out[2 + N:2 + 2 * N], out[2 + 2 * N:2 + 3 * N]
@@ -149,8 +148,19 @@ class loss_wrapper:
             return loss[0], None
         dpred = ops.loss_bwd(y_pred, y_true, G, c_mae, c_mse, c_int, lp_power=self.lp)
         if pi is not None:
-            ops.pi_loss_bwd(y_pred, pi[0], pi[1], pi[2], dpred)
+            self._pi_backward(y_pred, pi, coef, dpred)
         return loss[0], dpred
+
+    def _pi_partials(self, y_pred, rhs, dx, H, W):
+        """The physics-informed term of one batch -> (per-sample sums of the squared residual, residual points per sample, a callable giving
+        max|rhs| per sample, what _pi_backward needs)."""
+        rhs = rhs.to(device=y_pred.device, dtype=torch.float32).contiguous()
+        kern = self._pi_kernels(dx.to(y_pred.device), H, W)
+        sy, sx = kern.shape[-2], kern.shape[-1]
+        return ops.pi_loss_partials(y_pred, rhs, kern), (H - 2 * (sy // 2)) * (W - 2 * (sx // 2)), lambda: rhs.abs().amax(dim=(1, 2, 3)), (rhs, kern)
+
+    def _pi_backward(self, y_pred, pi, coef, dpred):
+        ops.pi_loss_bwd(y_pred, pi[0], pi[1], coef, dpred)
 
     def __call__(self, y_true, y_pred, rhs, dx):
         if self.data_format == 'channels_last':
@@ -169,6 +179,58 @@ class loss_wrapper:
     def mse_metric(self, y_true, y_pred):
         """tf.reduce_mean((pred - ground_truth)**2) of the last evaluated (micro-)batch (train_step :291)."""
         return self._last['mse'][0]
+
+
+class variable_density_loss_wrapper(loss_wrapper):
+    """loss_wrapper for the variable-density problem div((1/rho) grad u) = f.  Same constructor; `rhs` is the (N,2,H,W)
+    stack [rhs, rho] of dataset.variable_density_dataset_generator.  The MAE, MSE and integral terms are loss_wrapper's.  The physics-informed
+    term is the flux-form residual of the solver's own discretisation (dataset.variable_density_poisson_solve),
+        weight / (N (H-2)(W-2)) * sum over samples and interior nodes of (L_rho pred - rhs)^2,     each sample divided by max|rhs|^2 under `normalize`,
+    with its gradient w.r.t. the prediction on every node; rho gets none.  The flux form exists for the 5-point stencil only: `stencil_sizes` and
+    `orders` are accepted at 3 and 2, `inputs_have_max_domain_size_squared_normalization` at False.  One spacing per sample: dx (N,1), or (N,2) with
+    equal columns.  channels_first only."""
+
+    def _init_physics_informed(self, pcfg, ndims):
+        if self.data_format != 'channels_first':
+            raise NotImplementedError('variable_density_loss_wrapper: data_format channels_first only')
+        for key, want in (('stencil_sizes', 3), ('orders', 2)):
+            if key in pcfg and any(int(v) != want for v in np.atleast_1d(pcfg[key])):
+                raise NotImplementedError('variable_density_loss_wrapper: physics_informed_loss_config[%r] = %r - the flux-form residual is the 5-point '
+                                          'one (%s = %d)' % (key, pcfg[key], key, want))
+        if pcfg.get('inputs_have_max_domain_size_squared_normalization', False):
+            raise NotImplementedError("variable_density_loss_wrapper: physics_informed_loss_config['inputs_have_max_domain_size_squared_normalization'] is not "
+                                      'implemented for the flux-form residual')
+
+    @staticmethod
+    def _check_stack(stack, like):
+        if stack is None or stack.dim() != 4 or stack.shape[1] != 2 or tuple(stack.shape[2:]) != tuple(like.shape[2:]) or stack.shape[0] != like.shape[0]:
+            raise ValueError('variable_density_loss_wrapper: rhs must be the (N,2,H,W) stack [rhs, rho] matching the prediction %s, got %s'
+                             % (tuple(like.shape), None if stack is None else tuple(stack.shape)))
+
+    @staticmethod
+    def _spacing(dx, N):
+        """dx (N,), (N,1) or (N,2) -> (N,) on dx's device; differing columns are anisotropic spacing, which the solver does not do either."""
+        dx = dx.to(torch.float32).reshape(N, -1)
+        if dx.shape[1] == 2:
+            if not bool((dx[:, 0] == dx[:, 1]).all()):
+                raise NotImplementedError('variable_density_loss_wrapper: anisotropic spacing (dy != dx) is not supported')
+        elif dx.shape[1] != 1:
+            raise ValueError('variable_density_loss_wrapper: dx must be (N,1) or (N,2), got %s' % (tuple(dx.shape),))
+        return dx[:, 0].contiguous()
+
+    def _evaluate(self, y_true, y_pred, rhs, dx, want_grad):
+        if self.physics_informed_loss_weight != 0.0:
+            self._check_stack(rhs, y_pred)                   # refuse a one-channel rhs before any kernel runs (no copy is made here)
+        return super()._evaluate(y_true, y_pred, rhs, dx, want_grad)
+
+    def _pi_partials(self, y_pred, rhs, dx, H, W):
+        stack = rhs.to(device=y_pred.device, dtype=torch.float32)
+        f, rho = stack[:, 0].contiguous(), stack[:, 1].contiguous()
+        h = self._spacing(dx.to(y_pred.device), y_pred.shape[0])
+        return ops.varcoef_pi_loss_partials(y_pred, rho, f, h), (H - 2) * (W - 2), lambda: f.abs().amax(dim=(1, 2)), (f, rho, h)
+
+    def _pi_backward(self, y_pred, pi, coef, dpred):
+        ops.varcoef_pi_loss_bwd(y_pred, pi[1], pi[0], pi[2], coef.contiguous(), dpred)
 
 
 c_int_ = c_int

@@ -548,14 +548,20 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
     def __init__(self, data_format='channels_first', final_convolutions_config=None, pre_bottleneck_convolutions_config=None,
                  bottleneck_deconv_config=None, bottleneck_multilinear_config=None, input_normalization=None, output_scaling=None,
                  use_batchnorm=False, postsmoother_iterations=5, use_scaling=False, use_positional_embeddings=True, scaling_config=None,
-                 gradient_accumulation_steps=None, bc_type='dirichlet', device=None, seed=0, batchnorm_training=False, smoother_boundaries='frozen'):
+                 gradient_accumulation_steps=None, bc_type='dirichlet', device=None, seed=0, batchnorm_training=False, smoother_boundaries='frozen',
+                 density_input=False):
         """bc_type: 'dirichlet' or 'neumann' for all four edges (the reference), or - an extension - a dict 'left' | 'right' | 'bottom' | 'top' ->
         'dirichlet' | 'neumann' with the dataset's edge names (left: y = 0, right: y = H-1, bottom: x = 0, top: x = W-1 of the (N,1,H,W) output; a missing
         edge is Dirichlet, at a corner a Dirichlet edge wins).  A Neumann edge is enforced as the reference's SYMMETRIC ring does, to first order:
         u_0 = u_1.
         smoother_boundaries: 'frozen' - the post-smoother keeps the ring it is given, as the reference's does, so its sweeps move the interior away
         from a Neumann edge's mirror values; 'enforce' - the smoother re-imposes the model's Neumann edges after every sweep
-        (layers.JacobiIterationLayer(boundary_types=...)); with no Neumann edge there is nothing to enforce and the two are the same."""
+        (layers.JacobiIterationLayer(boundary_types=...)); with no Neumann edge there is nothing to enforce and the two are the same.
+        density_input (extension): the model of the variable-density problem div((1/rho) grad u) = f.  call takes
+        [stack (N,2,H,W), dx] with the stack [rhs, rho] of dataset.variable_density_dataset_generator; the first convolution sees [rhs, rho] and then
+        the positional channels; Scaling reads the rhs channel; the post-smoother is layers.VariableDensityJacobiLayer; the loss to compile is
+        losses.variable_density_loss_wrapper.  Dirichlet edges only, as the solver.  evaluate() / predict(return_stats=True) report the error
+        statistics; the residual columns of ops.error_stats are the constant-coefficient residual and are left at 0 for such a model."""
         if data_format not in ('channels_first', 'channels_last'):
             raise ValueError('data_format must be channels_first or channels_last')
         if pre_bottleneck_convolutions_config is None:
@@ -573,6 +579,12 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
             flags = (bc_type.lower() == 'neumann',) * 4
         if smoother_boundaries not in ('frozen', 'enforce'):
             raise ValueError("smoother_boundaries can only be 'frozen' or 'enforce'.")
+        self.density_input = bool(density_input)
+        if self.density_input and (isinstance(bc_type, dict) or any(flags)):
+            raise NotImplementedError('density_input=True needs bc_type "dirichlet": the variable-density solver, loss and smoother have Dirichlet edges '
+                                      'only (got bc_type %r)' % (bc_type,))
+        if self.density_input and data_format != 'channels_first':
+            raise NotImplementedError('density_input=True: the two-channel stack is channels_first (N,2,H,W) only')
         self._init_device(device, _CPU_NOTE_RAISES)
         self.ndims = 2
         self.data_format = data_format
@@ -595,7 +607,7 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
         pre = copy.deepcopy(pre_bottleneck_convolutions_config)
         mode, val = pre.pop('padding_mode', 'CONSTANT'), pre.pop('constant_padding_value', 0.0)
         self.pre = []
-        cin = 3 if use_positional_embeddings else 1
+        cin = (2 if self.density_input else 1) + (2 if use_positional_embeddings else 0)
         for k in range(len(pre['filters'])):
             a = get_init_arguments_from_config(pre, k, ['filters', 'kernel_sizes'], ['filters', 'kernel_size'])
             self.pre.append(L.ConvUnit(S, C, 'pre/conv%d' % k, a['kernel_size'], cin, a['filters'], padding_mode=mode, pad_value=val,
@@ -653,7 +665,10 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
         enforce = None
         if smoother_boundaries == 'enforce' and self.neumann_mask:
             enforce = {e: 'neumann' if f else 'dirichlet' for e, f in zip(('left', 'right', 'bottom', 'top'), flags)}
-        self.postsmoother = L.JacobiIterationLayer(postsmoother_iterations, boundary_types=enforce) if postsmoother_iterations > 0 else None
+        if self.density_input:
+            self.postsmoother = L.VariableDensityJacobiLayer(postsmoother_iterations) if postsmoother_iterations > 0 else None
+        else:
+            self.postsmoother = L.JacobiIterationLayer(postsmoother_iterations, boundary_types=enforce) if postsmoother_iterations > 0 else None
         self.scaling = L.Scaling(S, C, 'scaling', **scaling_config) if use_scaling else None
         S.finalize(self.device)
         S.initialize(seed)
@@ -676,18 +691,27 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
         return pyr
 
     def call(self, inp, training=False):
-        """reference :183-257.  inp = [rhs (N,1,H,W), dx (N,1)]; returns (N,1,H,W) (torch CUDA tensor)."""
+        """reference :183-257.  inp = [rhs (N,1,H,W), dx (N,1)]; returns (N,1,H,W) (torch CUDA tensor).  density_input: inp = [stack (N,2,H,W), dx],
+        the stack [rhs, rho]."""
         rhs, dx = inp
         rhs = _as_device(rhs, self.device)
         dx = _as_device(dx, self.device)
-        if rhs.dim() != 4 or rhs.shape[1] != 1:
+        if self.density_input:
+            if rhs.dim() != 4 or rhs.shape[1] != 2:
+                raise ValueError('a density_input model takes the stack [rhs, rho] of shape (N,2,H,W)')
+        elif rhs.dim() != 4 or rhs.shape[1] != 1:
             raise ValueError('rhs must have shape (N,1,H,W)')
-        dx = _dx_column(dx)
+        dx = self._spacing_column(dx)
         N, _, H, W = rhs.shape
         S = self.store
         S.refresh_bn()
-        rhs_hw = rhs.view(N, H, W)
-        x = ops.assemble_input(rhs_hw, self.use_positional_embeddings)
+        if self.density_input:
+            stack = rhs.contiguous()
+            rhs_hw, rho_hw = stack[:, 0].contiguous(), stack[:, 1].contiguous()      # the one-channel fields Scaling and the smoother read
+            x = ops.assemble_density_input(stack, self.use_positional_embeddings)
+        else:
+            rhs_hw = rhs.view(N, H, W)
+            x = ops.assemble_input(rhs_hw, self.use_positional_embeddings)
         # dense input [dx, Lx, Ly] (:193,:202): tiny (N,3) host-side assembly
         dense_inp = torch.cat([dx, dx * float(H - 1), dx * float(W - 1)], 1).contiguous()
         hint = None                                               # max|x| travels with the tensor from layer to layer (weight-gradient scaling)
@@ -771,7 +795,9 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
         if self.scaling is not None:
             x = self.scaling.forward(x, rhs_hw.view(N, H, W, 1), training=training)
         x = ops.bc_ring_edges_fwd(x, self.neumann_mask) if self.per_edge_bc else ops.bc_ring_fwd(x, self.neumann)     # :251
-        if self.postsmoother is not None:
+        if self.postsmoother is not None and self.density_input:
+            x = self.postsmoother.forward(x, rhs_hw.view(N, H, W, 1), rho_hw.view(N, H, W, 1), dx, training=training)
+        elif self.postsmoother is not None:
             x = self.postsmoother.forward(x, rhs_hw.view(N, H, W, 1), _dx_pair(dx), training=training)
         return x.view(N, 1, H, W)
 
@@ -860,21 +886,36 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
     # ------------------------------------------------------------------ training (reference :259-296)
     def _loss_and_grads(self, rhs, dx, y_true):
         pred = self.call([rhs, dx], training=True)
-        loss, dpred = self.loss_fn.value_and_grad(y_true, pred, rhs, _dx_pair(dx))
+        loss, dpred = self.loss_fn.value_and_grad(y_true, pred, rhs, dx if self.density_input else _dx_pair(dx))   # (one spacing per sample: no column check)
         self.backward(dpred)
         return loss, pred
+
+    def _spacing_column(self, dx):
+        """_dx_column; a density_input model refuses columns that differ (the first one alone would be used, and the loss would never see the other)."""
+        if self.density_input:
+            cols = dx.reshape(dx.shape[0], -1)
+            if cols.shape[1] > 1 and not bool((cols == cols[:, :1]).all()):
+                raise NotImplementedError('density_input=True: anisotropic spacing (dx columns that differ) is not supported - pass one spacing per '
+                                          'sample, dx of shape (N,1)')
+        return _dx_column(dx)
+
+    def _error_stats(self, pred, y_true, rhs, dx):
+        """density_input: `rhs` is the [rhs, rho] stack and the residual columns of ops.error_stats are the constant-coefficient residual - they stay 0."""
+        return _ModelBase._error_stats(pred, y_true, None if self.density_input else rhs, dx)
 
     def _dummy_batch(self, shape):
         N, H, W = shape
         g = torch.Generator(device='cpu').manual_seed(0)
         rhs = (torch.rand((N, 1, H, W), generator=g) * 2 - 1).to(self.device)
+        if self.density_input:                                    # [rhs, rho] with rho in [1, 2]
+            rhs = torch.cat([rhs, (torch.rand((N, 1, H, W), generator=g) + 1).to(self.device)], 1)
         return (rhs, torch.full((N, 1), 0.02, device=self.device)), (torch.rand((N, 1, H, W), generator=g) * 0.1).to(self.device)
 
     def _forward_backward(self, data):
         """forward, loss and backward of one batch (with the reference's gradient accumulation, :275-289): store.flat_g holds the gradient."""
         (rhs, dx), y_true = data
         rhs, dx, y_true = _as_device(rhs, self.device), _as_device(dx, self.device), _as_device(y_true, self.device)
-        dx = _dx_column(dx)
+        dx = self._spacing_column(dx)
         S = self.store
         if self.gradient_accumulation_steps is None:
             loss, pred = self._loss_and_grads(rhs, dx, y_true)
@@ -1108,6 +1149,9 @@ class Poisson_CNN_Legacy(_ModelBase):
         if jacobi_iterations > 0:
             # the reference constructor dereferences an unimported module name here (Poisson_CNN_Legacy.py:11) and raises NameError
             raise NotImplementedError('Poisson_CNN_Legacy: jacobi_iterations > 0 is unreachable in the reference (NameError at construction)')
+        if getattr(hpnn, 'density_input', False):
+            raise NotImplementedError('Poisson_CNN_Legacy around a density_input model is not built: the boundary network solves the constant-coefficient '
+                                      'problem - construct the Homogeneous_Poisson_NN_Legacy with density_input=False')
         self.hpnn, self.dbcnn = hpnn, dbcnn
         self._init_device(hpnn.device)
         self.data_format = getattr(hpnn, 'data_format', 'channels_first')

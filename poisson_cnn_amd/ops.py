@@ -1074,6 +1074,86 @@ def pi_loss_bwd(pred, rhs, kern, coef, dpred):
     return dpred
 
 
+# ----------------------------------------------------------------------------- variable-density training operators (csrc/varcoef_train.hip)
+def _varcoef_fields(who, fields, dx):
+    """Checks the one-channel fields of a variable-density call - name -> (N,H,W), (N,1,H,W) or (N,H,W,1) CUDA float32 tensor, all of one shape -
+    and dx (N,) or (N,1) -> (N, H, W, contiguous fields in order, contiguous dx (N,))."""
+    first = next(iter(fields.values()))
+    shape = [int(s) for s in first.shape]
+    if len(shape) == 4:
+        if shape[1] != 1 and shape[3] != 1:
+            raise ValueError('%s takes one-channel fields, got shape %s' % (who, tuple(first.shape)))
+        shape = [shape[0]] + (shape[2:] if shape[1] == 1 else shape[1:3])
+    if len(shape) != 3:
+        raise ValueError('%s: fields must be (N,H,W), (N,1,H,W) or (N,H,W,1), got %s' % (who, tuple(first.shape)))
+    N, H, W = shape
+    if H < 3 or W < 3:
+        raise ValueError('%s: the grid needs at least 3 points per axis, got %d x %d' % (who, H, W))
+    out = []
+    for name, t in fields.items():
+        if t.dtype != torch.float32 or not t.is_cuda or t.numel() != N * H * W or t.shape[0] != N:
+            raise ValueError('%s: %s must be a CUDA float32 tensor with the %d x %d x %d points of %s' % (who, name, N, H, W, next(iter(fields))))
+        if not t.is_contiguous():
+            raise ValueError('%s: %s must be contiguous' % (who, name))
+        out.append(t)
+    if dx.dtype != torch.float32 or not dx.is_cuda or dx.numel() != N:
+        raise ValueError('%s: dx must be a CUDA float32 tensor of one spacing per sample (%d values), got shape %s' % (who, N, tuple(dx.shape)))
+    return N, H, W, out, dx.contiguous()
+
+
+def varcoef_pi_loss_partials(pred, rho, rhs, dx):
+    """(N,) per-sample sums over the interior of (L_rho pred - rhs)^2, L_rho the flux-form div((1/rho) grad .) of DESIGN.md section 16/17."""
+    N, H, W, (pred, rho, rhs), dx = _varcoef_fields('varcoef_pi_loss_partials', {'pred': pred, 'rho': rho, 'rhs': rhs}, dx)
+    out = empty((N,), pred.device)
+    handle().call('pcnn_varcoef_pi_loss_partials', c_int(N), c_int(H), c_int(W), _p(pred), _p(rho), _p(rhs), _p(dx), _p(out))
+    return out
+
+
+def varcoef_pi_loss_bwd(pred, rho, rhs, dx, coef, dpred):
+    """dpred += coef[n] * d(varcoef_pi_loss_partials[n]) / d(pred), on all nodes (the ring included); returns dpred."""
+    N, H, W, (pred, rho, rhs, dpred), dx = _varcoef_fields('varcoef_pi_loss_bwd', {'pred': pred, 'rho': rho, 'rhs': rhs, 'dpred': dpred}, dx)
+    if coef.dtype != torch.float32 or not coef.is_cuda or tuple(coef.shape) != (N,) or not coef.is_contiguous():
+        raise ValueError('varcoef_pi_loss_bwd: coef must be a contiguous CUDA float32 (%d,) tensor' % N)
+    handle().call('pcnn_varcoef_pi_loss_bwd', c_int(N), c_int(H), c_int(W), _p(pred), _p(rho), _p(rhs), _p(dx), _p(coef), _p(dpred))
+    return dpred
+
+
+def varcoef_jacobi_k_max():
+    """The most sweeps one launch of the variable-density smoother fuses; more sweeps chain launches."""
+    return int(_lib.load().pcnn_varcoef_jacobi_max_sweeps())
+
+
+def varcoef_jacobi(u, rho, rhs, dx, n_sweeps):
+    """n_sweeps Jacobi sweeps of L_rho u = rhs: u' = (sum of beta_face * neighbour - dx^2 rhs) / (sum of beta_face) on interior nodes, the ring frozen."""
+    N, H, W, (u, rho, rhs), dx = _varcoef_fields('varcoef_jacobi', {'u': u, 'rho': rho, 'rhs': rhs}, dx)
+    if int(n_sweeps) < 1:
+        raise ValueError('varcoef_jacobi: n_sweeps must be at least 1, got %r' % (n_sweeps,))
+    out = torch.empty_like(u)
+    handle().call('pcnn_varcoef_jacobi_fwd', c_int(N), c_int(H), c_int(W), _p(rho), _p(u), _p(rhs), _p(dx), c_int(int(n_sweeps)), _p(out))
+    return out
+
+
+def varcoef_jacobi_bwd(dout, rho, dx, n_sweeps):
+    """The adjoint of varcoef_jacobi w.r.t. u (rho and rhs are data)."""
+    N, H, W, (dout, rho), dx = _varcoef_fields('varcoef_jacobi_bwd', {'dout': dout, 'rho': rho}, dx)
+    if int(n_sweeps) < 1:
+        raise ValueError('varcoef_jacobi_bwd: n_sweeps must be at least 1, got %r' % (n_sweeps,))
+    du = torch.empty_like(dout)
+    handle().call('pcnn_varcoef_jacobi_bwd', c_int(N), c_int(H), c_int(W), _p(rho), _p(dx), _p(dout), c_int(int(n_sweeps)), _p(du))
+    return du
+
+
+def assemble_density_input(stack, use_pos=True):
+    """The generator's (N,2,H,W) stack [rhs, rho] -> NHWC [rhs | rho | cos(pi y) | cos(pi x)] (the last two with use_pos)."""
+    if stack.dim() != 4 or stack.shape[1] != 2 or stack.dtype != torch.float32 or not stack.is_cuda or not stack.is_contiguous():
+        raise ValueError('assemble_density_input: needs a contiguous CUDA float32 (N,2,H,W) stack, got %s' % (tuple(stack.shape),))
+    N, _, H, W = stack.shape
+    C = 4 if use_pos else 2
+    out = empty((N, H, W, C), stack.device)
+    handle().call('pcnn_assemble_density_input', c_int(N), c_int(H), c_int(W), _p(stack), c_int(1 if use_pos else 0), _p(out), c_int(C))
+    return out
+
+
 ERROR_STATS = ('sum_abs_e', 'sum_e2', 'max_abs_e', 'sum_t2', 'max_abs_t', 'sum_r2', 'max_abs_r', 'sum_f2')       # the columns of error_stats
 
 

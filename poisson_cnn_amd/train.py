@@ -1,10 +1,12 @@
 """Optimizers, callbacks and the training entry point (drop-in for poisson_CNN/train/hpnn_legacy_train.py and train/utils.py).
 
-python -m poisson_cnn_amd.train config.json [--checkpoint_dir D] [--continue_from_checkpoint D] [--dataset_type analytical|analytical_mixed|numerical]
+python -m poisson_cnn_amd.train config.json [--checkpoint_dir D] [--continue_from_checkpoint D] [--dataset_type analytical|analytical_mixed|numerical|variable_density]
                                             [--learning_rate X|from_json]
 Under `torchrun` (WORLD_SIZE > 1) the batch is sharded over ranks and gradients are all-reduced over RCCL
 (parallel.DataParallel), replacing the reference's tf.distribute.MirroredStrategy (train/hpnn_legacy_train.py:37-38).
 `analytical_mixed` (extension): the analytic generator with a boundary type per edge, for a Homogeneous_Poisson_NN_Legacy whose bc_type is a dict.
+`variable_density` (extension): dataset.variable_density_dataset_generator, div((1/rho) grad u) = f with the input stack [rhs, rho], for
+--model hpnn with "density_input": true in the model section; the config's loss is then built as losses.variable_density_loss_wrapper.
 """
 import argparse
 import json
@@ -303,9 +305,9 @@ def main(argv=None):
     from . import configs
     from .utils import convert_tf_object_names
     from .models import Homogeneous_Poisson_NN_Legacy, Dirichlet_BC_NN_Legacy_2, Poisson_CNN_Legacy
-    from .losses import loss_wrapper
+    from .losses import loss_wrapper, variable_density_loss_wrapper
     from .dataset import (numerical_dataset_generator, reverse_poisson_dataset_generator, reverse_poisson_dataset_generator_homogeneous_neumann,
-                          reverse_poisson_dataset_generator_mixed)
+                          reverse_poisson_dataset_generator_mixed, variable_density_dataset_generator)
     from . import parallel
     p = argparse.ArgumentParser(description='Train the Homogeneous Poisson NN')
     p.add_argument('config', type=str)
@@ -318,9 +320,21 @@ def main(argv=None):
                    help='hpnn: train/hpnn_legacy_train.py (train/hpnn_train.py when the model section carries model_type); dbcnn: train/dbcnn_legacy_train.py; '
                         'pcnn: train/pcnn_end_to_end.py; unet: train/UNet.py; dbcnn_rnn: train/dbcnn_rnn_train.py')
     args = p.parse_args(argv)
-    if args.dataset_type not in ('numerical', 'analytical', 'analytical_mixed'):
+    if args.dataset_type not in ('numerical', 'analytical', 'analytical_mixed', 'variable_density'):
         raise ValueError('Invalid dataset type. Received: ' + args.dataset_type)
     config = convert_tf_object_names(configs.load_config(args.config))
+    msec = config.get('model', {})
+    density_model = bool(msec.get('density_input', False))
+    if args.dataset_type == 'variable_density' and (args.model != 'hpnn' or 'model_type' in msec or not density_model):
+        raise ValueError('--dataset_type variable_density yields the two-channel input [rhs, rho]: it needs --model hpnn and "density_input": true in the '
+                         "config's model section (got --model %s, density_input %r)" % (args.model, msec.get('density_input', False)))
+    if args.dataset_type == 'variable_density' and config.get('dataset', {}).get('boundaries', 'zero') != 'zero':
+        raise ValueError("--dataset_type variable_density trains the homogeneous model: it needs boundaries 'zero' in the dataset section (got %r; with "
+                         "'random' the generator yields the four edge arrays as further inputs, which no model here reads) - drop the key or set it to "
+                         "'zero'" % (config['dataset']['boundaries'],))
+    if density_model and args.dataset_type != 'variable_density':
+        raise ValueError('a model with "density_input": true reads the stack [rhs, rho], which only --dataset_type variable_density yields (got '
+                         '--dataset_type %s): pass --dataset_type variable_density or drop density_input from the model section' % args.dataset_type)
     if args.dataset_type == 'analytical_mixed' and (args.model != 'hpnn' or 'model_type' in config['model']
                                                     or not isinstance(config['model'].get('bc_type'), dict)):
         raise ValueError('--dataset_type analytical_mixed is the per-edge analytic generator of Homogeneous_Poisson_NN_Legacy: it needs --model hpnn and '
@@ -372,7 +386,9 @@ def main(argv=None):
             neumann = all(flags)
         else:
             neumann = bc_type.lower() == 'neumann'
-        if args.dataset_type == 'analytical_mixed':        # the quarter-wave / whole-wave series of the model's own edge types, homogeneous data
+        if args.dataset_type == 'variable_density':        # random smooth rhs and rho, the DST-preconditioned CG solve as ground truth (zero Dirichlet data)
+            dataset = variable_density_dataset_generator(**dcfg)
+        elif args.dataset_type == 'analytical_mixed':        # the quarter-wave / whole-wave series of the model's own edge types, homogeneous data
             dataset = reverse_poisson_dataset_generator_mixed(**dict(dcfg, boundary_types=bc_type))
         elif args.dataset_type == 'numerical' and isinstance(bc_type, dict):
             # homogeneous data on every edge (any boundaries string but 'random' is zero data): the mixed solver's ground truth for the model's edge types
@@ -385,7 +401,7 @@ def main(argv=None):
             dataset = reverse_poisson_dataset_generator(**dcfg)
         model = Homogeneous_Poisson_NN_Legacy(**config['model'])
     optimizer = choose_optimizer(config['training']['optimizer'])(**config['training']['optimizer_parameters'])
-    loss = loss_wrapper(global_batch_size=gbs, **config['training']['loss_parameters'])
+    loss = (variable_density_loss_wrapper if density_model else loss_wrapper)(global_batch_size=gbs, **config['training']['loss_parameters'])
     # the largest batch this run will see, for model.presize(): only where the generator draws its grid shape from a range (the analytic generators)
     rng_ = config['dataset'].get('random_output_shape_range')
     presize = None
