@@ -259,10 +259,7 @@ __global__ __launch_bounds__(1024) void pi_partials_kernel(int H, int W, int sy,
   }
   red[threadIdx.x] = acc;
   __syncthreads();
-  for (int st = 512; st > 0; st >>= 1) {
-    if ((int)threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
-    __syncthreads();
-  }
+  pcnn_block_sum<float, 1024>(red, threadIdx.x);
   if (threadIdx.x == 0) out[n] = red[0];
 }
 

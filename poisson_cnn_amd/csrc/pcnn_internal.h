@@ -35,6 +35,25 @@ __device__ __forceinline__ float pcnn_act_grad_from_out(float a, int act, float 
   }
 }
 
+// red[0] <- the sum of red[0 .. THREADS) by the plain halving tree, a barrier per level; the caller's barrier after filling red comes first.
+// Every thread of the block calls it with its index.  The order of the additions is fixed, so the same values give the same bits.
+template <class T, int THREADS>
+__device__ __forceinline__ void pcnn_block_sum(T* red, int tid) {
+#pragma unroll
+  for (int s = THREADS / 2; s > 0; s >>= 1) {
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+}
+
+// a 1-D grid of `block`-thread blocks over `total` items, at most maxb of them (grid-stride kernels take the rest), at least one
+static inline dim3 pcnn_grid1d(int64_t total, int block, int maxb) {
+  int64_t b = pcnn_cdiv64(total, block);
+  if (b > maxb) b = maxb;
+  if (b < 1) b = 1;
+  return dim3((unsigned)b);
+}
+
 // tf.pad index map.  Returns the source index in [0,n) or -1 for "use the constant".
 __device__ __forceinline__ int pcnn_pad_index(int i, int n, int mode) {
   if (i >= 0 && i < n) return i;

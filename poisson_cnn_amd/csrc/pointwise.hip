@@ -1,5 +1,5 @@
 // HBM-bound helpers of the hot path: epilogue backward + per-channel sums, tf.pad adjoint, axpby, per-sample and
-// per-channel scaling, BC ring, input assembly, Jacobi sweep, Adam/SGD.  All are single-pass streaming kernels over
+// per-channel scaling, BC ring, input assembly, Adam/SGD.  All are single-pass streaming kernels over
 // NHWC data (channel index fastest -> coalesced), reductions are two-stage and deterministic (no float atomics).
 #include "pcnn_internal.h"
 
@@ -472,37 +472,6 @@ __global__ void bc_ring_edges_bwd_kernel(int N, int H, int W, int mask, const fl
   }
 }
 
-// one weighted-Jacobi sweep of the 3x3 second-order Laplacian (layers/JacobiIterationLayer.py:43-54)
-__global__ void jacobi_kernel(int N, int H, int W, const float* __restrict__ u, const float* __restrict__ rhs, const float* __restrict__ dx,
-                              float* __restrict__ out) {
-  const int64_t total = (int64_t)N * H * W;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int xx = i % W; const int yy = (i / W) % H; const int n = i / ((int64_t)H * W);
-    if (yy == 0 || yy == H - 1 || xx == 0 || xx == W - 1) { out[i] = u[i]; continue; }
-    const float ay = 1.0f / (dx[2 * n] * dx[2 * n]), ax = 1.0f / (dx[2 * n + 1] * dx[2 * n + 1]);
-    const float cr = ay * (u[i - W] + u[i + W]) + ax * (u[i - 1] + u[i + 1]);
-    const float dinv = 1.0f / (-2.0f * ay - 2.0f * ax);
-    out[i] = dinv * (rhs[i] - cr);
-  }
-}
-
-// adjoint of the sweep w.r.t. u
-__global__ void jacobi_bwd_kernel(int N, int H, int W, const float* __restrict__ dout, const float* __restrict__ dx, float* __restrict__ du) {
-  const int64_t total = (int64_t)N * H * W;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int xx = i % W; const int yy = (i / W) % H; const int n = i / ((int64_t)H * W);
-    const float ay = 1.0f / (dx[2 * n] * dx[2 * n]), ax = 1.0f / (dx[2 * n + 1] * dx[2 * n + 1]);
-    const float dinv = 1.0f / (-2.0f * ay - 2.0f * ax);
-    auto interior = [&](int y, int x) { return y > 0 && y < H - 1 && x > 0 && x < W - 1; };
-    float v = interior(yy, xx) ? 0.f : dout[i];
-    if (yy - 1 >= 0 && interior(yy - 1, xx)) v -= dinv * ay * dout[i - W];
-    if (yy + 1 < H && interior(yy + 1, xx)) v -= dinv * ay * dout[i + W];
-    if (xx - 1 >= 0 && interior(yy, xx - 1)) v -= dinv * ax * dout[i - 1];
-    if (xx + 1 < W && interior(yy, xx + 1)) v -= dinv * ax * dout[i + 1];
-    du[i] = v;
-  }
-}
-
 // vhat != nullptr: the AMSGrad variant (tf.keras Adam(amsgrad=True)): the denominator uses the running maximum of v
 __global__ void adam_kernel(int64_t n, float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                             float* __restrict__ vhat, float lr_t, float beta1, float beta2, float eps, float gscale) {
@@ -545,12 +514,7 @@ __global__ void bn_fold_bwd_kernel(int n, const float* s1, const float* s2, cons
   dbeta[i] = s2[i];
 }
 
-static dim3 grid1d(int64_t total, int block = 256, int maxb = 8192) {
-  int64_t b = pcnn_cdiv64(total, block);
-  if (b > maxb) b = maxb;
-  if (b < 1) b = 1;
-  return dim3((unsigned)b);
-}
+static dim3 grid1d(int64_t total, int block = 256, int maxb = 8192) { return pcnn_grid1d(total, block, maxb); }
 
 }  // namespace
 
@@ -778,20 +742,6 @@ extern "C" int pcnn_bc_ring_bwd(pcnn_handle h, int N, int H, int W, int neumann,
   PCNN_REQUIRE(h, H >= 3 && W >= 3, "pcnn_bc_ring_bwd: grid %dx%d too small", H, W);
   hipLaunchKernelGGL(bc_ring_bwd_kernel, grid1d((int64_t)N * H * W), dim3(256), 0, h->stream, N, H, W, neumann, dy, dx);
   PCNN_CHECK_LAUNCH(h, "pcnn_bc_ring_bwd");
-  return 0;
-}
-
-extern "C" int pcnn_jacobi_sweep(pcnn_handle h, int N, int H, int W, const float* u, const float* rhs, const float* dx, float* out) {
-  PCNN_REQUIRE(h, h && u && rhs && dx && out && u != out, "pcnn_jacobi_sweep: bad argument");
-  hipLaunchKernelGGL(jacobi_kernel, grid1d((int64_t)N * H * W), dim3(256), 0, h->stream, N, H, W, u, rhs, dx, out);
-  PCNN_CHECK_LAUNCH(h, "pcnn_jacobi_sweep");
-  return 0;
-}
-
-extern "C" int pcnn_jacobi_sweep_bwd(pcnn_handle h, int N, int H, int W, const float* dout, const float* dx, float* du) {
-  PCNN_REQUIRE(h, h && dout && dx && du && dout != du, "pcnn_jacobi_sweep_bwd: bad argument");
-  hipLaunchKernelGGL(jacobi_bwd_kernel, grid1d((int64_t)N * H * W), dim3(256), 0, h->stream, N, H, W, dout, dx, du);
-  PCNN_CHECK_LAUNCH(h, "pcnn_jacobi_sweep_bwd");
   return 0;
 }
 

@@ -1,5 +1,7 @@
-// Weighted-Jacobi sweeps of a cross-shaped FD stencil of any odd size 3..9 per axis (layers/JacobiIterationLayer.py:7-66), several sweeps per
-// launch by temporal blocking in LDS, and the adjoint w.r.t. the guess blocked the same way.  DESIGN.md section 11.
+// Every Jacobi sweep of the constant-coefficient operator.  The one-sweep 3 x 3 pair (jacobi_kernel / jacobi_bwd_kernel: one launch per sweep, the
+// model's default route), and weighted-Jacobi sweeps of a cross-shaped FD stencil of any odd size 3..9 per axis (layers/JacobiIterationLayer.py:7-66),
+// several sweeps per launch by temporal blocking in LDS, with the adjoint w.r.t. the guess blocked the same way.  DESIGN.md section 11.
+// The walker, the tile frame, the launch chain and the launch checks are sweep_common.h's, shared with varcoef_train.hip.
 //
 // One sweep: new = dinv * (rhs - sum_taps tap * u) where ry <= y < H - ry and rx <= x < W - rx, new = u on the ring (:48-52).
 // A workgroup owns one JAC_TILE x JAC_TILE output tile of one sample.  After k sweeps the tile depends on the guess within k*ry rows and
@@ -15,7 +17,7 @@
 // (k - s) radii: each sweep's computed region includes the mirror sources of the band points it has to deliver, and the adjoint's includes the
 // band points that mirror into it.  The refresh reads values other threads wrote in the same sweep and has a barrier of its own; a sweep whose
 // region meets no Neumann band (workgroup-uniform) takes the BC == false path.  The BC == false instantiations are the code they were.
-#include "pcnn_internal.h"
+#include "sweep_common.h"
 
 #define JAC_TILE 64        // output tile edge
 #define JAC_HALO_MAX 8     // k * max(ry, rx) <= JAC_HALO_MAX: the LDS region is at most (64 + 16)^2 floats per buffer (BC adjoint: up to 2r - 1 more per axis)
@@ -23,15 +25,34 @@
 
 namespace {
 
-// Walks the rectangle (y0, x0, h, w) with the workgroup's threads in row-major order, without a division per point.
-template <class F>
-__device__ __forceinline__ void for_points(int tid, int y0, int x0, int h, int w, F body) {
-  int q = tid / w, r = tid - q * w;
-  const int dq = JAC_THREADS / w, dr = JAC_THREADS - dq * w;
-  while (q < h) {
-    body(y0 + q, x0 + r);
-    q += dq; r += dr;
-    if (r >= w) { r -= w; ++q; }
+// one weighted-Jacobi sweep of the 3x3 second-order Laplacian (layers/JacobiIterationLayer.py:43-54)
+__global__ void jacobi_kernel(int N, int H, int W, const float* __restrict__ u, const float* __restrict__ rhs, const float* __restrict__ dx,
+                              float* __restrict__ out) {
+  const int64_t total = (int64_t)N * H * W;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int xx = i % W; const int yy = (i / W) % H; const int n = i / ((int64_t)H * W);
+    if (yy == 0 || yy == H - 1 || xx == 0 || xx == W - 1) { out[i] = u[i]; continue; }
+    const float ay = 1.0f / (dx[2 * n] * dx[2 * n]), ax = 1.0f / (dx[2 * n + 1] * dx[2 * n + 1]);
+    const float cr = ay * (u[i - W] + u[i + W]) + ax * (u[i - 1] + u[i + 1]);
+    const float dinv = 1.0f / (-2.0f * ay - 2.0f * ax);
+    out[i] = dinv * (rhs[i] - cr);
+  }
+}
+
+// adjoint of the sweep w.r.t. u
+__global__ void jacobi_bwd_kernel(int N, int H, int W, const float* __restrict__ dout, const float* __restrict__ dx, float* __restrict__ du) {
+  const int64_t total = (int64_t)N * H * W;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int xx = i % W; const int yy = (i / W) % H; const int n = i / ((int64_t)H * W);
+    const float ay = 1.0f / (dx[2 * n] * dx[2 * n]), ax = 1.0f / (dx[2 * n + 1] * dx[2 * n + 1]);
+    const float dinv = 1.0f / (-2.0f * ay - 2.0f * ax);
+    auto interior = [&](int y, int x) { return y > 0 && y < H - 1 && x > 0 && x < W - 1; };
+    float v = interior(yy, xx) ? 0.f : dout[i];
+    if (yy - 1 >= 0 && interior(yy - 1, xx)) v -= dinv * ay * dout[i - W];
+    if (yy + 1 < H && interior(yy + 1, xx)) v -= dinv * ay * dout[i + W];
+    if (xx - 1 >= 0 && interior(yy, xx - 1)) v -= dinv * ax * dout[i - 1];
+    if (xx + 1 < W && interior(yy, xx + 1)) v -= dinv * ax * dout[i + 1];
+    du[i] = v;
   }
 }
 
@@ -81,11 +102,11 @@ __global__ __launch_bounds__(JAC_THREADS) void jacobi_fused_kernel(int H, int W,
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int SY = 2 * RY + 1, SX = 2 * RX + 1;
   const int n = blockIdx.z, tid = threadIdx.x;
-  const int ty0 = blockIdx.y * JAC_TILE, tx0 = blockIdx.x * JAC_TILE;
-  const int ty1 = min(ty0 + JAC_TILE, H), tx1 = min(tx0 + JAC_TILE, W);
+  pcnn_frame<JAC_TILE> f(H, W);
+  const int ty0 = f.ty0, ty1 = f.ty1, tx0 = f.tx0, tx1 = f.tx1;
   // the region held in LDS: the tile grown by k radii, clipped to the image (BC: D_0 of jac_range)
-  int ly0 = max(ty0 - k * RY, 0), ly1 = min(ty1 + k * RY, H);
-  int lx0 = max(tx0 - k * RX, 0), lx1 = min(tx1 + k * RX, W);
+  int ly0, ly1, lx0, lx1;
+  f.grow(k * RY, k * RX, ly0, ly1, lx0, lx1);
   int S = (JAC_TILE + 2 * k * RY) * (JAC_TILE + 2 * k * RX);         // floats per buffer as the host sized them
   if (BC) {
     int c0, c1;
@@ -93,7 +114,8 @@ __global__ __launch_bounds__(JAC_THREADS) void jacobi_fused_kernel(int H, int W,
     jac_range<BWD>(tx0, tx1, W, RX, k, 0, mask & 4, mask & 8, lx0, lx1, c0, c1);
     S = S_bc;
   }
-  const int LW = lx1 - lx0;
+  f.hold(ly0, ly1, lx0, lx1);
+  const int LW = f.LW;
   float* src = lds;
   float* dst = lds + S;
   float* rb = lds + 2 * S;                                            // forward only
@@ -107,16 +129,16 @@ __global__ __launch_bounds__(JAC_THREADS) void jacobi_fused_kernel(int H, int W,
   const float dinv = cn[SY + SX];
 
   const int64_t img = (int64_t)n * H * W;
-  for_points(tid, ly0, lx0, ly1 - ly0, LW, [&](int y, int x) { src[(y - ly0) * LW + (x - lx0)] = u[img + (int64_t)y * W + x]; });
+  pcnn_for_points<JAC_THREADS>(tid, ly0, lx0, ly1 - ly0, LW, [&](int y, int x) { src[f.at(y, x)] = u[img + (int64_t)y * W + x]; });
   if (!BWD) {
-    int ry0 = max(ty0 - (k - 1) * RY, 0), ry1 = min(ty1 + (k - 1) * RY, H);
-    int rx0 = max(tx0 - (k - 1) * RX, 0), rx1 = min(tx1 + (k - 1) * RX, W);
+    int ry0, ry1, rx0, rx1;
+    f.grow((k - 1) * RY, (k - 1) * RX, ry0, ry1, rx0, rx1);
     if (BC) {                                                         // the first sweep's computed region C_1; every later one lies inside it
       int d0, d1;
       jac_range<false>(ty0, ty1, H, RY, k, 1, mask & 1, mask & 2, d0, d1, ry0, ry1);
       jac_range<false>(tx0, tx1, W, RX, k, 1, mask & 4, mask & 8, d0, d1, rx0, rx1);
     }
-    for_points(tid, ry0, rx0, ry1 - ry0, rx1 - rx0, [&](int y, int x) { rb[(y - ly0) * LW + (x - lx0)] = rhs[img + (int64_t)y * W + x]; });
+    pcnn_for_points<JAC_THREADS>(tid, ry0, rx0, ry1 - ry0, rx1 - rx0, [&](int y, int x) { rb[f.at(y, x)] = rhs[img + (int64_t)y * W + x]; });
   }
   __syncthreads();
 
@@ -161,8 +183,8 @@ __global__ __launch_bounds__(JAC_THREADS) void jacobi_fused_kernel(int H, int W,
 
   for (int s = 1; s <= k; ++s) {
     const int g = k - s;                                              // radii this sweep's region still extends past the tile
-    int y0 = max(ty0 - g * RY, 0), y1 = min(ty1 + g * RY, H);
-    int x0 = max(tx0 - g * RX, 0), x1 = min(tx1 + g * RX, W);
+    int y0, y1, x0, x1;
+    f.grow(g * RY, g * RX, y0, y1, x0, x1);
     if (BC) {
       int cy0, cy1, cx0, cx1;                                         // forward: C_s; adjoint: G_s
       jac_range<BWD>(ty0, ty1, H, RY, k, s, mask & 1, mask & 2, y0, y1, cy0, cy1);
@@ -171,12 +193,12 @@ __global__ __launch_bounds__(JAC_THREADS) void jacobi_fused_kernel(int H, int W,
         // does what this sweep delivers meet a Neumann band?  (the same for every thread of the workgroup)
         const bool touch = ((mask & 1) && y0 < RY) || ((mask & 2) && y1 > H - RY) || ((mask & 4) && x0 < RX) || ((mask & 8) && x1 > W - RX);
         if (touch) {
-          for_points(tid, cy0, cx0, cy1 - cy0, cx1 - cx0, [&](int y, int x) {
+          pcnn_for_points<JAC_THREADS>(tid, cy0, cx0, cy1 - cy0, cx1 - cx0, [&](int y, int x) {
             const int c = (y - ly0) * LW + (x - lx0);
             dst[c] = point(src, c, y, x);
           });
           __syncthreads();                                            // the refresh reads this sweep's J(u) as other threads wrote it
-          for_points(tid, y0, x0, y1 - y0, x1 - x0, [&](int y, int x) {
+          pcnn_for_points<JAC_THREADS>(tid, y0, x0, y1 - y0, x1 - x0, [&](int y, int x) {
             const int c = (y - ly0) * LW + (x - lx0);
             int my, mx;
             const bool r = jac_refreshed<RY, RX>(y, x, H, W, mask, my, mx);   // sources are interior points: no refresh writes what another reads
@@ -194,7 +216,7 @@ __global__ __launch_bounds__(JAC_THREADS) void jacobi_fused_kernel(int H, int W,
         if (touch) {
           // R_m^T as a gather: a point that kept its own value passes its gradient on, and an interior point collects those of the band points
           // that mirrored it - along y, along x, and across a Neumann/Neumann corner - in this fixed order
-          for_points(tid, cy0, cx0, cy1 - cy0, cx1 - cx0, [&](int y, int x) {
+          pcnn_for_points<JAC_THREADS>(tid, cy0, cx0, cy1 - cy0, cx1 - cx0, [&](int y, int x) {
             const int c = (y - ly0) * LW + (x - lx0);
             int my, mx;
             float v = jac_refreshed<RY, RX>(y, x, H, W, mask, my, mx) ? 0.f : src[c];
@@ -214,7 +236,7 @@ __global__ __launch_bounds__(JAC_THREADS) void jacobi_fused_kernel(int H, int W,
             dst[c] = v;
           });
           __syncthreads();
-          for_points(tid, y0, x0, y1 - y0, x1 - x0, [&](int y, int x) {
+          pcnn_for_points<JAC_THREADS>(tid, y0, x0, y1 - y0, x1 - x0, [&](int y, int x) {
             const int c = (y - ly0) * LW + (x - lx0);
             const float v = point(dst, c, y, x);
             if (s == k) out[img + (int64_t)y * W + x] = v;
@@ -225,8 +247,8 @@ __global__ __launch_bounds__(JAC_THREADS) void jacobi_fused_kernel(int H, int W,
         }
       }
     }
-    for_points(tid, y0, x0, y1 - y0, x1 - x0, [&](int y, int x) {
-      const int c = (y - ly0) * LW + (x - lx0);
+    pcnn_for_points<JAC_THREADS>(tid, y0, x0, y1 - y0, x1 - x0, [&](int y, int x) {
+      const int c = f.at(y, x);
       const float v = point(src, c, y, x);
       if (s == k) out[img + (int64_t)y * W + x] = v;                 // the last sweep's region is the tile itself
       else dst[c] = v;
@@ -257,11 +279,8 @@ int jacobi_launch(pcnn_handle_s* h, int N, int H, int W, int sy, int sx, int k, 
     per = (size_t)mh * mw;
   }
   const size_t lds = (size_t)(BWD ? 2 : 3) * per * sizeof(float);
-  PCNN_REQUIRE(h, lds <= 160u * 1024u, "pcnn_jacobi_fused: %zu bytes of LDS for %d fused sweeps of a %d x %d stencil", lds, k, sy, sx);
-  auto go = [&](auto kernel) {
-    set_lds(kernel, lds);
-    hipLaunchKernelGGL(kernel, grid, dim3(JAC_THREADS), lds, h->stream, H, W, k, coef, u, rhs, out, mask, (int)per);
-  };
+  PCNN_REQUIRE_LDS(h, lds, "pcnn_jacobi_fused: %zu bytes of LDS for %d fused sweeps of a %d x %d stencil", lds, k, sy, sx);
+  auto go = [&](auto kernel) { pcnn_launch_lds(h, kernel, grid, JAC_THREADS, lds, H, W, k, coef, u, rhs, out, mask, (int)per); };
 #define JAC_CASE(A, B)                                        \
   case A * 8 + B:                                             \
     if (mask >= 0) go(jacobi_fused_kernel<A, B, BWD, true>);  \
@@ -278,39 +297,32 @@ int jacobi_launch(pcnn_handle_s* h, int N, int H, int W, int sy, int sx, int k, 
   return 0;
 }
 
-// n sweeps as ceil(n / k_max) launches of near-equal depth.  Intermediate results alternate between `out` and one handle-owned scratch image so
-// that the last launch writes `out` and no launch reads what it writes.
-template <bool BWD>
-int jacobi_chain(pcnn_handle_s* h, const char* name, int N, int H, int W, int sy, int sx, const float* coef, const float* u, const float* rhs,
-                 int n_sweeps, float* out, int mask = -1) {
-  const int kmax = pcnn_jacobi_fused_max_sweeps(sy, sx);
-  const int launches = pcnn_cdiv(n_sweeps, kmax);
-  float* tmp = nullptr;
-  if (launches > 1) {
-    if (pcnn_reserve(h, h->aux_ws, (size_t)N * H * W * sizeof(float), 0, name)) return 1;
-    tmp = static_cast<float*>(h->aux_ws.p);
-  }
-  const float* in = u;
-  int left = n_sweeps;
-  for (int l = 0; l < launches; ++l) {
-    const int k = pcnn_cdiv(left, launches - l);
-    float* to = ((launches - 1 - l) % 2 == 0) ? out : tmp;
-    const int rc = jacobi_launch<BWD>(h, N, H, W, sy, sx, k, coef, in, rhs, to, mask);
-    if (rc) return rc;
-    in = to;
-    left -= k;
-  }
-  PCNN_CHECK_LAUNCH(h, name);
-  return 0;
-}
-
 bool jacobi_shape_ok(int N, int H, int W, int sy, int sx, int n_sweeps) {
-  return N >= 1 && N <= 65535 && sy % 2 == 1 && sx % 2 == 1 && sy >= 3 && sy <= 9 && sx >= 3 && sx <= 9 && H > 2 * (sy / 2) && W > 2 * (sx / 2) && n_sweeps >= 1;
+  return pcnn_grid_ok(N, H, W) && sy % 2 == 1 && sx % 2 == 1 && sy >= 3 && sy <= 9 && sx >= 3 && sx <= 9 && H > 2 * (sy / 2) && W > 2 * (sx / 2) && n_sweeps >= 1;
 }
 
 // a Neumann edge's mirror sources must be interior points: three radii along every axis the mask touches
 bool jacobi_mask_ok(int H, int W, int sy, int sx, int mask) {
   return mask >= 0 && mask < 16 && (!(mask & 3) || H >= 3 * (sy / 2)) && (!(mask & 12) || W >= 3 * (sx / 2));
+}
+
+// The checks and the launch chain of the four fused entry points.  bc: the entry point takes a neumann_mask.
+template <bool BWD>
+int jacobi_run(pcnn_handle_s* h, const char* name, int N, int H, int W, int sy, int sx, const float* coef, const float* u, const float* rhs, int n_sweeps,
+               float* out, bool bc = false, int mask = 0) {
+  PCNN_REQUIRE(h, h && coef && u && (BWD || rhs) && out, "%s: null argument", name);
+  PCNN_REQUIRE(h, jacobi_shape_ok(N, H, W, sy, sx, n_sweeps),
+               "%s: needs odd stencil sizes in 3..9, H > 2*(sy/2), W > 2*(sx/2), n_sweeps >= 1 (got %d x %d stencil, %d x %d image, %d sweeps)", name, sy, sx, H, W,
+               n_sweeps);
+  PCNN_REQUIRE(h, !bc || jacobi_mask_ok(H, W, sy, sx, mask),
+               "%s: needs neumann_mask in 0..15, H >= 3*(sy/2) with a left or right Neumann edge, W >= 3*(sx/2) with a bottom or top one (got mask %d, "
+               "%d x %d stencil, %d x %d image)", name, mask, sy, sx, H, W);
+  if (BWD) PCNN_REQUIRE(h, out != u, "%s: du must not alias dout", name);
+  else PCNN_REQUIRE(h, out != u && out != rhs, "%s: out must not alias u or rhs", name);
+  // mask 0 runs the frozen-band kernels: the same bits, and measurably faster than the boundary-aware ones with nothing to refresh (DESIGN.md section 11)
+  const int m = bc && mask ? mask : -1;
+  return pcnn_sweep_chain(h, name, N, H, W, n_sweeps, pcnn_jacobi_fused_max_sweeps(sy, sx), u, out,
+                          [&](int k, const float* in, float* to) { return jacobi_launch<BWD>(h, N, H, W, sy, sx, k, coef, in, rhs, to, m); });
 }
 
 }  // namespace
@@ -324,46 +336,33 @@ extern "C" int pcnn_jacobi_fused_max_sweeps(int sy, int sx) {
 
 extern "C" int pcnn_jacobi_fused_fwd(pcnn_handle h, int N, int H, int W, int sy, int sx, const float* coef, const float* u, const float* rhs, int n_sweeps,
                                      float* out) {
-  PCNN_REQUIRE(h, h && coef && u && rhs && out, "pcnn_jacobi_fused_fwd: null argument");
-  PCNN_REQUIRE(h, jacobi_shape_ok(N, H, W, sy, sx, n_sweeps),
-               "pcnn_jacobi_fused_fwd: needs odd stencil sizes in 3..9, H > 2*(sy/2), W > 2*(sx/2), n_sweeps >= 1 (got %d x %d stencil, %d x %d image, %d sweeps)", sy, sx,
-               H, W, n_sweeps);
-  PCNN_REQUIRE(h, out != u && out != rhs, "pcnn_jacobi_fused_fwd: out must not alias u or rhs");
-  return jacobi_chain<false>(h, "pcnn_jacobi_fused_fwd", N, H, W, sy, sx, coef, u, rhs, n_sweeps, out);
+  return jacobi_run<false>(h, "pcnn_jacobi_fused_fwd", N, H, W, sy, sx, coef, u, rhs, n_sweeps, out);
 }
 
 extern "C" int pcnn_jacobi_fused_bwd(pcnn_handle h, int N, int H, int W, int sy, int sx, const float* coef, const float* dout, int n_sweeps, float* du) {
-  PCNN_REQUIRE(h, h && coef && dout && du, "pcnn_jacobi_fused_bwd: null argument");
-  PCNN_REQUIRE(h, jacobi_shape_ok(N, H, W, sy, sx, n_sweeps),
-               "pcnn_jacobi_fused_bwd: needs odd stencil sizes in 3..9, H > 2*(sy/2), W > 2*(sx/2), n_sweeps >= 1 (got %d x %d stencil, %d x %d image, %d sweeps)", sy, sx,
-               H, W, n_sweeps);
-  PCNN_REQUIRE(h, du != dout, "pcnn_jacobi_fused_bwd: du must not alias dout");
-  return jacobi_chain<true>(h, "pcnn_jacobi_fused_bwd", N, H, W, sy, sx, coef, dout, nullptr, n_sweeps, du);
+  return jacobi_run<true>(h, "pcnn_jacobi_fused_bwd", N, H, W, sy, sx, coef, dout, nullptr, n_sweeps, du);
 }
 
 extern "C" int pcnn_jacobi_fused_bc_fwd(pcnn_handle h, int N, int H, int W, int sy, int sx, const float* coef, const float* u, const float* rhs, int n_sweeps,
                                         int neumann_mask, float* out) {
-  PCNN_REQUIRE(h, h && coef && u && rhs && out, "pcnn_jacobi_fused_bc_fwd: null argument");
-  PCNN_REQUIRE(h, jacobi_shape_ok(N, H, W, sy, sx, n_sweeps),
-               "pcnn_jacobi_fused_bc_fwd: needs odd stencil sizes in 3..9, H > 2*(sy/2), W > 2*(sx/2), n_sweeps >= 1 (got %d x %d stencil, %d x %d image, %d sweeps)", sy,
-               sx, H, W, n_sweeps);
-  PCNN_REQUIRE(h, jacobi_mask_ok(H, W, sy, sx, neumann_mask),
-               "pcnn_jacobi_fused_bc_fwd: needs neumann_mask in 0..15, H >= 3*(sy/2) with a left or right Neumann edge, W >= 3*(sx/2) with a bottom or top one (got mask %d, "
-               "%d x %d stencil, %d x %d image)", neumann_mask, sy, sx, H, W);
-  PCNN_REQUIRE(h, out != u && out != rhs, "pcnn_jacobi_fused_bc_fwd: out must not alias u or rhs");
-  // mask 0 runs the frozen-band kernels: the same bits, and measurably faster than the boundary-aware ones with nothing to refresh (DESIGN.md section 11)
-  return jacobi_chain<false>(h, "pcnn_jacobi_fused_bc_fwd", N, H, W, sy, sx, coef, u, rhs, n_sweeps, out, neumann_mask ? neumann_mask : -1);
+  return jacobi_run<false>(h, "pcnn_jacobi_fused_bc_fwd", N, H, W, sy, sx, coef, u, rhs, n_sweeps, out, true, neumann_mask);
 }
 
 extern "C" int pcnn_jacobi_fused_bc_bwd(pcnn_handle h, int N, int H, int W, int sy, int sx, const float* coef, const float* dout, int n_sweeps, int neumann_mask,
                                         float* du) {
-  PCNN_REQUIRE(h, h && coef && dout && du, "pcnn_jacobi_fused_bc_bwd: null argument");
-  PCNN_REQUIRE(h, jacobi_shape_ok(N, H, W, sy, sx, n_sweeps),
-               "pcnn_jacobi_fused_bc_bwd: needs odd stencil sizes in 3..9, H > 2*(sy/2), W > 2*(sx/2), n_sweeps >= 1 (got %d x %d stencil, %d x %d image, %d sweeps)", sy,
-               sx, H, W, n_sweeps);
-  PCNN_REQUIRE(h, jacobi_mask_ok(H, W, sy, sx, neumann_mask),
-               "pcnn_jacobi_fused_bc_bwd: needs neumann_mask in 0..15, H >= 3*(sy/2) with a left or right Neumann edge, W >= 3*(sx/2) with a bottom or top one (got mask %d, "
-               "%d x %d stencil, %d x %d image)", neumann_mask, sy, sx, H, W);
-  PCNN_REQUIRE(h, du != dout, "pcnn_jacobi_fused_bc_bwd: du must not alias dout");
-  return jacobi_chain<true>(h, "pcnn_jacobi_fused_bc_bwd", N, H, W, sy, sx, coef, dout, nullptr, n_sweeps, du, neumann_mask ? neumann_mask : -1);
+  return jacobi_run<true>(h, "pcnn_jacobi_fused_bc_bwd", N, H, W, sy, sx, coef, dout, nullptr, n_sweeps, du, true, neumann_mask);
+}
+
+extern "C" int pcnn_jacobi_sweep(pcnn_handle h, int N, int H, int W, const float* u, const float* rhs, const float* dx, float* out) {
+  PCNN_REQUIRE(h, h && u && rhs && dx && out && u != out, "pcnn_jacobi_sweep: bad argument");
+  hipLaunchKernelGGL(jacobi_kernel, pcnn_grid1d((int64_t)N * H * W, 256, 8192), dim3(256), 0, h->stream, N, H, W, u, rhs, dx, out);
+  PCNN_CHECK_LAUNCH(h, "pcnn_jacobi_sweep");
+  return 0;
+}
+
+extern "C" int pcnn_jacobi_sweep_bwd(pcnn_handle h, int N, int H, int W, const float* dout, const float* dx, float* du) {
+  PCNN_REQUIRE(h, h && dout && dx && du && dout != du, "pcnn_jacobi_sweep_bwd: bad argument");
+  hipLaunchKernelGGL(jacobi_bwd_kernel, pcnn_grid1d((int64_t)N * H * W, 256, 8192), dim3(256), 0, h->stream, N, H, W, dout, dx, du);
+  PCNN_CHECK_LAUNCH(h, "pcnn_jacobi_sweep_bwd");
+  return 0;
 }

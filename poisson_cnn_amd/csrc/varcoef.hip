@@ -46,11 +46,7 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
   __syncthreads();
   red[t] = v;
   __syncthreads();
-#pragma unroll
-  for (int s = T / 2; s > 0; s >>= 1) {
-    if (t < s) red[t] += red[t + s];
-    __syncthreads();
-  }
+  pcnn_block_sum<double, T>(red, t);
   return red[0];
 }
 

@@ -5,8 +5,9 @@
 // on the (H-2) x (W-2) interior nodes; here the ring of u is part of the field (the model predicts it), so L maps all H W nodes to the interior.
 // The face coefficients are never stored: every kernel builds them from an LDS tile of rho.  No atomics: the loss sums are per-tile partials
 // (fixed tree) added per sample by a second one-block stage in a fixed order.  A sample's blocks read nothing of another sample.
+// The sweeps' walker, tile frame, launch chain and launch checks are sweep_common.h's, shared with stencil.hip.
 #include <math.h>
-#include "pcnn_internal.h"
+#include "sweep_common.h"
 
 #define VJ_TILE 64         // output tile edge of the sweeps
 #define VJ_HALO_MAX 8      // fused sweeps per launch: four LDS buffers of at most (64 + 2 * 8 + 2)^2 floats (107.6 KB)
@@ -64,11 +65,7 @@ __global__ __launch_bounds__(PT_THREADS) void vc_pi_partials_kernel(int H, int W
   }
   red[threadIdx.x] = s;
   __syncthreads();
-#pragma unroll
-  for (int w = PT_THREADS / 2; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-    __syncthreads();
-  }
+  pcnn_block_sum<float, PT_THREADS>(red, threadIdx.x);
   if (threadIdx.x == 0) part[(int64_t)n * tiles + blockIdx.y * gridDim.x + blockIdx.x] = red[0];
 }
 
@@ -80,11 +77,7 @@ __global__ __launch_bounds__(RED_THREADS) void vc_pi_reduce_kernel(int tiles, co
   for (int k = t; k < tiles; k += RED_THREADS) v += (double)part[(int64_t)n * tiles + k];
   red[t] = v;
   __syncthreads();
-#pragma unroll
-  for (int w = RED_THREADS / 2; w > 0; w >>= 1) {
-    if (t < w) red[t] += red[t + w];
-    __syncthreads();
-  }
+  pcnn_block_sum<double, RED_THREADS>(red, t);
   if (t == 0) out[n] = (float)red[0];
 }
 
@@ -132,18 +125,6 @@ __global__ __launch_bounds__(PT_THREADS) void vc_pi_bwd_kernel(int H, int W, con
   }
 }
 
-// Walks the rectangle (y0, x0, h, w) with the workgroup's threads in row-major order, without a division per point (as csrc/stencil.hip).
-template <class F>
-__device__ __forceinline__ void vj_points(int tid, int y0, int x0, int h, int w, F body) {
-  int q = tid / w, r = tid - q * w;
-  const int dq = VJ_THREADS / w, dr = VJ_THREADS - dq * w;
-  while (q < h) {
-    body(y0 + q, x0 + r);
-    q += dq; r += dr;
-    if (r >= w) { r -= w; ++q; }
-  }
-}
-
 // k sweeps in one launch by temporal blocking (DESIGN.md sections 11 and 17).  A workgroup owns a VJ_TILE^2 tile of one sample; after k sweeps the
 // tile depends on u within k nodes of it, clipped to the image where the frozen ring ends the dependence.  Sweep s of k computes the tile grown by
 // k - s nodes, ping-ponging between two LDS buffers; the last one stores the tile.  The arithmetic of a point does not depend on k or on the tile,
@@ -156,11 +137,11 @@ __global__ __launch_bounds__(VJ_THREADS) void vc_jacobi_kernel(int H, int W, int
                                                                const float* __restrict__ rhs, const float* __restrict__ dx, float* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int n = blockIdx.z, tid = threadIdx.x, g0 = k + (BWD ? 1 : 0);
-  const int ty0 = blockIdx.y * VJ_TILE, tx0 = blockIdx.x * VJ_TILE;
-  const int ty1 = min(ty0 + VJ_TILE, H), tx1 = min(tx0 + VJ_TILE, W);
-  // the LDS frame: the tile grown by g0 nodes, clipped to the image
-  const int ly0 = max(ty0 - g0, 0), ly1 = min(ty1 + g0, H), lx0 = max(tx0 - g0, 0), lx1 = min(tx1 + g0, W);
-  const int LW = lx1 - lx0;
+  pcnn_frame<VJ_TILE> f(H, W);
+  int y0, y1, x0, x1;
+  f.grow(g0, g0, y0, y1, x0, x1);                                     // the LDS frame: the tile grown by g0 nodes, clipped to the image
+  f.hold(y0, y1, x0, x1);
+  const int LW = f.LW;
   const int S = (VJ_TILE + 2 * g0) * (VJ_TILE + 2 * g0);              // floats per buffer as the host sized them
   float* src = lds;
   float* dst = lds + S;
@@ -168,16 +149,15 @@ __global__ __launch_bounds__(VJ_THREADS) void vc_jacobi_kernel(int H, int W, int
   float* rb = lds + 3 * S;
   const int64_t img = (int64_t)n * H * W;
   const float h = dx[n], h2 = h * h;
-  auto at = [&](int y, int x) { return (y - ly0) * LW + (x - lx0); };
 
-  vj_points(tid, ly0, lx0, ly1 - ly0, LW, [&](int y, int x) { rb[at(y, x)] = rho[img + (int64_t)y * W + x]; });
+  pcnn_for_points<VJ_THREADS>(tid, y0, x0, y1 - y0, LW, [&](int y, int x) { rb[f.at(y, x)] = rho[img + (int64_t)y * W + x]; });
   {
-    const int y0 = max(ty0 - k, 0), y1 = min(ty1 + k, H), x0 = max(tx0 - k, 0), x1 = min(tx1 + k, W);
-    vj_points(tid, y0, x0, y1 - y0, x1 - x0, [&](int y, int x) { src[at(y, x)] = u[img + (int64_t)y * W + x]; });
+    f.grow(k, k, y0, y1, x0, x1);
+    pcnn_for_points<VJ_THREADS>(tid, y0, x0, y1 - y0, x1 - x0, [&](int y, int x) { src[f.at(y, x)] = u[img + (int64_t)y * W + x]; });
     if (BWD) {
       __syncthreads();
-      vj_points(tid, y0, x0, y1 - y0, x1 - x0, [&](int y, int x) {
-        const int c = at(y, x);
+      pcnn_for_points<VJ_THREADS>(tid, y0, x0, y1 - y0, x1 - x0, [&](int y, int x) {
+        const int c = f.at(y, x);
         float v = 0.f;
         if (y >= 1 && y < H - 1 && x >= 1 && x < W - 1) {
           const float rc = rb[c];
@@ -186,8 +166,8 @@ __global__ __launch_bounds__(VJ_THREADS) void vc_jacobi_kernel(int H, int W, int
         fb[c] = v;
       });
     } else {
-      const int ry0 = max(ty0 - (k - 1), 0), ry1 = min(ty1 + (k - 1), H), rx0 = max(tx0 - (k - 1), 0), rx1 = min(tx1 + (k - 1), W);
-      vj_points(tid, ry0, rx0, ry1 - ry0, rx1 - rx0, [&](int y, int x) { fb[at(y, x)] = h2 * rhs[img + (int64_t)y * W + x]; });
+      f.grow(k - 1, k - 1, y0, y1, x0, x1);
+      pcnn_for_points<VJ_THREADS>(tid, y0, x0, y1 - y0, x1 - x0, [&](int y, int x) { fb[f.at(y, x)] = h2 * rhs[img + (int64_t)y * W + x]; });
     }
   }
   __syncthreads();
@@ -216,10 +196,9 @@ __global__ __launch_bounds__(VJ_THREADS) void vc_jacobi_kernel(int H, int W, int
   };
 
   for (int s = 1; s <= k; ++s) {
-    const int g = k - s;
-    const int y0 = max(ty0 - g, 0), y1 = min(ty1 + g, H), x0 = max(tx0 - g, 0), x1 = min(tx1 + g, W);
-    vj_points(tid, y0, x0, y1 - y0, x1 - x0, [&](int y, int x) {
-      const int c = at(y, x);
+    f.grow(k - s, k - s, y0, y1, x0, x1);
+    pcnn_for_points<VJ_THREADS>(tid, y0, x0, y1 - y0, x1 - x0, [&](int y, int x) {
+      const int c = f.at(y, x);
       const float v = point(src, c, y, x);
       if (s == k) out[img + (int64_t)y * W + x] = v;
       else dst[c] = v;
@@ -234,33 +213,8 @@ int vj_launch(pcnn_handle_s* h, int N, int H, int W, int k, const float* rho, co
   const dim3 grid((unsigned)pcnn_cdiv(W, VJ_TILE), (unsigned)pcnn_cdiv(H, VJ_TILE), (unsigned)N);
   const int e = VJ_TILE + 2 * (k + (BWD ? 1 : 0));
   const size_t lds = (size_t)4 * e * e * sizeof(float);
-  PCNN_REQUIRE(h, lds <= 160u * 1024u, "pcnn_varcoef_jacobi: %zu bytes of LDS for %d fused sweeps", lds, k);
-  set_lds(vc_jacobi_kernel<BWD>, lds);
-  hipLaunchKernelGGL(vc_jacobi_kernel<BWD>, grid, dim3(VJ_THREADS), lds, h->stream, H, W, k, rho, u, rhs, dx, out);
-  return 0;
-}
-
-// n sweeps as ceil(n / k_max) launches of near-equal depth; intermediates alternate between `out` and one handle-owned scratch image so that the
-// last launch writes `out` and no launch reads what it writes (jacobi_chain of csrc/stencil.hip).
-template <bool BWD>
-int vj_chain(pcnn_handle_s* h, const char* name, int N, int H, int W, const float* rho, const float* u, const float* rhs, const float* dx, int n_sweeps,
-             float* out) {
-  const int launches = pcnn_cdiv(n_sweeps, VJ_HALO_MAX);
-  float* tmp = nullptr;
-  if (launches > 1) {
-    if (pcnn_reserve(h, h->aux_ws, (size_t)N * H * W * sizeof(float), 0, name)) return 1;
-    tmp = static_cast<float*>(h->aux_ws.p);
-  }
-  const float* in = u;
-  int left = n_sweeps;
-  for (int l = 0; l < launches; ++l) {
-    const int k = pcnn_cdiv(left, launches - l);
-    float* to = ((launches - 1 - l) % 2 == 0) ? out : tmp;
-    if (int rc = vj_launch<BWD>(h, N, H, W, k, rho, in, rhs, dx, to)) return rc;
-    in = to;
-    left -= k;
-  }
-  PCNN_CHECK_LAUNCH(h, name);
+  PCNN_REQUIRE_LDS(h, lds, "pcnn_varcoef_jacobi: %zu bytes of LDS for %d fused sweeps", lds, k);
+  pcnn_launch_lds(h, vc_jacobi_kernel<BWD>, grid, VJ_THREADS, lds, H, W, k, rho, u, rhs, dx, out);
   return 0;
 }
 
@@ -281,7 +235,7 @@ __global__ void assemble_density_input_kernel(int N, int H, int W, const float* 
   }
 }
 
-bool vt_shape_ok(int N, int H, int W) { return N >= 1 && N <= 65535 && H >= 3 && W >= 3 && pcnn_cdiv(H, PT_ROWS) <= 65535; }
+bool vt_shape_ok(int N, int H, int W) { return pcnn_grid_ok(N, H, W) && H >= 3 && W >= 3 && pcnn_cdiv(H, PT_ROWS) <= 65535; }
 
 }  // namespace
 
@@ -318,7 +272,8 @@ extern "C" int pcnn_varcoef_jacobi_fwd(pcnn_handle h, int N, int H, int W, const
   PCNN_REQUIRE(h, vt_shape_ok(N, H, W) && n_sweeps >= 1, "pcnn_varcoef_jacobi_fwd: needs N in 1..65535, H, W >= 3, n_sweeps >= 1 (got %d, %d x %d, %d sweeps)", N, H,
                W, n_sweeps);
   PCNN_REQUIRE(h, out != u && out != rhs && out != rho, "pcnn_varcoef_jacobi_fwd: out must not alias an input");
-  return vj_chain<false>(h, "pcnn_varcoef_jacobi_fwd", N, H, W, rho, u, rhs, dx, n_sweeps, out);
+  return pcnn_sweep_chain(h, "pcnn_varcoef_jacobi_fwd", N, H, W, n_sweeps, VJ_HALO_MAX, u, out,
+                          [&](int k, const float* in, float* to) { return vj_launch<false>(h, N, H, W, k, rho, in, rhs, dx, to); });
 }
 
 extern "C" int pcnn_varcoef_jacobi_bwd(pcnn_handle h, int N, int H, int W, const float* rho, const float* dx, const float* dout, int n_sweeps, float* du) {
@@ -326,7 +281,8 @@ extern "C" int pcnn_varcoef_jacobi_bwd(pcnn_handle h, int N, int H, int W, const
   PCNN_REQUIRE(h, vt_shape_ok(N, H, W) && n_sweeps >= 1, "pcnn_varcoef_jacobi_bwd: needs N in 1..65535, H, W >= 3, n_sweeps >= 1 (got %d, %d x %d, %d sweeps)", N, H,
                W, n_sweeps);
   PCNN_REQUIRE(h, du != dout && du != rho, "pcnn_varcoef_jacobi_bwd: du must not alias an input");
-  return vj_chain<true>(h, "pcnn_varcoef_jacobi_bwd", N, H, W, rho, dout, nullptr, dx, n_sweeps, du);
+  return pcnn_sweep_chain(h, "pcnn_varcoef_jacobi_bwd", N, H, W, n_sweeps, VJ_HALO_MAX, dout, du,
+                          [&](int k, const float* in, float* to) { return vj_launch<true>(h, N, H, W, k, rho, in, nullptr, dx, to); });
 }
 
 extern "C" int pcnn_assemble_density_input(pcnn_handle h, int N, int H, int W, const float* stack, int use_pos, float* out, int ldo) {

@@ -690,28 +690,39 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
             pyr[f] = (ops.pool2d_fwd(x if parent is None else pyr[parent][0], f if parent is None else f // parent, 'average'), parent)
         return pyr
 
+    def _assemble(self, rhs):
+        """The network's NHWC input and the one-channel (N,H,W) fields Scaling and the smoother read: (x, rhs_hw, rho_hw - None without density_input)."""
+        if self.density_input:
+            if rhs.dim() != 4 or rhs.shape[1] != 2:
+                raise ValueError('a density_input model takes the stack [rhs, rho] of shape (N,2,H,W)')
+            stack = rhs.contiguous()
+            rhs_hw, rho_hw = stack[:, 0].contiguous(), stack[:, 1].contiguous()
+            return ops.assemble_density_input(stack, self.use_positional_embeddings), rhs_hw, rho_hw
+        if rhs.dim() != 4 or rhs.shape[1] != 1:
+            raise ValueError('rhs must have shape (N,1,H,W)')
+        rhs_hw = rhs.view(rhs.shape[0], rhs.shape[2], rhs.shape[3])
+        return ops.assemble_input(rhs_hw, self.use_positional_embeddings), rhs_hw, None
+
+    def _smooth(self, x, rhs_hw, rho_hw, dx, training):
+        """The post-smoother on the prediction x (N,H,W,1): the flux-form sweeps when there is a density field, else the constant-coefficient ones."""
+        if self.postsmoother is None:
+            return x
+        rhs = rhs_hw.unsqueeze(-1)
+        if rho_hw is not None:
+            return self.postsmoother.forward(x, rhs, rho_hw.unsqueeze(-1), dx, training=training)
+        return self.postsmoother.forward(x, rhs, _dx_pair(dx), training=training)
+
     def call(self, inp, training=False):
         """reference :183-257.  inp = [rhs (N,1,H,W), dx (N,1)]; returns (N,1,H,W) (torch CUDA tensor).  density_input: inp = [stack (N,2,H,W), dx],
         the stack [rhs, rho]."""
         rhs, dx = inp
         rhs = _as_device(rhs, self.device)
         dx = _as_device(dx, self.device)
-        if self.density_input:
-            if rhs.dim() != 4 or rhs.shape[1] != 2:
-                raise ValueError('a density_input model takes the stack [rhs, rho] of shape (N,2,H,W)')
-        elif rhs.dim() != 4 or rhs.shape[1] != 1:
-            raise ValueError('rhs must have shape (N,1,H,W)')
+        x, rhs_hw, rho_hw = self._assemble(rhs)                 # refuses a malformed rhs before anything else is looked at or done
         dx = self._spacing_column(dx)
-        N, _, H, W = rhs.shape
+        N, H, W = rhs_hw.shape
         S = self.store
         S.refresh_bn()
-        if self.density_input:
-            stack = rhs.contiguous()
-            rhs_hw, rho_hw = stack[:, 0].contiguous(), stack[:, 1].contiguous()      # the one-channel fields Scaling and the smoother read
-            x = ops.assemble_density_input(stack, self.use_positional_embeddings)
-        else:
-            rhs_hw = rhs.view(N, H, W)
-            x = ops.assemble_input(rhs_hw, self.use_positional_embeddings)
         # dense input [dx, Lx, Ly] (:193,:202): tiny (N,3) host-side assembly
         dense_inp = torch.cat([dx, dx * float(H - 1), dx * float(W - 1)], 1).contiguous()
         hint = None                                               # max|x| travels with the tensor from layer to layer (weight-gradient scaling)
@@ -795,11 +806,7 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
         if self.scaling is not None:
             x = self.scaling.forward(x, rhs_hw.view(N, H, W, 1), training=training)
         x = ops.bc_ring_edges_fwd(x, self.neumann_mask) if self.per_edge_bc else ops.bc_ring_fwd(x, self.neumann)     # :251
-        if self.postsmoother is not None and self.density_input:
-            x = self.postsmoother.forward(x, rhs_hw.view(N, H, W, 1), rho_hw.view(N, H, W, 1), dx, training=training)
-        elif self.postsmoother is not None:
-            x = self.postsmoother.forward(x, rhs_hw.view(N, H, W, 1), _dx_pair(dx), training=training)
-        return x.view(N, 1, H, W)
+        return self._smooth(x, rhs_hw, rho_hw, dx, training).view(N, 1, H, W)
 
     # ------------------------------------------------------------------ backward
     def backward(self, dpred):

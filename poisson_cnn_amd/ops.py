@@ -1009,37 +1009,40 @@ def jacobi_k_max(sy, sx):
     return int(_lib.load().pcnn_jacobi_fused_max_sweeps(int(sy), int(sx)))
 
 
+def _jacobi_fused_args(who, like, coef, stencil_sizes, neumann_mask):
+    """The shared part of jacobi_fused / jacobi_fused_bwd: (N, H, W, sy, sx) with `coef` checked against them, and which pair of entry points runs -
+    the mask as an int for the pcnn_jacobi_fused_bc_ ones, None for the frozen-band ones.  The calls themselves stay spelled out at the two call
+    sites, where tools/check_ctypes_calls.py reads them."""
+    N, H, W = like.shape[0], like.shape[1], like.shape[2]
+    sy, sx = int(stencil_sizes[0]), int(stencil_sizes[1])
+    if tuple(coef.shape) != (N, sy + sx + 1) or not coef.is_contiguous():
+        raise ValueError('%s: coef must be a contiguous (%d, %d) tensor' % (who, N, sy + sx + 1))
+    return (c_int(N), c_int(H), c_int(W), c_int(sy), c_int(sx)), (int(neumann_mask) if neumann_mask else None)
+
+
 def jacobi_fused(u, rhs, coef, stencil_sizes, n_sweeps, neumann_mask=0):
     """n_sweeps weighted-Jacobi sweeps of the cross-shaped stencil whose per-sample rows are `coef` (N, sy+sx+1): the H taps, the W taps (centres
     zero), 1 / diagonal.  u, rhs (N,H,W,1).  neumann_mask (bits as in bc_ring_edges_fwd) non-zero: after every sweep the frozen band is refreshed on
     its Neumann edges with the mirror image of the updated interior (pcnn_jacobi_fused_bc_fwd); 0: the band stays frozen, today's entry point."""
-    N, H, W = u.shape[0], u.shape[1], u.shape[2]
-    sy, sx = int(stencil_sizes[0]), int(stencil_sizes[1])
-    if tuple(coef.shape) != (N, sy + sx + 1) or not coef.is_contiguous():
-        raise ValueError('jacobi_fused: coef must be a contiguous (%d, %d) tensor' % (N, sy + sx + 1))
+    (N, H, W, sy, sx), mask = _jacobi_fused_args('jacobi_fused', u, coef, stencil_sizes, neumann_mask)
     u, rhs = u.contiguous(), rhs.contiguous()
     out = torch.empty_like(u)
-    if neumann_mask:
-        handle().call('pcnn_jacobi_fused_bc_fwd', c_int(N), c_int(H), c_int(W), c_int(sy), c_int(sx), _p(coef), _p(u), _p(rhs), c_int(n_sweeps),
-                      c_int(int(neumann_mask)), _p(out))
-        return out
-    handle().call('pcnn_jacobi_fused_fwd', c_int(N), c_int(H), c_int(W), c_int(sy), c_int(sx), _p(coef), _p(u), _p(rhs), c_int(n_sweeps), _p(out))
+    if mask is None:
+        handle().call('pcnn_jacobi_fused_fwd', N, H, W, sy, sx, _p(coef), _p(u), _p(rhs), c_int(n_sweeps), _p(out))
+    else:
+        handle().call('pcnn_jacobi_fused_bc_fwd', N, H, W, sy, sx, _p(coef), _p(u), _p(rhs), c_int(n_sweeps), c_int(mask), _p(out))
     return out
 
 
 def jacobi_fused_bwd(dout, coef, stencil_sizes, n_sweeps, neumann_mask=0):
     """The adjoint of jacobi_fused w.r.t. u."""
-    N, H, W = dout.shape[0], dout.shape[1], dout.shape[2]
-    sy, sx = int(stencil_sizes[0]), int(stencil_sizes[1])
-    if tuple(coef.shape) != (N, sy + sx + 1) or not coef.is_contiguous():
-        raise ValueError('jacobi_fused_bwd: coef must be a contiguous (%d, %d) tensor' % (N, sy + sx + 1))
+    (N, H, W, sy, sx), mask = _jacobi_fused_args('jacobi_fused_bwd', dout, coef, stencil_sizes, neumann_mask)
     dout = dout.contiguous()
     du = torch.empty_like(dout)
-    if neumann_mask:
-        handle().call('pcnn_jacobi_fused_bc_bwd', c_int(N), c_int(H), c_int(W), c_int(sy), c_int(sx), _p(coef), _p(dout), c_int(n_sweeps),
-                      c_int(int(neumann_mask)), _p(du))
-        return du
-    handle().call('pcnn_jacobi_fused_bwd', c_int(N), c_int(H), c_int(W), c_int(sy), c_int(sx), _p(coef), _p(dout), c_int(n_sweeps), _p(du))
+    if mask is None:
+        handle().call('pcnn_jacobi_fused_bwd', N, H, W, sy, sx, _p(coef), _p(dout), c_int(n_sweeps), _p(du))
+    else:
+        handle().call('pcnn_jacobi_fused_bc_bwd', N, H, W, sy, sx, _p(coef), _p(dout), c_int(n_sweeps), c_int(mask), _p(du))
     return du
 
 
@@ -1075,18 +1078,22 @@ def pi_loss_bwd(pred, rhs, kern, coef, dpred):
 
 
 # ----------------------------------------------------------------------------- variable-density training operators (csrc/varcoef_train.hip)
+def _one_channel_shape(who, t, what='fields'):
+    """(N, H, W) of a one-channel field given as (N,H,W), (N,1,H,W) or (N,H,W,1); `who` and `what` name the caller and its argument in the refusal."""
+    shape = [int(s) for s in t.shape]
+    if len(shape) == 4:
+        if shape[1] != 1 and shape[3] != 1:
+            raise ValueError('%s takes one-channel fields, got shape %s' % (who, tuple(shape)))
+        shape = [shape[0]] + (shape[2:] if shape[1] == 1 else shape[1:3])
+    if len(shape) != 3:
+        raise ValueError('%s: %s, got %s' % (who, what, tuple(t.shape)))
+    return tuple(shape)
+
+
 def _varcoef_fields(who, fields, dx):
     """Checks the one-channel fields of a variable-density call - name -> (N,H,W), (N,1,H,W) or (N,H,W,1) CUDA float32 tensor, all of one shape -
     and dx (N,) or (N,1) -> (N, H, W, contiguous fields in order, contiguous dx (N,))."""
-    first = next(iter(fields.values()))
-    shape = [int(s) for s in first.shape]
-    if len(shape) == 4:
-        if shape[1] != 1 and shape[3] != 1:
-            raise ValueError('%s takes one-channel fields, got shape %s' % (who, tuple(first.shape)))
-        shape = [shape[0]] + (shape[2:] if shape[1] == 1 else shape[1:3])
-    if len(shape) != 3:
-        raise ValueError('%s: fields must be (N,H,W), (N,1,H,W) or (N,H,W,1), got %s' % (who, tuple(first.shape)))
-    N, H, W = shape
+    N, H, W = _one_channel_shape(who, next(iter(fields.values())), 'fields must be (N,H,W), (N,1,H,W) or (N,H,W,1)')
     if H < 3 or W < 3:
         raise ValueError('%s: the grid needs at least 3 points per axis, got %d x %d' % (who, H, W))
     out = []
@@ -1161,14 +1168,7 @@ def error_stats(pred, target=None, rhs=None, dx=None):
     """(N, 8) per-sample statistics of a one-channel prediction (N,1,H,W) / (N,H,W) / (N,H,W,1) in one pass (pcnn_error_stats; columns: ERROR_STATS).
     e = pred - target, t = target over all points; r = 3 x 3 FD Laplacian of pred minus rhs, f = rhs over the interior, dx (N, 2) per axis.
     Without `target` the first five columns are 0, without `rhs` the last three."""
-    shape = [int(s) for s in pred.shape]
-    if len(shape) == 4:
-        if shape[1] != 1 and shape[3] != 1:
-            raise ValueError('error_stats takes one-channel fields, got shape %s' % (tuple(shape),))
-        shape = [shape[0]] + (shape[2:] if shape[1] == 1 else shape[1:3])
-    if len(shape) != 3:
-        raise ValueError('error_stats: pred must be (N,1,H,W), (N,H,W,1) or (N,H,W), got %s' % (tuple(pred.shape),))
-    N, H, W = shape
+    N, H, W = _one_channel_shape('error_stats', pred, 'pred must be (N,1,H,W), (N,H,W,1) or (N,H,W)')
     fields = {'pred': pred, 'target': target, 'rhs': rhs}
     for name, t in fields.items():
         if t is None:

@@ -342,3 +342,25 @@ def test_solver_args_normalisation(dx_form, edge_form, channel_axis, as_torch):
     assert tuple(got[1]['left'].shape) == (N, W) and tuple(got[1]['top'].shape) == (N, H)
     first = np.asarray(dx, dtype=np.float64).reshape(-1)[0] if dx_form == 'number' else np.asarray(dx, dtype=np.float64).reshape(N, -1)[:, 0]
     assert np.array_equal(got[2].numpy(), np.broadcast_to(np.float32(first), (N,)))
+
+
+def test_one_channel_shape_helper():
+    """The one shape normalisation behind ops.error_stats and the variable-density operators: the three accepted layouts of a one-channel field give
+    the same (N, H, W), and both refusals name the caller, in the words each caller used when it carried its own copy."""
+    import torch
+    from poisson_cnn_amd import ops
+    N, H, W = 2, 5, 7
+    layouts = [torch.zeros(N, H, W), torch.zeros(N, 1, H, W), torch.zeros(N, H, W, 1)]
+    assert [ops._one_channel_shape('f', t) for t in layouts] == [(N, H, W)] * 3
+    assert ops._one_channel_shape('f', torch.zeros(1, 1, 1, 1)) == (1, 1, 1)              # both channel axes are 1: read as (N,1,H,W)
+    with pytest.raises(ValueError, match=r'^varcoef_jacobi takes one-channel fields, got shape \(2, 3, 5, 7\)$'):
+        ops._one_channel_shape('varcoef_jacobi', torch.zeros(2, 3, 5, 7), 'fields must be (N,H,W), (N,1,H,W) or (N,H,W,1)')
+    with pytest.raises(ValueError, match=r'^varcoef_jacobi: fields must be \(N,H,W\), \(N,1,H,W\) or \(N,H,W,1\), got \(5, 7\)$'):
+        ops._one_channel_shape('varcoef_jacobi', torch.zeros(5, 7), 'fields must be (N,H,W), (N,1,H,W) or (N,H,W,1)')
+    # through the two callers: the shape is refused before anything asks for a device
+    with pytest.raises(ValueError, match=r'^error_stats takes one-channel fields, got shape \(2, 3, 5, 7\)$'):
+        ops.error_stats(torch.zeros(2, 3, 5, 7))
+    with pytest.raises(ValueError, match=r'^error_stats: pred must be \(N,1,H,W\), \(N,H,W,1\) or \(N,H,W\), got \(2, 5\)$'):
+        ops.error_stats(torch.zeros(2, 5))
+    with pytest.raises(ValueError, match=r'^varcoef_pi_loss_partials: fields must be \(N,H,W\), \(N,1,H,W\) or \(N,H,W,1\), got \(2, 5\)$'):
+        ops.varcoef_pi_loss_partials(torch.zeros(2, 5), torch.zeros(2, 5), torch.zeros(2, 5), torch.zeros(2))
