@@ -515,7 +515,7 @@ def _lead_shape(a, name, dims):
 
 
 def variable_density_poisson_solve(rho, rhses, boundaries, dx, dy=None, tol=1e-10, max_iterations=500, initial_guesses=None, check_every=8,
-                                   return_info=False, device=None):
+                                   return_info=False, device=None, check_start=False):
     """Solves div((1/rho) grad u) = f with Dirichlet data on the four edges, on the vertex-centred grid of multigrid_poisson_solve (same shapes
     and edge names: rhses (N,1,H,W) or (N,H,W); boundaries: dict with 'left'/'right' (N,W) and 'bottom'/'top' (N,H); dx one spacing per sample).
     rho (N,H,W) or (N,1,H,W) is given on every node, boundary nodes included, and must be positive.
@@ -530,7 +530,9 @@ def variable_density_poisson_solve(rho, rhses, boundaries, dx, dy=None, tol=1e-1
     max(beta) / min(beta), whatever the grid size).  A sample stops changing once ||r|| <= tol ||b||; the host looks at the convergence flags
     every `check_every` iterations, so max_iterations is rounded up to a multiple of check_every.  initial_guesses: optional (N,H,W) or
     (N,1,H,W) start values (read in fp64; only the interior is used).  A sample that has not converged when the iterations run out raises a
-    RuntimeWarning and is reported as converged = False.
+    RuntimeWarning and is reported as converged = False.  check_start=True also looks at the flags before the first iteration: a start that
+    already meets the tolerance then reports 0 iterations (by default the first look comes after check_every iterations); the solution is the
+    same, bit for bit.
 
     Returns soln (N,1,H,W) fp32; with return_info also a dict of per-sample numpy arrays `iterations` (a multiple of check_every), `converged`
     and `relative_residual` (||r|| / ||b|| of the recurrence)."""
@@ -566,7 +568,7 @@ def variable_density_poisson_solve(rho, rhses, boundaries, dx, dy=None, tol=1e-1
         g = initial_guesses if isinstance(initial_guesses, torch.Tensor) else torch.as_tensor(np.asarray(initial_guesses))
         x0 = g.to(device=dev, dtype=torch.float64).reshape(N, H, W).contiguous()
     soln, info = K.varcoef_pcg_solve(dens, r, b['left'], b['right'], b['bottom'], b['top'], d, tol=float(tol), max_iterations=int(max_iterations), x0=x0,
-                                     check_every=int(check_every))
+                                     check_every=int(check_every), check_start=bool(check_start))
     if not info['converged'].all():           # (a rho <= 0 or NaN on the device was refused inside, straight after the setup kernel's minimum)
         bad = np.flatnonzero(~info['converged'])
         warnings.warn('variable_density_poisson_solve: sample(s) %r not converged to tol = %g after %d iterations (relative residual %r)'

@@ -128,12 +128,14 @@ def varcoef_apply(rho, dx, p):
 VARCOEF_SCALARS = {'bb': 0, 'rr': 1, 'pq': 2, 'rho_min': 5}      # columns of the per-sample scalar table of pcnn_varcoef_pcg_* (8 doubles per sample)
 
 
-def varcoef_pcg_solve(rho, rhs, left, right, bottom, top, dx, tol=1e-10, max_iterations=500, x0=None, check_every=8):
+def varcoef_pcg_solve(rho, rhs, left, right, bottom, top, dx, tol=1e-10, max_iterations=500, x0=None, check_every=8, check_start=False):
     """Preconditioned conjugate gradients on the variable-density system (pcnn_varcoef_pcg_setup / _iterate / _finish).  rho, rhs (N,H,W),
     left/right (N,W), bottom/top (N,H), dx (N,): fp32 CUDA tensors; x0: optional (N,H,W) fp64 initial guess (its interior is used).
     The device runs check_every iterations per call; the host reads the N convergence flags between calls and nothing else.
     -> soln (N,H,W) fp32 and a dict of host arrays: iterations (the multiple of check_every at which the sample's flag was seen; for a sample that
     did not converge, all that were run), converged, relative_residual = ||r|| / ||b|| of the recurrence, rho_min.
+    check_start: also read the flags the setup launch raised for the start itself (||b - A x0|| <= tol ||b||): such a sample reports 0 iterations,
+    and no iteration is launched when every sample has one.  The solution's bits are the same either way - a flagged sample is frozen.
     A rho that is not positive everywhere (NaN included) raises ValueError straight after the setup launch."""
     N, H, W = rho.shape
     for name, t, shape in (('rho', rho, (N, H, W)), ('rhs', rhs, (N, H, W)), ('left', left, (N, W)), ('right', right, (N, W)), ('bottom', bottom, (N, H)),
@@ -157,7 +159,7 @@ def varcoef_pcg_solve(rho, rhs, left, right, bottom, top, dx, tol=1e-10, max_ite
     if not np.all(rho_min > 0):                                         # the setup kernel's minimum counts a NaN as -inf; nothing more is launched
         raise ValueError('rho must be positive everywhere (minimum per sample: %r)' % (rho_min.tolist(),))
     iterations = np.zeros(N, dtype=np.int64)
-    done = np.zeros(N, dtype=bool)
+    done = (flags.cpu().numpy() != 0) if check_start else np.zeros(N, dtype=bool)
     it = 0
     while it < max_iterations and not done.all():
         h.call('pcnn_varcoef_pcg_iterate', c_int(N), c_int(H), c_int(W), _p(rho), _p(dx), c_double(tol), c_int(it), c_int(check_every), _p(Sh), _p(lh),

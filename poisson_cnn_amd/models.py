@@ -910,6 +910,42 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
         """density_input: `rhs` is the [rhs, rho] stack and the residual columns of ops.error_stats are the constant-coefficient residual - they stay 0."""
         return _ModelBase._error_stats(pred, y_true, None if self.density_input else rhs, dx)
 
+    def solve(self, inputs, tol=1e-10, max_iterations=500, check_every=8, warm_start=True, compare_cold=False, return_info=False):
+        """The variable-density problem solved to `tol`, the conjugate-gradient iteration started from this model's prediction (DESIGN.md section
+        18).  inputs = [stack (N,2,H,W) = [rhs, rho], dx] as for call; the edges are zero, as the model's are.  Runs the inference-mode forward,
+        ops.varcoef_error_stats on the prediction, and dataset.variable_density_poisson_solve(rho, rhs, zero edges, dx, initial_guesses = the
+        prediction - None with warm_start=False -, tol, max_iterations, check_every).  Returns soln (N,1,H,W) fp32; with return_info also the
+        solver's dict (iterations, converged, relative_residual; a start that already meets tol reports 0 iterations) plus
+          prediction_relative_residual  sqrt(sum r^2 / sum f^2) of the prediction per sample, NaN where sum f^2 == 0 (the solver only uses the
+                                        prediction's interior, so this is the ||b - A x0|| / ||b|| it starts from when the prediction's edges are 0)
+          prediction_max_residual       max|r| per sample
+          cold_iterations               with compare_cold=True: the iterations of a second solve started at 0
+        How many iterations a prediction saves is measured (tools/bench_varcoef_warmstart.py), not promised.  Nothing in the model changes: no
+        BatchNormalization update, no gradient, no optimizer state."""
+        if not self.density_input:
+            raise ValueError('%s.solve() starts the iterative variable-density solve from a prediction and needs density_input=True; the '
+                             'constant-coefficient problem is solved directly by dataset.multigrid_poisson_solve, which needs no start' % self.model_name)
+        from . import dataset as D
+        stack, dx = inputs
+        stack, dx = _as_device(stack, self.device), _as_device(dx, self.device)
+        pred = self.call([stack, dx], training=False)              # refuses a malformed stack and spacing columns that differ
+        d = self._spacing_column(dx).reshape(-1)
+        N, _, H, W = stack.shape
+        rhs, rho = stack[:, 0].contiguous(), stack[:, 1].contiguous()
+        stats = ops.varcoef_error_stats(pred.to(torch.float32), rho, None, rhs, d)
+        zero = {k: torch.zeros((N, W if k in ('left', 'right') else H), dtype=torch.float32, device=self.device) for k in ('left', 'right', 'bottom', 'top')}
+        kw = dict(tol=tol, max_iterations=max_iterations, check_every=check_every, return_info=True, device=self.device, check_start=True)
+        soln, info = D.variable_density_poisson_solve(rho, rhs, zero, d, initial_guesses=pred if warm_start else None, **kw)
+        if not return_info:
+            return soln
+        s = stats.cpu().numpy().astype(np.float64)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            info['prediction_relative_residual'] = np.where(s[:, 7] > 0, np.sqrt(s[:, 5] / np.where(s[:, 7] > 0, s[:, 7], 1.0)), np.nan)
+        info['prediction_max_residual'] = s[:, 6]
+        if compare_cold:
+            info['cold_iterations'] = info['iterations'] if not warm_start else D.variable_density_poisson_solve(rho, rhs, zero, d, **kw)[1]['iterations']
+        return soln, info
+
     def _dummy_batch(self, shape):
         N, H, W = shape
         g = torch.Generator(device='cpu').manual_seed(0)

@@ -1190,6 +1190,38 @@ def error_stats(pred, target=None, rhs=None, dx=None):
     return out
 
 
+def varcoef_error_stats(pred, rho, target=None, rhs=None, dx=None):
+    """error_stats for the variable-density problem (pcnn_varcoef_error_stats; columns: ERROR_STATS; the same three layouts of a one-channel
+    field).  r = the flux-form operator div((1/rho) grad .) of DESIGN.md section 16 applied to pred - its own edge values are the Dirichlet
+    neighbours - minus rhs, over the interior; dx: one spacing per sample, (N,) or (N,1).  With zero edge values, and only then,
+    sqrt(sum_r2 / sum_f2) is the relative residual ||b - A x|| / ||b|| variable_density_poisson_solve would start from.  Without `target` the
+    first five columns are 0; without `rhs` the last three, and rho and dx are not read."""
+    who = 'varcoef_error_stats'
+    N, H, W = _one_channel_shape(who, pred, 'pred must be (N,1,H,W), (N,H,W,1) or (N,H,W)')
+    fields = {'pred': pred, 'target': target, 'rho': rho if rhs is not None else None, 'rhs': rhs}
+    if rhs is not None and rho is None:
+        raise ValueError('%s: rhs needs rho' % who)
+    for name, t in fields.items():
+        if t is None:
+            continue
+        if t.dtype != torch.float32 or not t.is_cuda or t.numel() != N * H * W:
+            raise ValueError('%s: %s must be a CUDA float32 tensor with the %d x %d x %d points of pred' % (who, name, N, H, W))
+        fields[name] = t.contiguous()
+    if rhs is not None:
+        if dx is None:
+            raise ValueError('%s: rhs needs dx' % who)
+        dx = dx.to(device=pred.device, dtype=torch.float32)
+        if dx.numel() != N:
+            raise ValueError('%s: dx must hold one spacing per sample (%d values), got shape %s' % (who, N, tuple(dx.shape)))
+        dx = dx.reshape(N).contiguous()
+    else:
+        dx = None
+    out = empty((N, 8), pred.device)
+    handle().call('pcnn_varcoef_error_stats', c_int(N), c_int(H), c_int(W), _p(fields['pred']), _p(fields['target']), _p(fields['rho']), _p(fields['rhs']),
+                  _p(dx), _p(out))
+    return out
+
+
 def adam_step(w, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0, vhat=None):
     weights_changed()                                                 # a raw-pointer write torch does not count: cached filter spectra go stale
     handle().call('pcnn_adam_amsgrad_step', c_int64(w.numel()), _p(w), _p(g), _p(m), _p(v), _p(vhat), c_float(lr), c_float(beta1), c_float(beta2),
