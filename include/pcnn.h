@@ -691,8 +691,8 @@ int pcnn_varcoef_jacobi_max_sweeps(void);
 /* out[n,y,x,0:2] = {stack[n,0,y,x], stack[n,1,y,x]} of the generator's (N,2,H,W) stack [rhs, rho], followed - use_pos - by the two positional
  * channels of pcnn_assemble_input; ldo >= 2 (4 with use_pos). */
 int pcnn_assemble_density_input(pcnn_handle h, int N, int H, int W, const float* stack, int use_pos, float* out, int ldo);
-/* Error statistics of a prediction of the variable-density problem in one pass over the four fields (csrc/varcoef_stats.hip, DESIGN.md section
- * 18).  out[8n..8n+7] has the layout of pcnn_error_stats, {sum|e|, sum e^2, max|e|, sum t^2, max|t|, sum r^2, max|r|, sum f^2}: e = pred - target
+/* Error statistics of a prediction of the variable-density problem in one pass over the four fields (csrc/error_stats.hip: the kernel of
+ * pcnn_error_stats with the flux-form residual of csrc/flux_form.h, the one pcnn_varcoef_pi_loss_partials sums).  out[8n..8n+7] has the layout of pcnn_error_stats, {sum|e|, sum e^2, max|e|, sum t^2, max|t|, sum r^2, max|r|, sum f^2}: e = pred - target
  * and t = target over all H W points; f = rhs[i,j] and
  *   r[i,j] = (L pred)[i,j] - rhs[i,j],  L the flux-form operator above with dx[n], pred's own edge values as the Dirichlet neighbours,
  * over the (H-2)(W-2) interior points, in fp32.  With zero edge values - and only then - sum r^2 / sum f^2 is ||b - A x||^2 / ||b||^2 of the

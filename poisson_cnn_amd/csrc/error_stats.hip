@@ -1,7 +1,14 @@
-// Per-sample error statistics of a prediction in one pass over pred, target and rhs (evaluate / predict / validation):
+// Per-sample error statistics of a prediction in one pass over pred, target and rhs (evaluate / predict / validation, DESIGN.md section 14;
+// model.solve of the variable-density problem, section 18):
 // out[n] = {sum|e|, sum e^2, max|e|, sum t^2, max|t|, sum r^2, max|r|, sum f^2}, e = pred - target, t = target over all H W points;
-// r = the 3 x 3 second-order FD Laplacian of pred minus rhs, f = rhs over the (H-2)(W-2) interior points.
-#include "pcnn_internal.h"
+// r = the residual of pred against rhs, f = rhs over the (H-2)(W-2) interior points.  One kernel, two residuals:
+//   pcnn_error_stats:          the 3 x 3 second-order FD Laplacian of pred minus rhs, one spacing per sample and axis (FivePoint);
+//   pcnn_varcoef_error_stats:  the flux-form operator of div((1/rho) grad u) = f applied to pred, minus rhs (FluxForm: pcnn_flux_residual of
+//                              flux_form.h, the one the training loss uses).  The prediction's own edge values act as the Dirichlet neighbours of r.
+//                              Only with zero (homogeneous) edge values is sum r^2 / sum f^2 the ||b - A x||^2 / ||b||^2 of the conjugate-gradient
+//                              solve: with other edge values b holds the boundary terms and sum f^2 is not ||b||^2.
+// No atomics, a fixed order everywhere: equal inputs give equal bits.
+#include "flux_form.h"
 
 namespace {
 
@@ -21,13 +28,44 @@ __device__ __forceinline__ float es_wave_reduce(float v, bool mx) {
 
 __device__ __forceinline__ bool es_is_max(int k) { return k == 2 || k == 4 || k == 6; }
 
+// The residual r at an interior point, built per sample from (n, H, W, pointers); dx is null where rhs is not given, and then neither dx nor rho
+// is read.  at(row, x, p, f): row = y W, p = pred there, f = rhs there.
+struct FivePoint {                                 // dx (N, 2): column 0 the H axis
+  static constexpr bool uses_rho = false;
+  const float* pn;
+  int W;
+  float ay = 0.f, ax = 0.f;
+  __device__ __forceinline__ FivePoint(int n, int H, int W_, const float* pn_, const float* rho, const float* dx) : pn(pn_), W(W_) {
+    if (dx) { ay = 1.0f / (dx[2 * n] * dx[2 * n]); ax = 1.0f / (dx[2 * n + 1] * dx[2 * n + 1]); }
+  }
+  __device__ __forceinline__ float at(int64_t row, int x, float p, float f) const {
+    return (pn[row - W + x] - 2.0f * p + pn[row + W + x]) * ay + (pn[row + x - 1] - 2.0f * p + pn[row + x + 1]) * ax - f;
+  }
+};
+struct FluxForm {                                  // dx (N,): dy = dx; rho is read here alone: with rhs, on interior points and their neighbours
+  static constexpr bool uses_rho = true;
+  const float* pn;
+  const float* dn;
+  int W;
+  float inv_h2 = 0.f;
+  __device__ __forceinline__ FluxForm(int n, int H, int W_, const float* pn_, const float* rho, const float* dx)
+      : pn(pn_), dn(dx ? rho + (int64_t)n * H * W_ : nullptr), W(W_) {
+    if (dx) inv_h2 = 1.0f / (dx[n] * dx[n]);
+  }
+  __device__ __forceinline__ float at(int64_t row, int x, float p, float f) const {
+    return pcnn_flux_residual(p, dn[row + x], pn[row - W + x], dn[row - W + x], pn[row + W + x], dn[row + W + x], pn[row + x - 1], dn[row + x - 1],
+                              pn[row + x + 1], dn[row + x + 1], inv_h2, f);
+  }
+};
+
 // grid (ES_BANDS, N): workgroup (b, n) owns rows [b rpb, (b + 1) rpb) of sample n, rpb = ceil(H / ES_BANDS).  Wave w takes the band's rows w, w + 16,
-// ...; its lanes stride over the columns, so every load of a row is one coalesced request.  The stencil's neighbours are plain loads of the rows above
-// and below: inside a band they hit the lines the neighbouring wave just fetched, across a band edge they come from L2.  A neighbour row is touched
-// only for 0 < y < H - 1, so every index stays inside sample n.
-__global__ __launch_bounds__(ES_WAVES * 64) void error_stats_partials_kernel(int H, int W, const float* __restrict__ pred, const float* __restrict__ tgt,
-                                                                             const float* __restrict__ rhs, const float* __restrict__ dx,
-                                                                             float* __restrict__ part) {
+// ...; its lanes stride over the columns, so every load of a row is one coalesced request.  The residual's neighbours are plain loads of the rows
+// above and below: inside a band they hit the lines the neighbouring wave just fetched, across a band edge they come from L2.  A neighbour is
+// loaded only for 0 < y < H - 1 and 0 < x < W - 1, so every index stays inside sample n.
+template <class Residual>
+__global__ __launch_bounds__(ES_WAVES * 64) void stats_partials_kernel(int H, int W, const float* __restrict__ pred, const float* __restrict__ tgt,
+                                                                       const float* __restrict__ rho, const float* __restrict__ rhs,
+                                                                       const float* __restrict__ dx, float* __restrict__ part) {
   __shared__ float red[ES_WAVES][ES_STATS];
   const int n = blockIdx.y, b = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int rpb = (H + ES_BANDS - 1) / ES_BANDS;
@@ -36,8 +74,7 @@ __global__ __launch_bounds__(ES_WAVES * 64) void error_stats_partials_kernel(int
   const float* pn = pred + base;
   const float* tn = tgt ? tgt + base : nullptr;
   const float* fn = rhs ? rhs + base : nullptr;
-  float ay = 0.f, ax = 0.f;
-  if (fn) { ay = 1.0f / (dx[2 * n] * dx[2 * n]); ax = 1.0f / (dx[2 * n + 1] * dx[2 * n + 1]); }
+  const Residual res(n, H, W, pn, rho, fn ? dx : nullptr);
   float s_ae = 0.f, s_e2 = 0.f, m_e = 0.f, s_t2 = 0.f, m_t = 0.f, s_r2 = 0.f, m_r = 0.f, s_f2 = 0.f;
   for (int y = y0 + wv; y < y1; y += ES_WAVES) {
     const int64_t row = (int64_t)y * W;
@@ -50,8 +87,7 @@ __global__ __launch_bounds__(ES_WAVES * 64) void error_stats_partials_kernel(int
         s_t2 += t * t; m_t = fmaxf(m_t, fabsf(t));
       }
       if (yin && x > 0 && x < W - 1) {
-        const float f = fn[row + x];
-        const float r = (pn[row - W + x] - 2.0f * p + pn[row + W + x]) * ay + (pn[row + x - 1] - 2.0f * p + pn[row + x + 1]) * ax - f;
+        const float f = fn[row + x], r = res.at(row, x, p, f);
         s_r2 += r * r; m_r = fmaxf(m_r, fabsf(r)); s_f2 += f * f;
       }
     }
@@ -73,7 +109,7 @@ __global__ __launch_bounds__(ES_WAVES * 64) void error_stats_partials_kernel(int
 }
 
 // one wave per sample: lane b holds band b's partials, the same butterfly combines them
-__global__ __launch_bounds__(64) void error_stats_final_kernel(const float* __restrict__ part, float* __restrict__ out) {
+__global__ __launch_bounds__(64) void stats_final_kernel(const float* __restrict__ part, float* __restrict__ out) {
   const int n = blockIdx.x, lane = threadIdx.x;
   const float* p = part + ((int64_t)n * ES_BANDS + lane) * ES_STATS;
 #pragma unroll
@@ -83,19 +119,32 @@ __global__ __launch_bounds__(64) void error_stats_final_kernel(const float* __re
   }
 }
 
+// the argument checks (each in the caller's name) and the two launches of both entry points
+template <class Residual>
+int stats_launch(pcnn_handle h, const char* who, int N, int H, int W, const float* pred, const float* target, const float* rho, const float* rhs, const float* dx,
+                 float* out) {
+  PCNN_REQUIRE(h, h && pred && out, "%s: null argument", who);
+  PCNN_REQUIRE(h, N >= 1 && N <= 65535 && H >= 1 && W >= 1, "%s: bad shape %d x %d x %d (1 <= N <= 65535)", who, N, H, W);
+  PCNN_REQUIRE(h, !Residual::uses_rho || !rhs || rho, "%s: rhs needs rho", who);
+  PCNN_REQUIRE(h, !rhs || dx, "%s: rhs needs dx", who);
+  PCNN_REQUIRE(h, !rhs || (H >= 3 && W >= 3), "%s: the residual needs H, W >= 3 (got %d x %d)", who, H, W);
+  static_assert(ES_BANDS == 64, "stats_final_kernel combines one band per lane of a wave");
+  const size_t need = (size_t)N * ES_BANDS * ES_STATS * sizeof(float);
+  if (pcnn_reserve(h, h->scratch, need, PCNN_SCRATCH_FLOOR, who)) return 1;
+  float* part = static_cast<float*>(h->scratch.p);
+  hipLaunchKernelGGL(stats_partials_kernel<Residual>, dim3(ES_BANDS, N), dim3(ES_WAVES * 64), 0, h->stream, H, W, pred, target, rho, rhs, dx, part);
+  hipLaunchKernelGGL(stats_final_kernel, dim3(N), dim3(64), 0, h->stream, part, out);
+  PCNN_CHECK_LAUNCH(h, who);
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int pcnn_error_stats(pcnn_handle h, int N, int H, int W, const float* pred, const float* target, const float* rhs, const float* dx, float* out) {
-  PCNN_REQUIRE(h, h && pred && out, "pcnn_error_stats: null argument");
-  PCNN_REQUIRE(h, N >= 1 && N <= 65535 && H >= 1 && W >= 1, "pcnn_error_stats: bad shape %d x %d x %d (1 <= N <= 65535)", N, H, W);
-  PCNN_REQUIRE(h, !rhs || dx, "pcnn_error_stats: rhs needs dx");
-  PCNN_REQUIRE(h, !rhs || (H >= 3 && W >= 3), "pcnn_error_stats: the residual needs H, W >= 3 (got %d x %d)", H, W);
-  static_assert(ES_BANDS == 64, "error_stats_final_kernel combines one band per lane of a wave");
-  const size_t need = (size_t)N * ES_BANDS * ES_STATS * sizeof(float);
-  if (pcnn_reserve(h, h->scratch, need, PCNN_SCRATCH_FLOOR, "pcnn_error_stats")) return 1;
-  float* part = static_cast<float*>(h->scratch.p);
-  hipLaunchKernelGGL(error_stats_partials_kernel, dim3(ES_BANDS, N), dim3(ES_WAVES * 64), 0, h->stream, H, W, pred, target, rhs, dx, part);
-  hipLaunchKernelGGL(error_stats_final_kernel, dim3(N), dim3(64), 0, h->stream, part, out);
-  PCNN_CHECK_LAUNCH(h, "pcnn_error_stats");
-  return 0;
+  return stats_launch<FivePoint>(h, "pcnn_error_stats", N, H, W, pred, target, nullptr, rhs, dx, out);
+}
+
+extern "C" int pcnn_varcoef_error_stats(pcnn_handle h, int N, int H, int W, const float* pred, const float* target, const float* rho, const float* rhs,
+                                        const float* dx, float* out) {
+  return stats_launch<FluxForm>(h, "pcnn_varcoef_error_stats", N, H, W, pred, target, rho, rhs, dx, out);
 }

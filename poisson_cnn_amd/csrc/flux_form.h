@@ -1,0 +1,31 @@
+// The discretisation of the variable-density problem div((1/rho) grad u) = f, once: the face coefficient, the fp32 flux-form
+// residual, and the 16 x 64 tile with its LDS node loader.  varcoef.hip (fp64 solve), varcoef_train.hip (loss, smoother) and error_stats.hip
+// (statistics) all take them from here.  The fp64 operator of the solve (stencil_at in varcoef.hip) is NOT here on purpose: it sums
+// ((a + b) + c) + d of pc - neighbour, the fp32 residual below (a + b) + (c + d) of neighbour - pc - two roundings, both pinned by goldens.
+#pragma once
+#include "pcnn_internal.h"
+
+// the tile of the per-tile kernels: FLUX_ROWS x FLUX_COLS nodes by FLUX_THREADS threads, a column and FLUX_RPT consecutive rows per thread
+constexpr int FLUX_ROWS = 16, FLUX_COLS = 64, FLUX_THREADS = 256, FLUX_RPT = FLUX_ROWS / (FLUX_THREADS / FLUX_COLS);
+
+// the coefficient of the face between two nodes: the harmonic mean of their 1 / rho
+template <class T>
+__device__ __forceinline__ T pcnn_beta_face(T a, T b) { return T(2) / (a + b); }
+
+// (L u - rhs) at an interior node: uc / rc the node's u / rho, (u?, r?) its four neighbours towards i-1, i+1, j-1, j+1.  Operation order, all fp32,
+// no contraction:  b_k = 2 / (rc + r_k),  d_k = u_k - uc,  s = (b_0 d_0 + b_1 d_1) + (b_2 d_2 + b_3 d_3),  r = s * inv_h2 - f
+__device__ __forceinline__ float pcnn_flux_residual(float uc, float rc, float u0, float r0, float u1, float r1, float u2, float r2, float u3, float r3,
+                                                    float inv_h2, float f) {
+  const float s = (pcnn_beta_face(rc, r0) * (u0 - uc) + pcnn_beta_face(rc, r1) * (u1 - uc)) +
+                  (pcnn_beta_face(rc, r2) * (u2 - uc) + pcnn_beta_face(rc, r3) * (u3 - uc));
+  return s * inv_h2 - f;
+}
+
+// nodes (I0 .. I0+LR-1) x (J0 .. J0+LC-1) of one sample's H x W field into LDS by the FLUX_THREADS threads; nodes outside the field read `fill`
+template <int LR, int LC, class T>
+__device__ __forceinline__ void pcnn_load_nodes(T (*t)[LC], const T* __restrict__ src, int H, int W, int I0, int J0, T fill) {
+  for (int e = threadIdx.x; e < LR * LC; e += FLUX_THREADS) {
+    const int r = e / LC, c = e % LC, i = I0 + r, j = J0 + c;
+    t[r][c] = (i >= 0 && i < H && j >= 0 && j < W) ? src[(int64_t)i * W + j] : fill;
+  }
+}

@@ -35,16 +35,20 @@ __device__ __forceinline__ float pcnn_act_grad_from_out(float a, int act, float 
   }
 }
 
-// red[0] <- the sum of red[0 .. THREADS) by the plain halving tree, a barrier per level; the caller's barrier after filling red comes first.
-// Every thread of the block calls it with its index.  The order of the additions is fixed, so the same values give the same bits.
-template <class T, int THREADS>
-__device__ __forceinline__ void pcnn_block_sum(T* red, int tid) {
+// red[0] <- op over red[0 .. THREADS) by the plain halving tree, a barrier per level; the caller's barrier after filling red comes first.
+// Every thread of the block calls it with its index.  The order of the operations is fixed, so the same values give the same bits.
+template <class T, int THREADS, class Op>
+__device__ __forceinline__ void pcnn_block_reduce(T* red, int tid, Op op) {
 #pragma unroll
   for (int s = THREADS / 2; s > 0; s >>= 1) {
-    if (tid < s) red[tid] += red[tid + s];
+    if (tid < s) red[tid] = op(red[tid], red[tid + s]);
     __syncthreads();
   }
 }
+struct pcnn_sum_op { template <class T> __device__ __forceinline__ T operator()(T a, T b) const { return a + b; } };
+struct pcnn_min_op { __device__ __forceinline__ double operator()(double a, double b) const { return fmin(a, b); } };
+template <class T, int THREADS>
+__device__ __forceinline__ void pcnn_block_sum(T* red, int tid) { pcnn_block_reduce<T, THREADS>(red, tid, pcnn_sum_op()); }
 
 // a 1-D grid of `block`-thread blocks over `total` items, at most maxb of them (grid-stride kernels take the rest), at least one
 static inline dim3 pcnn_grid1d(int64_t total, int block, int maxb) {

@@ -8,18 +8,20 @@
 // (fixed tree) reduced per sample by a second one-block stage in a fixed order, so results do not depend on the batch a sample is solved in.
 // The face coefficients are built on the fly from an LDS tile of rho with a one-point halo: 20 B per point and product (p 8, rho 4, q 8) against
 // 32 B with two fp64 face arrays built once per solve (p 8, faces 16, q 8).
+// The face coefficient, the 16 x 64 tile and the LDS node loader are flux_form.h's, shared with varcoef_train.hip and error_stats.hip; the fp64
+// operator sum (stencil_at) is this file's alone: its order ((a + b) + c) + d of pc - neighbour is not the fp32 residual's.
 #include <math.h>
-#include "pcnn_internal.h"
+#include <type_traits>
+#include "flux_form.h"
 
 namespace {
 
-constexpr int VT_ROWS = 16, VT_COLS = 64, VT_THREADS = 256, VT_RPT = VT_ROWS / (VT_THREADS / VT_COLS);   // tile of interior points; RPT: rows per thread
-constexpr int VT_LR = VT_ROWS + 2, VT_LC = VT_COLS + 2;                                                  // ... with its halo
+constexpr int VT_LR = FLUX_ROWS + 2, VT_LC = FLUX_COLS + 2;                                               // the tile of interior points with its halo
 constexpr int EW_THREADS = 256, EW_POINTS = 2048, EW_MAX_BLOCKS = 1024;                                   // element-wise kernels: blocks per SAMPLE
 // per-sample scalars (doubles) of the solve
 enum { VS_BB = 0, VS_RR = 1, VS_PQ = 2, VS_RZ0 = 3, VS_RZ1 = 4, VS_RHOMIN = 5, VS_STRIDE = 8 };
 
-static inline int vc_tiles(int H, int W) { return pcnn_cdiv(H - 2, VT_ROWS) * pcnn_cdiv(W - 2, VT_COLS); }
+static inline int vc_tiles(int H, int W) { return pcnn_cdiv(H - 2, FLUX_ROWS) * pcnn_cdiv(W - 2, FLUX_COLS); }
 static inline int vc_ew_blocks(int64_t per) {
   const int64_t b = pcnn_cdiv64(per, EW_POINTS);
   return (int)(b < 1 ? 1 : (b > EW_MAX_BLOCKS ? EW_MAX_BLOCKS : b));
@@ -39,7 +41,7 @@ static inline VcWs vc_layout(void* ws, int N, int H, int W) {
   return l;
 }
 
-// sum over the block's threads by a fixed tree; every thread gets the total
+// sum over the block's threads by the fixed tree of pcnn_block_reduce; every thread gets the total
 template <int T>
 __device__ __forceinline__ double block_sum(double v, double* red) {
   const int t = threadIdx.x;
@@ -53,7 +55,7 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
 // rho on nodes (I0 .. I0+17) x (J0 .. J0+65): the tile's nodes I0+1.., J0+1.. and their halo.  Nodes beyond the grid read 1 (never used by a stored point).
 __device__ __forceinline__ float load_rho_tile(float (*rs)[VT_LC], const float* __restrict__ rho_n, int H, int W, int I0, int J0) {
   float mn = INFINITY;
-  for (int e = threadIdx.x; e < VT_LR * VT_LC; e += VT_THREADS) {
+  for (int e = threadIdx.x; e < VT_LR * VT_LC; e += FLUX_THREADS) {
     const int r = e / VT_LC, c = e % VT_LC, i = I0 + r, j = J0 + c;
     float v = 1.f;
     if (i < H && j < W) {
@@ -70,10 +72,10 @@ struct Faces { double lo_i, hi_i, lo_j, hi_j; };
 __device__ __forceinline__ Faces faces_at(const float (*rs)[VT_LC], int r, int c) {
   const double rc = (double)rs[r + 1][c + 1];
   Faces f;
-  f.lo_i = 2.0 / (rc + (double)rs[r][c + 1]);
-  f.hi_i = 2.0 / (rc + (double)rs[r + 2][c + 1]);
-  f.lo_j = 2.0 / (rc + (double)rs[r + 1][c]);
-  f.hi_j = 2.0 / (rc + (double)rs[r + 1][c + 2]);
+  f.lo_i = pcnn_beta_face(rc, (double)rs[r][c + 1]);
+  f.hi_i = pcnn_beta_face(rc, (double)rs[r + 2][c + 1]);
+  f.lo_j = pcnn_beta_face(rc, (double)rs[r + 1][c]);
+  f.hi_j = pcnn_beta_face(rc, (double)rs[r + 1][c + 2]);
   return f;
 }
 __device__ __forceinline__ double stencil_at(const Faces& f, const double (*ps)[VT_LC], int r, int c, double inv_h2) {
@@ -82,26 +84,23 @@ __device__ __forceinline__ double stencil_at(const Faces& f, const double (*ps)[
 }
 
 // q = A p and the tile's share of p.q.  grid (column tiles, row tiles, N); part[n][tile]
-__global__ __launch_bounds__(VT_THREADS) void varcoef_apply_kernel(int H, int W, int cap, const float* __restrict__ rho, const float* __restrict__ dx,
-                                                                   const double* __restrict__ p, double* __restrict__ q, double* __restrict__ part) {
+__global__ __launch_bounds__(FLUX_THREADS) void varcoef_apply_kernel(int H, int W, int cap, const float* __restrict__ rho, const float* __restrict__ dx,
+                                                                     const double* __restrict__ p, double* __restrict__ q, double* __restrict__ part) {
   __shared__ float rs[VT_LR][VT_LC];
   __shared__ double ps[VT_LR][VT_LC];
-  __shared__ double red[VT_THREADS];
-  const int nh = H - 2, nw = W - 2, n = blockIdx.z, I0 = blockIdx.y * VT_ROWS, J0 = blockIdx.x * VT_COLS;
+  __shared__ double red[FLUX_THREADS];
+  const int nh = H - 2, nw = W - 2, n = blockIdx.z, I0 = blockIdx.y * FLUX_ROWS, J0 = blockIdx.x * FLUX_COLS;
   const int64_t per = (int64_t)nh * nw;
   const double* pn = p + (int64_t)n * per;
   load_rho_tile(rs, rho + (int64_t)n * H * W, H, W, I0, J0);
-  for (int e = threadIdx.x; e < VT_LR * VT_LC; e += VT_THREADS) {
-    const int r = e / VT_LC, c = e % VT_LC, ii = I0 + r - 1, jj = J0 + c - 1;     // interior indices; zero Dirichlet data outside
-    ps[r][c] = (ii >= 0 && ii < nh && jj >= 0 && jj < nw) ? pn[(int64_t)ii * nw + jj] : 0.0;
-  }
+  pcnn_load_nodes<VT_LR, VT_LC>(ps, pn, nh, nw, I0 - 1, J0 - 1, 0.0);               // interior indices; zero Dirichlet data outside
   __syncthreads();
   const double h = (double)dx[n], inv_h2 = 1.0 / (h * h);
-  const int c = threadIdx.x % VT_COLS, r0 = (threadIdx.x / VT_COLS) * VT_RPT;
+  const int c = threadIdx.x % FLUX_COLS, r0 = (threadIdx.x / FLUX_COLS) * FLUX_RPT;
   double s = 0.0;
   if (J0 + c < nw) {
 #pragma unroll
-    for (int k = 0; k < VT_RPT; ++k) {
+    for (int k = 0; k < FLUX_RPT; ++k) {
       const int r = r0 + k;
       if (I0 + r < nh) {
         const double v = stencil_at(faces_at(rs, r, c), ps, r, c, inv_h2);
@@ -110,34 +109,34 @@ __global__ __launch_bounds__(VT_THREADS) void varcoef_apply_kernel(int H, int W,
       }
     }
   }
-  const double tot = block_sum<VT_THREADS>(s, red);
+  const double tot = block_sum<FLUX_THREADS>(s, red);
   if (threadIdx.x == 0) part[(int64_t)n * cap + blockIdx.y * gridDim.x + blockIdx.x] = tot;
 }
 
 // Start of a solve: b from f, rho, the four boundary arrays and dx; x = x0 (interior of the optional initial guess, else 0); r = b - A x0; the tile's
 // shares of b.b and r.r and its minimum of rho.  left/right (N,W): values on rows 0 / H-1; bottom/top (N,H): values on columns 0 / W-1.
-__global__ __launch_bounds__(VT_THREADS) void varcoef_setup_kernel(int H, int W, int cap, int N, const float* __restrict__ rho, const float* __restrict__ f,
-                                                                   const float* __restrict__ left, const float* __restrict__ right,
-                                                                   const float* __restrict__ bottom, const float* __restrict__ top,
-                                                                   const float* __restrict__ dx, const double* __restrict__ x0, double* __restrict__ x,
-                                                                   double* __restrict__ rr_out, double* __restrict__ part) {
+__global__ __launch_bounds__(FLUX_THREADS) void varcoef_setup_kernel(int H, int W, int cap, int N, const float* __restrict__ rho, const float* __restrict__ f,
+                                                                     const float* __restrict__ left, const float* __restrict__ right,
+                                                                     const float* __restrict__ bottom, const float* __restrict__ top,
+                                                                     const float* __restrict__ dx, const double* __restrict__ x0, double* __restrict__ x,
+                                                                     double* __restrict__ rr_out, double* __restrict__ part) {
   __shared__ float rs[VT_LR][VT_LC];
   __shared__ double ps[VT_LR][VT_LC];
-  __shared__ double red[VT_THREADS];
-  const int nh = H - 2, nw = W - 2, n = blockIdx.z, I0 = blockIdx.y * VT_ROWS, J0 = blockIdx.x * VT_COLS;
+  __shared__ double red[FLUX_THREADS];
+  const int nh = H - 2, nw = W - 2, n = blockIdx.z, I0 = blockIdx.y * FLUX_ROWS, J0 = blockIdx.x * FLUX_COLS;
   const int64_t per = (int64_t)nh * nw;
   const float mn = load_rho_tile(rs, rho + (int64_t)n * H * W, H, W, I0, J0);
-  for (int e = threadIdx.x; e < VT_LR * VT_LC; e += VT_THREADS) {
+  for (int e = threadIdx.x; e < VT_LR * VT_LC; e += FLUX_THREADS) {
     const int r = e / VT_LC, c = e % VT_LC, ii = I0 + r - 1, jj = J0 + c - 1;
     ps[r][c] = (x0 && ii >= 0 && ii < nh && jj >= 0 && jj < nw) ? x0[((int64_t)n * H + ii + 1) * W + jj + 1] : 0.0;
   }
   __syncthreads();
   const double h = (double)dx[n], inv_h2 = 1.0 / (h * h);
-  const int c = threadIdx.x % VT_COLS, r0 = (threadIdx.x / VT_COLS) * VT_RPT;
+  const int c = threadIdx.x % FLUX_COLS, r0 = (threadIdx.x / FLUX_COLS) * FLUX_RPT;
   double sbb = 0.0, srr = 0.0;
   if (J0 + c < nw) {
 #pragma unroll
-    for (int k = 0; k < VT_RPT; ++k) {
+    for (int k = 0; k < FLUX_RPT; ++k) {
       const int r = r0 + k, ii = I0 + r, jj = J0 + c;
       if (ii < nh) {
         const Faces fc = faces_at(rs, r, c);
@@ -156,16 +155,12 @@ __global__ __launch_bounds__(VT_THREADS) void varcoef_setup_kernel(int H, int W,
     }
   }
   const int tile = blockIdx.y * gridDim.x + blockIdx.x;
-  const double tbb = block_sum<VT_THREADS>(sbb, red);
-  const double trr = block_sum<VT_THREADS>(srr, red);
+  const double tbb = block_sum<FLUX_THREADS>(sbb, red);
+  const double trr = block_sum<FLUX_THREADS>(srr, red);
   __syncthreads();
   red[threadIdx.x] = (double)mn;
   __syncthreads();
-#pragma unroll
-  for (int s = VT_THREADS / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] = fmin(red[threadIdx.x], red[threadIdx.x + s]);
-    __syncthreads();
-  }
+  pcnn_block_reduce<double, FLUX_THREADS>(red, threadIdx.x, pcnn_min_op());
   if (threadIdx.x == 0) {
     part[(int64_t)n * cap + tile] = tbb;
     part[((int64_t)N + n) * cap + tile] = trr;
@@ -179,19 +174,13 @@ template <int OP>
 __global__ __launch_bounds__(EW_THREADS) void varcoef_reduce_kernel(int count, int cap, const double* __restrict__ part, double* __restrict__ out,
                                                                     int stride, int slot, int check, double tol2, int* __restrict__ flags) {
   __shared__ double red[EW_THREADS];
+  const std::conditional_t<OP != 0, pcnn_min_op, pcnn_sum_op> op{};
   const int n = blockIdx.x, t = threadIdx.x;
   double v = OP ? (double)INFINITY : 0.0;
-  for (int k = t; k < count; k += EW_THREADS) {
-    const double a = part[(int64_t)n * cap + k];
-    v = OP ? fmin(v, a) : v + a;
-  }
+  for (int k = t; k < count; k += EW_THREADS) v = op(v, part[(int64_t)n * cap + k]);
   red[t] = v;
   __syncthreads();
-#pragma unroll
-  for (int s = EW_THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) red[t] = OP ? fmin(red[t], red[t + s]) : red[t] + red[t + s];
-    __syncthreads();
-  }
+  pcnn_block_reduce<double, EW_THREADS>(red, t, op);
   if (t == 0) {
     out[(int64_t)n * stride + slot] = red[0];
     if (check && red[0] <= tol2 * out[(int64_t)n * stride + VS_BB]) flags[n] = 1;
@@ -262,10 +251,10 @@ __global__ void varcoef_density_kernel(int64_t total, float lo, float hi, float*
 
 static int vc_check_shape(pcnn_handle h, const char* who, int N, int H, int W) {
   PCNN_REQUIRE(h, N >= 1 && N <= 65535, "%s: batch %d not in 1..65535", who, N);
-  PCNN_REQUIRE(h, H >= 3 && W >= 3 && pcnn_cdiv(H - 2, VT_ROWS) <= 65535, "%s: grid %d x %d unsupported", who, H, W);
+  PCNN_REQUIRE(h, H >= 3 && W >= 3 && pcnn_cdiv(H - 2, FLUX_ROWS) <= 65535, "%s: grid %d x %d unsupported", who, H, W);
   return 0;
 }
-static dim3 vc_tile_grid(int N, int H, int W) { return dim3(pcnn_cdiv(W - 2, VT_COLS), pcnn_cdiv(H - 2, VT_ROWS), N); }
+static dim3 vc_tile_grid(int N, int H, int W) { return dim3(pcnn_cdiv(W - 2, FLUX_COLS), pcnn_cdiv(H - 2, FLUX_ROWS), N); }
 
 // z = M^-1 r, M the constant-coefficient 5-point operator with zero Dirichlet data (its 1/dx^2 left out: a positive factor of M does not change the
 // iterates): z = S_h ((S_h r S_w) ./ (lam_h + lam_w)) S_w as four fp64 matrix-core products; q holds the half-transformed fields.  r.z -> scal slot.
@@ -289,7 +278,7 @@ extern "C" int pcnn_varcoef_apply(pcnn_handle h, int N, int H, int W, const floa
   const int cap = vc_cap(H, W), tiles = vc_tiles(H, W);
   if (int rc = pcnn_reserve(h, h->aux_ws, (size_t)N * cap * sizeof(double), 0, "pcnn_varcoef_apply")) return rc;
   double* part = static_cast<double*>(h->aux_ws.p);
-  hipLaunchKernelGGL(varcoef_apply_kernel, vc_tile_grid(N, H, W), dim3(VT_THREADS), 0, h->stream, H, W, cap, rho, dx, p, q, part);
+  hipLaunchKernelGGL(varcoef_apply_kernel, vc_tile_grid(N, H, W), dim3(FLUX_THREADS), 0, h->stream, H, W, cap, rho, dx, p, q, part);
   hipLaunchKernelGGL(varcoef_reduce_kernel<0>, dim3(N), dim3(EW_THREADS), 0, h->stream, tiles, cap, part, pq, 1, 0, 0, 0.0, (int*)nullptr);
   PCNN_CHECK_LAUNCH(h, "pcnn_varcoef_apply");
   return 0;
@@ -314,7 +303,7 @@ extern "C" int pcnn_varcoef_pcg_setup(pcnn_handle h, int N, int H, int W, const 
   const int64_t per = (int64_t)(H - 2) * (W - 2);
   if (hipMemsetAsync(flags, 0, (size_t)N * sizeof(int), h->stream) != hipSuccess || hipMemsetAsync(scal, 0, (size_t)N * VS_STRIDE * sizeof(double), h->stream) != hipSuccess)
     PCNN_FAIL(h, "pcnn_varcoef_pcg_setup: cannot clear the per-sample state");
-  hipLaunchKernelGGL(varcoef_setup_kernel, vc_tile_grid(N, H, W), dim3(VT_THREADS), 0, h->stream, H, W, w.cap, N, rho, rhs, left, right, bottom, top, dx, x0, w.x,
+  hipLaunchKernelGGL(varcoef_setup_kernel, vc_tile_grid(N, H, W), dim3(FLUX_THREADS), 0, h->stream, H, W, w.cap, N, rho, rhs, left, right, bottom, top, dx, x0, w.x,
                      w.r, w.part);
   hipLaunchKernelGGL(varcoef_reduce_kernel<0>, dim3(N), dim3(EW_THREADS), 0, h->stream, tiles, w.cap, w.part, scal, (int)VS_STRIDE, (int)VS_BB, 0, 0.0, (int*)nullptr);
   hipLaunchKernelGGL(varcoef_reduce_kernel<0>, dim3(N), dim3(EW_THREADS), 0, h->stream, tiles, w.cap, w.part + (size_t)N * w.cap, scal, (int)VS_STRIDE, (int)VS_RR, 1,
@@ -341,7 +330,7 @@ extern "C" int pcnn_varcoef_pcg_iterate(pcnn_handle h, int N, int H, int W, cons
   const int eb = vc_ew_blocks(per);
   for (int it = first_iteration; it < first_iteration + iterations; ++it) {
     const int cur = it & 1;                      // r.z of the current direction sits in slot VS_RZ0 + cur, the next one goes to the other slot
-    hipLaunchKernelGGL(varcoef_apply_kernel, vc_tile_grid(N, H, W), dim3(VT_THREADS), 0, h->stream, H, W, w.cap, rho, dx, w.p, w.q, w.part);
+    hipLaunchKernelGGL(varcoef_apply_kernel, vc_tile_grid(N, H, W), dim3(FLUX_THREADS), 0, h->stream, H, W, w.cap, rho, dx, w.p, w.q, w.part);
     hipLaunchKernelGGL(varcoef_reduce_kernel<0>, dim3(N), dim3(EW_THREADS), 0, h->stream, tiles, w.cap, w.part, scal, (int)VS_STRIDE, (int)VS_PQ, 0, 0.0, (int*)nullptr);
     hipLaunchKernelGGL(varcoef_update_xr_kernel, dim3(eb, N), dim3(EW_THREADS), 0, h->stream, per, w.cap, cur, scal, flags, w.p, w.q, w.x, w.r, w.part);
     hipLaunchKernelGGL(varcoef_reduce_kernel<0>, dim3(N), dim3(EW_THREADS), 0, h->stream, eb, w.cap, w.part, scal, (int)VS_STRIDE, (int)VS_RR, 1, tol * tol, flags);

@@ -1,12 +1,14 @@
 // Training-side operators of the variable-density problem div((1/rho) grad u) = f: the flux-form residual loss with its
 // gradient, and the Jacobi sweep of the same operator with its adjoint.  fp32 on one-channel (N,H,W) fields, one spacing per sample (dy = dx),
-// rho on every node.  The discretisation is that of csrc/varcoef.hip (section 16):
+// rho on every node.  The discretisation is that of csrc/varcoef.hip (section 16), held once in flux_form.h (pcnn_beta_face, pcnn_flux_residual, the
+// FLUX_ROWS x FLUX_COLS tile of the loss kernels - that of varcoef_apply_kernel - and its LDS loader pcnn_load_nodes):
 //   beta_face = 2 / (rho_a + rho_b),   (L u)[i,j] = sum over the four faces of beta_face (u[neighbour] - u[i,j]) / dx^2 = -(A u)[i,j]
 // on the (H-2) x (W-2) interior nodes; here the ring of u is part of the field (the model predicts it), so L maps all H W nodes to the interior.
 // The face coefficients are never stored: every kernel builds them from an LDS tile of rho.  No atomics: the loss sums are per-tile partials
 // (fixed tree) added per sample by a second one-block stage in a fixed order.  A sample's blocks read nothing of another sample.
 // The sweeps' walker, tile frame, launch chain and launch checks are sweep_common.h's, shared with stencil.hip.
 #include <math.h>
+#include "flux_form.h"
 #include "sweep_common.h"
 
 #define VJ_TILE 64         // output tile edge of the sweeps
@@ -15,57 +17,38 @@
 
 namespace {
 
-constexpr int PT_ROWS = 16, PT_COLS = 64, PT_THREADS = 256, PT_RPT = PT_ROWS / (PT_THREADS / PT_COLS);   // loss kernels: the tile of varcoef_apply_kernel
 constexpr int RED_THREADS = 256;
 
-__device__ __forceinline__ float beta_face(float a, float b) { return 2.f / (a + b); }
-
-// (L u - rhs) at an interior node: uc / rc the node's u / rho, (u?, r?) its four neighbours towards i-1, i+1, j-1, j+1
-__device__ __forceinline__ float flux_residual(float uc, float rc, float u0, float r0, float u1, float r1, float u2, float r2, float u3, float r3, float inv_h2,
-                                               float f) {
-  const float s = (beta_face(rc, r0) * (u0 - uc) + beta_face(rc, r1) * (u1 - uc)) + (beta_face(rc, r2) * (u2 - uc) + beta_face(rc, r3) * (u3 - uc));
-  return s * inv_h2 - f;
-}
-
-// nodes (I0 .. I0+LR-1) x (J0 .. J0+LC-1) of one sample's field into LDS; nodes outside the grid read `fill`
-template <int LR, int LC>
-__device__ __forceinline__ void load_nodes(float (*t)[LC], const float* __restrict__ src, int H, int W, int I0, int J0, float fill) {
-  for (int e = threadIdx.x; e < LR * LC; e += PT_THREADS) {
-    const int r = e / LC, c = e % LC, i = I0 + r, j = J0 + c;
-    t[r][c] = (i >= 0 && i < H && j >= 0 && j < W) ? src[(int64_t)i * W + j] : fill;
-  }
-}
-
 // part[n][tile] = the tile's sum of (L pred - rhs)^2.  grid (column tiles, row tiles, N) over the interior
-__global__ __launch_bounds__(PT_THREADS) void vc_pi_partials_kernel(int H, int W, int tiles, const float* __restrict__ pred, const float* __restrict__ rho,
-                                                                    const float* __restrict__ rhs, const float* __restrict__ dx, float* __restrict__ part) {
-  constexpr int LR = PT_ROWS + 2, LC = PT_COLS + 2;
+__global__ __launch_bounds__(FLUX_THREADS) void vc_pi_partials_kernel(int H, int W, int tiles, const float* __restrict__ pred, const float* __restrict__ rho,
+                                                                      const float* __restrict__ rhs, const float* __restrict__ dx, float* __restrict__ part) {
+  constexpr int LR = FLUX_ROWS + 2, LC = FLUX_COLS + 2;
   __shared__ float us[LR][LC];
   __shared__ float rs[LR][LC];
-  __shared__ float red[PT_THREADS];
-  const int nh = H - 2, nw = W - 2, n = blockIdx.z, I0 = blockIdx.y * PT_ROWS, J0 = blockIdx.x * PT_COLS;   // LDS (r, c) is node (I0 + r, J0 + c)
+  __shared__ float red[FLUX_THREADS];
+  const int nh = H - 2, nw = W - 2, n = blockIdx.z, I0 = blockIdx.y * FLUX_ROWS, J0 = blockIdx.x * FLUX_COLS;   // LDS (r, c) is node (I0 + r, J0 + c)
   const int64_t img = (int64_t)n * H * W;
-  load_nodes<LR, LC>(us, pred + img, H, W, I0, J0, 0.f);
-  load_nodes<LR, LC>(rs, rho + img, H, W, I0, J0, 1.f);
+  pcnn_load_nodes<LR, LC>(us, pred + img, H, W, I0, J0, 0.f);
+  pcnn_load_nodes<LR, LC>(rs, rho + img, H, W, I0, J0, 1.f);
   __syncthreads();
   const float h = dx[n], inv_h2 = 1.f / (h * h);
-  const int c = threadIdx.x % PT_COLS, r0 = (threadIdx.x / PT_COLS) * PT_RPT;
+  const int c = threadIdx.x % FLUX_COLS, r0 = (threadIdx.x / FLUX_COLS) * FLUX_RPT;
   float s = 0.f;
   if (J0 + c < nw) {
 #pragma unroll
-    for (int k = 0; k < PT_RPT; ++k) {
+    for (int k = 0; k < FLUX_RPT; ++k) {
       const int r = r0 + k;
       if (I0 + r < nh) {
         const int a = r + 1, b = c + 1;
-        const float e = flux_residual(us[a][b], rs[a][b], us[a - 1][b], rs[a - 1][b], us[a + 1][b], rs[a + 1][b], us[a][b - 1], rs[a][b - 1], us[a][b + 1],
-                                      rs[a][b + 1], inv_h2, rhs[img + (int64_t)(I0 + a) * W + J0 + b]);
+        const float e = pcnn_flux_residual(us[a][b], rs[a][b], us[a - 1][b], rs[a - 1][b], us[a + 1][b], rs[a + 1][b], us[a][b - 1], rs[a][b - 1],
+                                           us[a][b + 1], rs[a][b + 1], inv_h2, rhs[img + (int64_t)(I0 + a) * W + J0 + b]);
         s += e * e;
       }
     }
   }
   red[threadIdx.x] = s;
   __syncthreads();
-  pcnn_block_sum<float, PT_THREADS>(red, threadIdx.x);
+  pcnn_block_sum<float, FLUX_THREADS>(red, threadIdx.x);
   if (threadIdx.x == 0) part[(int64_t)n * tiles + blockIdx.y * gridDim.x + blockIdx.x] = red[0];
 }
 
@@ -84,41 +67,41 @@ __global__ __launch_bounds__(RED_THREADS) void vc_pi_reduce_kernel(int tiles, co
 // dpred += coef[n] * 2 L^T e, e = L pred - rhs.  Gather form: e on the tile's nodes and a one-node halo (zero outside the interior), then
 // (L^T e)[p] = sum over the faces of p of beta_face (e[neighbour] - e[p]) / dx^2 - the operator is symmetric, and on a ring node, where e[p] = 0,
 // the same expression is the sum of beta_face e[interior neighbour].  grid (column tiles, row tiles, N) over ALL nodes
-__global__ __launch_bounds__(PT_THREADS) void vc_pi_bwd_kernel(int H, int W, const float* __restrict__ pred, const float* __restrict__ rho,
-                                                               const float* __restrict__ rhs, const float* __restrict__ dx, const float* __restrict__ coef,
-                                                               float* __restrict__ dpred) {
-  constexpr int LR = PT_ROWS + 4, LC = PT_COLS + 4, ER = PT_ROWS + 2, EC = PT_COLS + 2;
+__global__ __launch_bounds__(FLUX_THREADS) void vc_pi_bwd_kernel(int H, int W, const float* __restrict__ pred, const float* __restrict__ rho,
+                                                                 const float* __restrict__ rhs, const float* __restrict__ dx, const float* __restrict__ coef,
+                                                                 float* __restrict__ dpred) {
+  constexpr int LR = FLUX_ROWS + 4, LC = FLUX_COLS + 4, ER = FLUX_ROWS + 2, EC = FLUX_COLS + 2;
   __shared__ float us[LR][LC];
   __shared__ float rs[LR][LC];
   __shared__ float es[ER][EC];
-  const int n = blockIdx.z, I0 = blockIdx.y * PT_ROWS, J0 = blockIdx.x * PT_COLS;     // us / rs (r, c) is node (I0 - 2 + r, J0 - 2 + c); es: (I0 - 1 + r, J0 - 1 + c)
+  const int n = blockIdx.z, I0 = blockIdx.y * FLUX_ROWS, J0 = blockIdx.x * FLUX_COLS;     // us / rs (r, c) is node (I0 - 2 + r, J0 - 2 + c); es: (I0 - 1 + r, J0 - 1 + c)
   const int64_t img = (int64_t)n * H * W;
-  load_nodes<LR, LC>(us, pred + img, H, W, I0 - 2, J0 - 2, 0.f);
-  load_nodes<LR, LC>(rs, rho + img, H, W, I0 - 2, J0 - 2, 1.f);
+  pcnn_load_nodes<LR, LC>(us, pred + img, H, W, I0 - 2, J0 - 2, 0.f);
+  pcnn_load_nodes<LR, LC>(rs, rho + img, H, W, I0 - 2, J0 - 2, 1.f);
   __syncthreads();
   const float h = dx[n], inv_h2 = 1.f / (h * h);
-  for (int e = threadIdx.x; e < ER * EC; e += PT_THREADS) {
+  for (int e = threadIdx.x; e < ER * EC; e += FLUX_THREADS) {
     const int r = e / EC, c = e % EC, i = I0 - 1 + r, j = J0 - 1 + c;
     float v = 0.f;
     if (i >= 1 && i < H - 1 && j >= 1 && j < W - 1) {
       const int a = r + 1, b = c + 1;
-      v = flux_residual(us[a][b], rs[a][b], us[a - 1][b], rs[a - 1][b], us[a + 1][b], rs[a + 1][b], us[a][b - 1], rs[a][b - 1], us[a][b + 1], rs[a][b + 1],
-                        inv_h2, rhs[img + (int64_t)i * W + j]);
+      v = pcnn_flux_residual(us[a][b], rs[a][b], us[a - 1][b], rs[a - 1][b], us[a + 1][b], rs[a + 1][b], us[a][b - 1], rs[a][b - 1], us[a][b + 1],
+                             rs[a][b + 1], inv_h2, rhs[img + (int64_t)i * W + j]);
     }
     es[r][c] = v;
   }
   __syncthreads();
   const float scale = 2.f * coef[n] * inv_h2;
-  const int c = threadIdx.x % PT_COLS, r0 = (threadIdx.x / PT_COLS) * PT_RPT;
+  const int c = threadIdx.x % FLUX_COLS, r0 = (threadIdx.x / FLUX_COLS) * FLUX_RPT;
   if (J0 + c < W) {
 #pragma unroll
-    for (int k = 0; k < PT_RPT; ++k) {
+    for (int k = 0; k < FLUX_RPT; ++k) {
       const int r = r0 + k;
       if (I0 + r < H) {
         const int a = r + 1, b = c + 1;                  // in es; rs is one further in
         const float ec = es[a][b], rc = rs[a + 1][b + 1];
-        const float g = (beta_face(rc, rs[a][b + 1]) * (es[a - 1][b] - ec) + beta_face(rc, rs[a + 2][b + 1]) * (es[a + 1][b] - ec)) +
-                        (beta_face(rc, rs[a + 1][b]) * (es[a][b - 1] - ec) + beta_face(rc, rs[a + 1][b + 2]) * (es[a][b + 1] - ec));
+        const float g = (pcnn_beta_face(rc, rs[a][b + 1]) * (es[a - 1][b] - ec) + pcnn_beta_face(rc, rs[a + 2][b + 1]) * (es[a + 1][b] - ec)) +
+                        (pcnn_beta_face(rc, rs[a + 1][b]) * (es[a][b - 1] - ec) + pcnn_beta_face(rc, rs[a + 1][b + 2]) * (es[a][b + 1] - ec));
         dpred[img + (int64_t)(I0 + r) * W + J0 + c] += scale * g;
       }
     }
@@ -161,7 +144,7 @@ __global__ __launch_bounds__(VJ_THREADS) void vc_jacobi_kernel(int H, int W, int
         float v = 0.f;
         if (y >= 1 && y < H - 1 && x >= 1 && x < W - 1) {
           const float rc = rb[c];
-          v = 1.f / ((beta_face(rc, rb[c - LW]) + beta_face(rc, rb[c + LW])) + (beta_face(rc, rb[c - 1]) + beta_face(rc, rb[c + 1])));
+          v = 1.f / ((pcnn_beta_face(rc, rb[c - LW]) + pcnn_beta_face(rc, rb[c + LW])) + (pcnn_beta_face(rc, rb[c - 1]) + pcnn_beta_face(rc, rb[c + 1])));
         }
         fb[c] = v;
       });
@@ -177,7 +160,7 @@ __global__ __launch_bounds__(VJ_THREADS) void vc_jacobi_kernel(int H, int W, int
     const float rc = rb[c];
     if (!BWD) {
       if (!interior) return in[c];
-      const float b0 = beta_face(rc, rb[c - LW]), b1 = beta_face(rc, rb[c + LW]), b2 = beta_face(rc, rb[c - 1]), b3 = beta_face(rc, rb[c + 1]);
+      const float b0 = pcnn_beta_face(rc, rb[c - LW]), b1 = pcnn_beta_face(rc, rb[c + LW]), b2 = pcnn_beta_face(rc, rb[c - 1]), b3 = pcnn_beta_face(rc, rb[c + 1]);
       const float num = (b0 * in[c - LW] + b1 * in[c + LW]) + (b2 * in[c - 1] + b3 * in[c + 1]);
       return (num - fb[c]) / ((b0 + b1) + (b2 + b3));
     }
@@ -185,12 +168,12 @@ __global__ __launch_bounds__(VJ_THREADS) void vc_jacobi_kernel(int H, int W, int
     const bool in_x = x >= 1 && x < W - 1, in_y = y >= 1 && y < H - 1;
     float acc = 0.f;
     if (in_x) {
-      if (y - 1 >= 1 && y - 1 < H - 1) acc += beta_face(rc, rb[c - LW]) * (fb[c - LW] * in[c - LW]);
-      if (y + 1 >= 1 && y + 1 < H - 1) acc += beta_face(rc, rb[c + LW]) * (fb[c + LW] * in[c + LW]);
+      if (y - 1 >= 1 && y - 1 < H - 1) acc += pcnn_beta_face(rc, rb[c - LW]) * (fb[c - LW] * in[c - LW]);
+      if (y + 1 >= 1 && y + 1 < H - 1) acc += pcnn_beta_face(rc, rb[c + LW]) * (fb[c + LW] * in[c + LW]);
     }
     if (in_y) {
-      if (x - 1 >= 1 && x - 1 < W - 1) acc += beta_face(rc, rb[c - 1]) * (fb[c - 1] * in[c - 1]);
-      if (x + 1 >= 1 && x + 1 < W - 1) acc += beta_face(rc, rb[c + 1]) * (fb[c + 1] * in[c + 1]);
+      if (x - 1 >= 1 && x - 1 < W - 1) acc += pcnn_beta_face(rc, rb[c - 1]) * (fb[c - 1] * in[c - 1]);
+      if (x + 1 >= 1 && x + 1 < W - 1) acc += pcnn_beta_face(rc, rb[c + 1]) * (fb[c + 1] * in[c + 1]);
     }
     return (interior ? 0.f : in[c]) + acc;
   };
@@ -235,7 +218,7 @@ __global__ void assemble_density_input_kernel(int N, int H, int W, const float* 
   }
 }
 
-bool vt_shape_ok(int N, int H, int W) { return pcnn_grid_ok(N, H, W) && H >= 3 && W >= 3 && pcnn_cdiv(H, PT_ROWS) <= 65535; }
+bool vt_shape_ok(int N, int H, int W) { return pcnn_grid_ok(N, H, W) && H >= 3 && W >= 3 && pcnn_cdiv(H, FLUX_ROWS) <= 65535; }
 
 }  // namespace
 
@@ -243,11 +226,11 @@ extern "C" int pcnn_varcoef_pi_loss_partials(pcnn_handle h, int N, int H, int W,
                                              float* out) {
   PCNN_REQUIRE(h, h && pred && rho && rhs && dx && out, "pcnn_varcoef_pi_loss_partials: null argument");
   PCNN_REQUIRE(h, vt_shape_ok(N, H, W), "pcnn_varcoef_pi_loss_partials: batch %d of %d x %d grids unsupported", N, H, W);
-  const dim3 grid(pcnn_cdiv(W - 2, PT_COLS), pcnn_cdiv(H - 2, PT_ROWS), N);
+  const dim3 grid(pcnn_cdiv(W - 2, FLUX_COLS), pcnn_cdiv(H - 2, FLUX_ROWS), N);
   const int tiles = (int)(grid.x * grid.y);
   if (int rc = pcnn_reserve(h, h->aux_ws, (size_t)N * tiles * sizeof(float), 0, "pcnn_varcoef_pi_loss_partials")) return rc;
   float* part = static_cast<float*>(h->aux_ws.p);
-  hipLaunchKernelGGL(vc_pi_partials_kernel, grid, dim3(PT_THREADS), 0, h->stream, H, W, tiles, pred, rho, rhs, dx, part);
+  hipLaunchKernelGGL(vc_pi_partials_kernel, grid, dim3(FLUX_THREADS), 0, h->stream, H, W, tiles, pred, rho, rhs, dx, part);
   hipLaunchKernelGGL(vc_pi_reduce_kernel, dim3(N), dim3(RED_THREADS), 0, h->stream, tiles, part, out);
   PCNN_CHECK_LAUNCH(h, "pcnn_varcoef_pi_loss_partials");
   return 0;
@@ -258,8 +241,8 @@ extern "C" int pcnn_varcoef_pi_loss_bwd(pcnn_handle h, int N, int H, int W, cons
   PCNN_REQUIRE(h, h && pred && rho && rhs && dx && coef && dpred, "pcnn_varcoef_pi_loss_bwd: null argument");
   PCNN_REQUIRE(h, vt_shape_ok(N, H, W), "pcnn_varcoef_pi_loss_bwd: batch %d of %d x %d grids unsupported", N, H, W);
   PCNN_REQUIRE(h, dpred != pred && dpred != rho && dpred != rhs, "pcnn_varcoef_pi_loss_bwd: dpred must not alias an input");
-  const dim3 grid(pcnn_cdiv(W, PT_COLS), pcnn_cdiv(H, PT_ROWS), N);
-  hipLaunchKernelGGL(vc_pi_bwd_kernel, grid, dim3(PT_THREADS), 0, h->stream, H, W, pred, rho, rhs, dx, coef, dpred);
+  const dim3 grid(pcnn_cdiv(W, FLUX_COLS), pcnn_cdiv(H, FLUX_ROWS), N);
+  hipLaunchKernelGGL(vc_pi_bwd_kernel, grid, dim3(FLUX_THREADS), 0, h->stream, H, W, pred, rho, rhs, dx, coef, dpred);
   PCNN_CHECK_LAUNCH(h, "pcnn_varcoef_pi_loss_bwd");
   return 0;
 }

@@ -1164,30 +1164,39 @@ def assemble_density_input(stack, use_pos=True):
 ERROR_STATS = ('sum_abs_e', 'sum_e2', 'max_abs_e', 'sum_t2', 'max_abs_t', 'sum_r2', 'max_abs_r', 'sum_f2')       # the columns of error_stats
 
 
-def error_stats(pred, target=None, rhs=None, dx=None):
-    """(N, 8) per-sample statistics of a one-channel prediction (N,1,H,W) / (N,H,W) / (N,H,W,1) in one pass (pcnn_error_stats; columns: ERROR_STATS).
-    e = pred - target, t = target over all points; r = 3 x 3 FD Laplacian of pred minus rhs, f = rhs over the interior, dx (N, 2) per axis.
-    Without `target` the first five columns are 0, without `rhs` the last three."""
-    N, H, W = _one_channel_shape('error_stats', pred, 'pred must be (N,1,H,W), (N,H,W,1) or (N,H,W)')
-    fields = {'pred': pred, 'target': target, 'rhs': rhs}
-    for name, t in fields.items():
+def _error_stats(who, launch, pred, target, rhs, dx, dx_cols, dx_error, rho=None, rhs_needs_rho=False):
+    """The checks of error_stats / varcoef_error_stats in the caller's name, dx as dx_cols values per sample, and launch(N, H, W, fields, dx, out)."""
+    N, H, W = _one_channel_shape(who, pred, 'pred must be (N,1,H,W), (N,H,W,1) or (N,H,W)')
+    if rhs_needs_rho and rhs is not None and rho is None:
+        raise ValueError('%s: rhs needs rho' % who)
+    f = {'pred': pred, 'target': target, 'rho': rho if rhs is not None else None, 'rhs': rhs}
+    for name, t in f.items():
         if t is None:
             continue
         if t.dtype != torch.float32 or not t.is_cuda or t.numel() != N * H * W:
-            raise ValueError('error_stats: %s must be a CUDA float32 tensor with the %d x %d x %d points of pred' % (name, N, H, W))
-        fields[name] = t.contiguous()
+            raise ValueError('%s: %s must be a CUDA float32 tensor with the %d x %d x %d points of pred' % (who, name, N, H, W))
+        f[name] = t.contiguous()
     if rhs is not None:
         if dx is None:
-            raise ValueError('error_stats: rhs needs dx')
-        dx = dx.to(device=pred.device, dtype=torch.float32).reshape(N, -1)
-        if dx.shape[1] != 2:
-            raise ValueError('error_stats: dx must be (N, 2), one spacing per axis')
-        dx = dx.contiguous()
+            raise ValueError('%s: rhs needs dx' % who)
+        dx = dx.to(device=pred.device, dtype=torch.float32)
+        if dx.numel() != N * dx_cols:
+            raise ValueError(dx_error % {'who': who, 'N': N, 'shape': tuple(dx.shape)})
+        dx = dx.reshape(N, dx_cols).contiguous()
     else:
         dx = None
     out = empty((N, 8), pred.device)
-    handle().call('pcnn_error_stats', c_int(N), c_int(H), c_int(W), _p(fields['pred']), _p(fields['target']), _p(fields['rhs']), _p(dx), _p(out))
+    launch(c_int(N), c_int(H), c_int(W), f, dx, out)
     return out
+
+
+def error_stats(pred, target=None, rhs=None, dx=None):
+    """(N, 8) per-sample statistics of a one-channel prediction (N,1,H,W) / (N,H,W,1) / (N,H,W) in one pass (pcnn_error_stats; columns: ERROR_STATS).
+    e = pred - target, t = target over all points; r = 3 x 3 FD Laplacian of pred minus rhs, f = rhs over the interior, dx (N, 2) per axis.
+    Without `target` the first five columns are 0, without `rhs` the last three."""
+    def launch(N, H, W, f, dx, out):
+        handle().call('pcnn_error_stats', N, H, W, _p(f['pred']), _p(f['target']), _p(f['rhs']), _p(dx), _p(out))
+    return _error_stats('error_stats', launch, pred, target, rhs, dx, 2, '%(who)s: dx must be (N, 2), one spacing per axis')
 
 
 def varcoef_error_stats(pred, rho, target=None, rhs=None, dx=None):
@@ -1196,30 +1205,10 @@ def varcoef_error_stats(pred, rho, target=None, rhs=None, dx=None):
     neighbours - minus rhs, over the interior; dx: one spacing per sample, (N,) or (N,1).  With zero edge values, and only then,
     sqrt(sum_r2 / sum_f2) is the relative residual ||b - A x|| / ||b|| variable_density_poisson_solve would start from.  Without `target` the
     first five columns are 0; without `rhs` the last three, and rho and dx are not read."""
-    who = 'varcoef_error_stats'
-    N, H, W = _one_channel_shape(who, pred, 'pred must be (N,1,H,W), (N,H,W,1) or (N,H,W)')
-    fields = {'pred': pred, 'target': target, 'rho': rho if rhs is not None else None, 'rhs': rhs}
-    if rhs is not None and rho is None:
-        raise ValueError('%s: rhs needs rho' % who)
-    for name, t in fields.items():
-        if t is None:
-            continue
-        if t.dtype != torch.float32 or not t.is_cuda or t.numel() != N * H * W:
-            raise ValueError('%s: %s must be a CUDA float32 tensor with the %d x %d x %d points of pred' % (who, name, N, H, W))
-        fields[name] = t.contiguous()
-    if rhs is not None:
-        if dx is None:
-            raise ValueError('%s: rhs needs dx' % who)
-        dx = dx.to(device=pred.device, dtype=torch.float32)
-        if dx.numel() != N:
-            raise ValueError('%s: dx must hold one spacing per sample (%d values), got shape %s' % (who, N, tuple(dx.shape)))
-        dx = dx.reshape(N).contiguous()
-    else:
-        dx = None
-    out = empty((N, 8), pred.device)
-    handle().call('pcnn_varcoef_error_stats', c_int(N), c_int(H), c_int(W), _p(fields['pred']), _p(fields['target']), _p(fields['rho']), _p(fields['rhs']),
-                  _p(dx), _p(out))
-    return out
+    def launch(N, H, W, f, dx, out):
+        handle().call('pcnn_varcoef_error_stats', N, H, W, _p(f['pred']), _p(f['target']), _p(f['rho']), _p(f['rhs']), _p(dx), _p(out))
+    return _error_stats('varcoef_error_stats', launch, pred, target, rhs, dx, 1,
+                        '%(who)s: dx must hold one spacing per sample (%(N)d values), got shape %(shape)s', rho, rhs_needs_rho=True)
 
 
 def adam_step(w, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0, vhat=None):

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests import test_gpu_varcoef_model as VM, varcoef_stats_twin as ST, varcoef_twin as VT
+from tests import error_stats_twin as ST, test_gpu_varcoef_model as VM, varcoef_twin as VT
 
 pytestmark = pytest.mark.gpu
 N, H, W = VM.N, VM.H, VM.W
@@ -57,7 +57,7 @@ def test_prediction_residual_is_the_twins_on_the_models_own_output():
     _, info = m.solve([stack, dx], return_info=True)
     pred = m([stack, dx]).cpu().numpy()
     f32 = lambda a: np.asarray(a, dtype=np.float32)
-    tw = ST.error_stats(pred, f32(rho), None, f32(rhs), f32(dx[:, 0]), float32_terms=True)
+    tw = ST.error_stats(pred, None, f32(rhs), f32(dx[:, 0]), f32(rho), float32_terms=True)
     want = np.sqrt(tw[:, 5] / tw[:, 7])
     got = info['prediction_relative_residual']
     print('prediction_relative_residual %r, twin %r, error / bound %.3g' % (got.tolist(), want.tolist(), (np.abs(got - want) / want).max() / TOL_RESIDUAL))

@@ -1,11 +1,11 @@
-"""pcnn_varcoef_error_stats (csrc/varcoef_stats.hip, ops.varcoef_error_stats) against tests/varcoef_stats_twin.py on the same fp32 inputs."""
+"""pcnn_varcoef_error_stats (csrc/error_stats.hip, ops.varcoef_error_stats) against tests/error_stats_twin.py on the same fp32 inputs."""
 from ctypes import c_int
 
 import numpy as np
 import pytest
 import torch
 
-from tests import varcoef_stats_twin as TW
+from tests import error_stats_twin as TW
 
 pytestmark = pytest.mark.gpu
 
@@ -53,7 +53,7 @@ def _case(H, W):
         dev = [torch.from_numpy(a).cuda() for a in arrs]
         got = _call(ops, *dev).cpu().numpy()
         pred, target, rho, rhs, dx = arrs
-        _CACHE[(H, W)] = (arrs, dev, got, TW.error_stats(pred, rho, target, rhs, dx, float32_terms=True), TW.error_stats(pred, rho, target, rhs, dx))
+        _CACHE[(H, W)] = (arrs, dev, got, TW.error_stats(pred, target, rhs, dx, rho, float32_terms=True), TW.error_stats(pred, target, rhs, dx, rho))
     return _CACHE[(H, W)]
 
 
@@ -127,5 +127,5 @@ def test_argument_errors_leave_the_handle_usable():
         with pytest.raises(RuntimeError, match=msg):
             ops.handle().call('pcnn_varcoef_error_stats', *dims, ops._p(pred), ops._p(target), ops._p(r), ops._p(rhs), ops._p(d), ops._p(out))
     ok = ops.varcoef_error_stats(two[0], None, two[1]).cpu().numpy()                        # H = 2 without rhs is fine
-    assert np.allclose(ok, TW.error_stats(two[0].cpu().numpy(), None, two[1].cpu().numpy()), rtol=1e-6)
+    assert np.allclose(ok, TW.error_stats(two[0].cpu().numpy(), two[1].cpu().numpy()), rtol=1e-6)
     assert np.array_equal(bits(_call(ops, pred, target, rho, rhs, dx).cpu().numpy()), bits(got))
