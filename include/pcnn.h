@@ -440,14 +440,15 @@ int pcnn_channel_scale_bwd_post(pcnn_handle h, int N, int64_t hw, int C, const f
 /* per-sample scalar scale: y[n,..] = x[n,..]*(1+g[n]) (layers/Scaling.py:55); bwd: dx, dg[n] = sum dy*x */
 int pcnn_sample_scale_fwd(pcnn_handle h, int N, int64_t per, const float* x, const float* g, float* y);
 int pcnn_sample_scale_bwd(pcnn_handle h, int N, int64_t per, const float* x, const float* g, const float* dy, float* dx, float* dg);
-/* BC ring (models/..Legacy.py:251): Dirichlet -> ring = 0 ; Neumann -> ring = adjacent interior.  1 channel. */
+/* BC ring (models/..Legacy.py:251): Dirichlet -> ring = 0 ; Neumann -> ring = adjacent interior.  1 channel.  These are pcnn_bc_ring_edges_fwd/bwd
+ * with neumann_mask = neumann ? 15 : 0. */
 int pcnn_bc_ring_fwd(pcnn_handle h, int N, int H, int W, int neumann, const float* x, float* y);
 int pcnn_bc_ring_bwd(pcnn_handle h, int N, int H, int W, int neumann, const float* dy, float* dx);
 /* The ring with a boundary type per edge (extension: the reference's bc_type is model-wide).  Edges are named as the dataset names them: on an
  * (N,1,H,W) tensor left is y = 0, right y = H-1, bottom x = 0, top x = W-1.  neumann_mask bit 0/1/2/3 set: the left/right/bottom/top edge is Neumann,
  * clear: Dirichlet (the order of pcnn_fd_poisson_mixed).  y = E_m x: interior points are copied; a ring point on any Dirichlet edge is 0 - at a corner a
  * Dirichlet edge wins - and any other ring point is x[clamp(y,1,H-2), clamp(x,1,W-2)], the first-order mirror u_0 = u_1 of tf.pad SYMMETRIC (a
- * Neumann/Neumann corner takes its diagonal neighbour).  bwd is E_m^T as a gather: no atomics, deterministic.  Mask 0 and mask 15 give the bits of
+ * Neumann/Neumann corner takes its diagonal neighbour).  bwd is E_m^T as a gather: no atomics, deterministic.  Mask 0 and mask 15 are
  * pcnn_bc_ring_fwd/bwd with neumann = 0 and 1.  H, W >= 3. */
 int pcnn_bc_ring_edges_fwd(pcnn_handle h, int N, int H, int W, int neumann_mask, const float* x, float* y);
 int pcnn_bc_ring_edges_bwd(pcnn_handle h, int N, int H, int W, int neumann_mask, const float* dy, float* dx);

@@ -67,10 +67,9 @@ def hpnn_mixed(boundary_types):
     'dirichlet' | 'neumann' (a missing edge is Dirichlet).  Its dataset section feeds reverse_poisson_dataset_generator_mixed (train.py
     --dataset_type analytical_mixed, which takes boundary_types from the model's bc_type); the numerical generator's mixed solver is the other
     ground truth.  The keys the Dirichlet analytic generator alone reads are dropped as in hpnn_neumann()."""
-    from .dataset import _neumann_flags
-    flags = _neumann_flags(boundary_types)
+    from .utils import BC_EDGES, neumann_flags
     cfg = hpnn()
-    cfg['model']['bc_type'] = {e: 'neumann' if f else 'dirichlet' for e, f in zip(('left', 'right', 'bottom', 'top'), flags)}
+    cfg['model']['bc_type'] = {e: 'neumann' if f else 'dirichlet' for e, f in zip(BC_EDGES, neumann_flags(boundary_types))}
     for k in ('taylor_degree_range', 'homogeneous_bc', 'return_boundaries'):
         cfg['dataset'].pop(k)
     return cfg

@@ -384,52 +384,9 @@ __global__ void sample_scale_final_kernel(int N, const float* __restrict__ part,
   dg[n] = s;
 }
 
-__global__ void bc_ring_fwd_kernel(int N, int H, int W, int neumann, const float* __restrict__ x, float* __restrict__ y) {
-  const int64_t total = (int64_t)N * H * W;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int xx = i % W; const int yy = (i / W) % H; const int64_t base = i - ((int64_t)yy * W + xx);
-    const bool ring = yy == 0 || yy == H - 1 || xx == 0 || xx == W - 1;
-    float v;
-    if (!ring) v = x[i];
-    else if (!neumann) v = 0.f;
-    else {
-      const int sy = yy == 0 ? 1 : (yy == H - 1 ? H - 2 : yy);
-      const int sx = xx == 0 ? 1 : (xx == W - 1 ? W - 2 : xx);
-      v = x[base + (int64_t)sy * W + sx];
-    }
-    y[i] = v;
-  }
-}
-
-__global__ void bc_ring_bwd_kernel(int N, int H, int W, int neumann, const float* __restrict__ dy, float* __restrict__ dx) {
-  const int64_t total = (int64_t)N * H * W;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int xx = i % W; const int yy = (i / W) % H; const int64_t base = i - ((int64_t)yy * W + xx);
-    const bool ring = yy == 0 || yy == H - 1 || xx == 0 || xx == W - 1;
-    float v = 0.f;
-    if (!ring) {
-      v = dy[i];
-      if (neumann) {
-        // interior cell (yy,xx) also feeds the ring cells that mirror it
-        const int ny = (yy == 1) + (yy == H - 2), nx = (xx == 1) + (xx == W - 2);
-        int ys[3], xs[3], cy = 0, cx = 0;
-        ys[cy++] = yy; xs[cx++] = xx;
-        if (yy == 1) ys[cy++] = 0;
-        if (yy == H - 2) ys[cy++] = H - 1;
-        if (xx == 1) xs[cx++] = 0;
-        if (xx == W - 2) xs[cx++] = W - 1;
-        (void)ny; (void)nx;
-        v = 0.f;
-        for (int a = 0; a < cy; ++a)
-          for (int b = 0; b < cx; ++b) v += dy[base + (int64_t)ys[a] * W + xs[b]];
-      }
-    }
-    dx[i] = v;
-  }
-}
-
 // The ring with a boundary type per edge (mask bit 0 / 1 / 2 / 3: the edge y = 0 / y = H-1 / x = 0 / x = W-1 is Neumann): a ring point on any
 // Dirichlet edge is 0 - at a corner the Dirichlet edge wins - and every other ring point takes the nearest interior point, as SYMMETRIC does.
+// Masks 0 and 15 are the reference's two modes (pcnn_bc_ring_fwd / pcnn_bc_ring_bwd).
 __global__ void bc_ring_edges_fwd_kernel(int N, int H, int W, int mask, const float* __restrict__ x, float* __restrict__ y) {
   const int64_t total = (int64_t)N * H * W;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -449,7 +406,7 @@ __global__ void bc_ring_edges_fwd_kernel(int N, int H, int W, int mask, const fl
 }
 
 // The transpose as a gather: an interior point collects the ring points that copied it.  A ring row or column is a candidate only where its edge
-// is Neumann, so a corner counts exactly when both of its edges are.  The order of the sum is bc_ring_bwd_kernel's.
+// is Neumann, so a corner counts exactly when both of its edges are.  The sum runs over rows, then columns, the point itself first.
 __global__ void bc_ring_edges_bwd_kernel(int N, int H, int W, int mask, const float* __restrict__ dy, float* __restrict__ dx) {
   const int64_t total = (int64_t)N * H * W;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -463,7 +420,7 @@ __global__ void bc_ring_edges_bwd_kernel(int N, int H, int W, int mask, const fl
       if (yy == H - 2 && (mask & 2)) ys[cy++] = H - 1;
       if (xx == 1 && (mask & 4)) xs[cx++] = 0;
       if (xx == W - 2 && (mask & 8)) xs[cx++] = W - 1;
-      if (mask == 0) v = dy[i];                                    // what bc_ring_bwd_kernel does without its neumann flag
+      if (mask == 0) v = dy[i];                                    // a copy, not 0.f + dy[i]: the all-Dirichlet adjoint keeps the sign of a zero
       else
         for (int a = 0; a < cy; ++a)
           for (int b = 0; b < cx; ++b) v += dy[base + (int64_t)ys[a] * W + xs[b]];
@@ -711,14 +668,6 @@ extern "C" int pcnn_sample_scale_bwd(pcnn_handle h, int N, int64_t per, const fl
   return 0;
 }
 
-extern "C" int pcnn_bc_ring_fwd(pcnn_handle h, int N, int H, int W, int neumann, const float* x, float* y) {
-  PCNN_REQUIRE(h, h && x && y, "pcnn_bc_ring_fwd: null argument");
-  PCNN_REQUIRE(h, H >= 3 && W >= 3, "pcnn_bc_ring_fwd: grid %dx%d too small", H, W);
-  hipLaunchKernelGGL(bc_ring_fwd_kernel, grid1d((int64_t)N * H * W), dim3(256), 0, h->stream, N, H, W, neumann, x, y);
-  PCNN_CHECK_LAUNCH(h, "pcnn_bc_ring_fwd");
-  return 0;
-}
-
 extern "C" int pcnn_bc_ring_edges_fwd(pcnn_handle h, int N, int H, int W, int neumann_mask, const float* x, float* y) {
   PCNN_REQUIRE(h, h && x && y, "pcnn_bc_ring_edges_fwd: null argument");
   PCNN_REQUIRE(h, H >= 3 && W >= 3, "pcnn_bc_ring_edges_fwd: grid %dx%d too small", H, W);
@@ -737,12 +686,12 @@ extern "C" int pcnn_bc_ring_edges_bwd(pcnn_handle h, int N, int H, int W, int ne
   return 0;
 }
 
+// the reference's two modes: every edge Dirichlet (neumann = 0) or every edge Neumann
+extern "C" int pcnn_bc_ring_fwd(pcnn_handle h, int N, int H, int W, int neumann, const float* x, float* y) {
+  return pcnn_bc_ring_edges_fwd(h, N, H, W, neumann ? 15 : 0, x, y);
+}
 extern "C" int pcnn_bc_ring_bwd(pcnn_handle h, int N, int H, int W, int neumann, const float* dy, float* dx) {
-  PCNN_REQUIRE(h, h && dy && dx, "pcnn_bc_ring_bwd: null argument");
-  PCNN_REQUIRE(h, H >= 3 && W >= 3, "pcnn_bc_ring_bwd: grid %dx%d too small", H, W);
-  hipLaunchKernelGGL(bc_ring_bwd_kernel, grid1d((int64_t)N * H * W), dim3(256), 0, h->stream, N, H, W, neumann, dy, dx);
-  PCNN_CHECK_LAUNCH(h, "pcnn_bc_ring_bwd");
-  return 0;
+  return pcnn_bc_ring_edges_bwd(h, N, H, W, neumann ? 15 : 0, dy, dx);
 }
 
 extern "C" int pcnn_adam_step(pcnn_handle h, int64_t n, float* w, const float* g, float* m, float* v, float lr, float beta1, float beta2,

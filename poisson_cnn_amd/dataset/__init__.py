@@ -19,6 +19,7 @@ import torch
 
 from . import _kernels as K
 from .. import ops
+from ..utils import neumann_flags
 
 
 # ----------------------------------------------------------------------------- host-side samplers (dataset/utils)
@@ -125,13 +126,7 @@ def _streams(seed, shard):
 _BOUNDARY_KEYS = ('left', 'top', 'right', 'bottom')
 
 
-def _neumann_flags(boundary_types):
-    bt = {k: 'dirichlet' for k in _BOUNDARY_KEYS}
-    for k, v in (boundary_types or {}).items():
-        if k not in bt or str(v).lower() not in ('dirichlet', 'neumann'):
-            raise ValueError("boundary_types maps 'left'/'right'/'bottom'/'top' to 'dirichlet' or 'neumann' (got %r: %r)" % (k, v))
-        bt[k] = str(v).lower()
-    return tuple(bt[k] == 'neumann' for k in ('left', 'right', 'bottom', 'top'))
+_neumann_flags = neumann_flags                    # (left, right, bottom, top): the one parser of boundary types, utils.neumann_flags
 
 
 class _generator:

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .utils import advanced_pad_amounts, canonical_activation, glorot_limit, same_pad_amounts, split_indices
+from .utils import advanced_pad_amounts, canonical_activation, glorot_limit, neumann_mask, same_pad_amounts, split_indices
 
 
 # ----------------------------------------------------------------------------- parameters
@@ -134,7 +134,7 @@ class ParamStore:
 
 class Context:
     """Per-model scratch: workspace + the scratch filter used by data-gradient convolutions - one set PER STREAM (the coarse bottleneck branches
-    of the homogeneous model run on streams of their own, models.Homogeneous_Poisson_NN_Legacy.call), so two streams never share a scratch buffer."""
+    of the homogeneous model run on streams of their own, models._BottleneckMerge), so two streams never share a scratch buffer."""
 
     def __init__(self):
         self._ws = {}
@@ -484,18 +484,18 @@ class _bottleneck_base:
         self.up = int(upsampling_factor) if upsampling_factor is not None else self.f
         self.downsampling_factor = self.f
         self.filters = filters
-        self.method = downsampling_method.lower()
+        self.down_method = downsampling_method.lower()
         self.pool = pool_downsampling_method.lower()
         kw = dict(padding_mode=padding_mode, pad_value=constant_padding_value, activation=conv_activation, use_bias=conv_use_bias)
         self.down_conv = None
         self.stages = []                                                # ConvUnit / resnet objects in call order (a conv's BN is fused into it)
         n_layers = 0                                                    # the reference's len(self.conv_layers): BN layers count
-        if self.method == 'conv':
+        if self.down_method == 'conv':
             if conv_downsampling_kernel_size is None:
                 raise ValueError('conv_downsampling_kernel_size is required for downsampling_method="conv"')
             self.down_conv = ConvUnit(store, ctx, name + '/downsample', conv_downsampling_kernel_size, cin, filters, stride=self.f, **kw)
             c = filters
-        elif self.method == 'pool':
+        elif self.down_method == 'pool':
             c = cin
             if use_resnet:
                 self.stages.append(ConvUnit(store, ctx, name + '/conv0', conv_kernel_size, cin, filters, **kw))
@@ -515,7 +515,7 @@ class _bottleneck_base:
                 c = filters
             i += 1
         # names kept from round 1 for the shipped (pool + resnet) configuration: conv0, res0, res1, ...
-        self.conv0 = self.stages[0] if (self.method == 'pool' and use_resnet) else None
+        self.conv0 = self.stages[0] if (self.down_method == 'pool' and use_resnet) else None
         self.res = [st for st in self.stages if isinstance(st, resnet)]
 
     def _down_and_convs(self, x, training, pooled=None):
@@ -553,6 +553,30 @@ class _bottleneck_base:
     def out_hw(self, H, W):
         return int((H / self.f) * self.up), int((W / self.f) * self.up)   # blocks/bottleneck_block.py:82,109
 
+    # The branch in two halves - its down-sampled convolution stages and the up-sampling that accumulates into the merge buffer - so that the model
+    # can run the first half of a coarse branch on a stream of its own (models._BottleneckMerge).  A subclass supplies the up-sampling:
+    #   up_into(o, hw, merged, alpha, beta)   merged = beta merged + alpha up(o), no state; `o` / `merged` may be the same batch slice of both
+    #   note_upsampled(o, training)           what the backward pass needs of `o` (the caller may up-sample `o` itself: ops.resize_fwd_multi)
+    #   backward_up(dmerged, alpha)           the up-sampling's adjoint (and its weight gradients) -> d o
+    # and resize_method: the ops.RESIZE name if ops.resize_fwd_multi can up-sample this branch together with others, else None.
+    resize_method = None
+
+    def forward_convs(self, x, training=True, pooled=None):
+        return self._down_and_convs(x, training, pooled)
+
+    def forward_up(self, o, hw, merged, alpha, beta, training=True):
+        self.note_upsampled(o, training)
+        self.up_into(o, hw, merged, alpha, beta)
+
+    def forward_into(self, x, merged, alpha, beta, training=True, pooled=None):
+        self.forward_up(self.forward_convs(x, training, pooled), (x.shape[1], x.shape[2]), merged, alpha, beta, training)
+
+    def backward_convs(self, dcoarse, d_in):
+        return self._backward_convs_and_down(dcoarse, d_in)
+
+    def backward_from(self, dmerged, alpha, d_in):
+        return self.backward_convs(self.backward_up(dmerged, alpha), d_in)
+
 
 class bottleneck_block_deconvupsample(_bottleneck_base):
     """blocks/bottleneck_block.py:88-118 + layers/deconvupscale.py."""
@@ -567,26 +591,13 @@ class bottleneck_block_deconvupsample(_bottleneck_base):
         if deconv_use_bias:
             store.add(name + '/deconv/bias', (self.filters,), 'glorot')
 
-    # The branch in two halves - its down-sampled convolution stages and the up-sampling that accumulates into the merge buffer - so that the model
-    # can run the first half of a coarse branch on a stream of its own (models.Homogeneous_Poisson_NN_Legacy.call / backward).
-    def forward_convs(self, x, training=True, pooled=None):
-        return self._down_and_convs(x, training, pooled)
-
-    def forward_up(self, o, hw, merged, alpha, beta, training=True):
-        self.note_upsampled(o, training)
-        self.up_into(o, hw, merged, alpha, beta)
-
     def up_into(self, o, hw, merged, alpha, beta):
-        """the up-sampling alone (no state): merged = beta merged + alpha deconv(o); `o` / `merged` may be the same batch slice of the branch output / merge buffer"""
         assert self.out_hw(*hw) == tuple(hw), 'deconv branch must restore the input resolution'
         ops.deconv_fwd(o, self.store.w[self.name + '/deconv/kernel'], self.store.w[self.name + '/deconv/bias'] if self.deconv_use_bias else None,
                        tuple(hw), self.up, alpha=alpha, beta=beta, out=merged)
 
     def note_upsampled(self, o, training=True):
         self.coarse = o if training else None
-
-    def forward_into(self, x, merged, alpha, beta, training=True, pooled=None):
-        self.forward_up(self.forward_convs(x, training, pooled), (x.shape[1], x.shape[2]), merged, alpha, beta, training)
 
     def backward_up(self, dmerged, alpha):
         g = self.store.g
@@ -597,48 +608,25 @@ class bottleneck_block_deconvupsample(_bottleneck_base):
                               dbias=g[self.name + '/deconv/bias'] if self.deconv_use_bias else None, ws=self.ctx.ws, kernel_size=(self.dk, self.dk))
         return ops.deconv_bwd_data(dmerged, k, (o.shape[1], o.shape[2]), self.up, alpha=alpha)
 
-    def backward_convs(self, dcoarse, d_in):
-        return self._backward_convs_and_down(dcoarse, d_in)
-
-    def backward_from(self, dmerged, alpha, d_in):
-        return self.backward_convs(self.backward_up(dmerged, alpha), d_in)
-
 
 class bottleneck_block_multilinearupsample(_bottleneck_base):
     """blocks/bottleneck_block.py:8-86 + layers/Upsample.py (tf.image.resize, half-pixel centres)."""
 
     def __init__(self, store, ctx, name, cin, *, resize_method='bilinear', **kw):
         super().__init__(store, ctx, name, cin, **kw)
-        self.method = resize_method.lower()
-        if self.method not in ops.RESIZE:
+        self.resize_method = resize_method.lower()
+        if self.resize_method not in ops.RESIZE:
             raise ValueError('unsupported resize method ' + resize_method)
-
-    def forward_convs(self, x, training=True, pooled=None):
-        return self._down_and_convs(x, training, pooled)
-
-    def forward_up(self, o, hw, merged, alpha, beta, training=True):
-        self.note_upsampled(o, training)
-        self.up_into(o, hw, merged, alpha, beta)
 
     def up_into(self, o, hw, merged, alpha, beta):
         assert self.out_hw(*hw) == tuple(hw)
-        ops.resize_fwd(o, tuple(hw), self.method, alpha=alpha, beta=beta, out=merged)
+        ops.resize_fwd(o, tuple(hw), self.resize_method, alpha=alpha, beta=beta, out=merged)
 
     def note_upsampled(self, o, training=True):
-        """what forward_up remembers for the backward pass (the caller may up-sample `o` itself: ops.resize_fwd_multi, batch chunks)"""
         self.coarse_hw = (o.shape[1], o.shape[2])
 
-    def forward_into(self, x, merged, alpha, beta, training=True, pooled=None):
-        self.forward_up(self.forward_convs(x, training, pooled), (x.shape[1], x.shape[2]), merged, alpha, beta, training)
-
     def backward_up(self, dmerged, alpha):
-        return ops.resize_bwd(dmerged, self.coarse_hw, self.method, alpha=alpha)
-
-    def backward_convs(self, dcoarse, d_in):
-        return self._backward_convs_and_down(dcoarse, d_in)
-
-    def backward_from(self, dmerged, alpha, d_in):
-        return self.backward_convs(self.backward_up(dmerged, alpha), d_in)
+        return ops.resize_bwd(dmerged, self.coarse_hw, self.resize_method, alpha=alpha)
 
 
 # ----------------------------------------------------------------------------- dense / scaling / jacobi
@@ -767,7 +755,7 @@ class JacobiIterationLayer:
     Orders must be even, at least 2 and below that axis's stencil size: an odd order has a zero centre coefficient (the reference divides by it and
     returns inf), and the Vandermonde system of get_fd_coefficients has no row for an order >= the stencil size.
 
-    boundary_types (extension): None keeps the ring frozen, as the reference does.  A dict edge -> 'dirichlet' | 'neumann' (dataset._neumann_flags)
+    boundary_types (extension): None keeps the ring frozen, as the reference does.  A dict edge -> 'dirichlet' | 'neumann' (utils.neumann_flags)
     runs the fused route for every stencil and re-imposes the Neumann edges after every sweep: their band takes the mirror image of the updated
     interior (first order, u_0 = u_1, as the model's SYMMETRIC ring), forward and adjoint; Dirichlet edges stay frozen."""
 
@@ -776,12 +764,11 @@ class JacobiIterationLayer:
         self.n = int(n_iterations)
         self.neumann_mask = None
         if boundary_types is not None:
-            from .dataset import _neumann_flags
             if not isinstance(boundary_types, dict):
                 raise ValueError("JacobiIterationLayer: boundary_types is None or a dict edge -> 'dirichlet' | 'neumann', got %r" % (boundary_types,))
             if fused is not None and not fused:
                 raise ValueError('JacobiIterationLayer: boundary_types runs on the fused kernels only (fused=False given)')
-            self.neumann_mask = sum(1 << i for i, f in enumerate(_neumann_flags(boundary_types)) if f)
+            self.neumann_mask = neumann_mask(boundary_types)
             fused = True
         ss = [stencil_sizes] * 2 if isinstance(stencil_sizes, (int, np.integer)) else list(stencil_sizes)
         od = [orders] * 2 if isinstance(orders, (int, np.integer)) else list(orders)

@@ -5,8 +5,8 @@ experiments/hpnn.json loads unchanged), `model([rhs, dx]) -> (N,1,H,W)`, `compil
 `train_step(((rhs, dx), y))`, `fit(sequence, epochs, callbacks)`, `trainable_variables`, `get_weights/set_weights`,
 `save_weights/load_weights`, `summary()`.  The API is channels_first like the reference configs; inside, data is NHWC.
 """
+import collections
 import copy
-
 import os
 
 import numpy as np
@@ -14,7 +14,7 @@ import torch
 
 from . import layers as L
 from . import ops
-from .utils import get_init_arguments_from_config, split_indices
+from .utils import BC_EDGES, get_init_arguments_from_config, neumann_flags, neumann_mask, split_indices
 
 
 def process_normalizations(normalizations):
@@ -541,6 +541,147 @@ class _ModelBase:
 
 _BRANCH_STREAMS = os.environ.get('PCNN_BRANCH_STREAMS', '1') != '0'      # 0: the coarse bottleneck branches stay on the main stream
 
+MergePlan = collections.namedtuple('MergePlan', 'pyramid order stream tail')
+
+
+def merge_plan(branches, H, W, coarse_factor):
+    """What the bottleneck merge does on an H x W grid - host arithmetic only, no tensor and no stream.  branches: one (factor, 'pool' | 'conv'
+    down-sampling, pool kind, resize method or None) per branch, in the model's order.  Returns
+      pyramid  {factor: parent factor or None}, in the order the levels are pooled.  The branches average-pool the SAME tensor by 2, 3, 4, 8, ...
+               (blocks/bottleneck_block.py:36-41): one full-resolution read each.  Where a factor f and an already pooled factor g | f both divide
+               the image (no SAME padding), pool_f = pool_{f/g} o pool_g exactly (equal-weight means of equal-size blocks), so only the factors
+               without a divisor read the full tensor.  A branch whose factor is a level takes that level as its input.
+      order    the branch indices in the order they accumulate into the merge buffer: the coarse ones (factor >= coarse_factor) last
+      stream   {coarse branch index: stream index}.  A branch that pools the full-resolution tensor itself (its factor does not divide the image)
+               accumulates its input gradient into d_initial in the backward pass: all such branches share stream 0, so that they do so one after
+               the other; every pyramid-fed one has a stream of its own
+      tail     the resize branches at the end of `order` that one ops.resize_fwd_multi pass sums: at most three, never the whole order, ended by
+               a branch without a resize method; fewer than two: none"""
+    pyramid = {}
+    for f in sorted({f for f, down, pool, _ in branches if down == 'pool' and pool in ('average', 'avg') and H % f == 0 and W % f == 0}):
+        pyramid[f] = max([g for g in pyramid if f % g == 0], default=None)
+    coarse = [i for i, b in enumerate(branches) if b[0] >= coarse_factor]
+    order = [i for i in range(len(branches)) if i not in coarse] + coarse
+    stream = {i: (k + 1 if branches[i][0] in pyramid else 0) for k, i in enumerate(coarse)}
+    ntail = 0
+    while ntail < min(3, len(order) - 1) and branches[order[-1 - ntail]][3] is not None:
+        ntail += 1
+    return MergePlan(pyramid, order, stream, order[len(order) - ntail:] if ntail >= 2 else [])
+
+
+class _BottleneckMerge:
+    """The merge stage of Homogeneous_Poisson_NN_Legacy (reference :204-222): every bottleneck branch reads `initial`, and their up-sampled outputs
+    are summed, scaled by 1 / (branches x filters), into the merge buffer.  forward() / backward() execute merge_plan(); between them this object
+    keeps `initial`, the pooling pyramid and the stream each branch ran on."""
+
+    def __init__(self, blocks, ctx, filters):
+        self.blocks, self.ctx = list(blocks), ctx
+        self.branches = [(b.f, b.down_method, b.pool, b.resize_method) for b in self.blocks]
+        self.alpha = 1.0 / float(len(self.blocks) * filters)     # :222
+        self._saved = None
+
+    def pool_pyramid(self, x, plan):
+        """{factor: pooled x} of plan.pyramid, each level pooled from its parent."""
+        pyr = {}
+        for f, parent in plan.pyramid.items():
+            pyr[f] = ops.pool2d_fwd(x if parent is None else pyr[parent], f if parent is None else f // parent, 'average')
+        return pyr
+
+    def forward(self, initial, merged, training, coarse_factor):
+        """merged (a channel slice of the concatenation buffer) = alpha * sum over the branches of up(convs(down(initial)))."""
+        H, W = initial.shape[1], initial.shape[2]
+        blocks, alpha = self.blocks, self.alpha
+        plan = merge_plan(self.branches, H, W, coarse_factor)
+        pyr = self.pool_pyramid(initial, plan)
+        # The eight branches are independent between the pooling pyramid and the merge buffer, and the coarse ones (factor >= 8: images of 128^2 and
+        # below at 1024^2) are chains of launches that fill a fraction of the chip - 7.9 ms per training step back to back (tools/probe_branches.py).
+        # Their convolution stages run on streams of their own (each stream has its libpcnn handle and its scratch, layers.Context), so that one
+        # branch's small or tailing launches fill the gaps of another's; only the up-sampling, which accumulates into the shared merge buffer, stays on
+        # the main stream.  The accumulation order is the same with and without the streams, so the result does not depend on the mode.
+        pending, streams = {}, {}
+        if plan.stream and self.ctx.use_side and _BRANCH_STREAMS:
+            ready = torch.cuda.Event()
+            ready.record(torch.cuda.current_stream())
+            for i, k in plan.stream.items():
+                st = self.ctx.branch_stream(k)
+                with torch.cuda.stream(st):
+                    st.wait_event(ready)
+                    o = blocks[i].forward_convs(initial, training, pyr.get(blocks[i].f))
+                    done = torch.cuda.Event()
+                    done.record(st)
+                pending[i] = (o, done)
+                if training:
+                    streams[i] = st
+        # The eight branches accumulate into the merge slice (8 x 1024^2 x 32 channels: 1.07 GB, read and written once per branch); the resize branches at the end of
+        # the order are summed in ONE read-modify-write pass (ops.resize_fwd_multi: the arithmetic and order of their separate calls, bit for bit).  (Measured and
+        # rejected, round 6: running the accumulation over batch chunks of <= 160 MB of merge slice, every branch per chunk, so that a chunk would stay in the 256 MB
+        # Infinity Cache between its passes - the single-stream step did not move, 195.4 vs 195.2 ms.)
+        tail = []
+        for n, i in enumerate(plan.order):
+            b = blocks[i]
+            if i in pending:                                          # (a branch is waited for right before ITS up-sampling: the later branches' convolution
+                o, done = pending[i]                                  # stages keep running on their streams under the earlier branches' up-sampling)
+                torch.cuda.current_stream().wait_event(done)
+                o.record_stream(torch.cuda.current_stream())
+            else:
+                o = b.forward_convs(initial, training, pyr.get(b.f))
+            b.note_upsampled(o, training)
+            if i in plan.tail:
+                tail.append((b, o))
+            else:
+                b.up_into(o, (H, W), merged, alpha, 0.0 if n == 0 else 1.0)
+        if tail and ops.resize_fwd_multi([o for _, o in tail], (H, W), [b.resize_method for b, _ in tail], alpha=alpha, beta=1.0, out=merged) is None:
+            for b, o in tail:
+                b.up_into(o, (H, W), merged, alpha, 1.0)
+        self._saved = (initial, pyr, plan.pyramid, streams) if training else None
+
+    def backward(self, dmerged, d_initial):
+        """Adds the merge stage's gradient with respect to `initial` into d_initial (and fills the branches' weight gradients)."""
+        initial, pyr, parents, streams = self._saved
+        self._saved = None
+        alpha = self.alpha
+        grads = {}
+        late = []
+        main = torch.cuda.current_stream()
+
+        def add(f, g):
+            grads[f] = g if f not in grads else ops.axpby(1.0, g, 1.0, grads[f])
+        for i, b in enumerate(self.blocks):
+            st = streams.get(i)
+            if st is None:
+                # a branch that pools the full-resolution tensor itself ADDS into d_initial: on the main stream that must come after every
+                # stream-run branch that did the same (they share stream 0 among themselves; ADVICE r4: non-default PCNN_COARSE_FACTOR / factor orders)
+                for _, g_prev, done_prev in late:
+                    if g_prev is None:
+                        main.wait_event(done_prev)
+                g = b.backward_from(dmerged, alpha, d_initial)
+                if g is not None:
+                    add(b.f, g)
+                continue
+            dco = b.backward_up(dmerged, alpha)                       # reads the shared gradient: main stream
+            ev = torch.cuda.Event()
+            ev.record(main)
+            with torch.cuda.stream(st):                               # the branch's convolution stages: the stream its saved activations live on
+                st.wait_event(ev)
+                dco.record_stream(st)
+                g = b.backward_convs(dco, d_initial)                 # pyramid-fed: returns the pooled gradient; else adds into d_initial (stream 0 only)
+                done = torch.cuda.Event()
+                done.record(st)
+            late.append((b, g, done))
+        for b, g, done in late:
+            main.wait_event(done)
+            if g is not None:
+                g.record_stream(main)
+                add(b.f, g)
+        for f in sorted(grads, reverse=True):                      # the pyramid's adjoint: coarsest level first, each into its parent
+            parent = parents[f]
+            if parent is None:
+                ops.pool2d_bwd(initial, grads[f], f, 'average', dx=d_initial, accumulate=True)
+            else:
+                if parent not in grads:
+                    grads[parent] = torch.zeros_like(pyr[parent])
+                ops.pool2d_bwd(pyr[parent], grads[f], f // parent, 'average', dx=grads[parent], accumulate=True)
+
 
 class Homogeneous_Poisson_NN_Legacy(_ModelBase):
     model_name = 'Homogeneous_Poisson_NN_Legacy'
@@ -570,13 +711,9 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
             raise ValueError('Provide a config for bottleneck blocks')
         if final_convolutions_config is None:
             raise ValueError('Provide a config for final convolutions')
-        if isinstance(bc_type, dict):
-            from .dataset import _neumann_flags
-            flags = _neumann_flags(bc_type)
-        elif not isinstance(bc_type, str) or bc_type.lower() not in ('dirichlet', 'neumann'):
+        if bc_type is None:
             raise ValueError('bc_type can only be neumann or dirichlet.')
-        else:
-            flags = (bc_type.lower() == 'neumann',) * 4
+        flags = neumann_flags(bc_type)
         if smoother_boundaries not in ('frozen', 'enforce'):
             raise ValueError("smoother_boundaries can only be 'frozen' or 'enforce'.")
         self.density_input = bool(density_input)
@@ -593,9 +730,8 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
         self.output_scaling = process_output_scaling_modes(output_scaling)
         self.use_batchnorm = use_batchnorm
         self.use_positional_embeddings = use_positional_embeddings
-        self.neumann = all(flags)
-        self.neumann_mask = sum(1 << i for i, f in enumerate(flags) if f)
-        self.per_edge_bc = isinstance(bc_type, dict)              # a dict runs the per-edge ring kernels, a string the reference's two modes as before
+        self.neumann_mask = neumann_mask(bc_type)                # the model's one record of its boundary types (bits as ops.bc_ring_fwd's)
+        self.per_edge_bc = isinstance(bc_type, dict)              # how bc_type was given; a uniform dict and the string run the same kernels
         self.store = S = L.ParamStore()
         # BatchNormalization mode inside train_step: False = moving statistics (what the reference's train_step most likely does,
         # SURVEY.md row H4), True = batch statistics + moving-average update (Keras training=True semantics, per replica)
@@ -631,6 +767,7 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
         self.bottleneck_multilinear_blocks = [L.bottleneck_block_multilinearupsample(S, C, 'multilinear_f%d' % a['downsampling_factor'], c0, use_batchnorm=use_batchnorm, **a)
                                               for a in mcfgs]
         # merge + post-merge (:71-76)
+        self.merge = _BottleneckMerge(self.bottleneck_deconv_blocks + self.bottleneck_multilinear_blocks, C, F)
         self.non_bottleneck_conv = L.ConvUnit(S, C, 'non_bottleneck_conv', 5, c0, F, pad='same', activation='leaky_relu')
         self.post_merge_conv = L.ConvUnit(S, C, 'post_merge_conv', 7, 2 * F, F, pad='same', activation='leaky_relu')
         self.post_merge_resnet = L.resnet(S, C, 'post_merge_resnet', F, 7, activation='leaky_relu')
@@ -664,7 +801,7 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
             din = u
         enforce = None
         if smoother_boundaries == 'enforce' and self.neumann_mask:
-            enforce = {e: 'neumann' if f else 'dirichlet' for e, f in zip(('left', 'right', 'bottom', 'top'), flags)}
+            enforce = {e: 'neumann' if f else 'dirichlet' for e, f in zip(BC_EDGES, flags)}
         if self.density_input:
             self.postsmoother = L.VariableDensityJacobiLayer(postsmoother_iterations) if postsmoother_iterations > 0 else None
         else:
@@ -678,18 +815,6 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
                                                                         # convolution stages on streams of their own; measured at 8 x 1024^2: none 243, >= 8: 238.9, all: 236 ms per step
 
     # ------------------------------------------------------------------ forward
-    def _pool_pyramid(self, x, blocks):
-        """The eight branches average-pool the SAME tensor by 2, 3, 4, 8, ..., 128 (blocks/bottleneck_block.py:36-41): eight full-resolution
-        reads.  Where a factor f and an already pooled factor g | f both divide the image (no SAME padding), pool_f = pool_{f/g} o pool_g
-        exactly (equal-weight means of equal-size blocks), so only the factors without a divisor read the full tensor.  {f: (tensor, parent g)}"""
-        N, H, W, _ = x.shape
-        fs = sorted({b.f for b in blocks if b.down_conv is None and b.pool in ('average', 'avg') and H % b.f == 0 and W % b.f == 0})
-        pyr = {}
-        for f in fs:
-            parent = max([g for g in pyr if f % g == 0], default=None)
-            pyr[f] = (ops.pool2d_fwd(x if parent is None else pyr[parent][0], f if parent is None else f // parent, 'average'), parent)
-        return pyr
-
     def _assemble(self, rhs):
         """The network's NHWC input and the one-channel (N,H,W) fields Scaling and the smoother read: (x, rhs_hw, rho_hw - None without density_input)."""
         if self.density_input:
@@ -732,63 +857,7 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
         initial = x
         F = self.filters
         cat = ops.empty((N, H, W, 2 * F), self.device)       # [non_bottleneck_conv | merged] (tf.concat axis=1, :224)
-        merged = cat[..., F:]
-        blocks = self.bottleneck_deconv_blocks + self.bottleneck_multilinear_blocks
-        alpha = 1.0 / float(len(blocks) * F)                     # :222
-        pyr = self._pool_pyramid(initial, blocks)
-        # The eight branches are independent between the pooling pyramid and the merge buffer, and the coarse ones (factor >= 8: images of 128^2 and
-        # below at 1024^2) are chains of launches that fill a fraction of the chip - 7.9 ms per training step back to back (tools/probe_branches.py).
-        # Their convolution stages run on streams of their own (each stream has its libpcnn handle and its scratch, layers.Context), so that one
-        # branch's small or tailing launches fill the gaps of another's; only the up-sampling, which accumulates into the shared merge buffer, stays on
-        # the main stream.  The accumulation order is the same with and without the streams, so the result does not depend on the mode.
-        coarse = [b for b in blocks if b.f >= self.COARSE_FACTOR]
-        order = [b for b in blocks if b not in coarse] + coarse
-        pending = {}
-        self._branch_streams = {}
-        if coarse and self.ctx.use_side and _BRANCH_STREAMS:
-            main = torch.cuda.current_stream()
-            ready = torch.cuda.Event()
-            ready.record(main)
-            for k, b in enumerate(coarse):
-                # a branch that pools the full-resolution tensor itself (its factor does not divide the image) accumulates its input gradient
-                # into d_initial in the backward pass: all such branches share stream 0, so that they do so one after the other
-                st = self.ctx.branch_stream(k + 1 if b.f in pyr else 0)
-                with torch.cuda.stream(st):
-                    st.wait_event(ready)
-                    o = b.forward_convs(initial, training, pyr[b.f][0] if b.f in pyr else None)
-                    done = torch.cuda.Event()
-                    done.record(st)
-                pending[b] = (o, done)
-                if training:
-                    self._branch_streams[b] = st
-        # The eight branches accumulate into the merge slice (8 x 1024^2 x 32 channels: 1.07 GB, read and written once per branch); the resize branches at the end of
-        # the order are summed in ONE read-modify-write pass (ops.resize_fwd_multi: the arithmetic and order of their separate calls, bit for bit).  (Measured and
-        # rejected, round 6: running the accumulation over batch chunks of <= 160 MB of merge slice, every branch per chunk, so that a chunk would stay in the 256 MB
-        # Infinity Cache between its passes - the single-stream step did not move, 195.4 vs 195.2 ms.)
-        ntail = 0
-        while ntail < min(3, len(order) - 1) and hasattr(order[len(order) - 1 - ntail], 'method'):
-            ntail += 1
-        if ntail < 2:
-            ntail = 0
-        tail = []
-        for i, b in enumerate(order):
-            if b in pending:                                          # (a branch is waited for right before ITS up-sampling: the later branches' convolution
-                o, done = pending[b]                                  # stages keep running on their streams under the earlier branches' up-sampling)
-                torch.cuda.current_stream().wait_event(done)
-                o.record_stream(torch.cuda.current_stream())
-            else:
-                o = b.forward_convs(initial, training, pyr[b.f][0] if b.f in pyr else None)
-            b.note_upsampled(o, training)
-            if i >= len(order) - ntail:
-                tail.append((b, o))
-            else:
-                b.up_into(o, (H, W), merged, alpha, 0.0 if i == 0 else 1.0)
-        if tail:
-            beta0 = 0.0 if ntail == len(order) else 1.0
-            if ops.resize_fwd_multi([o for _, o in tail], (H, W), [b.method for b, _ in tail], alpha=alpha, beta=beta0, out=merged) is None:
-                for k, (b, o) in enumerate(tail):
-                    b.up_into(o, (H, W), merged, alpha, beta0 if k == 0 else 1.0)
-        self._pyr = pyr if training else None
+        self.merge.forward(initial, cat[..., F:], training, self.COARSE_FACTOR)     # the bottleneck branches, summed (:204-222)
         self.non_bottleneck_conv.forward(initial, out=cat[..., :F], training=training)
         x = self.post_merge_conv.forward(cat, training=training)
         x = self.post_merge_resnet.forward(x, training=training, x_absmax=self.post_merge_conv.out_absmax)
@@ -797,7 +866,7 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
             d = lyr.forward(d, training=training)
         xs = ops.channel_scale_fwd(x, d)                          # :231
         if training:
-            self._saved = {'initial': initial, 'scale_in': x, 'dx_info': d, 'shape': (N, H, W)}
+            self._saved = {'scale_in': x, 'dx_info': d, 'shape': (N, H, W)}
         x = xs
         hint = None
         for lyr in self.final:
@@ -805,7 +874,7 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
             hint = lyr.out_absmax
         if self.scaling is not None:
             x = self.scaling.forward(x, rhs_hw.view(N, H, W, 1), training=training)
-        x = ops.bc_ring_edges_fwd(x, self.neumann_mask) if self.per_edge_bc else ops.bc_ring_fwd(x, self.neumann)     # :251
+        x = ops.bc_ring_fwd(x, self.neumann_mask)               # :251
         return self._smooth(x, rhs_hw, rho_hw, dx, training).view(N, 1, H, W)
 
     # ------------------------------------------------------------------ backward
@@ -818,7 +887,7 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
         d = dpred.contiguous().view(N, H, W, 1)
         if self.postsmoother is not None:
             d = self.postsmoother.backward(d)
-        d = ops.bc_ring_edges_bwd(d, self.neumann_mask) if self.per_edge_bc else ops.bc_ring_bwd(d, self.neumann)
+        d = ops.bc_ring_bwd(d, self.neumann_mask)
         if self.scaling is not None:
             d = self.scaling.backward(d)
         ready = False                                              # the gradient arriving at a layer already went through its activation backward
@@ -841,49 +910,7 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
         d = self.post_merge_resnet.backward(d, inplace=True, dz_ready=fused is not None, post=post)
         dcat = self.post_merge_conv.backward(d, inplace=True, dz_ready=post is not None and post.applied)
         d_initial = self.non_bottleneck_conv.backward(dcat[..., :F], inplace=False)
-        dmerged = dcat[..., F:]
-        blocks = self.bottleneck_deconv_blocks + self.bottleneck_multilinear_blocks
-        alpha = 1.0 / float(len(blocks) * F)
-        grads = {}
-        late = []
-        main = torch.cuda.current_stream()
-        for b in blocks:
-            st = self._branch_streams.get(b)
-            if st is None:
-                # a branch that pools the full-resolution tensor itself ADDS into d_initial: on the main stream that must come after every
-                # stream-run branch that did the same (they share stream 0 among themselves; ADVICE r4: non-default PCNN_COARSE_FACTOR / factor orders)
-                for _, g_prev, done_prev in late:
-                    if g_prev is None:
-                        main.wait_event(done_prev)
-                g = b.backward_from(dmerged, alpha, d_initial)
-                if g is not None:
-                    grads[b.f] = g if b.f not in grads else ops.axpby(1.0, g, 1.0, grads[b.f])
-                continue
-            dco = b.backward_up(dmerged, alpha)                       # reads the shared gradient: main stream
-            ev = torch.cuda.Event()
-            ev.record(main)
-            with torch.cuda.stream(st):                               # the branch's convolution stages: the stream its saved activations live on
-                st.wait_event(ev)
-                dco.record_stream(st)
-                g = b.backward_convs(dco, d_initial)                 # pyramid-fed: returns the pooled gradient; else adds into d_initial (stream 0 only)
-                done = torch.cuda.Event()
-                done.record(st)
-            late.append((b, g, done))
-        for b, g, done in late:
-            main.wait_event(done)
-            if g is not None:
-                g.record_stream(main)
-                grads[b.f] = g if b.f not in grads else ops.axpby(1.0, g, 1.0, grads[b.f])
-        self._branch_streams = {}
-        for f in sorted(grads, reverse=True):                      # the pyramid's adjoint: coarsest level first, each into its parent
-            parent = self._pyr[f][1]
-            if parent is None:
-                ops.pool2d_bwd(sv['initial'], grads[f], f, 'average', dx=d_initial, accumulate=True)
-            else:
-                if parent not in grads:
-                    grads[parent] = torch.zeros_like(self._pyr[parent][0])
-                ops.pool2d_bwd(self._pyr[parent][0], grads[f], f // parent, 'average', dx=grads[parent], accumulate=True)
-        self._pyr = None
+        self.merge.backward(dcat[..., F:], d_initial)
         d = d_initial
         for i, c in enumerate(reversed(self.pre)):
             d = c.backward(d, need_dx=(i < len(self.pre) - 1), inplace=True)

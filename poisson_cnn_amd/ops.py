@@ -955,34 +955,28 @@ def sample_scale_bwd(x, g, dy):
     return dx, dg
 
 
-def bc_ring_fwd(x, neumann):
+def _ring_mask(mask):
+    """A flag (bool: the reference's two modes, every edge Dirichlet / every edge Neumann) or a per-edge mask -> the mask."""
+    return (15 if mask else 0) if isinstance(mask, bool) else int(mask)
+
+
+def bc_ring_fwd(x, mask):
+    """The boundary ring: mask bit 0 / 1 / 2 / 3 set = the left (y = 0) / right (y = H-1) / bottom (x = 0) / top (x = W-1) edge is Neumann, clear =
+    Dirichlet; at a corner a Dirichlet edge wins.  False / True stand for 0 / 15.  x (N,H,W,1)."""
     N, H, W = x.shape[0], x.shape[1], x.shape[2]
     y = torch.empty_like(x)
-    handle().call('pcnn_bc_ring_fwd', c_int(N), c_int(H), c_int(W), c_int(1 if neumann else 0), _p(x), _p(y))
+    handle().call('pcnn_bc_ring_edges_fwd', c_int(N), c_int(H), c_int(W), c_int(_ring_mask(mask)), _p(x), _p(y))
     return y
 
 
-def bc_ring_bwd(dy, neumann):
+def bc_ring_bwd(dy, mask):
     N, H, W = dy.shape[0], dy.shape[1], dy.shape[2]
     dx = torch.empty_like(dy)
-    handle().call('pcnn_bc_ring_bwd', c_int(N), c_int(H), c_int(W), c_int(1 if neumann else 0), _p(dy), _p(dx))
+    handle().call('pcnn_bc_ring_edges_bwd', c_int(N), c_int(H), c_int(W), c_int(_ring_mask(mask)), _p(dy), _p(dx))
     return dx
 
 
-def bc_ring_edges_fwd(x, mask):
-    """The ring with a boundary type per edge: mask bit 0 / 1 / 2 / 3 set = the left (y = 0) / right (y = H-1) / bottom (x = 0) / top (x = W-1) edge is
-    Neumann, clear = Dirichlet; at a corner a Dirichlet edge wins.  x (N,H,W,1)."""
-    N, H, W = x.shape[0], x.shape[1], x.shape[2]
-    y = torch.empty_like(x)
-    handle().call('pcnn_bc_ring_edges_fwd', c_int(N), c_int(H), c_int(W), c_int(int(mask)), _p(x), _p(y))
-    return y
-
-
-def bc_ring_edges_bwd(dy, mask):
-    N, H, W = dy.shape[0], dy.shape[1], dy.shape[2]
-    dx = torch.empty_like(dy)
-    handle().call('pcnn_bc_ring_edges_bwd', c_int(N), c_int(H), c_int(W), c_int(int(mask)), _p(dy), _p(dx))
-    return dx
+bc_ring_edges_fwd, bc_ring_edges_bwd = bc_ring_fwd, bc_ring_bwd          # the names the per-edge pair had while there were two
 
 
 def jacobi_sweep(u, rhs, dx2):

@@ -303,7 +303,7 @@ def load_model_checkpoint(model, checkpoint_path, **unused):
 
 def main(argv=None):
     from . import configs
-    from .utils import convert_tf_object_names
+    from .utils import convert_tf_object_names, neumann_flags
     from .models import Homogeneous_Poisson_NN_Legacy, Dirichlet_BC_NN_Legacy_2, Poisson_CNN_Legacy
     from .losses import loss_wrapper, variable_density_loss_wrapper
     from .dataset import (numerical_dataset_generator, reverse_poisson_dataset_generator, reverse_poisson_dataset_generator_homogeneous_neumann,
@@ -377,15 +377,11 @@ def main(argv=None):
         model = classes[model_type](**mcfg)
     else:
         bc_type = config['model'].get('bc_type', 'dirichlet')
-        if isinstance(bc_type, dict):                # per-edge boundary types (extension): the numerical generator's mixed Dirichlet/Neumann solve
-            from .dataset import _neumann_flags
-            flags = _neumann_flags(bc_type)
-            if args.dataset_type == 'analytical' and any(flags) and not all(flags):
-                raise ValueError('there is no analytic mixed Dirichlet/Neumann generator behind --dataset_type analytical: a per-edge bc_type needs '
-                                 '--dataset_type analytical_mixed or numerical (got %r)' % (bc_type,))
-            neumann = all(flags)
-        else:
-            neumann = bc_type.lower() == 'neumann'
+        flags = neumann_flags(bc_type)               # a dict: per-edge boundary types (extension), the numerical generator's mixed Dirichlet/Neumann solve
+        if args.dataset_type == 'analytical' and any(flags) and not all(flags):
+            raise ValueError('there is no analytic mixed Dirichlet/Neumann generator behind --dataset_type analytical: a per-edge bc_type needs '
+                             '--dataset_type analytical_mixed or numerical (got %r)' % (bc_type,))
+        neumann = all(flags)
         if args.dataset_type == 'variable_density':        # random smooth rhs and rho, the DST-preconditioned CG solve as ground truth (zero Dirichlet data)
             dataset = variable_density_dataset_generator(**dcfg)
         elif args.dataset_type == 'analytical_mixed':        # the quarter-wave / whole-wave series of the model's own edge types, homogeneous data

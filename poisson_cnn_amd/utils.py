@@ -62,6 +62,31 @@ def split_indices(n, sections):
     return np.cumsum([0] + [per + 1] * extra + [per] * (sections - extra))
 
 
+BC_EDGES = ('left', 'right', 'bottom', 'top')        # of the (N,1,H,W) field: y = 0, y = H-1, x = 0, x = W-1 - the bit order of pcnn_bc_ring_edges_fwd's mask
+
+
+def neumann_flags(bc_type):
+    """The boundary types of a model or a dataset -> (left, right, bottom, top), True where the edge is Neumann.  bc_type: 'dirichlet' or 'neumann'
+    for all four edges, or a dict edge -> 'dirichlet' | 'neumann' (a missing edge is Dirichlet; None is the empty dict)."""
+    if isinstance(bc_type, str):
+        if bc_type.lower() not in ('dirichlet', 'neumann'):
+            raise ValueError('bc_type can only be neumann or dirichlet.')
+        return (bc_type.lower() == 'neumann',) * 4
+    if bc_type is not None and not isinstance(bc_type, dict):
+        raise ValueError('bc_type can only be neumann or dirichlet.')
+    bt = dict.fromkeys(BC_EDGES, 'dirichlet')
+    for k, v in (bc_type or {}).items():
+        if k not in bt or str(v).lower() not in ('dirichlet', 'neumann'):
+            raise ValueError("boundary_types maps 'left'/'right'/'bottom'/'top' to 'dirichlet' or 'neumann' (got %r: %r)" % (k, v))
+        bt[k] = str(v).lower()
+    return tuple(bt[k] == 'neumann' for k in BC_EDGES)
+
+
+def neumann_mask(bc_type):
+    """neumann_flags as the kernels' mask: bit 0 / 1 / 2 / 3 set = the left / right / bottom / top edge is Neumann."""
+    return sum(1 << i for i, f in enumerate(neumann_flags(bc_type)) if f)
+
+
 def glorot_limit(shape):
     if len(shape) == 1:
         fi = fo = shape[0]

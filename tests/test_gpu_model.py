@@ -114,6 +114,33 @@ def test_tiny_model_train_step(bc, pi_w):
         assert np.array_equal(w0[n], w1[n])
 
 
+def test_merge_whose_last_three_branches_include_a_deconv_branch():
+    """Deconv factors [2, 3] with multilinear factors [4, 8]: of the last three branches in merge order one up-samples by transposed convolution.
+    Before models.merge_plan the one-pass ops.resize_fwd_multi tail took it for a resize branch and call() raised KeyError: 'pool'."""
+    from poisson_cnn_amd.losses import loss_wrapper
+    from poisson_cnn_amd.train import SGD
+    full = configs.hpnn_tiny()
+    cfg = full['model']
+    cfg['bottleneck_multilinear_config'].update(downsampling_factors=[4, 8], upsampling_factors=[4, 8], conv_kernel_sizes=[3, 3], n_convs=[2, 2])
+    lossp = dict(full['training']['loss_parameters'])
+    model, p = build(cfg, 27)
+    assert [model.merge.branches[i][3] for i in (0, 1)] == [None, None] and len(model.merge.branches) == 4
+    rhs, dx = make_inputs(2, 36, 40, 29)
+    ref = ohpnn.forward(np_ops, cfg, p, rhs, dx)
+    y = model([rhs, dx]).cpu().numpy()
+    print('forward rel-L2', rel(y, ref))
+    assert y.shape == ref.shape and rel(y, ref) < TOL_FWD
+    target = np.random.default_rng(3).standard_normal(rhs.shape).astype(np.float32).astype(np.float64) * 0.1
+    _, _, ref_g = _train_reference(cfg, p, rhs, dx, target, lossp, 2)
+    model.compile(loss=loss_wrapper(global_batch_size=2, **lossp), optimizer=SGD(learning_rate=0.0))
+    model.train_step(((rhs, dx), target))
+    names = model.store.trainable_names()
+    flat = np.concatenate([model.store.g[n].cpu().numpy().ravel() for n in names])
+    flat_ref = np.concatenate([ref_g[n].ravel() for n in names])
+    print('flat gradient rel-L2', rel(flat, flat_ref))
+    assert rel(flat, flat_ref) < TOL_GRAD
+
+
 def test_gradient_accumulation_equals_full_batch():
     from poisson_cnn_amd.losses import loss_wrapper
     from poisson_cnn_amd.train import SGD

@@ -364,3 +364,81 @@ def test_one_channel_shape_helper():
         ops.error_stats(torch.zeros(2, 5))
     with pytest.raises(ValueError, match=r'^varcoef_pi_loss_partials: fields must be \(N,H,W\), \(N,1,H,W\) or \(N,H,W,1\), got \(2, 5\)$'):
         ops.varcoef_pi_loss_partials(torch.zeros(2, 5), torch.zeros(2, 5), torch.zeros(2, 5), torch.zeros(2))
+
+
+# ------------------------------------------------------------------------------------------------------------------ the bottleneck merge's plan
+def _branches(cfg):
+    from poisson_cnn_amd.models import Homogeneous_Poisson_NN_Legacy
+    return Homogeneous_Poisson_NN_Legacy(device='cpu', **cfg).merge.branches
+
+
+def test_merge_plan_of_the_shipped_configurations():
+    """models.merge_plan against values worked out by hand from the code it replaced (Homogeneous_Poisson_NN_Legacy.call before the merge object):
+    branches = deconv blocks by descending factor, then multilinear blocks by descending factor; with COARSE_FACTOR 2 every branch is coarse, so the
+    order is that list; a level's parent is its largest already pooled divisor; stream = position + 1 for a pyramid-fed branch, 0 for one whose
+    factor does not divide the grid; the tail is the last min(3, branches - 1) branches."""
+    from poisson_cnn_amd.models import merge_plan
+    hp = _branches(configs.hpnn()['model'])
+    assert [b[0] for b in hp] == [16, 8, 4, 3, 2, 128, 64, 32]
+    assert [b[3] for b in hp] == [None] * 5 + ['nearest', 'bilinear', 'bicubic'] and all(b[1:3] == ('pool', 'average') for b in hp)
+    p = merge_plan(hp, 1024, 1024, 2)
+    assert p.pyramid == {2: None, 4: 2, 8: 4, 16: 8, 32: 16, 64: 32, 128: 64} and list(p.pyramid) == [2, 4, 8, 16, 32, 64, 128]     # 3 does not divide 1024
+    assert p.order == [0, 1, 2, 3, 4, 5, 6, 7] and p.tail == [5, 6, 7]
+    assert p.stream == {0: 1, 1: 2, 2: 3, 3: 0, 4: 5, 5: 6, 6: 7, 7: 8}
+    # PCNN_COARSE_FACTOR = 8 on a grid only factor 2 divides (tests/test_gpu_model.py): factors 4, 3, 2 first on the main stream, every coarse branch on stream 0
+    p = merge_plan(hp, 250, 246, 8)
+    assert p.pyramid == {2: None} and p.order == [2, 3, 4, 0, 1, 5, 6, 7] and p.stream == {0: 0, 1: 0, 5: 0, 6: 0, 7: 0} and p.tail == [5, 6, 7]
+    tiny = _branches(configs.hpnn_tiny()['model'])
+    assert [b[0] for b in tiny] == [3, 2, 16, 8, 4] and [b[3] for b in tiny] == [None, None, 'nearest', 'bilinear', 'bicubic']
+    p = merge_plan(tiny, 36, 40, 2)                  # 2 and 4 divide 36 x 40; 3, 8 and 16 do not
+    assert p.pyramid == {2: None, 4: 2} and p.order == [0, 1, 2, 3, 4] and p.tail == [2, 3, 4] and p.stream == {0: 0, 1: 2, 2: 0, 3: 0, 4: 5}
+    p = merge_plan(tiny, 48, 48, 2)                  # every factor divides: 16 <- 8 <- 4 <- 2, and 3 on its own
+    assert p.pyramid == {2: None, 3: None, 4: 2, 8: 4, 16: 8} and p.order == [0, 1, 2, 3, 4] and p.tail == [2, 3, 4]
+    assert p.stream == {0: 1, 1: 2, 2: 3, 3: 4, 4: 5}
+
+
+def test_merge_plan_tail_holds_resize_branches_only():
+    """Deconv [2, 3] + multilinear [4, 8] used to send the factor-2 deconv branch into ops.resize_fwd_multi (KeyError: 'pool')."""
+    import itertools
+    from poisson_cnn_amd.models import merge_plan
+    cfg = configs.hpnn_tiny()['model']
+    cfg['bottleneck_multilinear_config'].update(downsampling_factors=[4, 8], upsampling_factors=[4, 8], conv_kernel_sizes=[3, 3], n_convs=[2, 2])
+    br = _branches(cfg)
+    assert [(b[0], b[3]) for b in br] == [(3, None), (2, None), (8, 'bilinear'), (4, 'bicubic')]
+    assert merge_plan(br, 36, 40, 2).tail == [2, 3]
+    dec = [(f, 'pool', 'average', None) for f in (4, 3, 2)]
+    assert merge_plan(dec, 36, 40, 2).tail == []                                              # three deconv branches alone: no tail
+    res = lambda f: (f, 'pool', 'average', 'bilinear')
+    assert merge_plan(dec + [res(8)], 36, 40, 2).tail == []                                    # fewer than two: none
+    assert merge_plan([res(8), res(4)], 36, 40, 2).tail == []                                  # never the whole order
+    assert merge_plan([res(16), res(8), res(4)], 36, 40, 2).tail == [1, 2]
+    assert merge_plan([res(32), res(16), res(8), res(4), res(2)], 64, 64, 2).tail == [2, 3, 4]  # at most three
+    for n in range(1, 6):                                                                      # every mix of up to five branches, two coarse factors
+        for kinds in itertools.product((None, 'nearest'), repeat=n):
+            for cf in (2, 8):
+                b = [(f, 'pool', 'average', m) for f, m in zip((2, 3, 4, 8, 16), kinds)]
+                p = merge_plan(b, 48, 40, cf)
+                assert sorted(p.order) == list(range(n)) and p.tail == p.order[len(p.order) - len(p.tail):] and len(p.tail) in (0, 2, 3)
+                assert len(p.tail) < n and all(b[i][3] is not None for i in p.tail)
+
+
+def test_bc_type_parser():
+    """utils.neumann_flags / neumann_mask: a string and the equivalent dict agree; the bit order is pcnn_bc_ring_edges_fwd's - bit 0: y = 0 (left),
+    bit 1: y = H-1 (right), bit 2: x = 0 (bottom), bit 3: x = W-1 (top)."""
+    from poisson_cnn_amd.dataset import _neumann_flags
+    assert utils.BC_EDGES == ('left', 'right', 'bottom', 'top') and _neumann_flags is utils.neumann_flags
+    for name, mask in (('dirichlet', 0), ('neumann', 15), ('Neumann', 15)):
+        assert utils.neumann_mask(name) == utils.neumann_mask({e: name for e in utils.BC_EDGES}) == mask
+        assert utils.neumann_flags(name) == utils.neumann_flags({e: name for e in utils.BC_EDGES}) == (mask == 15,) * 4
+    assert [utils.neumann_mask({e: 'neumann'}) for e in ('left', 'right', 'bottom', 'top')] == [1, 2, 4, 8]
+    assert utils.neumann_mask({'left': 'neumann', 'top': 'Neumann', 'right': 'dirichlet'}) == 9 and utils.neumann_mask({}) == utils.neumann_mask(None) == 0
+    for bad in ('periodic', 3, {'north': 'neumann'}, {'left': 'periodic'}):
+        with pytest.raises(ValueError):
+            utils.neumann_flags(bad)
+    from poisson_cnn_amd.models import Homogeneous_Poisson_NN_Legacy
+    cfg = configs.hpnn_tiny()['model']
+    assert Homogeneous_Poisson_NN_Legacy(device='cpu', **dict(cfg, bc_type={'bottom': 'neumann'})).neumann_mask == 4
+    assert Homogeneous_Poisson_NN_Legacy(device='cpu', **dict(cfg, bc_type='neumann')).neumann_mask == 15
+    assert configs.hpnn_mixed({'top': 'neumann'})['model']['bc_type'] == {'left': 'dirichlet', 'right': 'dirichlet', 'bottom': 'dirichlet', 'top': 'neumann'}
+    with pytest.raises(ValueError):
+        Homogeneous_Poisson_NN_Legacy(device='cpu', **dict(cfg, bc_type=None))

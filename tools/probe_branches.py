@@ -5,17 +5,17 @@ import os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from poisson_cnn_amd import configs, ops
-from poisson_cnn_amd.models import Homogeneous_Poisson_NN_Legacy
+from poisson_cnn_amd.models import Homogeneous_Poisson_NN_Legacy, merge_plan
 model = Homogeneous_Poisson_NN_Legacy(**configs.hpnn()['model'])
 model.ctx.use_side = False
 N, H = 8, 1024
 initial = torch.randn(N, H, H, 32, device='cuda')
-blocks = model.bottleneck_deconv_blocks + model.bottleneck_multilinear_blocks
-pyr = model._pool_pyramid(initial, blocks)
+merge = model.merge
+pyr = merge.pool_pyramid(initial, merge_plan(merge.branches, H, H, model.COARSE_FACTOR))
 tot_f = tot_b = 0.0
-for b in blocks:
-    pooled = pyr[b.f][0] if b.f in pyr else None
-    def fwd(): return b._down_and_convs(initial, True, pooled)
+for b in merge.blocks:
+    pooled = pyr.get(b.f)
+    def fwd(): return b.forward_convs(initial, True, pooled)
     o = fwd(); torch.cuda.synchronize()
     ts = []
     for _ in range(5):
@@ -25,7 +25,7 @@ for b in blocks:
     tb = []
     for _ in range(5):
         o = fwd(); dco = torch.randn_like(o); torch.cuda.synchronize()
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True); s.record(); b._backward_convs_and_down(dco, d_in); e.record(); torch.cuda.synchronize(); tb.append(s.elapsed_time(e))
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True); s.record(); b.backward_convs(dco, d_in); e.record(); torch.cuda.synchronize(); tb.append(s.elapsed_time(e))
     tbm = float(np.median(tb))
     print('%-18s f=%3d coarse %4d^2: conv stages forward %.3f ms, backward %.3f ms' % (b.name, b.f, o.shape[1], tf, tbm))
     if b.f >= 8: tot_f += tf; tot_b += tbm
