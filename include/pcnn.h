@@ -649,7 +649,8 @@ int pcnn_scale_samples(pcnn_handle h, int N, int64_t per, const float* s, float*
 int pcnn_varcoef_apply(pcnn_handle h, int N, int H, int W, const float* rho, const float* dx, const double* p, double* q, double* pq);
 /* Conjugate gradients on A u = b, preconditioned by the constant-coefficient DST solve z = S_h ((S_h r S_w) ./ (lam_h + lam_w)) S_w (S, lam: device
  * copies of pcnn_dst_setup output; four pcnn_batched_gemm_f64 products per iteration).  State lives on the device: `workspace`
- * (pcnn_varcoef_pcg_workspace bytes), scal (N x 8 doubles per sample: b.b, r.r, p.q, r.z (two slots), min rho, 2 unused) and flags (N ints).
+ * (pcnn_varcoef_pcg_workspace bytes), scal (N x 8 doubles per sample: b.b, r.r, p.q, r.z (two slots), min rho, 2 that only the
+ * *_bc_* entry points below use) and flags (N ints).
  *   setup:   b, x = interior of the initial guess x0 ((N,H,W) fp64, NULL: 0), r = b - A x, first direction; scal[n][5] = min rho[n], a NaN counting as
  *            -inf (the caller refuses anything but a positive minimum); flags[n] = 1 where ||r|| <= tol ||b|| already.  The workspace, scal and
  *            flags need no initialisation: setup writes every value before it is read, whatever the memory held.
@@ -668,6 +669,36 @@ int pcnn_varcoef_pcg_iterate(pcnn_handle h, int N, int H, int W, const float* rh
                              double* scal, int* flags);
 int pcnn_varcoef_pcg_finish(pcnn_handle h, int N, int H, int W, const void* workspace, const float* left, const float* right, const float* bottom,
                             const float* top, float* soln);
+/* The same problem with per-edge Dirichlet / Neumann conditions.  neumann_mask, the edge arrays and the unknowns are those of
+ * pcnn_fd_poisson_mixed: bit 0/1/2/3 = left / right / bottom / top is Neumann, its array then holds du/dn along the outward normal and its nodes are
+ * unknowns - mh x mw of them, rows (bit 0 ? 0 : 1) .. (bit 1 ? H-1 : H-2) and columns likewise with bits 2 / 3; at a corner a Dirichlet edge wins.
+ * p, q, x and the workspace are sized by mh x mw.  rho and rhs are read on Neumann edge nodes too.
+ *   operator: a Neumann edge node has no outward neighbour; the inward face of that direction counts twice, 2 beta_in (u_c - u_in) / dx^2 (both
+ *             directions at a Neumann/Neumann corner).  Faces between two nodes of one Neumann edge are ordinary faces.
+ *   b:        -f, plus beta / dx^2 times the value of every Dirichlet neighbour, plus 2 g / (rho_c dx) for every Neumann edge the node lies on: the
+ *             coefficient 1 / rho_c of the boundary face of the node's half cell (second order; the mirrored face's beta would be first order).
+ *   weights:  w = w_i w_j, 1/2 per Neumann edge the node lies on.  W A is symmetric - positive definite with a Dirichlet edge, semi-definite with the
+ *             constants as null space for mask 15 - and the loop is conjugate gradients in the W inner product: pq, b.b, r.r, r.z are sums of w (..),
+ *             a sample is flagged when sum w r^2 <= tol^2 sum w b^2.  For mask 0 every w is 1: the bits of the entry points above.
+ *   preconditioner: the constant-coefficient operator of the same edge types, z = V_h ((Vinv_h r VinvT_w) ./ (lam_h + lam_w)) VT_w with the six arrays of
+ *             pcnn_fd_poisson_mixed (normalised to V^T W V = I per axis, as dataset/_kernels.py axis_decomposition returns them); the lam = 0 mode is dropped.
+ *   mask 15:  setup replaces b by b - (sum w b) / (sum w), the compatibility projection, and b.b is the projected b's; scal[n][6] = sum w b and
+ *             scal[n][7] = sum w b^2 of the b as given (0 for other masks).  finish subtracts (sum w x) / (sum w) from x in the workspace before it
+ *             writes: the solution with zero trapezoidal integral, whatever mean the initial guess had.
+ * Otherwise each entry point is its counterpart above, and refuses a mask outside 0..15 as well.  No atomics; fixed-order reductions. */
+int pcnn_varcoef_bc_apply(pcnn_handle h, int N, int H, int W, int neumann_mask, const float* rho, const float* dx, const double* p, double* q,
+                          double* pq);
+size_t pcnn_varcoef_bc_pcg_workspace(int N, int H, int W, int neumann_mask);
+int pcnn_varcoef_bc_pcg_setup(pcnn_handle h, int N, int H, int W, int neumann_mask, const float* rho, const float* rhs, const float* left,
+                              const float* right, const float* bottom, const float* top, const float* dx, const double* x0, double tol,
+                              const double* Vinv_h, const double* V_h, const double* lam_h, const double* VinvT_w, const double* VT_w,
+                              const double* lam_w, void* workspace, size_t workspace_bytes, double* scal, int* flags);
+int pcnn_varcoef_bc_pcg_iterate(pcnn_handle h, int N, int H, int W, int neumann_mask, const float* rho, const float* dx, double tol,
+                                int first_iteration, int iterations, const double* Vinv_h, const double* V_h, const double* lam_h,
+                                const double* VinvT_w, const double* VT_w, const double* lam_w, void* workspace, size_t workspace_bytes, double* scal,
+                                int* flags);
+int pcnn_varcoef_bc_pcg_finish(pcnn_handle h, int N, int H, int W, int neumann_mask, void* workspace, const float* left, const float* right,
+                               const float* bottom, const float* top, float* soln);
 /* g[i] = lo + (hi - lo) min(|g[i]|, 1): a density field from a smooth function scaled to max|g| = 1 (the reference takes 1e-7 + |g|) */
 int pcnn_varcoef_density(pcnn_handle h, int64_t total, float lo, float hi, float* g);
 

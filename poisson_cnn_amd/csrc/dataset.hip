@@ -73,13 +73,7 @@ __global__ __launch_bounds__(256) void gemm_f64_kernel(int M, int Nn, int K, con
 // closed by the second-order ghost node u_ghost = u_inner + 2 dx g: SURVEY 8f rank 4).  types bit 0/1/2/3 = left / right / bottom / top is
 // Neumann; 0 is the all-Dirichlet system of dataset/solvers/cholesky.py:85,114-117.  The unknowns are rows i0..i1 x columns j0..j1:
 //   4 u_ij - [neighbours] = -dx^2 f_ij + (Dirichlet neighbours' values) + 2 dx g on Neumann edges, the mirrored neighbour counted twice.
-struct FdUnknowns { int i0, i1, j0, j1, mh, mw; };
-__host__ __device__ inline FdUnknowns fd_unknowns(int H, int W, int types) {
-  FdUnknowns u;
-  u.i0 = (types & 1) ? 0 : 1; u.i1 = (types & 2) ? H - 1 : H - 2; u.j0 = (types & 4) ? 0 : 1; u.j1 = (types & 8) ? W - 1 : W - 2;
-  u.mh = u.i1 - u.i0 + 1; u.mw = u.j1 - u.j0 + 1;
-  return u;
-}
+// (FdUnknowns / fd_unknowns: pcnn_internal.h - the variable-density solve of varcoef.hip has the same unknowns.)
 
 // The edge terms are added in the order bottom, top, left, right (F[..., 1:-1, 1] += bottom, F[..., 1:-1, -2] += top, F[..., 1, 1:-1] += left,
 // F[..., -2, 1:-1] += right) on every route: fp64 addition is not associative, and an unknown next to a row edge and a column edge gets both.

@@ -6,6 +6,16 @@
 void pcnn_comm_release(pcnn_handle_s* h);   // collective.hip
 void pcnn_filter_cache_free(pcnn_handle_s* h);   // spectral_conv.hip
 
+// The unknowns of a 5-point solve with per-edge Dirichlet / Neumann conditions: rows i0..i1 x columns j0..j1 of the H x W grid (mh x mw of them).
+// types bit 0/1/2/3 = left / right / bottom / top is Neumann: that edge's nodes are unknowns, a Dirichlet edge's are given.
+struct FdUnknowns { int i0, i1, j0, j1, mh, mw; };
+__host__ __device__ inline FdUnknowns fd_unknowns(int H, int W, int types) {
+  FdUnknowns u;
+  u.i0 = (types & 1) ? 0 : 1; u.i1 = (types & 2) ? H - 1 : H - 2; u.j0 = (types & 4) ? 0 : 1; u.j1 = (types & 8) ? W - 1 : W - 2;
+  u.mh = u.i1 - u.i0 + 1; u.mw = u.j1 - u.j0 + 1;
+  return u;
+}
+
 // dataset.hip: the two steps of the FD Poisson pipeline that varcoef.hip runs too.
 // dst = A_h src A_w per sample (A_h mh x mh and A_w mw x mw, shared by the batch) as two pcnn_batched_gemm_f64: mid = A_h src, dst = mid A_w; dst may be src
 int pcnn_two_sided_gemm_f64(pcnn_handle h, int N, int mh, int mw, const double* A_h, const double* src, const double* A_w, double* mid, double* dst);

@@ -1,9 +1,18 @@
-// Variable-density Poisson problem div((1/rho) grad u) = f on the dataset's vertex-centred grid (one spacing per sample, dy = dx), Dirichlet data on
-// the four edges: the flux-form operator, and a conjugate-gradient solve preconditioned by the constant-coefficient DST solve.
+// Variable-density Poisson problem div((1/rho) grad u) = f on the dataset's vertex-centred grid (one spacing per sample, dy = dx), each edge with
+// Dirichlet data or (the *_bc_* entry points) a Neumann condition du/dn = g: the flux-form operator, and a conjugate-gradient solve preconditioned by
+// the constant-coefficient solve of the same edge types (DESIGN.md sections 16 and 19).
 //   beta_{i+1/2,j} = 2 / (rho[i,j] + rho[i+1,j])                                  (the first matrix of dataset/generators/variable_density)
 //   (A u)[i,j] = ( beta_{i+1/2,j} (u[i,j] - u[i+1,j]) + beta_{i-1/2,j} (u[i,j] - u[i-1,j])
-//                + beta_{i,j+1/2} (u[i,j] - u[i,j+1]) + beta_{i,j-1/2} (u[i,j] - u[i,j-1]) ) / dx^2       on the (H-2) x (W-2) interior nodes,
-//   A u = b,  b = -f + (Dirichlet neighbours' values, each times its face coefficient / dx^2):  A is symmetric positive definite.
+//                + beta_{i,j+1/2} (u[i,j] - u[i,j+1]) + beta_{i,j-1/2} (u[i,j] - u[i,j-1]) ) / dx^2       on the unknowns,
+//   A u = b,  b = -f + (Dirichlet neighbours' values, each times its face coefficient / dx^2).
+// All four edges Dirichlet (BC = false): the unknowns are the (H-2) x (W-2) interior nodes and A is symmetric positive definite.
+// With Neumann edges (BC = true; neumann_mask bit 0/1/2/3 = left / right / bottom / top) the unknowns are fd_unknowns(H, W, mask), a Neumann edge's
+// nodes included.  Such a node has no outward neighbour: the inward face of that direction counts twice (the tiles load rho and p with the mirrored
+// index, so the stencil code is the same), and b gains 2 g / (rho_c dx) - the coefficient 1 / rho_c of the boundary face of the node's half cell, NOT
+// the mirrored face's beta (that closure is first order).  With w = w_i w_j, w_i = 1/2 on a Neumann edge's row, W A is symmetric: the loop is PCG in
+// the W inner product, every dot product a sum of w (..).  For mask 0 every w is 1 and the BC = true kernels give the bits of the BC = false ones.
+// All four Neumann (mask 15): W A is semi-definite with the constants as null space; setup projects b (b - sum w b / sum w), finish removes the
+// w-mean of x.
 // Everything is fp64; rho, f, the boundary arrays and dx are read as fp32 and converted.  No atomics: every dot product is a per-block partial sum
 // (fixed tree) reduced per sample by a second one-block stage in a fixed order, so results do not depend on the batch a sample is solved in.
 // The face coefficients are built on the fly from an LDS tile of rho with a one-point halo: 20 B per point and product (p 8, rho 4, q 8) against
@@ -19,27 +28,56 @@ namespace {
 constexpr int VT_LR = FLUX_ROWS + 2, VT_LC = FLUX_COLS + 2;                                               // the tile of interior points with its halo
 constexpr int EW_THREADS = 256, EW_POINTS = 2048, EW_MAX_BLOCKS = 1024;                                   // element-wise kernels: blocks per SAMPLE
 // per-sample scalars (doubles) of the solve
-enum { VS_BB = 0, VS_RR = 1, VS_PQ = 2, VS_RZ0 = 3, VS_RZ1 = 4, VS_RHOMIN = 5, VS_STRIDE = 8 };
+// (mask 15 only: VS_WB = sum w b and VS_BBRAW = sum w b^2 of the b before its projection; 0 otherwise)
+enum { VS_BB = 0, VS_RR = 1, VS_PQ = 2, VS_RZ0 = 3, VS_RZ1 = 4, VS_RHOMIN = 5, VS_WB = 6, VS_BBRAW = 7, VS_STRIDE = 8 };
 
-static inline int vc_tiles(int H, int W) { return pcnn_cdiv(H - 2, FLUX_ROWS) * pcnn_cdiv(W - 2, FLUX_COLS); }
+// Everything below is sized by the mh x mw unknowns: (H-2) x (W-2) when all four edges are Dirichlet
+static inline int vc_tiles(int mh, int mw) { return pcnn_cdiv(mh, FLUX_ROWS) * pcnn_cdiv(mw, FLUX_COLS); }
 static inline int vc_ew_blocks(int64_t per) {
   const int64_t b = pcnn_cdiv64(per, EW_POINTS);
   return (int)(b < 1 ? 1 : (b > EW_MAX_BLOCKS ? EW_MAX_BLOCKS : b));
 }
-static inline int vc_cap(int H, int W) {
-  const int t = vc_tiles(H, W), e = vc_ew_blocks((int64_t)(H - 2) * (W - 2));
+static inline int vc_cap(int mh, int mw) {
+  const int t = vc_tiles(mh, mw), e = vc_ew_blocks((int64_t)mh * mw);
   return t > e ? t : e;
 }
-// workspace: x, r, p, q, z (N x (H-2) x (W-2) doubles each; q and z double as the two GEMM intermediates) and three partial-sum arrays of N x cap
+// workspace: x, r, p, q, z (N x mh x mw doubles each; q and z double as the two GEMM intermediates) and three partial-sum arrays of N x cap
 struct VcWs { double *x, *r, *p, *q, *z, *part; int cap; };
-static inline size_t vc_bytes(int N, int H, int W) { return (5 * (size_t)N * (H - 2) * (W - 2) + 3 * (size_t)N * vc_cap(H, W)) * sizeof(double); }
-static inline VcWs vc_layout(void* ws, int N, int H, int W) {
+static inline size_t vc_bytes(int N, int mh, int mw) { return (5 * (size_t)N * mh * mw + 3 * (size_t)N * vc_cap(mh, mw)) * sizeof(double); }
+static inline VcWs vc_layout(void* ws, int N, int mh, int mw) {
   VcWs l;
-  const size_t v = (size_t)N * (H - 2) * (W - 2);
-  l.cap = vc_cap(H, W);
+  const size_t v = (size_t)N * mh * mw;
+  l.cap = vc_cap(mh, mw);
   l.x = static_cast<double*>(ws); l.r = l.x + v; l.p = l.r + v; l.q = l.p + v; l.z = l.q + v; l.part = l.z + v;
   return l;
 }
+
+// the weight of unknown (ii, jj) of mh x mw in the W inner product: 1/2 per Neumann edge the node lies on (the first / last unknown row or column)
+__device__ __forceinline__ double vc_weight(int ii, int jj, int mh, int mw, int mask) {
+  const double wi = ((ii == 0 && (mask & 1)) || (ii == mh - 1 && (mask & 2))) ? 0.5 : 1.0;
+  const double wj = ((jj == 0 && (mask & 4)) || (jj == mw - 1 && (mask & 8))) ? 0.5 : 1.0;
+  return wi * wj;
+}
+// What the tile entry at index i of an n-long axis reads: i itself; beyond a Neumann end (lo / hi) the mirrored inward neighbour, which makes the
+// inward face count twice; otherwise -1: zero Dirichlet data, or tile overhang no stored point uses.  n >= 2 whenever an end is Neumann.
+__device__ __forceinline__ int vc_mirror(int i, int n, bool lo, bool hi) {
+  if (i == -1 && lo) return 1;
+  if (i == n && hi) return n - 2;
+  return (i >= 0 && i < n) ? i : -1;
+}
+// (row, column) of the flat index k = blockIdx.x * EW_THREADS + threadIdx.x + m * gridDim.x * EW_THREADS of the element-wise kernels, m = 0, 1, ..:
+// one division at the start, none per point.  At most EW_MAX_BLOCKS * EW_THREADS = 2^18 per step: int is enough.
+struct VcWalk {
+  int ii, jj, di, dj, mw;
+  __device__ __forceinline__ VcWalk(int mw_) : mw(mw_) {
+    const int k0 = blockIdx.x * EW_THREADS + threadIdx.x, stride = gridDim.x * EW_THREADS;
+    ii = k0 / mw; jj = k0 % mw; di = stride / mw; dj = stride % mw;
+  }
+  __device__ __forceinline__ void next() {
+    ii += di; jj += dj;
+    if (jj >= mw) { jj -= mw; ++ii; }
+  }
+};
 
 // sum over the block's threads by the fixed tree of pcnn_block_reduce; every thread gets the total
 template <int T>
@@ -53,10 +91,18 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
 }
 
 // rho on nodes (I0 .. I0+17) x (J0 .. J0+65): the tile's nodes I0+1.., J0+1.. and their halo.  Nodes beyond the grid read 1 (never used by a stored point).
+// BC: I0 / J0 is -1 for the first tile of an axis whose low edge is Neumann; node -1 then reads node 1 and node H (W) reads node H-2 (W-2), the
+// mirrored inward neighbour of an edge node (beyond a Dirichlet edge this is overhang).
+template <bool BC>
 __device__ __forceinline__ float load_rho_tile(float (*rs)[VT_LC], const float* __restrict__ rho_n, int H, int W, int I0, int J0) {
   float mn = INFINITY;
   for (int e = threadIdx.x; e < VT_LR * VT_LC; e += FLUX_THREADS) {
-    const int r = e / VT_LC, c = e % VT_LC, i = I0 + r, j = J0 + c;
+    const int r = e / VT_LC, c = e % VT_LC;
+    int i = I0 + r, j = J0 + c;
+    if (BC) {
+      i = i < 0 ? 1 : (i == H ? H - 2 : i);
+      j = j < 0 ? 1 : (j == W ? W - 2 : j);
+    }
     float v = 1.f;
     if (i < H && j < W) {
       v = rho_n[(int64_t)i * W + j];
@@ -83,17 +129,27 @@ __device__ __forceinline__ double stencil_at(const Faces& f, const double (*ps)[
   return (f.lo_i * (pc - ps[r][c + 1]) + f.hi_i * (pc - ps[r + 2][c + 1]) + f.lo_j * (pc - ps[r + 1][c]) + f.hi_j * (pc - ps[r + 1][c + 2])) * inv_h2;
 }
 
-// q = A p and the tile's share of p.q.  grid (column tiles, row tiles, N); part[n][tile]
-__global__ __launch_bounds__(FLUX_THREADS) void varcoef_apply_kernel(int H, int W, int cap, const float* __restrict__ rho, const float* __restrict__ dx,
+// q = A p and the tile's share of p.q (BC: of sum w p q).  grid (column tiles, row tiles, N) over the nh x nw unknowns; part[n][tile]
+template <bool BC>
+__global__ __launch_bounds__(FLUX_THREADS) void varcoef_apply_kernel(int H, int W, int cap, int mask, const float* __restrict__ rho, const float* __restrict__ dx,
                                                                      const double* __restrict__ p, double* __restrict__ q, double* __restrict__ part) {
   __shared__ float rs[VT_LR][VT_LC];
   __shared__ double ps[VT_LR][VT_LC];
   __shared__ double red[FLUX_THREADS];
-  const int nh = H - 2, nw = W - 2, n = blockIdx.z, I0 = blockIdx.y * FLUX_ROWS, J0 = blockIdx.x * FLUX_COLS;
+  const FdUnknowns u = fd_unknowns(H, W, BC ? mask : 0);
+  const int nh = u.mh, nw = u.mw, n = blockIdx.z, I0 = blockIdx.y * FLUX_ROWS, J0 = blockIdx.x * FLUX_COLS;
   const int64_t per = (int64_t)nh * nw;
   const double* pn = p + (int64_t)n * per;
-  load_rho_tile(rs, rho + (int64_t)n * H * W, H, W, I0, J0);
-  pcnn_load_nodes<VT_LR, VT_LC>(ps, pn, nh, nw, I0 - 1, J0 - 1, 0.0);               // interior indices; zero Dirichlet data outside
+  load_rho_tile<BC>(rs, rho + (int64_t)n * H * W, H, W, u.i0 + I0 - 1, u.j0 + J0 - 1);
+  if (BC) {
+    for (int e = threadIdx.x; e < VT_LR * VT_LC; e += FLUX_THREADS) {
+      const int r = e / VT_LC, c = e % VT_LC;
+      const int ii = vc_mirror(I0 + r - 1, nh, mask & 1, mask & 2), jj = vc_mirror(J0 + c - 1, nw, mask & 4, mask & 8);
+      ps[r][c] = (ii >= 0 && jj >= 0) ? pn[(int64_t)ii * nw + jj] : 0.0;
+    }
+  } else {
+    pcnn_load_nodes<VT_LR, VT_LC>(ps, pn, nh, nw, I0 - 1, J0 - 1, 0.0);             // interior indices; zero Dirichlet data outside
+  }
   __syncthreads();
   const double h = (double)dx[n], inv_h2 = 1.0 / (h * h);
   const int c = threadIdx.x % FLUX_COLS, r0 = (threadIdx.x / FLUX_COLS) * FLUX_RPT;
@@ -105,7 +161,8 @@ __global__ __launch_bounds__(FLUX_THREADS) void varcoef_apply_kernel(int H, int 
       if (I0 + r < nh) {
         const double v = stencil_at(faces_at(rs, r, c), ps, r, c, inv_h2);
         q[(int64_t)n * per + (int64_t)(I0 + r) * nw + J0 + c] = v;
-        s += ps[r + 1][c + 1] * v;
+        const double pv = ps[r + 1][c + 1] * v;
+        s += BC ? vc_weight(I0 + r, J0 + c, nh, nw, mask) * pv : pv;
       }
     }
   }
@@ -113,22 +170,32 @@ __global__ __launch_bounds__(FLUX_THREADS) void varcoef_apply_kernel(int H, int 
   if (threadIdx.x == 0) part[(int64_t)n * cap + blockIdx.y * gridDim.x + blockIdx.x] = tot;
 }
 
-// Start of a solve: b from f, rho, the four boundary arrays and dx; x = x0 (interior of the optional initial guess, else 0); r = b - A x0; the tile's
-// shares of b.b and r.r and its minimum of rho.  left/right (N,W): values on rows 0 / H-1; bottom/top (N,H): values on columns 0 / W-1.
-__global__ __launch_bounds__(FLUX_THREADS) void varcoef_setup_kernel(int H, int W, int cap, int N, const float* __restrict__ rho, const float* __restrict__ f,
-                                                                     const float* __restrict__ left, const float* __restrict__ right,
-                                                                     const float* __restrict__ bottom, const float* __restrict__ top,
-                                                                     const float* __restrict__ dx, const double* __restrict__ x0, double* __restrict__ x,
-                                                                     double* __restrict__ rr_out, double* __restrict__ part) {
+// Start of a solve: b from f, rho, the four boundary arrays and dx; x = x0 (the unknowns of the optional initial guess, else 0); r = b - A x0; the
+// tile's shares of b.b and r.r and its minimum of rho.  left/right (N,W): values on rows 0 / H-1; bottom/top (N,H): values on columns 0 / W-1 - or,
+// on a Neumann edge (BC), du/dn there: such a node's b gains 2 g / (rho_c dx) per Neumann edge it lies on, and the sums are weighted.
+// mask 15 (b_out != NULL): b is kept in b_out for the projection pass, and the second partial is the tile's share of sum w b - r.r is summed there.
+template <bool BC>
+__global__ __launch_bounds__(FLUX_THREADS) void varcoef_setup_kernel(int H, int W, int cap, int N, int mask, const float* __restrict__ rho,
+                                                                     const float* __restrict__ f, const float* __restrict__ left,
+                                                                     const float* __restrict__ right, const float* __restrict__ bottom,
+                                                                     const float* __restrict__ top, const float* __restrict__ dx,
+                                                                     const double* __restrict__ x0, double* __restrict__ x, double* __restrict__ rr_out,
+                                                                     double* __restrict__ b_out, double* __restrict__ part) {
   __shared__ float rs[VT_LR][VT_LC];
   __shared__ double ps[VT_LR][VT_LC];
   __shared__ double red[FLUX_THREADS];
-  const int nh = H - 2, nw = W - 2, n = blockIdx.z, I0 = blockIdx.y * FLUX_ROWS, J0 = blockIdx.x * FLUX_COLS;
+  const FdUnknowns u = fd_unknowns(H, W, BC ? mask : 0);
+  const int nh = u.mh, nw = u.mw, n = blockIdx.z, I0 = blockIdx.y * FLUX_ROWS, J0 = blockIdx.x * FLUX_COLS;
   const int64_t per = (int64_t)nh * nw;
-  const float mn = load_rho_tile(rs, rho + (int64_t)n * H * W, H, W, I0, J0);
+  const float mn = load_rho_tile<BC>(rs, rho + (int64_t)n * H * W, H, W, u.i0 + I0 - 1, u.j0 + J0 - 1);
   for (int e = threadIdx.x; e < VT_LR * VT_LC; e += FLUX_THREADS) {
-    const int r = e / VT_LC, c = e % VT_LC, ii = I0 + r - 1, jj = J0 + c - 1;
-    ps[r][c] = (x0 && ii >= 0 && ii < nh && jj >= 0 && jj < nw) ? x0[((int64_t)n * H + ii + 1) * W + jj + 1] : 0.0;
+    const int r = e / VT_LC, c = e % VT_LC;
+    int ii = I0 + r - 1, jj = J0 + c - 1;
+    if (BC) {
+      ii = vc_mirror(ii, nh, mask & 1, mask & 2);
+      jj = vc_mirror(jj, nw, mask & 4, mask & 8);
+    }
+    ps[r][c] = (x0 && ii >= 0 && ii < nh && jj >= 0 && jj < nw) ? x0[((int64_t)n * H + ii + u.i0) * W + jj + u.j0] : 0.0;
   }
   __syncthreads();
   const double h = (double)dx[n], inv_h2 = 1.0 / (h * h);
@@ -139,18 +206,37 @@ __global__ __launch_bounds__(FLUX_THREADS) void varcoef_setup_kernel(int H, int 
     for (int k = 0; k < FLUX_RPT; ++k) {
       const int r = r0 + k, ii = I0 + r, jj = J0 + c;
       if (ii < nh) {
+        const int i = ii + u.i0, j = jj + u.j0;                                     // the node
         const Faces fc = faces_at(rs, r, c);
-        double b = -(double)f[((int64_t)n * H + ii + 1) * W + jj + 1];
-        if (ii == 0) b += fc.lo_i * inv_h2 * (double)left[(int64_t)n * W + jj + 1];
-        if (ii == nh - 1) b += fc.hi_i * inv_h2 * (double)right[(int64_t)n * W + jj + 1];
-        if (jj == 0) b += fc.lo_j * inv_h2 * (double)bottom[(int64_t)n * H + ii + 1];
-        if (jj == nw - 1) b += fc.hi_j * inv_h2 * (double)top[(int64_t)n * H + ii + 1];
+        const double gl = (double)left[(int64_t)n * W + j], gr = (double)right[(int64_t)n * W + j];
+        const double gb = (double)bottom[(int64_t)n * H + i], gt = (double)top[(int64_t)n * H + i];
+        const double gn = BC ? 2.0 / ((double)rs[r + 1][c + 1] * h) : 0.0;          // Neumann: 1 / rho_c of the half cell's boundary face
+        double b = -(double)f[((int64_t)n * H + i) * W + j];
+        if (BC && i == 0) b += gn * gl;                                              // (row 0 is an unknown only when left is Neumann)
+        else if (i == 1 && !(BC && (mask & 1))) b += fc.lo_i * inv_h2 * gl;
+        if (BC && i == H - 1) b += gn * gr;
+        else if (i == H - 2 && !(BC && (mask & 2))) b += fc.hi_i * inv_h2 * gr;
+        if (BC && j == 0) b += gn * gb;
+        else if (j == 1 && !(BC && (mask & 4))) b += fc.lo_j * inv_h2 * gb;
+        if (BC && j == W - 1) b += gn * gt;
+        else if (j == W - 2 && !(BC && (mask & 8))) b += fc.hi_j * inv_h2 * gt;
         const double res = b - stencil_at(fc, ps, r, c, inv_h2);
         const int64_t o = (int64_t)n * per + (int64_t)ii * nw + jj;
         x[o] = ps[r + 1][c + 1];
         rr_out[o] = res;
-        sbb += b * b;
-        srr += res * res;
+        if (BC) {
+          const double w = vc_weight(ii, jj, nh, nw, mask);
+          sbb += w * (b * b);
+          if (b_out) {
+            b_out[o] = b;
+            srr += w * b;
+          } else {
+            srr += w * (res * res);
+          }
+        } else {
+          sbb += b * b;
+          srr += res * res;
+        }
       }
     }
   }
@@ -166,6 +252,48 @@ __global__ __launch_bounds__(FLUX_THREADS) void varcoef_setup_kernel(int H, int 
     part[((int64_t)N + n) * cap + tile] = trr;
     part[((int64_t)2 * N + n) * cap + tile] = red[0];
   }
+}
+
+// mask 15, after the setup kernel: b and r lose m = sum w b / sum w (the compatibility projection: W A has the constants as null space, so a
+// solvable b has sum w b = 0); the block's shares of sum w b^2 and sum w r^2 of the projected fields.  grid (blocks per sample, N)
+__global__ __launch_bounds__(EW_THREADS) void varcoef_project_kernel(int mh, int mw, int cap, int N, double sum_w, const double* __restrict__ scal,
+                                                                     const double* __restrict__ b, double* __restrict__ r, double* __restrict__ part) {
+  __shared__ double red[EW_THREADS];
+  const int n = blockIdx.y;
+  const int64_t per = (int64_t)mh * mw, base = (int64_t)n * per;
+  const double m = scal[n * VS_STRIDE + VS_WB] / sum_w;
+  double sbb = 0.0, srr = 0.0;
+  VcWalk at(mw);
+  for (int64_t k = (int64_t)blockIdx.x * EW_THREADS + threadIdx.x; k < per; k += (int64_t)gridDim.x * EW_THREADS, at.next()) {
+    const double w = vc_weight(at.ii, at.jj, mh, mw, 15), bp = b[base + k] - m, rp = r[base + k] - m;
+    r[base + k] = rp;
+    sbb += w * (bp * bp);
+    srr += w * (rp * rp);
+  }
+  const double tbb = block_sum<EW_THREADS>(sbb, red);
+  const double trr = block_sum<EW_THREADS>(srr, red);
+  if (threadIdx.x == 0) {
+    part[(int64_t)n * cap + blockIdx.x] = tbb;
+    part[((int64_t)N + n) * cap + blockIdx.x] = trr;
+  }
+}
+
+// mask 15, at the finish: the block's share of sum w x (mean == NULL), then x -= mean[n] / sum w: the solution whose trapezoidal integral vanishes
+__global__ __launch_bounds__(EW_THREADS) void varcoef_mean_kernel(int mh, int mw, int cap, double sum_w, const double* __restrict__ mean, double* __restrict__ x,
+                                                                  double* __restrict__ part) {
+  __shared__ double red[EW_THREADS];
+  const int n = blockIdx.y;
+  const int64_t per = (int64_t)mh * mw, base = (int64_t)n * per;
+  const double m = mean ? mean[n] / sum_w : 0.0;
+  double s = 0.0;
+  VcWalk at(mw);
+  for (int64_t k = (int64_t)blockIdx.x * EW_THREADS + threadIdx.x; k < per; k += (int64_t)gridDim.x * EW_THREADS, at.next()) {
+    if (mean) x[base + k] -= m;
+    else s += vc_weight(at.ii, at.jj, mh, mw, 15) * x[base + k];
+  }
+  if (mean) return;                                  // uniform over the grid
+  const double tot = block_sum<EW_THREADS>(s, red);
+  if (threadIdx.x == 0) part[(int64_t)n * cap + blockIdx.x] = tot;
 }
 
 // second stage of every reduction: one block per sample adds (OP 0) or takes the minimum (OP 1) of its `count` partials in a fixed order and stores
@@ -189,7 +317,10 @@ __global__ __launch_bounds__(EW_THREADS) void varcoef_reduce_kernel(int count, i
 
 // x += alpha p, r -= alpha q with alpha = (r.z) / (p.q) from the sample's scalars; the block's share of the new r.r.  alpha = 0 for a flagged
 // sample: x and r are then neither changed nor written and p and q are not read, so nothing they hold can reach x.  grid (blocks per sample, N)
-__global__ __launch_bounds__(EW_THREADS) void varcoef_update_xr_kernel(int64_t per, int cap, int cur, const double* __restrict__ scal, const int* __restrict__ flags,
+// BC: the share of sum w r^2 over the mh x mw unknowns (per = mh mw), in the same order: for mask 0 the same bits.
+template <bool BC>
+__global__ __launch_bounds__(EW_THREADS) void varcoef_update_xr_kernel(int64_t per, int mh, int mw, int mask, int cap, int cur, const double* __restrict__ scal,
+                                                                       const int* __restrict__ flags,
                                                                        const double* __restrict__ p, const double* __restrict__ q, double* __restrict__ x,
                                                                        double* __restrict__ r, double* __restrict__ part) {
   __shared__ double red[EW_THREADS];
@@ -198,6 +329,7 @@ __global__ __launch_bounds__(EW_THREADS) void varcoef_update_xr_kernel(int64_t p
   const double alpha = (flags[n] || !(pq > 0.0)) ? 0.0 : rz / pq;
   const int64_t base = (int64_t)n * per;
   double s = 0.0;
+  VcWalk at(BC ? mw : 1);
   for (int64_t k = (int64_t)blockIdx.x * EW_THREADS + threadIdx.x; k < per; k += (int64_t)gridDim.x * EW_THREADS) {
     double rn = r[base + k];
     if (alpha != 0.0) {                            // uniform over the block
@@ -205,7 +337,12 @@ __global__ __launch_bounds__(EW_THREADS) void varcoef_update_xr_kernel(int64_t p
       rn -= alpha * q[base + k];
       r[base + k] = rn;
     }
-    s += rn * rn;
+    if (BC) {
+      s += vc_weight(at.ii, at.jj, mh, mw, mask) * (rn * rn);
+      at.next();
+    } else {
+      s += rn * rn;
+    }
   }
   const double tot = block_sum<EW_THREADS>(s, red);
   if (threadIdx.x == 0) part[(int64_t)n * cap + blockIdx.x] = tot;
@@ -213,6 +350,9 @@ __global__ __launch_bounds__(EW_THREADS) void varcoef_update_xr_kernel(int64_t p
 
 // the eigenvalue division of the preconditioner, in place on the coefficients c = S_h r S_w: c / (lam_h + lam_w).  S is orthonormal and symmetric,
 // so r.z = sum c^2 / (lam_h + lam_w): the block's share of r.z comes from this pass and needs no further read of r and z.
+// BC: c = Vinv_h r Vinv_w^T with V^T W V = I per axis, so Vinv = V^T W and sum w r z is the same sum c^2 / (lam_h + lam_w).  The null mode of the
+// all-Neumann operator (lam_h + lam_w = 0) is dropped, as fd_divide_kernel drops it: z then has no constant part.
+template <bool BC>
 __global__ __launch_bounds__(EW_THREADS) void varcoef_divide_kernel(int nh, int nw, int cap, const double* __restrict__ lam_h, const double* __restrict__ lam_w,
                                                                     double* __restrict__ T, double* __restrict__ part) {
   __shared__ double red[EW_THREADS];
@@ -223,7 +363,7 @@ __global__ __launch_bounds__(EW_THREADS) void varcoef_divide_kernel(int nh, int 
     const double li = lam_h[i];
     double* row = Tn + (int64_t)i * nw;
     for (int j = threadIdx.x; j < nw; j += EW_THREADS) {
-      const double c = row[j], z = c / (li + lam_w[j]);
+      const double c = row[j], l = li + lam_w[j], z = (!BC || fabs(l) > 1e-13) ? c / l : 0.0;
       row[j] = z;
       s += c * z;
     }
@@ -249,107 +389,196 @@ __global__ void varcoef_density_kernel(int64_t total, float lo, float hi, float*
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) g[i] = lo + (hi - lo) * fminf(fabsf(g[i]), 1.f);
 }
 
-static int vc_check_shape(pcnn_handle h, const char* who, int N, int H, int W) {
+// the six arrays of a preconditioner: per axis the eigenbasis of the constant-coefficient 1-D operator on that axis' unknowns, the second axis'
+// matrices transposed (applied from the right) - pcnn_fd_poisson_mixed's.  All-Dirichlet: the orthonormal DST-I matrix S for all four.
+struct VcBasis { const double *Vinv_h, *V_h, *lam_h, *VinvT_w, *VT_w, *lam_w; };
+
+// the shape checks of every entry point; u: the unknowns of the mask (0 for the all-Dirichlet entry points)
+static int vc_check_shape(pcnn_handle h, const char* who, int N, int H, int W, int mask, FdUnknowns* u) {
   PCNN_REQUIRE(h, N >= 1 && N <= 65535, "%s: batch %d not in 1..65535", who, N);
-  PCNN_REQUIRE(h, H >= 3 && W >= 3 && pcnn_cdiv(H - 2, FLUX_ROWS) <= 65535, "%s: grid %d x %d unsupported", who, H, W);
+  PCNN_REQUIRE(h, mask >= 0 && mask < 16, "%s: neumann_mask %d not in 0..15", who, mask);
+  PCNN_REQUIRE(h, H >= 3 && W >= 3, "%s: grid %d x %d unsupported", who, H, W);
+  *u = fd_unknowns(H, W, mask);
+  PCNN_REQUIRE(h, pcnn_cdiv(u->mh, FLUX_ROWS) <= 65535, "%s: grid %d x %d unsupported", who, H, W);
   return 0;
 }
-static dim3 vc_tile_grid(int N, int H, int W) { return dim3(pcnn_cdiv(W - 2, FLUX_COLS), pcnn_cdiv(H - 2, FLUX_ROWS), N); }
+static dim3 vc_tile_grid(int N, const FdUnknowns& u) { return dim3(pcnn_cdiv(u.mw, FLUX_COLS), pcnn_cdiv(u.mh, FLUX_ROWS), N); }
 
-// z = M^-1 r, M the constant-coefficient 5-point operator with zero Dirichlet data (its 1/dx^2 left out: a positive factor of M does not change the
-// iterates): z = S_h ((S_h r S_w) ./ (lam_h + lam_w)) S_w as four fp64 matrix-core products; q holds the half-transformed fields.  r.z -> scal slot.
-static int vc_precondition(pcnn_handle h, int N, int H, int W, const VcWs& w, const double* S_h, const double* lam_h, const double* S_w, const double* lam_w,
-                           double* scal, int slot) {
-  const int nh = H - 2, nw = W - 2;
-  const int64_t per = (int64_t)nh * nw;
+// z = M^-1 r, M the constant-coefficient 5-point operator of the same edge types with zero data (its 1/dx^2 left out: a positive factor of M does not
+// change the iterates): z = V_h ((Vinv_h r VinvT_w) ./ (lam_h + lam_w)) VT_w as four fp64 matrix-core products; q holds the half-transformed fields.
+// r.z (BC: sum w r z) -> scal slot.
+template <bool BC>
+static int vc_precondition(pcnn_handle h, int N, const FdUnknowns& u, const VcWs& w, const VcBasis& B, double* scal, int slot) {
+  const int64_t per = (int64_t)u.mh * u.mw;
   const int eb = vc_ew_blocks(per);
-  if (int rc = pcnn_two_sided_gemm_f64(h, N, nh, nw, S_h, w.r, S_w, w.q, w.z)) return rc;
-  hipLaunchKernelGGL(varcoef_divide_kernel, dim3(eb, N), dim3(EW_THREADS), 0, h->stream, nh, nw, w.cap, lam_h, lam_w, w.z, w.part);
+  if (int rc = pcnn_two_sided_gemm_f64(h, N, u.mh, u.mw, B.Vinv_h, w.r, B.VinvT_w, w.q, w.z)) return rc;
+  hipLaunchKernelGGL(varcoef_divide_kernel<BC>, dim3(eb, N), dim3(EW_THREADS), 0, h->stream, u.mh, u.mw, w.cap, B.lam_h, B.lam_w, w.z, w.part);
   hipLaunchKernelGGL(varcoef_reduce_kernel<0>, dim3(N), dim3(EW_THREADS), 0, h->stream, eb, w.cap, w.part, scal, (int)VS_STRIDE, slot, 0, 0.0, (int*)nullptr);
   PCNN_CHECK_LAUNCH(h, "pcnn_varcoef_pcg(divide)");
-  return pcnn_two_sided_gemm_f64(h, N, nh, nw, S_h, w.z, S_w, w.q, w.z);
+  return pcnn_two_sided_gemm_f64(h, N, u.mh, u.mw, B.V_h, w.z, B.VT_w, w.q, w.z);
+}
+
+// The bodies of the entry points: BC = false behind the all-Dirichlet names (mask 0, S for every basis matrix), BC = true behind the *_bc_* names.
+template <bool BC>
+static int vc_apply(pcnn_handle h, const char* who, int N, int H, int W, int mask, const float* rho, const float* dx, const double* p, double* q, double* pq) {
+  PCNN_REQUIRE(h, h && rho && dx && p && q && pq, "%s: null argument", who);
+  FdUnknowns u;
+  if (int rc = vc_check_shape(h, who, N, H, W, mask, &u)) return rc;
+  const int cap = vc_cap(u.mh, u.mw), tiles = vc_tiles(u.mh, u.mw);
+  if (int rc = pcnn_reserve(h, h->aux_ws, (size_t)N * cap * sizeof(double), 0, who)) return rc;
+  double* part = static_cast<double*>(h->aux_ws.p);
+  hipLaunchKernelGGL(varcoef_apply_kernel<BC>, vc_tile_grid(N, u), dim3(FLUX_THREADS), 0, h->stream, H, W, cap, mask, rho, dx, p, q, part);
+  hipLaunchKernelGGL(varcoef_reduce_kernel<0>, dim3(N), dim3(EW_THREADS), 0, h->stream, tiles, cap, part, pq, 1, 0, 0, 0.0, (int*)nullptr);
+  PCNN_CHECK_LAUNCH(h, who);
+  return 0;
+}
+
+template <bool BC>
+static int vc_setup(pcnn_handle h, const char* who, int N, int H, int W, int mask, const float* rho, const float* rhs, const float* left, const float* right,
+                    const float* bottom, const float* top, const float* dx, const double* x0, double tol, const VcBasis& B, void* workspace,
+                    size_t workspace_bytes, double* scal, int* flags) {
+  PCNN_REQUIRE(h, h && rho && rhs && left && right && bottom && top && dx && B.Vinv_h && B.V_h && B.lam_h && B.VinvT_w && B.VT_w && B.lam_w && workspace && scal &&
+                      flags, "%s: null argument", who);
+  FdUnknowns u;
+  if (int rc = vc_check_shape(h, who, N, H, W, mask, &u)) return rc;
+  PCNN_REQUIRE(h, tol > 0.0, "%s: tol must be positive", who);
+  const VcWs w = vc_layout(workspace, N, u.mh, u.mw);
+  PCNN_REQUIRE(h, workspace_bytes >= vc_bytes(N, u.mh, u.mw), "%s: workspace of %zu B, %zu B needed", who, workspace_bytes, vc_bytes(N, u.mh, u.mw));
+  const int tiles = vc_tiles(u.mh, u.mw);
+  const int64_t per = (int64_t)u.mh * u.mw;
+  const int eb = vc_ew_blocks(per);
+  const bool singular = BC && mask == 15;
+  double* part_rr = w.part + (size_t)N * w.cap;
+  if (hipMemsetAsync(flags, 0, (size_t)N * sizeof(int), h->stream) != hipSuccess || hipMemsetAsync(scal, 0, (size_t)N * VS_STRIDE * sizeof(double), h->stream) != hipSuccess)
+    PCNN_FAIL(h, "%s: cannot clear the per-sample state", who);
+  hipLaunchKernelGGL(varcoef_setup_kernel<BC>, vc_tile_grid(N, u), dim3(FLUX_THREADS), 0, h->stream, H, W, w.cap, N, mask, rho, rhs, left, right, bottom, top, dx, x0,
+                     w.x, w.r, singular ? w.q : (double*)nullptr, w.part);
+  int bb_count = tiles;
+  if (singular) {            // sum w b^2 and sum w b of the b as given, then the projection: b.b and r.r are the projected fields'
+    const double sum_w = (double)(H - 1) * (double)(W - 1);
+    hipLaunchKernelGGL(varcoef_reduce_kernel<0>, dim3(N), dim3(EW_THREADS), 0, h->stream, tiles, w.cap, w.part, scal, (int)VS_STRIDE, (int)VS_BBRAW, 0, 0.0, (int*)nullptr);
+    hipLaunchKernelGGL(varcoef_reduce_kernel<0>, dim3(N), dim3(EW_THREADS), 0, h->stream, tiles, w.cap, part_rr, scal, (int)VS_STRIDE, (int)VS_WB, 0, 0.0, (int*)nullptr);
+    hipLaunchKernelGGL(varcoef_project_kernel, dim3(eb, N), dim3(EW_THREADS), 0, h->stream, u.mh, u.mw, w.cap, N, sum_w, scal, w.q, w.r, w.part);
+    bb_count = eb;
+  }
+  hipLaunchKernelGGL(varcoef_reduce_kernel<0>, dim3(N), dim3(EW_THREADS), 0, h->stream, bb_count, w.cap, w.part, scal, (int)VS_STRIDE, (int)VS_BB, 0, 0.0, (int*)nullptr);
+  hipLaunchKernelGGL(varcoef_reduce_kernel<0>, dim3(N), dim3(EW_THREADS), 0, h->stream, bb_count, w.cap, part_rr, scal, (int)VS_STRIDE, (int)VS_RR, 1, tol * tol, flags);
+  hipLaunchKernelGGL(varcoef_reduce_kernel<1>, dim3(N), dim3(EW_THREADS), 0, h->stream, tiles, w.cap, w.part + (size_t)2 * N * w.cap, scal, (int)VS_STRIDE,
+                     (int)VS_RHOMIN, 0, 0.0, (int*)nullptr);
+  PCNN_CHECK_LAUNCH(h, who);
+  if (int rc = vc_precondition<BC>(h, N, u, w, B, scal, VS_RZ0)) return rc;
+  hipLaunchKernelGGL(varcoef_update_p_kernel, dim3(eb, N), dim3(EW_THREADS), 0, h->stream, per, 1, 1, scal, flags, w.z, w.p);
+  PCNN_CHECK_LAUNCH(h, who);
+  return 0;
+}
+
+template <bool BC>
+static int vc_iterate(pcnn_handle h, const char* who, int N, int H, int W, int mask, const float* rho, const float* dx, double tol, int first_iteration,
+                      int iterations, const VcBasis& B, void* workspace, size_t workspace_bytes, double* scal, int* flags) {
+  PCNN_REQUIRE(h, h && rho && dx && B.Vinv_h && B.V_h && B.lam_h && B.VinvT_w && B.VT_w && B.lam_w && workspace && scal && flags, "%s: null argument", who);
+  FdUnknowns u;
+  if (int rc = vc_check_shape(h, who, N, H, W, mask, &u)) return rc;
+  PCNN_REQUIRE(h, tol > 0.0 && first_iteration >= 0 && iterations >= 1, "%s: bad tol or iteration range", who);
+  const VcWs w = vc_layout(workspace, N, u.mh, u.mw);
+  PCNN_REQUIRE(h, workspace_bytes >= vc_bytes(N, u.mh, u.mw), "%s: workspace of %zu B, %zu B needed", who, workspace_bytes, vc_bytes(N, u.mh, u.mw));
+  const int tiles = vc_tiles(u.mh, u.mw);
+  const int64_t per = (int64_t)u.mh * u.mw;
+  const int eb = vc_ew_blocks(per);
+  for (int it = first_iteration; it < first_iteration + iterations; ++it) {
+    const int cur = it & 1;                      // r.z of the current direction sits in slot VS_RZ0 + cur, the next one goes to the other slot
+    hipLaunchKernelGGL(varcoef_apply_kernel<BC>, vc_tile_grid(N, u), dim3(FLUX_THREADS), 0, h->stream, H, W, w.cap, mask, rho, dx, w.p, w.q, w.part);
+    hipLaunchKernelGGL(varcoef_reduce_kernel<0>, dim3(N), dim3(EW_THREADS), 0, h->stream, tiles, w.cap, w.part, scal, (int)VS_STRIDE, (int)VS_PQ, 0, 0.0, (int*)nullptr);
+    hipLaunchKernelGGL(varcoef_update_xr_kernel<BC>, dim3(eb, N), dim3(EW_THREADS), 0, h->stream, per, u.mh, u.mw, mask, w.cap, cur, scal, flags, w.p, w.q, w.x, w.r,
+                       w.part);
+    hipLaunchKernelGGL(varcoef_reduce_kernel<0>, dim3(N), dim3(EW_THREADS), 0, h->stream, eb, w.cap, w.part, scal, (int)VS_STRIDE, (int)VS_RR, 1, tol * tol, flags);
+    PCNN_CHECK_LAUNCH(h, who);
+    if (int rc = vc_precondition<BC>(h, N, u, w, B, scal, VS_RZ0 + (cur ^ 1))) return rc;
+    hipLaunchKernelGGL(varcoef_update_p_kernel, dim3(eb, N), dim3(EW_THREADS), 0, h->stream, per, cur, 0, scal, flags, w.z, w.p);
+    PCNN_CHECK_LAUNCH(h, who);
+  }
+  return 0;
+}
+
+// soln: the unknowns from x, the Dirichlet ring from the boundary arrays, as every FD solve here writes it.  mask 15: x first loses its w-mean.
+static int vc_finish(pcnn_handle h, const char* who, int N, int H, int W, int mask, void* workspace, const float* left, const float* right, const float* bottom,
+                     const float* top, float* soln) {
+  PCNN_REQUIRE(h, h && workspace && left && right && bottom && top && soln, "%s: null argument", who);
+  FdUnknowns u;
+  if (int rc = vc_check_shape(h, who, N, H, W, mask, &u)) return rc;
+  const VcWs w = vc_layout(workspace, N, u.mh, u.mw);
+  if (mask == 15) {
+    const int eb = vc_ew_blocks((int64_t)u.mh * u.mw);
+    const double sum_w = (double)(H - 1) * (double)(W - 1);
+    double* mean = w.part + (size_t)N * w.cap;     // the second partial-sum array: N doubles are enough
+    hipLaunchKernelGGL(varcoef_mean_kernel, dim3(eb, N), dim3(EW_THREADS), 0, h->stream, u.mh, u.mw, w.cap, sum_w, (const double*)nullptr, w.x, w.part);
+    hipLaunchKernelGGL(varcoef_reduce_kernel<0>, dim3(N), dim3(EW_THREADS), 0, h->stream, eb, w.cap, w.part, mean, 1, 0, 0, 0.0, (int*)nullptr);
+    hipLaunchKernelGGL(varcoef_mean_kernel, dim3(eb, N), dim3(EW_THREADS), 0, h->stream, u.mh, u.mw, w.cap, sum_w, (const double*)mean, w.x, w.part);
+  }
+  pcnn_fd_write_soln(h, N, H, W, mask, w.x, left, right, bottom, top, soln);
+  PCNN_CHECK_LAUNCH(h, who);
+  return 0;
 }
 
 }  // namespace
 
 extern "C" int pcnn_varcoef_apply(pcnn_handle h, int N, int H, int W, const float* rho, const float* dx, const double* p, double* q, double* pq) {
-  PCNN_REQUIRE(h, h && rho && dx && p && q && pq, "pcnn_varcoef_apply: null argument");
-  if (int rc = vc_check_shape(h, "pcnn_varcoef_apply", N, H, W)) return rc;
-  const int cap = vc_cap(H, W), tiles = vc_tiles(H, W);
-  if (int rc = pcnn_reserve(h, h->aux_ws, (size_t)N * cap * sizeof(double), 0, "pcnn_varcoef_apply")) return rc;
-  double* part = static_cast<double*>(h->aux_ws.p);
-  hipLaunchKernelGGL(varcoef_apply_kernel, vc_tile_grid(N, H, W), dim3(FLUX_THREADS), 0, h->stream, H, W, cap, rho, dx, p, q, part);
-  hipLaunchKernelGGL(varcoef_reduce_kernel<0>, dim3(N), dim3(EW_THREADS), 0, h->stream, tiles, cap, part, pq, 1, 0, 0, 0.0, (int*)nullptr);
-  PCNN_CHECK_LAUNCH(h, "pcnn_varcoef_apply");
-  return 0;
+  return vc_apply<false>(h, "pcnn_varcoef_apply", N, H, W, 0, rho, dx, p, q, pq);
 }
 
 extern "C" size_t pcnn_varcoef_pcg_workspace(int N, int H, int W) {
   if (N < 1 || H < 3 || W < 3) return 0;
-  return vc_bytes(N, H, W);
+  return vc_bytes(N, H - 2, W - 2);
 }
 
 extern "C" int pcnn_varcoef_pcg_setup(pcnn_handle h, int N, int H, int W, const float* rho, const float* rhs, const float* left, const float* right,
                                       const float* bottom, const float* top, const float* dx, const double* x0, double tol, const double* S_h,
                                       const double* lam_h, const double* S_w, const double* lam_w, void* workspace, size_t workspace_bytes, double* scal,
                                       int* flags) {
-  PCNN_REQUIRE(h, h && rho && rhs && left && right && bottom && top && dx && S_h && lam_h && S_w && lam_w && workspace && scal && flags,
-               "pcnn_varcoef_pcg_setup: null argument");
-  if (int rc = vc_check_shape(h, "pcnn_varcoef_pcg_setup", N, H, W)) return rc;
-  PCNN_REQUIRE(h, tol > 0.0, "pcnn_varcoef_pcg_setup: tol must be positive");
-  const VcWs w = vc_layout(workspace, N, H, W);
-  PCNN_REQUIRE(h, workspace_bytes >= vc_bytes(N, H, W), "pcnn_varcoef_pcg_setup: workspace of %zu B, %zu B needed", workspace_bytes, vc_bytes(N, H, W));
-  const int tiles = vc_tiles(H, W);
-  const int64_t per = (int64_t)(H - 2) * (W - 2);
-  if (hipMemsetAsync(flags, 0, (size_t)N * sizeof(int), h->stream) != hipSuccess || hipMemsetAsync(scal, 0, (size_t)N * VS_STRIDE * sizeof(double), h->stream) != hipSuccess)
-    PCNN_FAIL(h, "pcnn_varcoef_pcg_setup: cannot clear the per-sample state");
-  hipLaunchKernelGGL(varcoef_setup_kernel, vc_tile_grid(N, H, W), dim3(FLUX_THREADS), 0, h->stream, H, W, w.cap, N, rho, rhs, left, right, bottom, top, dx, x0, w.x,
-                     w.r, w.part);
-  hipLaunchKernelGGL(varcoef_reduce_kernel<0>, dim3(N), dim3(EW_THREADS), 0, h->stream, tiles, w.cap, w.part, scal, (int)VS_STRIDE, (int)VS_BB, 0, 0.0, (int*)nullptr);
-  hipLaunchKernelGGL(varcoef_reduce_kernel<0>, dim3(N), dim3(EW_THREADS), 0, h->stream, tiles, w.cap, w.part + (size_t)N * w.cap, scal, (int)VS_STRIDE, (int)VS_RR, 1,
-                     tol * tol, flags);
-  hipLaunchKernelGGL(varcoef_reduce_kernel<1>, dim3(N), dim3(EW_THREADS), 0, h->stream, tiles, w.cap, w.part + (size_t)2 * N * w.cap, scal, (int)VS_STRIDE,
-                     (int)VS_RHOMIN, 0, 0.0, (int*)nullptr);
-  PCNN_CHECK_LAUNCH(h, "pcnn_varcoef_pcg_setup");
-  if (int rc = vc_precondition(h, N, H, W, w, S_h, lam_h, S_w, lam_w, scal, VS_RZ0)) return rc;
-  hipLaunchKernelGGL(varcoef_update_p_kernel, dim3(vc_ew_blocks(per), N), dim3(EW_THREADS), 0, h->stream, per, 1, 1, scal, flags, w.z, w.p);
-  PCNN_CHECK_LAUNCH(h, "pcnn_varcoef_pcg_setup(direction)");
-  return 0;
+  return vc_setup<false>(h, "pcnn_varcoef_pcg_setup", N, H, W, 0, rho, rhs, left, right, bottom, top, dx, x0, tol, VcBasis{S_h, S_h, lam_h, S_w, S_w, lam_w}, workspace,
+                         workspace_bytes, scal, flags);
 }
 
 extern "C" int pcnn_varcoef_pcg_iterate(pcnn_handle h, int N, int H, int W, const float* rho, const float* dx, double tol, int first_iteration, int iterations,
                                         const double* S_h, const double* lam_h, const double* S_w, const double* lam_w, void* workspace, size_t workspace_bytes,
                                         double* scal, int* flags) {
-  PCNN_REQUIRE(h, h && rho && dx && S_h && lam_h && S_w && lam_w && workspace && scal && flags, "pcnn_varcoef_pcg_iterate: null argument");
-  if (int rc = vc_check_shape(h, "pcnn_varcoef_pcg_iterate", N, H, W)) return rc;
-  PCNN_REQUIRE(h, tol > 0.0 && first_iteration >= 0 && iterations >= 1, "pcnn_varcoef_pcg_iterate: bad tol or iteration range");
-  const VcWs w = vc_layout(workspace, N, H, W);
-  PCNN_REQUIRE(h, workspace_bytes >= vc_bytes(N, H, W), "pcnn_varcoef_pcg_iterate: workspace of %zu B, %zu B needed", workspace_bytes, vc_bytes(N, H, W));
-  const int tiles = vc_tiles(H, W);
-  const int64_t per = (int64_t)(H - 2) * (W - 2);
-  const int eb = vc_ew_blocks(per);
-  for (int it = first_iteration; it < first_iteration + iterations; ++it) {
-    const int cur = it & 1;                      // r.z of the current direction sits in slot VS_RZ0 + cur, the next one goes to the other slot
-    hipLaunchKernelGGL(varcoef_apply_kernel, vc_tile_grid(N, H, W), dim3(FLUX_THREADS), 0, h->stream, H, W, w.cap, rho, dx, w.p, w.q, w.part);
-    hipLaunchKernelGGL(varcoef_reduce_kernel<0>, dim3(N), dim3(EW_THREADS), 0, h->stream, tiles, w.cap, w.part, scal, (int)VS_STRIDE, (int)VS_PQ, 0, 0.0, (int*)nullptr);
-    hipLaunchKernelGGL(varcoef_update_xr_kernel, dim3(eb, N), dim3(EW_THREADS), 0, h->stream, per, w.cap, cur, scal, flags, w.p, w.q, w.x, w.r, w.part);
-    hipLaunchKernelGGL(varcoef_reduce_kernel<0>, dim3(N), dim3(EW_THREADS), 0, h->stream, eb, w.cap, w.part, scal, (int)VS_STRIDE, (int)VS_RR, 1, tol * tol, flags);
-    PCNN_CHECK_LAUNCH(h, "pcnn_varcoef_pcg_iterate(update)");
-    if (int rc = vc_precondition(h, N, H, W, w, S_h, lam_h, S_w, lam_w, scal, VS_RZ0 + (cur ^ 1))) return rc;
-    hipLaunchKernelGGL(varcoef_update_p_kernel, dim3(eb, N), dim3(EW_THREADS), 0, h->stream, per, cur, 0, scal, flags, w.z, w.p);
-    PCNN_CHECK_LAUNCH(h, "pcnn_varcoef_pcg_iterate(direction)");
-  }
-  return 0;
+  return vc_iterate<false>(h, "pcnn_varcoef_pcg_iterate", N, H, W, 0, rho, dx, tol, first_iteration, iterations, VcBasis{S_h, S_h, lam_h, S_w, S_w, lam_w}, workspace,
+                           workspace_bytes, scal, flags);
 }
 
 extern "C" int pcnn_varcoef_pcg_finish(pcnn_handle h, int N, int H, int W, const void* workspace, const float* left, const float* right, const float* bottom,
                                        const float* top, float* soln) {
-  PCNN_REQUIRE(h, h && workspace && left && right && bottom && top && soln, "pcnn_varcoef_pcg_finish: null argument");
-  if (int rc = vc_check_shape(h, "pcnn_varcoef_pcg_finish", N, H, W)) return rc;
-  const VcWs w = vc_layout(const_cast<void*>(workspace), N, H, W);
-  pcnn_fd_write_soln(h, N, H, W, 0, w.x, left, right, bottom, top, soln);     // interior from x, the ring as every FD solve here writes it
-  PCNN_CHECK_LAUNCH(h, "pcnn_varcoef_pcg_finish");
-  return 0;
+  return vc_finish(h, "pcnn_varcoef_pcg_finish", N, H, W, 0, const_cast<void*>(workspace), left, right, bottom, top, soln);     // mask 0 only reads it
+}
+
+extern "C" int pcnn_varcoef_bc_apply(pcnn_handle h, int N, int H, int W, int neumann_mask, const float* rho, const float* dx, const double* p, double* q,
+                                     double* pq) {
+  return vc_apply<true>(h, "pcnn_varcoef_bc_apply", N, H, W, neumann_mask, rho, dx, p, q, pq);
+}
+
+extern "C" size_t pcnn_varcoef_bc_pcg_workspace(int N, int H, int W, int neumann_mask) {
+  if (N < 1 || H < 3 || W < 3 || neumann_mask < 0 || neumann_mask > 15) return 0;
+  const FdUnknowns u = fd_unknowns(H, W, neumann_mask);
+  return vc_bytes(N, u.mh, u.mw);
+}
+
+extern "C" int pcnn_varcoef_bc_pcg_setup(pcnn_handle h, int N, int H, int W, int neumann_mask, const float* rho, const float* rhs, const float* left,
+                                         const float* right, const float* bottom, const float* top, const float* dx, const double* x0, double tol,
+                                         const double* Vinv_h, const double* V_h, const double* lam_h, const double* VinvT_w, const double* VT_w,
+                                         const double* lam_w, void* workspace, size_t workspace_bytes, double* scal, int* flags) {
+  return vc_setup<true>(h, "pcnn_varcoef_bc_pcg_setup", N, H, W, neumann_mask, rho, rhs, left, right, bottom, top, dx, x0, tol,
+                        VcBasis{Vinv_h, V_h, lam_h, VinvT_w, VT_w, lam_w}, workspace, workspace_bytes, scal, flags);
+}
+
+extern "C" int pcnn_varcoef_bc_pcg_iterate(pcnn_handle h, int N, int H, int W, int neumann_mask, const float* rho, const float* dx, double tol, int first_iteration,
+                                           int iterations, const double* Vinv_h, const double* V_h, const double* lam_h, const double* VinvT_w,
+                                           const double* VT_w, const double* lam_w, void* workspace, size_t workspace_bytes, double* scal, int* flags) {
+  return vc_iterate<true>(h, "pcnn_varcoef_bc_pcg_iterate", N, H, W, neumann_mask, rho, dx, tol, first_iteration, iterations,
+                          VcBasis{Vinv_h, V_h, lam_h, VinvT_w, VT_w, lam_w}, workspace, workspace_bytes, scal, flags);
+}
+
+extern "C" int pcnn_varcoef_bc_pcg_finish(pcnn_handle h, int N, int H, int W, int neumann_mask, void* workspace, const float* left, const float* right,
+                                          const float* bottom, const float* top, float* soln) {
+  return vc_finish(h, "pcnn_varcoef_bc_pcg_finish", N, H, W, neumann_mask, workspace, left, right, bottom, top, soln);
 }
 
 extern "C" int pcnn_varcoef_density(pcnn_handle h, int64_t total, float lo, float hi, float* g) {

@@ -510,7 +510,7 @@ def _lead_shape(a, name, dims):
 
 
 def variable_density_poisson_solve(rho, rhses, boundaries, dx, dy=None, tol=1e-10, max_iterations=500, initial_guesses=None, check_every=8,
-                                   return_info=False, device=None, check_start=False):
+                                   return_info=False, device=None, check_start=False, boundary_types=None):
     """Solves div((1/rho) grad u) = f with Dirichlet data on the four edges, on the vertex-centred grid of multigrid_poisson_solve (same shapes
     and edge names: rhses (N,1,H,W) or (N,H,W); boundaries: dict with 'left'/'right' (N,W) and 'bottom'/'top' (N,H); dx one spacing per sample).
     rho (N,H,W) or (N,1,H,W) is given on every node, boundary nodes included, and must be positive.
@@ -529,10 +529,29 @@ def variable_density_poisson_solve(rho, rhses, boundaries, dx, dy=None, tol=1e-1
     already meets the tolerance then reports 0 iterations (by default the first look comes after check_every iterations); the solution is the
     same, bit for bit.
 
+    boundary_types: dict edge -> 'dirichlet' | 'neumann' as mixed_bc_poisson_solve takes it (a missing edge is Dirichlet); None or all Dirichlet is
+    the solve described above, untouched.  A Neumann edge's array holds g = du/dn along the outward normal, its nodes are unknowns (rho and f are
+    read there too) and a Dirichlet edge wins a corner; a Dirichlet node has the value the edge arrays give it, rows 0 / H-1 first.  With A = -L:
+      rows   (A u)_c = sum_k beta_k (u_c - u_k) / dx^2 over the four directions; a Neumann edge node has no outward neighbour and the inward face
+             of that direction counts twice, 2 beta_in (u_c - u_in) (both directions at a Neumann/Neumann corner); faces along the edge are ordinary.
+      b      -f_c, plus beta_k / dx^2 times each Dirichlet neighbour's value, plus 2 g / (rho_c dx) for each Neumann edge that contains the node:
+             1 / rho_c is the coefficient on the boundary face of the node's half cell.  (The mirrored ghost node's 2 beta_in g / dx is first order;
+             this form is second order.)
+      w      = w_i w_j with 1/2 on a Neumann edge's row / column, else 1: W A is symmetric - positive definite with a Dirichlet edge - and the
+             solver is conjugate gradients in the W inner product, preconditioned by the constant-coefficient solve of the same edge types
+             (mixed_bc_poisson_solve's): a sample stops at sum w r^2 <= tol^2 sum w b^2, and the condition number bound above carries over.
+             rho = c everywhere gives mixed_bc_poisson_solve's system with f replaced by c f.
+      all four Neumann: W A has the constants as null space.  b is replaced by b - (sum w b) / (sum w), the compatibility projection, and the
+             returned solution has zero trapezoidal integral (mixed_bc_poisson_solve's convention), whatever mean the initial guess has.  info's
+             `compatibility_defect` = |sum w b| / sqrt(sum w * sum w b^2) in [0, 1] tells how incompatible the data were, and `rhs_shift` the
+             constant the projection added to f: the solution satisfies the discrete equation of f + rhs_shift.
+
     Returns soln (N,1,H,W) fp32; with return_info also a dict of per-sample numpy arrays `iterations` (a multiple of check_every), `converged`
-    and `relative_residual` (||r|| / ||b|| of the recurrence)."""
+    and `relative_residual` (||r|| / ||b|| of the recurrence), and with a Neumann edge `compatibility_defect` and `rhs_shift` (zeros unless all four
+    edges are Neumann)."""
     import warnings
     # everything that can be refused without a device is refused first
+    neumann = _neumann_flags(boundary_types) if boundary_types is not None else (False,) * 4
     rs = _lead_shape(rhses, 'rhses', 3)
     if _lead_shape(rho, 'rho', 3) != rs:
         raise ValueError('rho %r and rhses %r must have the same (N,H,W)' % (tuple(rho.shape), tuple(rhses.shape)))
@@ -563,14 +582,15 @@ def variable_density_poisson_solve(rho, rhses, boundaries, dx, dy=None, tol=1e-1
         g = initial_guesses if isinstance(initial_guesses, torch.Tensor) else torch.as_tensor(np.asarray(initial_guesses))
         x0 = g.to(device=dev, dtype=torch.float64).reshape(N, H, W).contiguous()
     soln, info = K.varcoef_pcg_solve(dens, r, b['left'], b['right'], b['bottom'], b['top'], d, tol=float(tol), max_iterations=int(max_iterations), x0=x0,
-                                     check_every=int(check_every), check_start=bool(check_start))
+                                     check_every=int(check_every), check_start=bool(check_start), neumann=neumann if any(neumann) else None)
     if not info['converged'].all():           # (a rho <= 0 or NaN on the device was refused inside, straight after the setup kernel's minimum)
         bad = np.flatnonzero(~info['converged'])
         warnings.warn('variable_density_poisson_solve: sample(s) %r not converged to tol = %g after %d iterations (relative residual %r)'
                       % (bad.tolist(), tol, int(info['iterations'].max()), info['relative_residual'][bad].tolist()), RuntimeWarning, stacklevel=2)
     soln = soln.view(N, 1, H, W)
     if return_info:
-        return soln, {k: info[k] for k in ('iterations', 'converged', 'relative_residual')}
+        keys = ('iterations', 'converged', 'relative_residual') + (('compatibility_defect', 'rhs_shift') if any(neumann) else ())
+        return soln, {k: info[k] for k in keys}
     return soln
 
 
@@ -590,13 +610,20 @@ class variable_density_dataset_generator(numerical_dataset_generator):
     rho = lo + (hi - lo) |g| / max|g| with g a smooth random field (the bicubic up-sampling of random control points the numerical generator
     uses) and (lo, hi) = density_range: the reference takes 1e-7 + |g|, whose ratio max/min is unbounded; density_range bounds the condition
     number of the preconditioned system by hi / lo.  One grid shape per batch (output_shape, or drawn from random_output_shape_range), one
-    spacing per sample from random_dx_range."""
+    spacing per sample from random_dx_range.
+
+    boundary_types: dict edge -> 'dirichlet' | 'neumann' (variable_density_poisson_solve's; None: all Dirichlet).  A Neumann edge's array is its
+    du/dn: zeros with boundaries = 'zero', the drawn smooth function with 'random' - the draws are the same whatever the types.  With all four
+    edges Neumann the right-hand side returned is the one the solution satisfies: the drawn one plus the constant of the solver's compatibility
+    projection (last_info['rhs_shift']).  The models' variable-density path does not take Neumann edges yet."""
 
     def __init__(self, batch_size=1, batches_per_epoch=1, output_shape=None, random_output_shape_range=((64, 85), (64, 85)), density_range=(1.0, 10.0),
                  rhs_smoothness_range=(5, 20), density_smoothness_range=(5, 20), boundaries='zero', random_dx_range=(0.005, 0.05), rhs_max_magnitude=1.0,
-                 boundary_max_magnitude=1.0, tol=1e-10, max_iterations=500, seed=0, device=None, return_keras_style=True, shard=None):
+                 boundary_max_magnitude=1.0, tol=1e-10, max_iterations=500, seed=0, device=None, return_keras_style=True, shard=None, boundary_types=None):
         super().__init__(batch_size=batch_size, batches_per_epoch=batches_per_epoch, return_keras_style=return_keras_style, seed=seed, device=device,
                          shard=shard)
+        self.boundary_types = boundary_types
+        self.neumann_flags = _neumann_flags(boundary_types) if boundary_types is not None else (False,) * 4      # (left, right, bottom, top)
         lo, hi = float(density_range[0]), float(density_range[1])
         if not 0.0 < lo <= hi:
             raise ValueError('density_range = (lo, hi) needs 0 < lo <= hi, got %r' % (density_range,))
@@ -635,7 +662,9 @@ class variable_density_dataset_generator(numerical_dataset_generator):
             bc[k] = self._edge(ctrl, lengths[k], self.boundary_max_magnitude)
         d = self._dev(dx)
         soln, self.last_info = variable_density_poisson_solve(rho, rhs, bc, d, tol=self.tol, max_iterations=self.max_iterations, return_info=True,
-                                                              device=self.device)
+                                                              device=self.device, boundary_types=self.boundary_types)
+        if all(self.neumann_flags):                                        # the equation (rhs, soln) satisfies: the solver projected its b
+            rhs = rhs + torch.as_tensor(self.last_info['rhs_shift'], dtype=torch.float32, device=rhs.device).view(N, 1, 1)
         frho = torch.stack([rhs, rho], dim=1)
         if not self.return_keras_style:
             return soln, frho

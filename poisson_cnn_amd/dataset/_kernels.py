@@ -110,33 +110,95 @@ def _chk_varcoef(t, name, shape, dtype=torch.float32):
     return t
 
 
-def varcoef_apply(rho, dx, p):
+def _neumann_mask(neumann):
+    flags = [bool(v) for v in neumann]
+    if len(flags) != 4:
+        raise ValueError('neumann must be four flags (left, right, bottom, top), got %r' % (neumann,))
+    return sum(int(v) << k for k, v in enumerate(flags))
+
+
+def varcoef_unknowns(H, W, neumann):
+    """Row range (i0, i1) and column range (j0, j1), both inclusive, of the unknowns for `neumann` = (left, right, bottom, top): a Neumann edge's
+    nodes are unknowns, a Dirichlet edge's are not (fd_unknowns of csrc/pcnn_internal.h)."""
+    nl, nr, nb, nt = [bool(v) for v in neumann]
+    return (0 if nl else 1, H - 1 if nr else H - 2), (0 if nb else 1, W - 1 if nt else W - 2)
+
+
+def varcoef_weights(H, W, neumann, device=None):
+    """(w_i (mh,), w_j (mw,)) fp64: the axis weights of the W inner product of the solve with Neumann edges, 1/2 on a Neumann edge's row / column -
+    the weights of axis_decomposition; w = w_i[:, None] * w_j[None, :]."""
+    (i0, i1), (j0, j1) = varcoef_unknowns(H, W, neumann)
+    wi, wj = torch.ones(i1 - i0 + 1, dtype=torch.float64, device=device), torch.ones(j1 - j0 + 1, dtype=torch.float64, device=device)
+    for w, lo, hi in ((wi, neumann[0], neumann[1]), (wj, neumann[2], neumann[3])):
+        if lo:
+            w[0] = 0.5
+        if hi:
+            w[-1] = 0.5
+    return wi, wj
+
+
+def _varcoef_bases(H, W, neumann, device):
+    """The six arrays (Vinv_h, V_h, lam_h, VinvT_w, VT_w, lam_w) of the preconditioner.  An axis with two Dirichlet ends takes the DST-I matrix of
+    dst_matrices for all of its matrices - the basis axis_decomposition reproduces for those ends, symmetric and its own inverse, and the one the
+    all-Dirichlet entry points use, so mask 0 gives their bits; any other axis takes axis_decomposition's, cached like fd_poisson_mixed's."""
+    nl, nr, nb, nt = [bool(v) for v in neumann]
+    if nl or nr:
+        Vih, Vh, lh, _ = axis_decomposition(H, nl, nr, device)
+    else:
+        Vh, lh = dst_matrices(H, device)
+        Vih = Vh
+    if nb or nt:
+        Viw, Vw, lw, _ = axis_decomposition(W, nb, nt, device)
+        key = ('T', W, nb, nt, str(device))
+        if key not in _axis_cache:
+            _axis_cache[key] = (Viw.t().contiguous(), Vw.t().contiguous())
+        ViwT, VwT = _axis_cache[key]
+    else:
+        VwT, lw = dst_matrices(W, device)
+        ViwT = VwT
+    return Vih, Vh, lh, ViwT, VwT, lw
+
+
+def varcoef_apply(rho, dx, p, neumann=None):
     """q = A p of the variable-density flux-form operator (include/pcnn.h, pcnn_varcoef_apply) with zero Dirichlet data, and the per-sample p.q
-    of the same pass.  rho (N,H,W) fp32, dx (N,) fp32, p (N,H-2,W-2) fp64 -> q (N,H-2,W-2) fp64, pq (N,) fp64."""
+    of the same pass.  rho (N,H,W) fp32, dx (N,) fp32, p (N,H-2,W-2) fp64 -> q (N,H-2,W-2) fp64, pq (N,) fp64.
+    neumann = (left, right, bottom, top) flags: pcnn_varcoef_bc_apply - p and q cover the unknowns of varcoef_unknowns, a Neumann edge's nodes
+    included, and pq is the weighted sum w p q (varcoef_weights).  None: the all-Dirichlet entry point."""
     if rho.dim() != 3:
         raise ValueError('rho must be (N,H,W)')
     N, H, W = rho.shape
+    (i0, i1), (j0, j1) = varcoef_unknowns(H, W, neumann if neumann is not None else (False,) * 4)
     _chk_varcoef(rho, 'rho', (N, H, W))
     _chk_varcoef(dx, 'dx', (N,))
-    _chk_varcoef(p, 'p', (N, H - 2, W - 2), torch.float64)
+    _chk_varcoef(p, 'p', (N, i1 - i0 + 1, j1 - j0 + 1), torch.float64)
     q = torch.empty_like(p)
     pq = torch.empty((N,), dtype=torch.float64, device=p.device)
-    handle().call('pcnn_varcoef_apply', c_int(N), c_int(H), c_int(W), _p(rho), _p(dx), _p(p), _p(q), _p(pq))
+    if neumann is None:
+        handle().call('pcnn_varcoef_apply', c_int(N), c_int(H), c_int(W), _p(rho), _p(dx), _p(p), _p(q), _p(pq))
+    else:
+        handle().call('pcnn_varcoef_bc_apply', c_int(N), c_int(H), c_int(W), c_int(_neumann_mask(neumann)), _p(rho), _p(dx), _p(p), _p(q), _p(pq))
     return q, pq
 
 
-VARCOEF_SCALARS = {'bb': 0, 'rr': 1, 'pq': 2, 'rho_min': 5}      # columns of the per-sample scalar table of pcnn_varcoef_pcg_* (8 doubles per sample)
+# columns of the per-sample scalar table of pcnn_varcoef_pcg_* (8 doubles per sample); wb, bb_raw: sum w b and sum w b^2 before the mask-15 projection
+VARCOEF_SCALARS = {'bb': 0, 'rr': 1, 'pq': 2, 'rho_min': 5, 'wb': 6, 'bb_raw': 7}
 
 
-def varcoef_pcg_solve(rho, rhs, left, right, bottom, top, dx, tol=1e-10, max_iterations=500, x0=None, check_every=8, check_start=False):
+def varcoef_pcg_solve(rho, rhs, left, right, bottom, top, dx, tol=1e-10, max_iterations=500, x0=None, check_every=8, check_start=False, neumann=None):
     """Preconditioned conjugate gradients on the variable-density system (pcnn_varcoef_pcg_setup / _iterate / _finish).  rho, rhs (N,H,W),
-    left/right (N,W), bottom/top (N,H), dx (N,): fp32 CUDA tensors; x0: optional (N,H,W) fp64 initial guess (its interior is used).
+    left/right (N,W), bottom/top (N,H), dx (N,): fp32 CUDA tensors; x0: optional (N,H,W) fp64 initial guess (its unknowns are used).
     The device runs check_every iterations per call; the host reads the N convergence flags between calls and nothing else.
     -> soln (N,H,W) fp32 and a dict of host arrays: iterations (the multiple of check_every at which the sample's flag was seen; for a sample that
-    did not converge, all that were run), converged, relative_residual = ||r|| / ||b|| of the recurrence, rho_min.
+    did not converge, all that were run), converged, relative_residual = ||r|| / ||b|| of the recurrence, rho_min, compatibility_defect, rhs_shift.
     check_start: also read the flags the setup launch raised for the start itself (||b - A x0|| <= tol ||b||): such a sample reports 0 iterations,
     and no iteration is launched when every sample has one.  The solution's bits are the same either way - a flagged sample is frozen.
-    A rho that is not positive everywhere (NaN included) raises ValueError straight after the setup launch."""
+    A rho that is not positive everywhere (NaN included) raises ValueError straight after the setup launch.
+    neumann = (left, right, bottom, top) flags: the pcnn_varcoef_bc_pcg_* entry points (include/pcnn.h) - a flagged edge's array holds du/dn along
+    the outward normal and its nodes are unknowns; norms are those of the W inner product.  None: the all-Dirichlet entry points; four False flags
+    run the same problem through the *_bc_* ones and give the same bits.  All four True: the data need not be compatible - setup projects b, and
+    compatibility_defect = |sum w b| / sqrt(sum w * sum w b^2) in [0, 1] says how far it was; rhs_shift is the constant (sum w b) / (sum w) the
+    projection took from b, i.e. the solution solves the system of rhs + rhs_shift; the solution has zero trapezoidal integral.  Both are 0
+    for every other mask."""
     N, H, W = rho.shape
     for name, t, shape in (('rho', rho, (N, H, W)), ('rhs', rhs, (N, H, W)), ('left', left, (N, W)), ('right', right, (N, W)), ('bottom', bottom, (N, H)),
                            ('top', top, (N, H)), ('dx', dx, (N,))):
@@ -146,15 +208,32 @@ def varcoef_pcg_solve(rho, rhs, left, right, bottom, top, dx, tol=1e-10, max_ite
     if not (tol > 0 and max_iterations >= 1 and check_every >= 1):
         raise ValueError('tol must be positive, max_iterations and check_every at least 1')
     dev = rho.device
-    Sh, lh = dst_matrices(H, dev)
-    Sw, lw = dst_matrices(W, dev)
-    nbytes = int(_lib.load().pcnn_varcoef_pcg_workspace(c_int(N), c_int(H), c_int(W)))
-    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
-    scal = torch.empty((N, 8), dtype=torch.float64, device=dev)
+    lib, h = _lib.load(), handle()
+    # the three stages as closures, one set per family of entry points: every call site spelled out (tools/check_ctypes_calls.py reads them)
+    if neumann is None:
+        Sh, lh = dst_matrices(H, dev)
+        Sw, lw = dst_matrices(W, dev)
+        nbytes = int(lib.pcnn_varcoef_pcg_workspace(c_int(N), c_int(H), c_int(W)))
+        ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+        setup = lambda: h.call('pcnn_varcoef_pcg_setup', c_int(N), c_int(H), c_int(W), _p(rho), _p(rhs), _p(left), _p(right), _p(bottom), _p(top), _p(dx), _p(x0),
+                               c_double(tol), _p(Sh), _p(lh), _p(Sw), _p(lw), _p(ws), c_size_t(nbytes), _p(scal), _p(flags))
+        iterate = lambda it: h.call('pcnn_varcoef_pcg_iterate', c_int(N), c_int(H), c_int(W), _p(rho), _p(dx), c_double(tol), c_int(it), c_int(check_every),
+                                    _p(Sh), _p(lh), _p(Sw), _p(lw), _p(ws), c_size_t(nbytes), _p(scal), _p(flags))
+        finish = lambda: h.call('pcnn_varcoef_pcg_finish', c_int(N), c_int(H), c_int(W), _p(ws), _p(left), _p(right), _p(bottom), _p(top), _p(soln))
+    else:
+        mask = _neumann_mask(neumann)
+        Vih, Vh, lh, ViwT, VwT, lw = _varcoef_bases(H, W, neumann, dev)
+        nbytes = int(lib.pcnn_varcoef_bc_pcg_workspace(c_int(N), c_int(H), c_int(W), c_int(mask)))
+        ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+        setup = lambda: h.call('pcnn_varcoef_bc_pcg_setup', c_int(N), c_int(H), c_int(W), c_int(mask), _p(rho), _p(rhs), _p(left), _p(right), _p(bottom), _p(top),
+                               _p(dx), _p(x0), c_double(tol), _p(Vih), _p(Vh), _p(lh), _p(ViwT), _p(VwT), _p(lw), _p(ws), c_size_t(nbytes), _p(scal), _p(flags))
+        iterate = lambda it: h.call('pcnn_varcoef_bc_pcg_iterate', c_int(N), c_int(H), c_int(W), c_int(mask), _p(rho), _p(dx), c_double(tol), c_int(it),
+                                    c_int(check_every), _p(Vih), _p(Vh), _p(lh), _p(ViwT), _p(VwT), _p(lw), _p(ws), c_size_t(nbytes), _p(scal), _p(flags))
+        finish = lambda: h.call('pcnn_varcoef_bc_pcg_finish', c_int(N), c_int(H), c_int(W), c_int(mask), _p(ws), _p(left), _p(right), _p(bottom), _p(top),
+                                _p(soln))
+    scal = torch.empty((N, 8), dtype=torch.float64, device=dev)                  # (the closures above find scal, flags and soln when they are called)
     flags = torch.empty((N,), dtype=torch.int32, device=dev)
-    h = handle()
-    h.call('pcnn_varcoef_pcg_setup', c_int(N), c_int(H), c_int(W), _p(rho), _p(rhs), _p(left), _p(right), _p(bottom), _p(top), _p(dx), _p(x0), c_double(tol),
-           _p(Sh), _p(lh), _p(Sw), _p(lw), _p(ws), c_size_t(nbytes), _p(scal), _p(flags))
+    setup()
     rho_min = scal[:, VARCOEF_SCALARS['rho_min']].cpu().numpy()
     if not np.all(rho_min > 0):                                         # the setup kernel's minimum counts a NaN as -inf; nothing more is launched
         raise ValueError('rho must be positive everywhere (minimum per sample: %r)' % (rho_min.tolist(),))
@@ -162,20 +241,22 @@ def varcoef_pcg_solve(rho, rhs, left, right, bottom, top, dx, tol=1e-10, max_ite
     done = (flags.cpu().numpy() != 0) if check_start else np.zeros(N, dtype=bool)
     it = 0
     while it < max_iterations and not done.all():
-        h.call('pcnn_varcoef_pcg_iterate', c_int(N), c_int(H), c_int(W), _p(rho), _p(dx), c_double(tol), c_int(it), c_int(check_every), _p(Sh), _p(lh),
-               _p(Sw), _p(lw), _p(ws), c_size_t(nbytes), _p(scal), _p(flags))
+        iterate(it)
         it += check_every
         f = flags.cpu().numpy() != 0                                    # the one host read per check_every iterations
         iterations[f & ~done] = it
         done |= f
     iterations[~done] = it
     soln = torch.empty((N, H, W), dtype=torch.float32, device=dev)
-    h.call('pcnn_varcoef_pcg_finish', c_int(N), c_int(H), c_int(W), _p(ws), _p(left), _p(right), _p(bottom), _p(top), _p(soln))
+    finish()
     s = scal.cpu().numpy()
-    bb, rr = s[:, VARCOEF_SCALARS['bb']], s[:, VARCOEF_SCALARS['rr']]
+    bb, rr, wb, raw = (s[:, VARCOEF_SCALARS[k]] for k in ('bb', 'rr', 'wb', 'bb_raw'))
+    sum_w = float((H - 1) * (W - 1))                                    # of mask 15, the only mask with wb, raw != 0
     with np.errstate(divide='ignore', invalid='ignore'):
         rel = np.where(bb > 0, np.sqrt(rr / np.where(bb > 0, bb, 1.0)), 0.0)
-    return soln, {'iterations': iterations, 'converged': done, 'relative_residual': rel, 'rho_min': rho_min}
+        defect = np.where(raw > 0, np.abs(wb) / np.sqrt(sum_w * np.where(raw > 0, raw, 1.0)), 0.0)
+    return soln, {'iterations': iterations, 'converged': done, 'relative_residual': rel, 'rho_min': rho_min, 'compatibility_defect': defect,
+                  'rhs_shift': wb / sum_w}
 
 
 def varcoef_density(g, lo, hi):

@@ -332,6 +332,10 @@ def main(argv=None):
         raise ValueError("--dataset_type variable_density trains the homogeneous model: it needs boundaries 'zero' in the dataset section (got %r; with "
                          "'random' the generator yields the four edge arrays as further inputs, which no model here reads) - drop the key or set it to "
                          "'zero'" % (config['dataset']['boundaries'],))
+    if args.dataset_type == 'variable_density' and any(neumann_flags(config.get('dataset', {}).get('boundary_types'))):
+        raise ValueError('--dataset_type variable_density with Neumann boundary_types %r in the dataset section: the solver and the generator take '
+                         'per-edge Neumann boundaries, but the model does not - Homogeneous_Poisson_NN_Legacy(density_input=True) has no Neumann bc_type and '
+                         'its flux-form loss and smoother keep every edge fixed; drop boundary_types' % (config['dataset']['boundary_types'],))
     if density_model and args.dataset_type != 'variable_density':
         raise ValueError('a model with "density_input": true reads the stack [rhs, rho], which only --dataset_type variable_density yields (got '
                          '--dataset_type %s): pass --dataset_type variable_density or drop density_input from the model section' % args.dataset_type)
