@@ -149,7 +149,11 @@ typedef struct {
 int pcnn_conv2d_fwd(pcnn_handle h, const pcnn_conv_desc* d, const float* x, const float* w, const float* bias,
                     const float* bn_scale, const float* bn_shift, const float* residual, float* y, float* act_out);
 /* Same, and y_absmax[0] = max|y| over the tensor (device float, NULL = skip): when y is the input of the next convolution, that
- * layer's weight gradient takes it as its x_absmax hint (pcnn_conv2d_wgrad_hint) */
+ * layer's weight gradient takes it as its x_absmax hint (pcnn_conv2d_wgrad_hint).  The value is overwritten (not accumulated into), is the maximum
+ * of the very floats that were stored (after the residual add), ignores NaNs and is clamped to 3.0e38 when the tensor holds an inf.  Every route of
+ * this call honours it - the narrow vector-ALU kernels, both direct MFMA kernels, the split forward kernel and all spectral inverse kernels, also
+ * when a workspace limit splits the layer into several launches (tests/test_gpu_absmax.py).  Out of scope: the wide-channel kernels of
+ * csrc/conv_wide.hip (pcnn_wide_*) are reached through entry points of their own and have no such output. */
 int pcnn_conv2d_fwd_absmax(pcnn_handle h, const pcnn_conv_desc* d, const float* x, const float* w, const float* bias,
                            const float* bn_scale, const float* bn_shift, const float* residual, float* y, float* act_out, float* y_absmax);
 
@@ -168,7 +172,12 @@ size_t pcnn_conv2d_wgrad_workspace(const pcnn_conv_desc* d);
 int pcnn_conv2d_wgrad(pcnn_handle h, const pcnn_conv_desc* d, const float* x, const float* dz, float* dw,
                       void* workspace, size_t workspace_bytes);
 /* Same with optional hints: x_absmax / dz_absmax point to device floats holding max|x| / max|dz| (exact, or any finite upper bound
- * within a factor 2^10: the scale only has to keep the fp16 halves in range), NULL = compute here.  Ignored in the fp32 math mode. */
+ * within a factor 2^10: the scale only has to keep the fp16 halves in range), NULL = compute here.  Ignored in the fp32 math mode.
+ * A hint is about the tensor alone: the constant of a CONSTANT-padded layer (d->pad_value) is taken into x's scale by the library itself, so a
+ * padding value far above max|x| does not overflow the halves.  An inf / NaN hint is clamped (the scale falls back to 1).
+ * tests/test_gpu_absmax.py pins this contract: exact hints give the same bits as no hints; hints 2^5 and 2^10 too large for either tensor or both
+ * stay at the unhinted error (measured 2.0e-7 rel-L2 against fp64 for all three factors on 3x3 20 -> 24, bound 5e-6); the hints that layers.py
+ * and models.py thread through a training step satisfy max|t| <= hint <= 2^10 max|t| for the tensors they are handed with. */
 int pcnn_conv2d_wgrad_hint(pcnn_handle h, const pcnn_conv_desc* d, const float* x, const float* dz, float* dw,
                            void* workspace, size_t workspace_bytes, const float* x_absmax, const float* dz_absmax);
 

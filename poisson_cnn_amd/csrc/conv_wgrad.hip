@@ -360,6 +360,7 @@ struct SplitPlanes {
   int64_t nquad[2]; int cq[2]; int C[2]; int ld[2]; int vec[2];     // quads in total, quads per pixel, channels, source channel stride, 1 = float4-loadable, 2 = and dense
   unsigned* maxbits;
   const float* hint[2];                                              // device max|.| supplied by the caller (NULL: computed by split_absmax_kernel)
+  float floor[2];                                                    // values the planes must hold besides the tensor's own: |pad_value| of a CONSTANT-padded x
   int zN, zHo, zWo, zTY, zWp, zC, zCp;                                // dz unit planes: [N][TY = ceil(Ho/8)][Wp = 32*ceil(Wo/32)][Cp] units of 8 rows
 };
 
@@ -381,8 +382,8 @@ __global__ __launch_bounds__(256) void split_absmax_kernel(SplitPlanes sp) {
   const int which = blockIdx.y;
   if (sp.hint[which]) {                // the producer already knows the maximum
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-      const float v = fabsf(sp.hint[which][0]);
-      sp.maxbits[which] = __float_as_uint(v <= 3.0e38f ? v : 3.0e38f);
+      const float v = fabsf(sp.hint[which][0]);                      // (inf / nan: clamped BEFORE the floor - fmaxf would drop a nan in favour of the floor)
+      sp.maxbits[which] = __float_as_uint(fmaxf(v <= 3.0e38f ? v : 3.0e38f, sp.floor[which]));
     }
     return;
   }
@@ -405,7 +406,7 @@ __global__ __launch_bounds__(256) void split_absmax_kernel(SplitPlanes sp) {
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
   __syncthreads();
   if (threadIdx.x == 0) {
-    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    mx = fmaxf(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])), sp.floor[which]);
     if (!(mx <= 3.0e38f)) mx = 3.0e38f;               // inf / nan: keep the scale finite, the result carries the nan anyway
     atomicMax(sp.maxbits + which, __float_as_uint(mx));
   }
@@ -757,6 +758,8 @@ extern "C" int pcnn_conv2d_wgrad_hint(pcnn_handle h, const pcnn_conv_desc* d, co
     pp.maxbits = reinterpret_cast<unsigned*>(base);
     _Float16* planes = reinterpret_cast<_Float16*>(base + 256);
     pp.src[0] = x; pp.src[1] = dz; pp.hint[0] = x_absmax; pp.hint[1] = dz_absmax;
+    // the padding constant goes through x's scale into the fp16 planes as well: 0.3 beside max|x| = 1e-12 would overflow them (every dw entry NaN)
+    pp.floor[0] = d->pad_mode == PCNN_PAD_CONSTANT ? std::fabs(d->pad_value) : 0.f; pp.floor[1] = 0.f;
     pp.hi[0] = planes; pp.lo[0] = planes + plane_elems_x(&pd);
     pp.hi[1] = pp.lo[0] + plane_elems_x(&pd); pp.lo[1] = pp.hi[1] + plane_elems_z(&pd);
     pp.cq[0] = pd.Cin >> 2; pp.cq[1] = pd.Cout >> 2; pp.C[0] = d->Cin; pp.C[1] = d->Cout; pp.ld[0] = d->ldx; pp.ld[1] = d->ldy;
