@@ -729,6 +729,23 @@ int pcnn_varcoef_jacobi_fwd(pcnn_handle h, int N, int H, int W, const float* rho
 /* the adjoint of those sweeps w.r.t. u: du = J^T dout (rho and rhs get no gradient).  du aliases no input. */
 int pcnn_varcoef_jacobi_bwd(pcnn_handle h, int N, int H, int W, const float* rho, const float* dx, const float* dout, int n_sweeps, float* du);
 int pcnn_varcoef_jacobi_max_sweeps(void);
+/* The four operators above with a boundary type per edge (neumann_mask as for pcnn_varcoef_bc_apply: bit 0/1/2/3 set = the
+ * left / right / bottom / top edge is Neumann with du/dn = 0).  The unknowns are fd_unknowns(H, W, neumann_mask): a Neumann edge's nodes are unknowns, a
+ * Dirichlet edge wins a corner and keeps whatever the field holds there.  At an unknown c
+ *   (L u)_c = sum_k m_k beta_k (u_k - u_c) / dx^2,  m = 2 on the inward face of a Neumann edge node in that edge's direction (it has no outward
+ * neighbour), 1 otherwise - the half-cell closure of the solver.  With w = w_i w_j, w_i = 1/2 on a Neumann edge's row:
+ *   partials: out[n] = sum over the unknowns of w (L pred - rhs)^2;   bwd: dpred += coef[n] * d(out[n]) / d(pred) on all nodes, a gather;
+ *   jacobi:   u'_c = (sum_k m_k beta_k u_k - dx^2 rhs_c) / (sum_k m_k beta_k) on the unknowns, Dirichlet nodes frozen;  bwd: its adjoint w.r.t. u.
+ * neumann_mask 0 runs the kernels of the entry points above: the same bits.  The same aliasing rules, scratch and sweep fusion; refused: a mask
+ * outside 0..15, H or W below 3. */
+int pcnn_varcoef_bc_pi_loss_partials(pcnn_handle h, int N, int H, int W, const float* pred, const float* rho, const float* rhs, const float* dx,
+                                     float* out /*N*/, int neumann_mask);
+int pcnn_varcoef_bc_pi_loss_bwd(pcnn_handle h, int N, int H, int W, const float* pred, const float* rho, const float* rhs, const float* dx,
+                                const float* coef /*N*/, float* dpred, int neumann_mask);
+int pcnn_varcoef_bc_jacobi_fwd(pcnn_handle h, int N, int H, int W, const float* rho, const float* u, const float* rhs, const float* dx, int n_sweeps,
+                               float* out, int neumann_mask);
+int pcnn_varcoef_bc_jacobi_bwd(pcnn_handle h, int N, int H, int W, const float* rho, const float* dx, const float* dout, int n_sweeps, float* du,
+                               int neumann_mask);
 /* out[n,y,x,0:2] = {stack[n,0,y,x], stack[n,1,y,x]} of the generator's (N,2,H,W) stack [rhs, rho], followed - use_pos - by the two positional
  * channels of pcnn_assemble_input; ldo >= 2 (4 with use_pos). */
 int pcnn_assemble_density_input(pcnn_handle h, int N, int H, int W, const float* stack, int use_pos, float* out, int ldo);

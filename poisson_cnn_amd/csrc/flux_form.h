@@ -1,5 +1,5 @@
 // The discretisation of the variable-density problem div((1/rho) grad u) = f, once: the face coefficient, the fp32 flux-form
-// residual, and the 16 x 64 tile with its LDS node loader.  varcoef.hip (fp64 solve), varcoef_train.hip (loss, smoother) and error_stats.hip
+// residual, the 16 x 64 tile with its LDS node loader, and the weight / mirrored index of the per-edge Neumann closure.  varcoef.hip (fp64 solve), varcoef_train.hip (loss, smoother) and error_stats.hip
 // (statistics) all take them from here.  The fp64 operator of the solve (stencil_at in varcoef.hip) is NOT here on purpose: it sums
 // ((a + b) + c) + d of pc - neighbour, the fp32 residual below (a + b) + (c + d) of neighbour - pc - two roundings, both pinned by goldens.
 #pragma once
@@ -19,6 +19,31 @@ __device__ __forceinline__ float pcnn_flux_residual(float uc, float rc, float u0
   const float s = (pcnn_beta_face(rc, r0) * (u0 - uc) + pcnn_beta_face(rc, r1) * (u1 - uc)) +
                   (pcnn_beta_face(rc, r2) * (u2 - uc) + pcnn_beta_face(rc, r3) * (u3 - uc));
   return s * inv_h2 - f;
+}
+
+// Per-edge Neumann boundaries (DESIGN.md sections 19 and 20; neumann_mask bit 0/1/2/3 = left / right / bottom / top, unknowns fd_unknowns):
+// the weight of unknown (ii, jj) of mh x mw in the W inner product: 1/2 per Neumann edge the node lies on (the first / last unknown row or column)
+__device__ __forceinline__ double vc_weight(int ii, int jj, int mh, int mw, int mask) {
+  const double wi = ((ii == 0 && (mask & 1)) || (ii == mh - 1 && (mask & 2))) ? 0.5 : 1.0;
+  const double wj = ((jj == 0 && (mask & 4)) || (jj == mw - 1 && (mask & 8))) ? 0.5 : 1.0;
+  return wi * wj;
+}
+// What the tile entry at index i of an n-long axis reads: i itself; beyond a Neumann end (lo / hi) the mirrored inward neighbour, which makes the
+// inward face count twice; otherwise -1: zero Dirichlet data, or tile overhang no stored point uses.  n >= 2 whenever an end is Neumann.
+__device__ __forceinline__ int vc_mirror(int i, int n, bool lo, bool hi) {
+  if (i == -1 && lo) return 1;
+  if (i == n && hi) return n - 2;
+  return (i >= 0 && i < n) ? i : -1;
+}
+
+// pcnn_load_nodes over nodes, with node -1 / H (W) of an axis whose end is Neumann reading its mirror image (vc_mirror)
+template <int LR, int LC, class T>
+__device__ __forceinline__ void pcnn_load_nodes_mirrored(T (*t)[LC], const T* __restrict__ src, int H, int W, int I0, int J0, int mask, T fill) {
+  for (int e = threadIdx.x; e < LR * LC; e += FLUX_THREADS) {
+    const int r = e / LC, c = e % LC;
+    const int i = vc_mirror(I0 + r, H, mask & 1, mask & 2), j = vc_mirror(J0 + c, W, mask & 4, mask & 8);
+    t[r][c] = (i >= 0 && j >= 0) ? src[(int64_t)i * W + j] : fill;
+  }
 }
 
 // nodes (I0 .. I0+LR-1) x (J0 .. J0+LC-1) of one sample's H x W field into LDS by the FLUX_THREADS threads; nodes outside the field read `fill`

@@ -52,19 +52,7 @@ static inline VcWs vc_layout(void* ws, int N, int mh, int mw) {
   return l;
 }
 
-// the weight of unknown (ii, jj) of mh x mw in the W inner product: 1/2 per Neumann edge the node lies on (the first / last unknown row or column)
-__device__ __forceinline__ double vc_weight(int ii, int jj, int mh, int mw, int mask) {
-  const double wi = ((ii == 0 && (mask & 1)) || (ii == mh - 1 && (mask & 2))) ? 0.5 : 1.0;
-  const double wj = ((jj == 0 && (mask & 4)) || (jj == mw - 1 && (mask & 8))) ? 0.5 : 1.0;
-  return wi * wj;
-}
-// What the tile entry at index i of an n-long axis reads: i itself; beyond a Neumann end (lo / hi) the mirrored inward neighbour, which makes the
-// inward face count twice; otherwise -1: zero Dirichlet data, or tile overhang no stored point uses.  n >= 2 whenever an end is Neumann.
-__device__ __forceinline__ int vc_mirror(int i, int n, bool lo, bool hi) {
-  if (i == -1 && lo) return 1;
-  if (i == n && hi) return n - 2;
-  return (i >= 0 && i < n) ? i : -1;
-}
+// (the weight vc_weight of an unknown in the W inner product and the mirrored tile index vc_mirror are flux_form.h's, shared with varcoef_train.hip)
 // (row, column) of the flat index k = blockIdx.x * EW_THREADS + threadIdx.x + m * gridDim.x * EW_THREADS of the element-wise kernels, m = 0, 1, ..:
 // one division at the start, none per point.  At most EW_MAX_BLOCKS * EW_THREADS = 2^18 per step: int is enough.
 struct VcWalk {

@@ -615,7 +615,8 @@ class variable_density_dataset_generator(numerical_dataset_generator):
     boundary_types: dict edge -> 'dirichlet' | 'neumann' (variable_density_poisson_solve's; None: all Dirichlet).  A Neumann edge's array is its
     du/dn: zeros with boundaries = 'zero', the drawn smooth function with 'random' - the draws are the same whatever the types.  With all four
     edges Neumann the right-hand side returned is the one the solution satisfies: the drawn one plus the constant of the solver's compatibility
-    projection (last_info['rhs_shift']).  The models' variable-density path does not take Neumann edges yet."""
+    projection (last_info['rhs_shift']).  Homogeneous_Poisson_NN_Legacy(density_input=True, boundary_types=...) trains on such batches (DESIGN.md
+    section 20)."""
 
     def __init__(self, batch_size=1, batches_per_epoch=1, output_shape=None, random_output_shape_range=((64, 85), (64, 85)), density_range=(1.0, 10.0),
                  rhs_smoothness_range=(5, 20), density_smoothness_range=(5, 20), boundaries='zero', random_dx_range=(0.005, 0.05), rhs_max_magnitude=1.0,

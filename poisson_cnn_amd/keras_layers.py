@@ -534,13 +534,14 @@ class JacobiIterationLayer(_Layer):
 class VariableDensityJacobiLayer(_Layer):
     """Jacobi sweeps of the variable-density problem div((1/rho) grad u) = rhs (layers.VariableDensityJacobiLayer; no counterpart in the reference):
     call([guess, rhs, rho, dx]) with one-channel tensors and dx (N,1), or (N,2) with equal columns.  backward(dout) is the gradient w.r.t. the guess.
-    Dirichlet (frozen) edges, isotropic spacing."""
+    Isotropic spacing.  boundary_types: None - Dirichlet (frozen) edges - or a dict edge -> 'dirichlet' | 'neumann': the sweeps then move the Neumann
+    edges' nodes too, by the solver's half-cell closure with du/dn = 0 (layers.VariableDensityJacobiLayer)."""
 
-    def __init__(self, n_iterations=5, ndims=None, data_format='channels_first', device=None):
+    def __init__(self, n_iterations=5, ndims=None, data_format='channels_first', device=None, boundary_types=None):
         super().__init__(data_format, device)
         if ndims not in (None, 2):
             raise NotImplementedError('VariableDensityJacobiLayer: 2-D only')
-        self.layer = L.VariableDensityJacobiLayer(n_iterations)
+        self.layer = L.VariableDensityJacobiLayer(n_iterations, boundary_types=boundary_types)
         self.built = True
 
     def call(self, inputs, training=False):

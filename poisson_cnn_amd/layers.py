@@ -838,10 +838,17 @@ class VariableDensityJacobiLayer:
     u' = (sum over the four faces of beta_face * neighbour - dx^2 rhs) / (sum of beta_face) on interior nodes, beta_face = 2 / (rho_a + rho_b), the
     ring frozen.  With rho = c everywhere this is JacobiIterationLayer's ([3,3],[2,2]) sweep with rhs replaced by c * rhs.  Up to
     ops.varcoef_jacobi_k_max() sweeps run per launch (csrc/varcoef_train.hip).  backward is the adjoint w.r.t. the guess; rho and rhs are data.
-    Dirichlet (frozen) edges and one spacing per sample only."""
+    One spacing per sample only.
+    boundary_types: None keeps every edge frozen.  A dict edge -> 'dirichlet' | 'neumann' (utils.neumann_flags) makes the nodes
+    of the Neumann edges unknowns of the sweep, as they are of dataset.variable_density_poisson_solve: such a node has no outward neighbour and its
+    inward face counts twice (du/dn = 0, second order) - not the first-order mirror JacobiIterationLayer re-imposes.  Dirichlet edges stay frozen and
+    win the corners."""
 
-    def __init__(self, n_iterations=5):
+    def __init__(self, n_iterations=5, boundary_types=None):
         self.n = int(n_iterations)
+        if boundary_types is not None and not isinstance(boundary_types, dict):
+            raise ValueError("VariableDensityJacobiLayer: boundary_types is None or a dict edge -> 'dirichlet' | 'neumann', got %r" % (boundary_types,))
+        self.neumann_mask = neumann_mask(boundary_types)
         self.saved = None
 
     def forward(self, guess, rhs, rho, dx, training=True):
@@ -851,11 +858,11 @@ class VariableDensityJacobiLayer:
         dx = dx.reshape(-1).contiguous()
         rho = rho.contiguous()
         self.saved = (rho, dx) if training else None
-        return ops.varcoef_jacobi(guess.contiguous(), rho, rhs.contiguous(), dx, self.n)
+        return ops.varcoef_jacobi(guess.contiguous(), rho, rhs.contiguous(), dx, self.n, self.neumann_mask)
 
     def backward(self, dout):
         if self.n < 1:
             return dout
         rho, dx = self.saved
         self.saved = None
-        return ops.varcoef_jacobi_bwd(dout.contiguous(), rho, dx, self.n)
+        return ops.varcoef_jacobi_bwd(dout.contiguous(), rho, dx, self.n, self.neumann_mask)

@@ -188,7 +188,25 @@ class variable_density_loss_wrapper(loss_wrapper):
         weight / (N (H-2)(W-2)) * sum over samples and interior nodes of (L_rho pred - rhs)^2,     each sample divided by max|rhs|^2 under `normalize`,
     with its gradient w.r.t. the prediction on every node; rho gets none.  The flux form exists for the 5-point stencil only: `stencil_sizes` and
     `orders` are accepted at 3 and 2, `inputs_have_max_domain_size_squared_normalization` at False.  One spacing per sample: dx (N,1), or (N,2) with
-    equal columns.  channels_first only."""
+    equal columns.  channels_first only.
+    boundary_types: None, or a dict edge -> 'dirichlet' | 'neumann' as the solver and the generator take it.  The residual is
+    then summed over the unknowns of those edge types - a Neumann edge's nodes included, with the solver's half-cell closure and du/dn = 0 - each
+    weighted by w = w_i w_j (1/2 on a Neumann edge's row), and divided by N sum(w); all Dirichlet is today's N (H-2)(W-2)."""
+
+    def __init__(self, *args, boundary_types=None, **kwargs):
+        from .utils import neumann_mask
+        if boundary_types is not None and not isinstance(boundary_types, dict):
+            raise ValueError("variable_density_loss_wrapper: boundary_types is None or a dict edge -> 'dirichlet' | 'neumann', got %r" % (boundary_types,))
+        self.boundary_types = boundary_types
+        self.neumann_mask = neumann_mask(boundary_types)           # refuses an unknown edge name or type
+        super().__init__(*args, **kwargs)
+
+    def weight_sum(self, H, W):
+        """sum(w) over the unknowns: (rows - half a row per Neumann left / right edge) x (columns likewise); (H-2)(W-2) for all Dirichlet."""
+        m = self.neumann_mask
+        if m == 0:
+            return (H - 2) * (W - 2)
+        return (H - 2 + 0.5 * ((m & 1) + (m >> 1 & 1))) * (W - 2 + 0.5 * ((m >> 2 & 1) + (m >> 3 & 1)))
 
     def _init_physics_informed(self, pcfg, ndims):
         if self.data_format != 'channels_first':
@@ -227,10 +245,10 @@ class variable_density_loss_wrapper(loss_wrapper):
         stack = rhs.to(device=y_pred.device, dtype=torch.float32)
         f, rho = stack[:, 0].contiguous(), stack[:, 1].contiguous()
         h = self._spacing(dx.to(y_pred.device), y_pred.shape[0])
-        return ops.varcoef_pi_loss_partials(y_pred, rho, f, h), (H - 2) * (W - 2), lambda: f.abs().amax(dim=(1, 2)), (f, rho, h)
+        return ops.varcoef_pi_loss_partials(y_pred, rho, f, h, self.neumann_mask), self.weight_sum(H, W), lambda: f.abs().amax(dim=(1, 2)), (f, rho, h)
 
     def _pi_backward(self, y_pred, pi, coef, dpred):
-        ops.varcoef_pi_loss_bwd(y_pred, pi[1], pi[0], pi[2], coef.contiguous(), dpred)
+        ops.varcoef_pi_loss_bwd(y_pred, pi[1], pi[0], pi[2], coef.contiguous(), dpred, self.neumann_mask)
 
 
 c_int_ = c_int

@@ -690,7 +690,7 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
                  bottleneck_deconv_config=None, bottleneck_multilinear_config=None, input_normalization=None, output_scaling=None,
                  use_batchnorm=False, postsmoother_iterations=5, use_scaling=False, use_positional_embeddings=True, scaling_config=None,
                  gradient_accumulation_steps=None, bc_type='dirichlet', device=None, seed=0, batchnorm_training=False, smoother_boundaries='frozen',
-                 density_input=False):
+                 density_input=False, boundary_types=None):
         """bc_type: 'dirichlet' or 'neumann' for all four edges (the reference), or - an extension - a dict 'left' | 'right' | 'bottom' | 'top' ->
         'dirichlet' | 'neumann' with the dataset's edge names (left: y = 0, right: y = H-1, bottom: x = 0, top: x = W-1 of the (N,1,H,W) output; a missing
         edge is Dirichlet, at a corner a Dirichlet edge wins).  A Neumann edge is enforced as the reference's SYMMETRIC ring does, to first order:
@@ -701,8 +701,16 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
         density_input (extension): the model of the variable-density problem div((1/rho) grad u) = f.  call takes
         [stack (N,2,H,W), dx] with the stack [rhs, rho] of dataset.variable_density_dataset_generator; the first convolution sees [rhs, rho] and then
         the positional channels; Scaling reads the rhs channel; the post-smoother is layers.VariableDensityJacobiLayer; the loss to compile is
-        losses.variable_density_loss_wrapper.  Dirichlet edges only, as the solver.  evaluate() / predict(return_stats=True) report the error
-        statistics; the residual columns of ops.error_stats are the constant-coefficient residual and are left at 0 for such a model."""
+        losses.variable_density_loss_wrapper.  bc_type stays 'dirichlet' (it is the constant-coefficient model's switch and means the first-order
+        SYMMETRIC ring); Neumann edges of the variable-density problem come in under boundary_types.  evaluate() / predict(return_stats=True) report the error
+        statistics; the residual columns of ops.error_stats are the constant-coefficient residual and are left at 0 for such a model.
+        boundary_types (density_input=True only): None, or a dict edge -> 'dirichlet' | 'neumann' as the variable-density solver
+        and generator take it (a missing edge is Dirichlet).  The nodes of a Neumann edge are unknowns with du/dn = 0 in the solver's half-cell
+        closure.  The ring is ops.bc_ring_fwd with that mask: Dirichlet edges become 0, a Neumann edge takes the mirror value, which is the
+        smoother's starting value there; the post-smoother is layers.VariableDensityJacobiLayer(boundary_types=...), whose sweeps then move the
+        Neumann edges' nodes by that closure.  Compile losses.variable_density_loss_wrapper with the same boundary_types.  All four edges Neumann
+        is allowed and the model removes no mean: the residual term is blind to constants, the supervised terms (MAE, MSE, integral) pin the
+        mean to the target's - the generator's solutions have zero w-mean."""
         if data_format not in ('channels_first', 'channels_last'):
             raise ValueError('data_format must be channels_first or channels_last')
         if pre_bottleneck_convolutions_config is None:
@@ -720,6 +728,14 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
         if self.density_input and (isinstance(bc_type, dict) or any(flags)):
             raise NotImplementedError('density_input=True needs bc_type "dirichlet": the variable-density solver, loss and smoother have Dirichlet edges '
                                       'only (got bc_type %r)' % (bc_type,))
+        if boundary_types is not None:
+            if not self.density_input:
+                raise ValueError('boundary_types is the keyword of the variable-density model (density_input=True); the constant-coefficient '
+                                 "model takes its boundary types as bc_type ('dirichlet', 'neumann' or a dict per edge), got boundary_types %r" % (boundary_types,))
+            if not isinstance(boundary_types, dict):
+                raise ValueError("boundary_types is None or a dict edge -> 'dirichlet' | 'neumann', got %r" % (boundary_types,))
+            flags = neumann_flags(boundary_types)                 # refuses an unknown edge name or type
+        self.boundary_types = None if boundary_types is None else {e: 'neumann' if f else 'dirichlet' for e, f in zip(BC_EDGES, flags)}
         if self.density_input and data_format != 'channels_first':
             raise NotImplementedError('density_input=True: the two-channel stack is channels_first (N,2,H,W) only')
         self._init_device(device, _CPU_NOTE_RAISES)
@@ -730,7 +746,7 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
         self.output_scaling = process_output_scaling_modes(output_scaling)
         self.use_batchnorm = use_batchnorm
         self.use_positional_embeddings = use_positional_embeddings
-        self.neumann_mask = neumann_mask(bc_type)                # the model's one record of its boundary types (bits as ops.bc_ring_fwd's)
+        self.neumann_mask = neumann_mask(bc_type if boundary_types is None else boundary_types)   # the model's one record of its boundary types (bits as ops.bc_ring_fwd's)
         self.per_edge_bc = isinstance(bc_type, dict)              # how bc_type was given; a uniform dict and the string run the same kernels
         self.store = S = L.ParamStore()
         # BatchNormalization mode inside train_step: False = moving statistics (what the reference's train_step most likely does,
@@ -803,7 +819,7 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
         if smoother_boundaries == 'enforce' and self.neumann_mask:
             enforce = {e: 'neumann' if f else 'dirichlet' for e, f in zip(BC_EDGES, flags)}
         if self.density_input:
-            self.postsmoother = L.VariableDensityJacobiLayer(postsmoother_iterations) if postsmoother_iterations > 0 else None
+            self.postsmoother = L.VariableDensityJacobiLayer(postsmoother_iterations, boundary_types=self.boundary_types) if postsmoother_iterations > 0 else None
         else:
             self.postsmoother = L.JacobiIterationLayer(postsmoother_iterations, boundary_types=enforce) if postsmoother_iterations > 0 else None
         self.scaling = L.Scaling(S, C, 'scaling', **scaling_config) if use_scaling else None
@@ -947,6 +963,10 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
                                         prediction's interior, so this is the ||b - A x0|| / ||b|| it starts from when the prediction's edges are 0)
           prediction_max_residual       max|r| per sample
           cold_iterations               with compare_cold=True: the iterations of a second solve started at 0
+        A model with boundary_types solves with those edge types and du/dn = 0 on the Neumann edges:
+        variable_density_poisson_solve(boundary_types=..., zero data); prediction_relative_residual is then sqrt(sum w r^2 / sum w f^2) over the
+        unknowns, r from ops.varcoef_pi_loss_partials with the mask - the ||b - A x0||_W / ||b||_W the solver starts from (all four edges Neumann:
+        before its projection of b) - and prediction_max_residual is None: the statistics kernel has no Neumann variant.
         How many iterations a prediction saves is measured (tools/bench_varcoef_warmstart.py), not promised.  Nothing in the model changes: no
         BatchNormalization update, no gradient, no optimizer state."""
         if not self.density_input:
@@ -959,16 +979,29 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
         d = self._spacing_column(dx).reshape(-1)
         N, _, H, W = stack.shape
         rhs, rho = stack[:, 0].contiguous(), stack[:, 1].contiguous()
-        stats = ops.varcoef_error_stats(pred.to(torch.float32), rho, None, rhs, d)
+        mask = self.neumann_mask
+        if mask:
+            rr = ops.varcoef_pi_loss_partials(pred.to(torch.float32).contiguous(), rho, rhs, d, mask)
+            wi, wj = torch.ones(H, device=self.device), torch.ones(W, device=self.device)        # w on all nodes, 0 on the Dirichlet ones
+            wi[0], wi[-1], wj[0], wj[-1] = 0.5 * (mask & 1), 0.5 * (mask >> 1 & 1), 0.5 * (mask >> 2 & 1), 0.5 * (mask >> 3 & 1)
+            ff = (torch.outer(wi, wj).double() * rhs.double() ** 2).sum(dim=(1, 2))
+        else:
+            stats = ops.varcoef_error_stats(pred.to(torch.float32), rho, None, rhs, d)
         zero = {k: torch.zeros((N, W if k in ('left', 'right') else H), dtype=torch.float32, device=self.device) for k in ('left', 'right', 'bottom', 'top')}
         kw = dict(tol=tol, max_iterations=max_iterations, check_every=check_every, return_info=True, device=self.device, check_start=True)
+        if mask:
+            kw['boundary_types'] = self.boundary_types
         soln, info = D.variable_density_poisson_solve(rho, rhs, zero, d, initial_guesses=pred if warm_start else None, **kw)
         if not return_info:
             return soln
-        s = stats.cpu().numpy().astype(np.float64)
+        if mask:
+            s = np.zeros((N, 8))
+            s[:, 5], s[:, 7] = rr.cpu().numpy().astype(np.float64), ff.cpu().numpy()
+        else:
+            s = stats.cpu().numpy().astype(np.float64)
         with np.errstate(divide='ignore', invalid='ignore'):
             info['prediction_relative_residual'] = np.where(s[:, 7] > 0, np.sqrt(s[:, 5] / np.where(s[:, 7] > 0, s[:, 7], 1.0)), np.nan)
-        info['prediction_max_residual'] = s[:, 6]
+        info['prediction_max_residual'] = None if mask else s[:, 6]
         if compare_cold:
             info['cold_iterations'] = info['iterations'] if not warm_start else D.variable_density_poisson_solve(rho, rhs, zero, d, **kw)[1]['iterations']
         return soln, info

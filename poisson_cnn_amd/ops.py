@@ -1102,20 +1102,42 @@ def _varcoef_fields(who, fields, dx):
     return N, H, W, out, dx.contiguous()
 
 
-def varcoef_pi_loss_partials(pred, rho, rhs, dx):
-    """(N,) per-sample sums over the interior of (L_rho pred - rhs)^2, L_rho the flux-form div((1/rho) grad .) of DESIGN.md section 16/17."""
+def _varcoef_mask(who, neumann_mask):
+    """neumann_mask of the variable-density operators: an int 0..15 (bits as bc_ring_fwd's) or four flags (left, right, bottom, top) -> the int."""
+    if isinstance(neumann_mask, (tuple, list)):
+        if len(neumann_mask) != 4:
+            raise ValueError('%s: neumann_mask takes an int or four flags (left, right, bottom, top), got %r' % (who, neumann_mask))
+        return sum(1 << i for i, f in enumerate(neumann_mask) if f)
+    mask = int(neumann_mask)
+    if not 0 <= mask <= 15:
+        raise ValueError('%s: neumann_mask %r not in 0..15' % (who, neumann_mask))
+    return mask
+
+
+def varcoef_pi_loss_partials(pred, rho, rhs, dx, neumann_mask=0):
+    """(N,) per-sample sums over the interior of (L_rho pred - rhs)^2, L_rho the flux-form div((1/rho) grad .) of DESIGN.md section 16/17.
+    neumann_mask (an int, bits as bc_ring_fwd's, or four flags) non-zero: the sums of w (L_rho pred - rhs)^2 over the unknowns of that mask with the
+    half-cell closure on its Neumann edges (pcnn_varcoef_bc_pi_loss_partials); 0: today's entry point."""
     N, H, W, (pred, rho, rhs), dx = _varcoef_fields('varcoef_pi_loss_partials', {'pred': pred, 'rho': rho, 'rhs': rhs}, dx)
+    mask = _varcoef_mask('varcoef_pi_loss_partials', neumann_mask)
     out = empty((N,), pred.device)
-    handle().call('pcnn_varcoef_pi_loss_partials', c_int(N), c_int(H), c_int(W), _p(pred), _p(rho), _p(rhs), _p(dx), _p(out))
+    if mask == 0:
+        handle().call('pcnn_varcoef_pi_loss_partials', c_int(N), c_int(H), c_int(W), _p(pred), _p(rho), _p(rhs), _p(dx), _p(out))
+    else:
+        handle().call('pcnn_varcoef_bc_pi_loss_partials', c_int(N), c_int(H), c_int(W), _p(pred), _p(rho), _p(rhs), _p(dx), _p(out), c_int(mask))
     return out
 
 
-def varcoef_pi_loss_bwd(pred, rho, rhs, dx, coef, dpred):
+def varcoef_pi_loss_bwd(pred, rho, rhs, dx, coef, dpred, neumann_mask=0):
     """dpred += coef[n] * d(varcoef_pi_loss_partials[n]) / d(pred), on all nodes (the ring included); returns dpred."""
     N, H, W, (pred, rho, rhs, dpred), dx = _varcoef_fields('varcoef_pi_loss_bwd', {'pred': pred, 'rho': rho, 'rhs': rhs, 'dpred': dpred}, dx)
+    mask = _varcoef_mask('varcoef_pi_loss_bwd', neumann_mask)
     if coef.dtype != torch.float32 or not coef.is_cuda or tuple(coef.shape) != (N,) or not coef.is_contiguous():
         raise ValueError('varcoef_pi_loss_bwd: coef must be a contiguous CUDA float32 (%d,) tensor' % N)
-    handle().call('pcnn_varcoef_pi_loss_bwd', c_int(N), c_int(H), c_int(W), _p(pred), _p(rho), _p(rhs), _p(dx), _p(coef), _p(dpred))
+    if mask == 0:
+        handle().call('pcnn_varcoef_pi_loss_bwd', c_int(N), c_int(H), c_int(W), _p(pred), _p(rho), _p(rhs), _p(dx), _p(coef), _p(dpred))
+    else:
+        handle().call('pcnn_varcoef_bc_pi_loss_bwd', c_int(N), c_int(H), c_int(W), _p(pred), _p(rho), _p(rhs), _p(dx), _p(coef), _p(dpred), c_int(mask))
     return dpred
 
 
@@ -1124,23 +1146,33 @@ def varcoef_jacobi_k_max():
     return int(_lib.load().pcnn_varcoef_jacobi_max_sweeps())
 
 
-def varcoef_jacobi(u, rho, rhs, dx, n_sweeps):
-    """n_sweeps Jacobi sweeps of L_rho u = rhs: u' = (sum of beta_face * neighbour - dx^2 rhs) / (sum of beta_face) on interior nodes, the ring frozen."""
+def varcoef_jacobi(u, rho, rhs, dx, n_sweeps, neumann_mask=0):
+    """n_sweeps Jacobi sweeps of L_rho u = rhs: u' = (sum of beta_face * neighbour - dx^2 rhs) / (sum of beta_face) on interior nodes, the ring frozen.
+    neumann_mask non-zero: the sweeps move the unknowns of that mask - a Neumann edge's nodes too, their inward face counted twice - and keep the
+    Dirichlet nodes frozen (pcnn_varcoef_bc_jacobi_fwd)."""
     N, H, W, (u, rho, rhs), dx = _varcoef_fields('varcoef_jacobi', {'u': u, 'rho': rho, 'rhs': rhs}, dx)
+    mask = _varcoef_mask('varcoef_jacobi', neumann_mask)
     if int(n_sweeps) < 1:
         raise ValueError('varcoef_jacobi: n_sweeps must be at least 1, got %r' % (n_sweeps,))
     out = torch.empty_like(u)
-    handle().call('pcnn_varcoef_jacobi_fwd', c_int(N), c_int(H), c_int(W), _p(rho), _p(u), _p(rhs), _p(dx), c_int(int(n_sweeps)), _p(out))
+    if mask == 0:
+        handle().call('pcnn_varcoef_jacobi_fwd', c_int(N), c_int(H), c_int(W), _p(rho), _p(u), _p(rhs), _p(dx), c_int(int(n_sweeps)), _p(out))
+    else:
+        handle().call('pcnn_varcoef_bc_jacobi_fwd', c_int(N), c_int(H), c_int(W), _p(rho), _p(u), _p(rhs), _p(dx), c_int(int(n_sweeps)), _p(out), c_int(mask))
     return out
 
 
-def varcoef_jacobi_bwd(dout, rho, dx, n_sweeps):
+def varcoef_jacobi_bwd(dout, rho, dx, n_sweeps, neumann_mask=0):
     """The adjoint of varcoef_jacobi w.r.t. u (rho and rhs are data)."""
     N, H, W, (dout, rho), dx = _varcoef_fields('varcoef_jacobi_bwd', {'dout': dout, 'rho': rho}, dx)
+    mask = _varcoef_mask('varcoef_jacobi_bwd', neumann_mask)
     if int(n_sweeps) < 1:
         raise ValueError('varcoef_jacobi_bwd: n_sweeps must be at least 1, got %r' % (n_sweeps,))
     du = torch.empty_like(dout)
-    handle().call('pcnn_varcoef_jacobi_bwd', c_int(N), c_int(H), c_int(W), _p(rho), _p(dx), _p(dout), c_int(int(n_sweeps)), _p(du))
+    if mask == 0:
+        handle().call('pcnn_varcoef_jacobi_bwd', c_int(N), c_int(H), c_int(W), _p(rho), _p(dx), _p(dout), c_int(int(n_sweeps)), _p(du))
+    else:
+        handle().call('pcnn_varcoef_bc_jacobi_bwd', c_int(N), c_int(H), c_int(W), _p(rho), _p(dx), _p(dout), c_int(int(n_sweeps)), _p(du), c_int(mask))
     return du
 
 

@@ -332,10 +332,23 @@ def main(argv=None):
         raise ValueError("--dataset_type variable_density trains the homogeneous model: it needs boundaries 'zero' in the dataset section (got %r; with "
                          "'random' the generator yields the four edge arrays as further inputs, which no model here reads) - drop the key or set it to "
                          "'zero'" % (config['dataset']['boundaries'],))
-    if args.dataset_type == 'variable_density' and any(neumann_flags(config.get('dataset', {}).get('boundary_types'))):
+    model_bt = msec.get('boundary_types') if density_model else None
+    if args.dataset_type == 'variable_density' and model_bt is not None:
+        # the model, its loss and the generator's ground truth share one set of edge types: the dataset section names the same ones or none
+        if not isinstance(model_bt, dict):
+            raise ValueError("the model section's boundary_types is a dict edge -> 'dirichlet' | 'neumann', got %r" % (model_bt,))
+        dsec = config.setdefault('dataset', {})
+        if dsec.get('boundary_types') is None:
+            dsec['boundary_types'] = dict(model_bt)
+        elif neumann_flags(dsec['boundary_types']) != neumann_flags(model_bt):
+            raise ValueError('--dataset_type variable_density: the model section has boundary_types %r and the dataset section %r - the ground truth '
+                             'must be solved with the edge types the model and its loss use; make the two equal or drop the dataset section\'s'
+                             % (model_bt, dsec['boundary_types']))
+    elif args.dataset_type == 'variable_density' and any(neumann_flags(config.get('dataset', {}).get('boundary_types'))):
         raise ValueError('--dataset_type variable_density with Neumann boundary_types %r in the dataset section: the solver and the generator take '
                          'per-edge Neumann boundaries, but the model does not - Homogeneous_Poisson_NN_Legacy(density_input=True) has no Neumann bc_type and '
-                         'its flux-form loss and smoother keep every edge fixed; drop boundary_types' % (config['dataset']['boundary_types'],))
+                         'its flux-form loss and smoother keep every edge fixed; drop boundary_types, or give the model section the same '
+                         '"boundary_types" (the keyword of the variable-density model, loss and smoother)' % (config['dataset']['boundary_types'],))
     if density_model and args.dataset_type != 'variable_density':
         raise ValueError('a model with "density_input": true reads the stack [rhs, rho], which only --dataset_type variable_density yields (got '
                          '--dataset_type %s): pass --dataset_type variable_density or drop density_input from the model section' % args.dataset_type)
@@ -401,7 +414,10 @@ def main(argv=None):
             dataset = reverse_poisson_dataset_generator(**dcfg)
         model = Homogeneous_Poisson_NN_Legacy(**config['model'])
     optimizer = choose_optimizer(config['training']['optimizer'])(**config['training']['optimizer_parameters'])
-    loss = (variable_density_loss_wrapper if density_model else loss_wrapper)(global_batch_size=gbs, **config['training']['loss_parameters'])
+    if density_model:                                # the flux-form loss with the model's edge types (None: all Dirichlet)
+        loss = variable_density_loss_wrapper(global_batch_size=gbs, **dict(config['training']['loss_parameters'], boundary_types=model_bt))
+    else:
+        loss = loss_wrapper(global_batch_size=gbs, **config['training']['loss_parameters'])
     # the largest batch this run will see, for model.presize(): only where the generator draws its grid shape from a range (the analytic generators)
     rng_ = config['dataset'].get('random_output_shape_range')
     presize = None

@@ -18,6 +18,11 @@ Traffic model (B per grid point; T x U the tile, halo reads counted, 4-byte fiel
   adjoint, per launch of k: dout on (64+2k)^2, rho on (64+2k+2)^2, one write                     sibling: the same without rho
 
     python tools/bench_varcoef_train.py [--calls 20] [--repeats 7] [--warmup 3] [--out profiles/varcoef_train_bench.json (the default)]
+
+--neumann-mask 0,5,15 measures something else with the same cases and protocol, and writes no JSON: the four kernels through
+the all-Dirichlet entry points (mask 0) and, alternating with them, through the pcnn_varcoef_bc_* entry points for every non-zero mask of the
+list; one line per case with each route's median, minimum and maximum per-call time and the ratio of the medians to mask 0.  `--neumann-mask 0` times
+the old entry points alone (with PCNN_LIBRARY naming another build of the library: the same figures for that build).
 """
 import argparse
 import json
@@ -62,7 +67,13 @@ def main():
     ap.add_argument('--repeats', type=int, default=7)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'varcoef_train_bench.json'))
+    ap.add_argument('--neumann-mask', default=None, help='comma list of masks 0..15: time the kernels per mask instead of beside their siblings')
     args = ap.parse_args()
+    masks = None
+    if args.neumann_mask is not None:
+        masks = sorted({int(m) for m in args.neumann_mask.split(',')})
+        if not masks or masks[0] < 0 or masks[-1] > 15:
+            raise SystemExit('--neumann-mask takes masks in 0..15, got %r' % args.neumann_mask)
     from ctypes import c_int
     import torch
     from poisson_cnn_amd import ops
@@ -100,6 +111,40 @@ def main():
             pairs.append(('jacobi_bwd', n,
                           lambda n=n: h.call('pcnn_varcoef_jacobi_bwd', *dims, p(rho), p(dx), p(gr), c_int(n), p(out)),
                           lambda n=n, rows=rows: h.call('pcnn_jacobi_fused_bwd', *dims, c_int(3), c_int(3), p(rows), p(gr), c_int(n), p(out))))
+        if masks is not None:
+            bc = lambda m: c_int(m)
+            for kind, n, mine, _ in pairs:
+                routes = [('mask 0', mine)]
+                for m in (m for m in masks if m):
+                    if kind == 'pi_partials':
+                        fn = lambda m=m: h.call('pcnn_varcoef_bc_pi_loss_partials', *dims, p(u), p(rho), p(rhs), p(dx), p(sums), bc(m))
+                    elif kind == 'pi_bwd':
+                        fn = lambda m=m: h.call('pcnn_varcoef_bc_pi_loss_bwd', *dims, p(u), p(rho), p(rhs), p(dx), p(coef), p(dpred), bc(m))
+                    elif kind == 'jacobi_fwd':
+                        fn = lambda m=m, n=n: h.call('pcnn_varcoef_bc_jacobi_fwd', *dims, p(rho), p(u), p(rhs), p(dx), c_int(n), p(out), bc(m))
+                    else:
+                        fn = lambda m=m, n=n: h.call('pcnn_varcoef_bc_jacobi_bwd', *dims, p(rho), p(dx), p(gr), c_int(n), p(out), bc(m))
+                    routes.append(('mask %d' % m, fn))
+                for _, fn in routes:
+                    for _ in range(args.warmup):
+                        fn()
+                torch.cuda.synchronize()
+                times = [[] for _ in routes]
+                for _ in range(args.repeats):
+                    for i, (_, fn) in enumerate(routes):
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        for _ in range(args.calls):
+                            fn()
+                        e1.record()
+                        e1.synchronize()
+                        times[i].append(e0.elapsed_time(e1) / args.calls)
+                times = [sorted(t) for t in times]
+                base = times[0][len(times[0]) // 2]
+                print('%-11s %4dx%4dx%4d n=%d: ' % (kind, N, S, S, n) + ' | '.join('%s %.4f ms (min %.4f, max %.4f)%s' % (
+                    name, t[len(t) // 2], t[0], t[-1], '' if i == 0 else ' x%.3f' % (t[len(t) // 2] / base)) for i, ((name, _), t) in enumerate(zip(routes, times))),
+                    flush=True)
+            continue
         for kind, n, mine, sibling in pairs:
             routes = [('varcoef', mine), ('sibling', sibling)]
             for _, fn in routes:
@@ -129,7 +174,7 @@ def main():
             print('%-11s %4dx%4dx%4d n=%d: ' % (kind, N, S, S, n) + ' | '.join('%s %.3f ms (%.1f B/px, %.0f GB/s = %.2f of copy, spread %.1f%%)' % (
                 r['route'], r['median_ms'], r['model_bytes_per_px'], r['model_GBps'], r['of_copy_rate'], 100 * r['spread']) for r in case['routes'])
                 + ' | ratio %.2f' % case['varcoef_over_sibling'], flush=True)
-    if args.out:
+    if args.out and masks is None:
         with open(args.out, 'w') as f:
             json.dump(res, f, indent=1)
     print(json.dumps({'varcoef_train_bench': 'done', 'cases': len(res['cases'])}))
