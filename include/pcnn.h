@@ -759,6 +759,15 @@ int pcnn_assemble_density_input(pcnn_handle h, int N, int H, int W, const float*
 int pcnn_varcoef_error_stats(pcnn_handle h, int N, int H, int W, const float* pred, const float* target /* may be NULL */,
                              const float* rho /* required with rhs */, const float* rhs /* may be NULL */,
                              const float* dx /* N; required with rhs */, float* out /* N x 8 */);
+/* pcnn_varcoef_error_stats with per-edge Neumann boundaries (neumann_mask 0..15, bits as above).  Entries 0..4 are the same.
+ * The residual's domain is the unknowns of the mask - the interior plus the nodes of every Neumann edge, a Dirichlet edge wins a corner - and r
+ * there is the same fp32 flux-form residual with the neighbour beyond a Neumann edge read at its mirrored index, for pred and rho alike (du/dn = 0,
+ * the inward face counts twice: the r of pcnn_varcoef_bc_pi_loss_partials); beyond a Dirichlet edge pred's own edge value is the neighbour.
+ * out[8n+5] = sum w r^2 and out[8n+7] = sum w f^2 with w = 1/2 per Neumann edge the unknown lies on; out[8n+6] = max|r|, unweighted.  Mask 0
+ * gives the bits of pcnn_varcoef_error_stats.  The same NULL rules, launches and fixed orders. */
+int pcnn_varcoef_bc_error_stats(pcnn_handle h, int N, int H, int W, int neumann_mask, const float* pred, const float* target /* may be NULL */,
+                                const float* rho /* required with rhs */, const float* rhs /* may be NULL */,
+                                const float* dx /* N; required with rhs */, float* out /* N x 8 */);
 
 /* tf.keras.layers.LayerNormalization() over the last axis of an (N, F) matrix (epsilon 1e-3 in Keras): the optional final layer of the
  * metalearning hyper-networks (layers/metalearning_conv.py:128-129).  fwd also returns the per-row mean and 1/sqrt(var + eps) for bwd. */

@@ -690,7 +690,7 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
                  bottleneck_deconv_config=None, bottleneck_multilinear_config=None, input_normalization=None, output_scaling=None,
                  use_batchnorm=False, postsmoother_iterations=5, use_scaling=False, use_positional_embeddings=True, scaling_config=None,
                  gradient_accumulation_steps=None, bc_type='dirichlet', device=None, seed=0, batchnorm_training=False, smoother_boundaries='frozen',
-                 density_input=False, boundary_types=None):
+                 density_input=False, boundary_types=None, residual_metrics=False):
         """bc_type: 'dirichlet' or 'neumann' for all four edges (the reference), or - an extension - a dict 'left' | 'right' | 'bottom' | 'top' ->
         'dirichlet' | 'neumann' with the dataset's edge names (left: y = 0, right: y = H-1, bottom: x = 0, top: x = W-1 of the (N,1,H,W) output; a missing
         edge is Dirichlet, at a corner a Dirichlet edge wins).  A Neumann edge is enforced as the reference's SYMMETRIC ring does, to first order:
@@ -710,7 +710,13 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
         smoother's starting value there; the post-smoother is layers.VariableDensityJacobiLayer(boundary_types=...), whose sweeps then move the
         Neumann edges' nodes by that closure.  Compile losses.variable_density_loss_wrapper with the same boundary_types.  All four edges Neumann
         is allowed and the model removes no mean: the residual term is blind to constants, the supervised terms (MAE, MSE, integral) pin the
-        mean to the target's - the generator's solutions have zero w-mean."""
+        mean to the target's - the generator's solutions have zero w-mean.
+        residual_metrics (density_input=True only; default False: nothing above changes): True fills the residual columns
+        of the statistics with the flux-form figures of ops.varcoef_error_stats(neumann_mask=the model's) - sum w r^2, max|r|, sum w f^2 over the
+        unknowns, du/dn = 0 on a Neumann edge - so test_step, evaluate, predict(return_stats=True) and fit(validation_data=...) report
+        rel_residual = mean of sqrt(sum w r^2 / sum w f^2), the prediction_relative_residual of solve(), and callbacks can monitor
+        val_rel_residual; solve(return_info=True) then returns prediction_max_residual with Neumann edges too.  It adds no variable: a
+        checkpoint holds no trace of it."""
         if data_format not in ('channels_first', 'channels_last'):
             raise ValueError('data_format must be channels_first or channels_last')
         if pre_bottleneck_convolutions_config is None:
@@ -736,6 +742,10 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
                 raise ValueError("boundary_types is None or a dict edge -> 'dirichlet' | 'neumann', got %r" % (boundary_types,))
             flags = neumann_flags(boundary_types)                 # refuses an unknown edge name or type
         self.boundary_types = None if boundary_types is None else {e: 'neumann' if f else 'dirichlet' for e, f in zip(BC_EDGES, flags)}
+        if residual_metrics and not self.density_input:
+            raise ValueError('residual_metrics=True reports the flux-form residual of the variable-density model and needs density_input=True; the '
+                             'constant-coefficient model always reports its 3 x 3 residual')
+        self.residual_metrics = bool(residual_metrics)
         if self.density_input and data_format != 'channels_first':
             raise NotImplementedError('density_input=True: the two-channel stack is channels_first (N,2,H,W) only')
         self._init_device(device, _CPU_NOTE_RAISES)
@@ -950,8 +960,14 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
         return _dx_column(dx)
 
     def _error_stats(self, pred, y_true, rhs, dx):
-        """density_input: `rhs` is the [rhs, rho] stack and the residual columns of ops.error_stats are the constant-coefficient residual - they stay 0."""
-        return _ModelBase._error_stats(pred, y_true, None if self.density_input else rhs, dx)
+        """density_input: `rhs` is the [rhs, rho] stack and the residual columns of ops.error_stats are the constant-coefficient residual - they stay 0,
+        unless residual_metrics asks for the flux-form ones (ops.varcoef_error_stats with the model's mask)."""
+        if not self.residual_metrics:
+            return _ModelBase._error_stats(pred, y_true, None if self.density_input else rhs, dx)
+        N, _, H, W = pred.shape
+        if H < 3 or W < 3:
+            return ops.varcoef_error_stats(pred, None, y_true), (H, W)
+        return ops.varcoef_error_stats(pred, rhs[:, 1].contiguous(), y_true, rhs[:, 0].contiguous(), _dx_column(dx), neumann_mask=self.neumann_mask), (H, W)
 
     def solve(self, inputs, tol=1e-10, max_iterations=500, check_every=8, warm_start=True, compare_cold=False, return_info=False):
         """The variable-density problem solved to `tol`, the conjugate-gradient iteration started from this model's prediction (DESIGN.md section
@@ -966,7 +982,8 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
         A model with boundary_types solves with those edge types and du/dn = 0 on the Neumann edges:
         variable_density_poisson_solve(boundary_types=..., zero data); prediction_relative_residual is then sqrt(sum w r^2 / sum w f^2) over the
         unknowns, r from ops.varcoef_pi_loss_partials with the mask - the ||b - A x0||_W / ||b||_W the solver starts from (all four edges Neumann:
-        before its projection of b) - and prediction_max_residual is None: the statistics kernel has no Neumann variant.
+        before its projection of b) - and prediction_max_residual is None unless the model was built with residual_metrics=True: then it is the
+        max|r| column of ops.varcoef_error_stats(neumann_mask=...), the same r.
         How many iterations a prediction saves is measured (tools/bench_varcoef_warmstart.py), not promised.  Nothing in the model changes: no
         BatchNormalization update, no gradient, no optimizer state."""
         if not self.density_input:
@@ -985,6 +1002,7 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
             wi, wj = torch.ones(H, device=self.device), torch.ones(W, device=self.device)        # w on all nodes, 0 on the Dirichlet ones
             wi[0], wi[-1], wj[0], wj[-1] = 0.5 * (mask & 1), 0.5 * (mask >> 1 & 1), 0.5 * (mask >> 2 & 1), 0.5 * (mask >> 3 & 1)
             ff = (torch.outer(wi, wj).double() * rhs.double() ** 2).sum(dim=(1, 2))
+            rmax = ops.varcoef_error_stats(pred.to(torch.float32), rho, None, rhs, d, neumann_mask=mask)[:, 6] if self.residual_metrics else None
         else:
             stats = ops.varcoef_error_stats(pred.to(torch.float32), rho, None, rhs, d)
         zero = {k: torch.zeros((N, W if k in ('left', 'right') else H), dtype=torch.float32, device=self.device) for k in ('left', 'right', 'bottom', 'top')}
@@ -997,11 +1015,13 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
         if mask:
             s = np.zeros((N, 8))
             s[:, 5], s[:, 7] = rr.cpu().numpy().astype(np.float64), ff.cpu().numpy()
+            if rmax is not None:
+                s[:, 6] = rmax.cpu().numpy().astype(np.float64)
         else:
             s = stats.cpu().numpy().astype(np.float64)
         with np.errstate(divide='ignore', invalid='ignore'):
             info['prediction_relative_residual'] = np.where(s[:, 7] > 0, np.sqrt(s[:, 5] / np.where(s[:, 7] > 0, s[:, 7], 1.0)), np.nan)
-        info['prediction_max_residual'] = None if mask else s[:, 6]
+        info['prediction_max_residual'] = s[:, 6] if (not mask or self.residual_metrics) else None
         if compare_cold:
             info['cold_iterations'] = info['iterations'] if not warm_start else D.variable_density_poisson_solve(rho, rhs, zero, d, **kw)[1]['iterations']
         return soln, info

@@ -1225,13 +1225,21 @@ def error_stats(pred, target=None, rhs=None, dx=None):
     return _error_stats('error_stats', launch, pred, target, rhs, dx, 2, '%(who)s: dx must be (N, 2), one spacing per axis')
 
 
-def varcoef_error_stats(pred, rho, target=None, rhs=None, dx=None):
+def varcoef_error_stats(pred, rho, target=None, rhs=None, dx=None, neumann_mask=0):
     """error_stats for the variable-density problem (pcnn_varcoef_error_stats; columns: ERROR_STATS; the same three layouts of a one-channel
     field).  r = the flux-form operator div((1/rho) grad .) of DESIGN.md section 16 applied to pred - its own edge values are the Dirichlet
     neighbours - minus rhs, over the interior; dx: one spacing per sample, (N,) or (N,1).  With zero edge values, and only then,
     sqrt(sum_r2 / sum_f2) is the relative residual ||b - A x|| / ||b|| variable_density_poisson_solve would start from.  Without `target` the
-    first five columns are 0; without `rhs` the last three, and rho and dx are not read."""
+    first five columns are 0; without `rhs` the last three, and rho and dx are not read.
+    neumann_mask (an int, bits as bc_ring_fwd's, or four flags) non-zero: pcnn_varcoef_bc_error_stats - r over the unknowns
+    of that mask, a Neumann edge's nodes included with the du/dn = 0 closure of varcoef_pi_loss_partials, and the columns sum_r2 / sum_f2 hold
+    sum w r^2 / sum w f^2, w = 1/2 per Neumann edge a node lies on; max_abs_r is unweighted.  0: today's entry point."""
+    mask = _varcoef_mask('varcoef_error_stats', neumann_mask)
+
     def launch(N, H, W, f, dx, out):
+        if mask:
+            handle().call('pcnn_varcoef_bc_error_stats', N, H, W, c_int(mask), _p(f['pred']), _p(f['target']), _p(f['rho']), _p(f['rhs']), _p(dx), _p(out))
+            return
         handle().call('pcnn_varcoef_error_stats', N, H, W, _p(f['pred']), _p(f['target']), _p(f['rho']), _p(f['rhs']), _p(dx), _p(out))
     return _error_stats('varcoef_error_stats', launch, pred, target, rhs, dx, 1,
                         '%(who)s: dx must hold one spacing per sample (%(N)d values), got shape %(shape)s', rho, rhs_needs_rho=True)
