@@ -710,6 +710,35 @@ int pcnn_varcoef_bc_pcg_finish(pcnn_handle h, int N, int H, int W, int neumann_m
                                const float* bottom, const float* top, float* soln);
 /* g[i] = lo + (hi - lo) min(|g[i]|, 1): a density field from a smooth function scaled to max|g| = 1 (the reference takes 1e-7 + |g|) */
 int pcnn_varcoef_density(pcnn_handle h, int64_t total, float lo, float hi, float* g);
+/* The smooth profile: g (N x per) -> lo + (hi - lo) (g - min g) / (max g - min g), minimum and maximum per sample by a fixed-order block reduction
+ * (two launches, no atomics); a constant sample gives lo.  No kink where g changes sign: the densities the scaled preconditioner below is for. */
+int pcnn_varcoef_density_smooth(pcnn_handle h, int N, int64_t per, float lo, float hi, float* g);
+/* The solves above with the diagonally scaled preconditioner z = s o M^-1 (s o r) (Concus and Golub): M the constant-coefficient
+ * operator of the plain entry points, s = d^-1/2 in fp64, d = diag(A) / diag(M) - the mean of the node's four face coefficients, the inward one twice
+ * on a Neumann edge node.  For smooth rho the iteration count then depends on the derivatives of log rho, not on max rho / min rho; for a rho with
+ * kinks or jumps it is no better than the plain preconditioner and can be worse: opt-in.  rho = constant gives s = constant, the plain iterates.
+ * Arguments, scal, flags and every guarantee are those of the entry points without the suffix: fixed-order reductions, no atomics, results
+ * independent of the batch, a flagged sample frozen bit for bit, no dependence on what the workspace held, min rho in scal[n][5].  The workspace
+ * holds one more field (s, built by setup): size it with the *_workspace_scaled query.  The same launches per iteration: s o r is written by the
+ * pass that updates r, s o z formed by the pass that updates p, and r.z still comes from the division pass.  x and the partial sums lie where the
+ * plain layout has them: finish with pcnn_varcoef_pcg_finish / pcnn_varcoef_bc_pcg_finish. */
+size_t pcnn_varcoef_pcg_workspace_scaled(int N, int H, int W);
+int pcnn_varcoef_pcg_setup_scaled(pcnn_handle h, int N, int H, int W, const float* rho, const float* rhs, const float* left, const float* right,
+                                  const float* bottom, const float* top, const float* dx, const double* x0, double tol, const double* S_h,
+                                  const double* lam_h, const double* S_w, const double* lam_w, void* workspace, size_t workspace_bytes, double* scal,
+                                  int* flags);
+int pcnn_varcoef_pcg_iterate_scaled(pcnn_handle h, int N, int H, int W, const float* rho, const float* dx, double tol, int first_iteration,
+                                    int iterations, const double* S_h, const double* lam_h, const double* S_w, const double* lam_w, void* workspace,
+                                    size_t workspace_bytes, double* scal, int* flags);
+size_t pcnn_varcoef_bc_pcg_workspace_scaled(int N, int H, int W, int neumann_mask);
+int pcnn_varcoef_bc_pcg_setup_scaled(pcnn_handle h, int N, int H, int W, int neumann_mask, const float* rho, const float* rhs, const float* left,
+                                     const float* right, const float* bottom, const float* top, const float* dx, const double* x0, double tol,
+                                     const double* Vinv_h, const double* V_h, const double* lam_h, const double* VinvT_w, const double* VT_w,
+                                     const double* lam_w, void* workspace, size_t workspace_bytes, double* scal, int* flags);
+int pcnn_varcoef_bc_pcg_iterate_scaled(pcnn_handle h, int N, int H, int W, int neumann_mask, const float* rho, const float* dx, double tol,
+                                       int first_iteration, int iterations, const double* Vinv_h, const double* V_h, const double* lam_h,
+                                       const double* VinvT_w, const double* VT_w, const double* lam_w, void* workspace, size_t workspace_bytes,
+                                       double* scal, int* flags);
 
 /* ---- training on the variable-density problem (csrc/varcoef_train.hip) ------------------- */
 /* fp32 on one-channel (N,H,W) fields, dx (N) one spacing per sample, rho (N,H,W) read on every node; the discretisation above:

@@ -19,6 +19,10 @@
 // 32 B with two fp64 face arrays built once per solve (p 8, faces 16, q 8).
 // The face coefficient, the 16 x 64 tile and the LDS node loader are flux_form.h's, shared with varcoef_train.hip and error_stats.hip; the fp64
 // operator sum (stencil_at) is this file's alone: its order ((a + b) + c) + d of pc - neighbour is not the fp32 residual's.
+// The *_scaled entry points (SC = true) precondition with s o M^-1 (s o r), s = d^-1/2 and d = diag(A) / diag(M) the mean of the
+// node's four face coefficients (the inward one twice on a Neumann edge, as in A and in M): one more fp64 field s behind the partial sums, built by the
+// setup launch; s o r goes to z - the buffer the transform then reads - from the pass that updates r, and p = s o z + beta p.  The SC = false
+// instantiations are the code of the plain entry points, unchanged.
 #include <math.h>
 #include <type_traits>
 #include "flux_form.h"
@@ -42,13 +46,17 @@ static inline int vc_cap(int mh, int mw) {
   return t > e ? t : e;
 }
 // workspace: x, r, p, q, z (N x mh x mw doubles each; q and z double as the two GEMM intermediates) and three partial-sum arrays of N x cap
-struct VcWs { double *x, *r, *p, *q, *z, *part; int cap; };
-static inline size_t vc_bytes(int N, int mh, int mw) { return (5 * (size_t)N * mh * mw + 3 * (size_t)N * vc_cap(mh, mw)) * sizeof(double); }
+// scaled: the field s follows the partial sums, so x and part sit where the shared finish looks for them
+struct VcWs { double *x, *r, *p, *q, *z, *part, *s; int cap; };
+static inline size_t vc_bytes(int N, int mh, int mw, bool scaled = false) {
+  return ((scaled ? 6 : 5) * (size_t)N * mh * mw + 3 * (size_t)N * vc_cap(mh, mw)) * sizeof(double);
+}
 static inline VcWs vc_layout(void* ws, int N, int mh, int mw) {
   VcWs l;
   const size_t v = (size_t)N * mh * mw;
   l.cap = vc_cap(mh, mw);
   l.x = static_cast<double*>(ws); l.r = l.x + v; l.p = l.r + v; l.q = l.p + v; l.z = l.q + v; l.part = l.z + v;
+  l.s = l.part + 3 * (size_t)N * l.cap;          // (only the scaled workspace reaches that far)
   return l;
 }
 
@@ -162,13 +170,15 @@ __global__ __launch_bounds__(FLUX_THREADS) void varcoef_apply_kernel(int H, int 
 // tile's shares of b.b and r.r and its minimum of rho.  left/right (N,W): values on rows 0 / H-1; bottom/top (N,H): values on columns 0 / W-1 - or,
 // on a Neumann edge (BC), du/dn there: such a node's b gains 2 g / (rho_c dx) per Neumann edge it lies on, and the sums are weighted.
 // mask 15 (b_out != NULL): b is kept in b_out for the projection pass, and the second partial is the tile's share of sum w b - r.r is summed there.
-template <bool BC>
+// SC: s = (mean of the four face coefficients)^-1/2 -> s_out and s o r -> t_out (mask 15: the projection pass writes it, from the projected r).
+template <bool BC, bool SC>
 __global__ __launch_bounds__(FLUX_THREADS) void varcoef_setup_kernel(int H, int W, int cap, int N, int mask, const float* __restrict__ rho,
                                                                      const float* __restrict__ f, const float* __restrict__ left,
                                                                      const float* __restrict__ right, const float* __restrict__ bottom,
                                                                      const float* __restrict__ top, const float* __restrict__ dx,
                                                                      const double* __restrict__ x0, double* __restrict__ x, double* __restrict__ rr_out,
-                                                                     double* __restrict__ b_out, double* __restrict__ part) {
+                                                                     double* __restrict__ b_out, double* __restrict__ part, double* __restrict__ s_out,
+                                                                     double* __restrict__ t_out) {
   __shared__ float rs[VT_LR][VT_LC];
   __shared__ double ps[VT_LR][VT_LC];
   __shared__ double red[FLUX_THREADS];
@@ -212,6 +222,11 @@ __global__ __launch_bounds__(FLUX_THREADS) void varcoef_setup_kernel(int H, int 
         const int64_t o = (int64_t)n * per + (int64_t)ii * nw + jj;
         x[o] = ps[r + 1][c + 1];
         rr_out[o] = res;
+        if (SC) {
+          const double sc = 1.0 / sqrt(0.25 * (((fc.lo_i + fc.hi_i) + fc.lo_j) + fc.hi_j));
+          s_out[o] = sc;
+          if (!b_out) t_out[o] = sc * res;
+        }
         if (BC) {
           const double w = vc_weight(ii, jj, nh, nw, mask);
           sbb += w * (b * b);
@@ -244,8 +259,11 @@ __global__ __launch_bounds__(FLUX_THREADS) void varcoef_setup_kernel(int H, int 
 
 // mask 15, after the setup kernel: b and r lose m = sum w b / sum w (the compatibility projection: W A has the constants as null space, so a
 // solvable b has sum w b = 0); the block's shares of sum w b^2 and sum w r^2 of the projected fields.  grid (blocks per sample, N)
+// SC: t = s o (the projected r)
+template <bool SC>
 __global__ __launch_bounds__(EW_THREADS) void varcoef_project_kernel(int mh, int mw, int cap, int N, double sum_w, const double* __restrict__ scal,
-                                                                     const double* __restrict__ b, double* __restrict__ r, double* __restrict__ part) {
+                                                                     const double* __restrict__ b, double* __restrict__ r, double* __restrict__ part,
+                                                                     const double* __restrict__ s, double* __restrict__ t) {
   __shared__ double red[EW_THREADS];
   const int n = blockIdx.y;
   const int64_t per = (int64_t)mh * mw, base = (int64_t)n * per;
@@ -255,6 +273,7 @@ __global__ __launch_bounds__(EW_THREADS) void varcoef_project_kernel(int mh, int
   for (int64_t k = (int64_t)blockIdx.x * EW_THREADS + threadIdx.x; k < per; k += (int64_t)gridDim.x * EW_THREADS, at.next()) {
     const double w = vc_weight(at.ii, at.jj, mh, mw, 15), bp = b[base + k] - m, rp = r[base + k] - m;
     r[base + k] = rp;
+    if (SC) t[base + k] = s[base + k] * rp;
     sbb += w * (bp * bp);
     srr += w * (rp * rp);
   }
@@ -306,17 +325,20 @@ __global__ __launch_bounds__(EW_THREADS) void varcoef_reduce_kernel(int count, i
 // x += alpha p, r -= alpha q with alpha = (r.z) / (p.q) from the sample's scalars; the block's share of the new r.r.  alpha = 0 for a flagged
 // sample: x and r are then neither changed nor written and p and q are not read, so nothing they hold can reach x.  grid (blocks per sample, N)
 // BC: the share of sum w r^2 over the mh x mw unknowns (per = mh mw), in the same order: for mask 0 the same bits.
-template <bool BC>
+// SC: t = s o r, what the transform reads next, from the r this pass holds in a register.  It is written for a flagged sample too (t shares z's
+// memory, which the back-transform has overwritten since): from r and s alone, and a flagged sample's alpha = 0 keeps it away from x.
+template <bool BC, bool SC>
 __global__ __launch_bounds__(EW_THREADS) void varcoef_update_xr_kernel(int64_t per, int mh, int mw, int mask, int cap, int cur, const double* __restrict__ scal,
                                                                        const int* __restrict__ flags,
                                                                        const double* __restrict__ p, const double* __restrict__ q, double* __restrict__ x,
-                                                                       double* __restrict__ r, double* __restrict__ part) {
+                                                                       double* __restrict__ r, double* __restrict__ part, const double* __restrict__ s,
+                                                                       double* __restrict__ t) {
   __shared__ double red[EW_THREADS];
   const int n = blockIdx.y;
   const double pq = scal[n * VS_STRIDE + VS_PQ], rz = scal[n * VS_STRIDE + VS_RZ0 + cur];
   const double alpha = (flags[n] || !(pq > 0.0)) ? 0.0 : rz / pq;
   const int64_t base = (int64_t)n * per;
-  double s = 0.0;
+  double sum = 0.0;
   VcWalk at(BC ? mw : 1);
   for (int64_t k = (int64_t)blockIdx.x * EW_THREADS + threadIdx.x; k < per; k += (int64_t)gridDim.x * EW_THREADS) {
     double rn = r[base + k];
@@ -325,14 +347,15 @@ __global__ __launch_bounds__(EW_THREADS) void varcoef_update_xr_kernel(int64_t p
       rn -= alpha * q[base + k];
       r[base + k] = rn;
     }
+    if (SC) t[base + k] = s[base + k] * rn;
     if (BC) {
-      s += vc_weight(at.ii, at.jj, mh, mw, mask) * (rn * rn);
+      sum += vc_weight(at.ii, at.jj, mh, mw, mask) * (rn * rn);
       at.next();
     } else {
-      s += rn * rn;
+      sum += rn * rn;
     }
   }
-  const double tot = block_sum<EW_THREADS>(s, red);
+  const double tot = block_sum<EW_THREADS>(sum, red);
   if (threadIdx.x == 0) part[(int64_t)n * cap + blockIdx.x] = tot;
 }
 
@@ -362,19 +385,64 @@ __global__ __launch_bounds__(EW_THREADS) void varcoef_divide_kernel(int nh, int 
 
 // p = z + beta p, beta = (r.z)_new / (r.z)_old from the sample's scalars; 0 for a flagged sample and for the first direction (first = 1).
 // With beta = 0 the old p is not read: before the first direction it is memory nobody has written, and 0 * NaN is NaN.
+// SC: z arrives as M^-1 (s o r) and is multiplied by s here, where it is first consumed.
+template <bool SC>
 __global__ __launch_bounds__(EW_THREADS) void varcoef_update_p_kernel(int64_t per, int cur, int first, const double* __restrict__ scal, const int* __restrict__ flags,
-                                                                      const double* __restrict__ z, double* __restrict__ p) {
+                                                                      const double* __restrict__ z, double* __restrict__ p, const double* __restrict__ s) {
   const int n = blockIdx.y;
   const double rz_old = scal[n * VS_STRIDE + VS_RZ0 + cur], rz_new = scal[n * VS_STRIDE + VS_RZ0 + (cur ^ 1)];
   const double beta = (first || flags[n] || !(rz_old > 0.0)) ? 0.0 : rz_new / rz_old;
   const int64_t base = (int64_t)n * per;
-  for (int64_t k = (int64_t)blockIdx.x * EW_THREADS + threadIdx.x; k < per; k += (int64_t)gridDim.x * EW_THREADS)
-    p[base + k] = beta != 0.0 ? z[base + k] + beta * p[base + k] : z[base + k];
+  for (int64_t k = (int64_t)blockIdx.x * EW_THREADS + threadIdx.x; k < per; k += (int64_t)gridDim.x * EW_THREADS) {
+    const double zk = SC ? s[base + k] * z[base + k] : z[base + k];
+    p[base + k] = beta != 0.0 ? zk + beta * p[base + k] : zk;
+  }
 }
 
 // g -> lo + (hi - lo) |g|: a density field from a smooth function already scaled to max|g| = 1
 __global__ void varcoef_density_kernel(int64_t total, float lo, float hi, float* __restrict__ g) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) g[i] = lo + (hi - lo) * fminf(fabsf(g[i]), 1.f);
+}
+
+// The smooth profile, g -> lo + (hi - lo) (g - min g) / (max g - min g) per sample, in two launches of grid (blocks per sample, N).
+// First the block's minimum and maximum of g[n] by the fixed tree -> mm[n][block][0 / 1] ...
+constexpr int DS_MAX_BLOCKS = EW_THREADS;          // at most one partial per thread of the second launch
+struct vc_fmin_op { __device__ __forceinline__ float operator()(float a, float b) const { return fminf(a, b); } };
+struct vc_fmax_op { __device__ __forceinline__ float operator()(float a, float b) const { return fmaxf(a, b); } };
+__global__ __launch_bounds__(EW_THREADS) void varcoef_density_range_kernel(int64_t per, const float* __restrict__ g, float* __restrict__ mm) {
+  __shared__ float lo_s[EW_THREADS], hi_s[EW_THREADS];
+  const int n = blockIdx.y, t = threadIdx.x;
+  const float* gn = g + (int64_t)n * per;
+  float mn = INFINITY, mx = -INFINITY;
+  for (int64_t k = (int64_t)blockIdx.x * EW_THREADS + t; k < per; k += (int64_t)gridDim.x * EW_THREADS) {
+    const float v = gn[k];
+    mn = fminf(mn, v);
+    mx = fmaxf(mx, v);
+  }
+  lo_s[t] = mn;
+  hi_s[t] = mx;
+  __syncthreads();
+  pcnn_block_reduce<float, EW_THREADS>(lo_s, t, vc_fmin_op());
+  pcnn_block_reduce<float, EW_THREADS>(hi_s, t, vc_fmax_op());
+  if (t == 0) {
+    mm[((int64_t)n * gridDim.x + blockIdx.x) * 2] = lo_s[0];
+    mm[((int64_t)n * gridDim.x + blockIdx.x) * 2 + 1] = hi_s[0];
+  }
+}
+// ... then every block reduces its sample's gridDim.x partials by the same tree (so all blocks of a sample hold the same two numbers) and maps its
+// points.  A constant g gives lo.  min and max are exact in any order; the map is clamped to [lo, hi] against the rounding of its last addition.
+__global__ __launch_bounds__(EW_THREADS) void varcoef_density_smooth_kernel(int64_t per, float lo, float hi, const float* __restrict__ mm, float* __restrict__ g) {
+  __shared__ float lo_s[EW_THREADS], hi_s[EW_THREADS];
+  const int n = blockIdx.y, t = threadIdx.x;
+  lo_s[t] = t < (int)gridDim.x ? mm[((int64_t)n * gridDim.x + t) * 2] : INFINITY;
+  hi_s[t] = t < (int)gridDim.x ? mm[((int64_t)n * gridDim.x + t) * 2 + 1] : -INFINITY;
+  __syncthreads();
+  pcnn_block_reduce<float, EW_THREADS>(lo_s, t, vc_fmin_op());
+  pcnn_block_reduce<float, EW_THREADS>(hi_s, t, vc_fmax_op());
+  const float mn = lo_s[0], span = hi_s[0] - mn, inv = span > 0.f ? 1.f / span : 0.f;
+  float* gn = g + (int64_t)n * per;
+  for (int64_t k = (int64_t)blockIdx.x * EW_THREADS + t; k < per; k += (int64_t)gridDim.x * EW_THREADS)
+    gn[k] = fminf(fmaxf(lo + (hi - lo) * ((gn[k] - mn) * inv), lo), hi);
 }
 
 // the six arrays of a preconditioner: per axis the eigenbasis of the constant-coefficient 1-D operator on that axis' unknowns, the second axis'
@@ -395,11 +463,13 @@ static dim3 vc_tile_grid(int N, const FdUnknowns& u) { return dim3(pcnn_cdiv(u.m
 // z = M^-1 r, M the constant-coefficient 5-point operator of the same edge types with zero data (its 1/dx^2 left out: a positive factor of M does not
 // change the iterates): z = V_h ((Vinv_h r VinvT_w) ./ (lam_h + lam_w)) VT_w as four fp64 matrix-core products; q holds the half-transformed fields.
 // r.z (BC: sum w r z) -> scal slot.
-template <bool BC>
+// SC: the transform reads t = s o r, which the pass before left in z, and z comes out as M^-1 t: with c the coefficients of t the division pass' sum
+// c^2 / (lam_h + lam_w) is (s o r).M^-1 (s o r) = r.(s o M^-1 (s o r)), the r.z of the scaled preconditioner (diag(s) commutes with the weights).
+template <bool BC, bool SC>
 static int vc_precondition(pcnn_handle h, int N, const FdUnknowns& u, const VcWs& w, const VcBasis& B, double* scal, int slot) {
   const int64_t per = (int64_t)u.mh * u.mw;
   const int eb = vc_ew_blocks(per);
-  if (int rc = pcnn_two_sided_gemm_f64(h, N, u.mh, u.mw, B.Vinv_h, w.r, B.VinvT_w, w.q, w.z)) return rc;
+  if (int rc = pcnn_two_sided_gemm_f64(h, N, u.mh, u.mw, B.Vinv_h, SC ? w.z : w.r, B.VinvT_w, w.q, w.z)) return rc;
   hipLaunchKernelGGL(varcoef_divide_kernel<BC>, dim3(eb, N), dim3(EW_THREADS), 0, h->stream, u.mh, u.mw, w.cap, B.lam_h, B.lam_w, w.z, w.part);
   hipLaunchKernelGGL(varcoef_reduce_kernel<0>, dim3(N), dim3(EW_THREADS), 0, h->stream, eb, w.cap, w.part, scal, (int)VS_STRIDE, slot, 0, 0.0, (int*)nullptr);
   PCNN_CHECK_LAUNCH(h, "pcnn_varcoef_pcg(divide)");
@@ -421,7 +491,7 @@ static int vc_apply(pcnn_handle h, const char* who, int N, int H, int W, int mas
   return 0;
 }
 
-template <bool BC>
+template <bool BC, bool SC>
 static int vc_setup(pcnn_handle h, const char* who, int N, int H, int W, int mask, const float* rho, const float* rhs, const float* left, const float* right,
                     const float* bottom, const float* top, const float* dx, const double* x0, double tol, const VcBasis& B, void* workspace,
                     size_t workspace_bytes, double* scal, int* flags) {
@@ -431,7 +501,7 @@ static int vc_setup(pcnn_handle h, const char* who, int N, int H, int W, int mas
   if (int rc = vc_check_shape(h, who, N, H, W, mask, &u)) return rc;
   PCNN_REQUIRE(h, tol > 0.0, "%s: tol must be positive", who);
   const VcWs w = vc_layout(workspace, N, u.mh, u.mw);
-  PCNN_REQUIRE(h, workspace_bytes >= vc_bytes(N, u.mh, u.mw), "%s: workspace of %zu B, %zu B needed", who, workspace_bytes, vc_bytes(N, u.mh, u.mw));
+  PCNN_REQUIRE(h, workspace_bytes >= vc_bytes(N, u.mh, u.mw, SC), "%s: workspace of %zu B, %zu B needed", who, workspace_bytes, vc_bytes(N, u.mh, u.mw, SC));
   const int tiles = vc_tiles(u.mh, u.mw);
   const int64_t per = (int64_t)u.mh * u.mw;
   const int eb = vc_ew_blocks(per);
@@ -439,14 +509,16 @@ static int vc_setup(pcnn_handle h, const char* who, int N, int H, int W, int mas
   double* part_rr = w.part + (size_t)N * w.cap;
   if (hipMemsetAsync(flags, 0, (size_t)N * sizeof(int), h->stream) != hipSuccess || hipMemsetAsync(scal, 0, (size_t)N * VS_STRIDE * sizeof(double), h->stream) != hipSuccess)
     PCNN_FAIL(h, "%s: cannot clear the per-sample state", who);
-  hipLaunchKernelGGL(varcoef_setup_kernel<BC>, vc_tile_grid(N, u), dim3(FLUX_THREADS), 0, h->stream, H, W, w.cap, N, mask, rho, rhs, left, right, bottom, top, dx, x0,
-                     w.x, w.r, singular ? w.q : (double*)nullptr, w.part);
+  double* const sc = SC ? w.s : (double*)nullptr;
+  hipLaunchKernelGGL((varcoef_setup_kernel<BC, SC>), vc_tile_grid(N, u), dim3(FLUX_THREADS), 0, h->stream, H, W, w.cap, N, mask, rho, rhs, left, right, bottom, top, dx,
+                     x0, w.x, w.r, singular ? w.q : (double*)nullptr, w.part, sc, SC ? w.z : (double*)nullptr);
   int bb_count = tiles;
   if (singular) {            // sum w b^2 and sum w b of the b as given, then the projection: b.b and r.r are the projected fields'
     const double sum_w = (double)(H - 1) * (double)(W - 1);
     hipLaunchKernelGGL(varcoef_reduce_kernel<0>, dim3(N), dim3(EW_THREADS), 0, h->stream, tiles, w.cap, w.part, scal, (int)VS_STRIDE, (int)VS_BBRAW, 0, 0.0, (int*)nullptr);
     hipLaunchKernelGGL(varcoef_reduce_kernel<0>, dim3(N), dim3(EW_THREADS), 0, h->stream, tiles, w.cap, part_rr, scal, (int)VS_STRIDE, (int)VS_WB, 0, 0.0, (int*)nullptr);
-    hipLaunchKernelGGL(varcoef_project_kernel, dim3(eb, N), dim3(EW_THREADS), 0, h->stream, u.mh, u.mw, w.cap, N, sum_w, scal, w.q, w.r, w.part);
+    hipLaunchKernelGGL(varcoef_project_kernel<SC>, dim3(eb, N), dim3(EW_THREADS), 0, h->stream, u.mh, u.mw, w.cap, N, sum_w, scal, w.q, w.r, w.part, (const double*)sc,
+                       SC ? w.z : (double*)nullptr);
     bb_count = eb;
   }
   hipLaunchKernelGGL(varcoef_reduce_kernel<0>, dim3(N), dim3(EW_THREADS), 0, h->stream, bb_count, w.cap, w.part, scal, (int)VS_STRIDE, (int)VS_BB, 0, 0.0, (int*)nullptr);
@@ -454,13 +526,13 @@ static int vc_setup(pcnn_handle h, const char* who, int N, int H, int W, int mas
   hipLaunchKernelGGL(varcoef_reduce_kernel<1>, dim3(N), dim3(EW_THREADS), 0, h->stream, tiles, w.cap, w.part + (size_t)2 * N * w.cap, scal, (int)VS_STRIDE,
                      (int)VS_RHOMIN, 0, 0.0, (int*)nullptr);
   PCNN_CHECK_LAUNCH(h, who);
-  if (int rc = vc_precondition<BC>(h, N, u, w, B, scal, VS_RZ0)) return rc;
-  hipLaunchKernelGGL(varcoef_update_p_kernel, dim3(eb, N), dim3(EW_THREADS), 0, h->stream, per, 1, 1, scal, flags, w.z, w.p);
+  if (int rc = vc_precondition<BC, SC>(h, N, u, w, B, scal, VS_RZ0)) return rc;
+  hipLaunchKernelGGL(varcoef_update_p_kernel<SC>, dim3(eb, N), dim3(EW_THREADS), 0, h->stream, per, 1, 1, scal, flags, w.z, w.p, (const double*)sc);
   PCNN_CHECK_LAUNCH(h, who);
   return 0;
 }
 
-template <bool BC>
+template <bool BC, bool SC>
 static int vc_iterate(pcnn_handle h, const char* who, int N, int H, int W, int mask, const float* rho, const float* dx, double tol, int first_iteration,
                       int iterations, const VcBasis& B, void* workspace, size_t workspace_bytes, double* scal, int* flags) {
   PCNN_REQUIRE(h, h && rho && dx && B.Vinv_h && B.V_h && B.lam_h && B.VinvT_w && B.VT_w && B.lam_w && workspace && scal && flags, "%s: null argument", who);
@@ -468,20 +540,21 @@ static int vc_iterate(pcnn_handle h, const char* who, int N, int H, int W, int m
   if (int rc = vc_check_shape(h, who, N, H, W, mask, &u)) return rc;
   PCNN_REQUIRE(h, tol > 0.0 && first_iteration >= 0 && iterations >= 1, "%s: bad tol or iteration range", who);
   const VcWs w = vc_layout(workspace, N, u.mh, u.mw);
-  PCNN_REQUIRE(h, workspace_bytes >= vc_bytes(N, u.mh, u.mw), "%s: workspace of %zu B, %zu B needed", who, workspace_bytes, vc_bytes(N, u.mh, u.mw));
+  PCNN_REQUIRE(h, workspace_bytes >= vc_bytes(N, u.mh, u.mw, SC), "%s: workspace of %zu B, %zu B needed", who, workspace_bytes, vc_bytes(N, u.mh, u.mw, SC));
   const int tiles = vc_tiles(u.mh, u.mw);
   const int64_t per = (int64_t)u.mh * u.mw;
   const int eb = vc_ew_blocks(per);
+  double* const sc = SC ? w.s : (double*)nullptr;
   for (int it = first_iteration; it < first_iteration + iterations; ++it) {
     const int cur = it & 1;                      // r.z of the current direction sits in slot VS_RZ0 + cur, the next one goes to the other slot
     hipLaunchKernelGGL(varcoef_apply_kernel<BC>, vc_tile_grid(N, u), dim3(FLUX_THREADS), 0, h->stream, H, W, w.cap, mask, rho, dx, w.p, w.q, w.part);
     hipLaunchKernelGGL(varcoef_reduce_kernel<0>, dim3(N), dim3(EW_THREADS), 0, h->stream, tiles, w.cap, w.part, scal, (int)VS_STRIDE, (int)VS_PQ, 0, 0.0, (int*)nullptr);
-    hipLaunchKernelGGL(varcoef_update_xr_kernel<BC>, dim3(eb, N), dim3(EW_THREADS), 0, h->stream, per, u.mh, u.mw, mask, w.cap, cur, scal, flags, w.p, w.q, w.x, w.r,
-                       w.part);
+    hipLaunchKernelGGL((varcoef_update_xr_kernel<BC, SC>), dim3(eb, N), dim3(EW_THREADS), 0, h->stream, per, u.mh, u.mw, mask, w.cap, cur, scal, flags, w.p, w.q, w.x,
+                       w.r, w.part, (const double*)sc, SC ? w.z : (double*)nullptr);
     hipLaunchKernelGGL(varcoef_reduce_kernel<0>, dim3(N), dim3(EW_THREADS), 0, h->stream, eb, w.cap, w.part, scal, (int)VS_STRIDE, (int)VS_RR, 1, tol * tol, flags);
     PCNN_CHECK_LAUNCH(h, who);
-    if (int rc = vc_precondition<BC>(h, N, u, w, B, scal, VS_RZ0 + (cur ^ 1))) return rc;
-    hipLaunchKernelGGL(varcoef_update_p_kernel, dim3(eb, N), dim3(EW_THREADS), 0, h->stream, per, cur, 0, scal, flags, w.z, w.p);
+    if (int rc = vc_precondition<BC, SC>(h, N, u, w, B, scal, VS_RZ0 + (cur ^ 1))) return rc;
+    hipLaunchKernelGGL(varcoef_update_p_kernel<SC>, dim3(eb, N), dim3(EW_THREADS), 0, h->stream, per, cur, 0, scal, flags, w.z, w.p, (const double*)sc);
     PCNN_CHECK_LAUNCH(h, who);
   }
   return 0;
@@ -522,14 +595,14 @@ extern "C" int pcnn_varcoef_pcg_setup(pcnn_handle h, int N, int H, int W, const 
                                       const float* bottom, const float* top, const float* dx, const double* x0, double tol, const double* S_h,
                                       const double* lam_h, const double* S_w, const double* lam_w, void* workspace, size_t workspace_bytes, double* scal,
                                       int* flags) {
-  return vc_setup<false>(h, "pcnn_varcoef_pcg_setup", N, H, W, 0, rho, rhs, left, right, bottom, top, dx, x0, tol, VcBasis{S_h, S_h, lam_h, S_w, S_w, lam_w}, workspace,
+  return vc_setup<false, false>(h, "pcnn_varcoef_pcg_setup", N, H, W, 0, rho, rhs, left, right, bottom, top, dx, x0, tol, VcBasis{S_h, S_h, lam_h, S_w, S_w, lam_w}, workspace,
                          workspace_bytes, scal, flags);
 }
 
 extern "C" int pcnn_varcoef_pcg_iterate(pcnn_handle h, int N, int H, int W, const float* rho, const float* dx, double tol, int first_iteration, int iterations,
                                         const double* S_h, const double* lam_h, const double* S_w, const double* lam_w, void* workspace, size_t workspace_bytes,
                                         double* scal, int* flags) {
-  return vc_iterate<false>(h, "pcnn_varcoef_pcg_iterate", N, H, W, 0, rho, dx, tol, first_iteration, iterations, VcBasis{S_h, S_h, lam_h, S_w, S_w, lam_w}, workspace,
+  return vc_iterate<false, false>(h, "pcnn_varcoef_pcg_iterate", N, H, W, 0, rho, dx, tol, first_iteration, iterations, VcBasis{S_h, S_h, lam_h, S_w, S_w, lam_w}, workspace,
                            workspace_bytes, scal, flags);
 }
 
@@ -553,14 +626,14 @@ extern "C" int pcnn_varcoef_bc_pcg_setup(pcnn_handle h, int N, int H, int W, int
                                          const float* right, const float* bottom, const float* top, const float* dx, const double* x0, double tol,
                                          const double* Vinv_h, const double* V_h, const double* lam_h, const double* VinvT_w, const double* VT_w,
                                          const double* lam_w, void* workspace, size_t workspace_bytes, double* scal, int* flags) {
-  return vc_setup<true>(h, "pcnn_varcoef_bc_pcg_setup", N, H, W, neumann_mask, rho, rhs, left, right, bottom, top, dx, x0, tol,
+  return vc_setup<true, false>(h, "pcnn_varcoef_bc_pcg_setup", N, H, W, neumann_mask, rho, rhs, left, right, bottom, top, dx, x0, tol,
                         VcBasis{Vinv_h, V_h, lam_h, VinvT_w, VT_w, lam_w}, workspace, workspace_bytes, scal, flags);
 }
 
 extern "C" int pcnn_varcoef_bc_pcg_iterate(pcnn_handle h, int N, int H, int W, int neumann_mask, const float* rho, const float* dx, double tol, int first_iteration,
                                            int iterations, const double* Vinv_h, const double* V_h, const double* lam_h, const double* VinvT_w,
                                            const double* VT_w, const double* lam_w, void* workspace, size_t workspace_bytes, double* scal, int* flags) {
-  return vc_iterate<true>(h, "pcnn_varcoef_bc_pcg_iterate", N, H, W, neumann_mask, rho, dx, tol, first_iteration, iterations,
+  return vc_iterate<true, false>(h, "pcnn_varcoef_bc_pcg_iterate", N, H, W, neumann_mask, rho, dx, tol, first_iteration, iterations,
                           VcBasis{Vinv_h, V_h, lam_h, VinvT_w, VT_w, lam_w}, workspace, workspace_bytes, scal, flags);
 }
 
@@ -576,5 +649,61 @@ extern "C" int pcnn_varcoef_density(pcnn_handle h, int64_t total, float lo, floa
   if (blocks > 16384) blocks = 16384;
   hipLaunchKernelGGL(varcoef_density_kernel, dim3((unsigned)blocks), dim3(256), 0, h->stream, total, lo, hi, g);
   PCNN_CHECK_LAUNCH(h, "pcnn_varcoef_density");
+  return 0;
+}
+
+// ---- the diagonally scaled preconditioner: the SC = true instantiations; finish is the plain entry points'
+extern "C" size_t pcnn_varcoef_pcg_workspace_scaled(int N, int H, int W) {
+  if (N < 1 || H < 3 || W < 3) return 0;
+  return vc_bytes(N, H - 2, W - 2, true);
+}
+
+extern "C" int pcnn_varcoef_pcg_setup_scaled(pcnn_handle h, int N, int H, int W, const float* rho, const float* rhs, const float* left, const float* right,
+                                             const float* bottom, const float* top, const float* dx, const double* x0, double tol, const double* S_h,
+                                             const double* lam_h, const double* S_w, const double* lam_w, void* workspace, size_t workspace_bytes, double* scal,
+                                             int* flags) {
+  return vc_setup<false, true>(h, "pcnn_varcoef_pcg_setup_scaled", N, H, W, 0, rho, rhs, left, right, bottom, top, dx, x0, tol, VcBasis{S_h, S_h, lam_h, S_w, S_w, lam_w},
+                               workspace, workspace_bytes, scal, flags);
+}
+
+extern "C" int pcnn_varcoef_pcg_iterate_scaled(pcnn_handle h, int N, int H, int W, const float* rho, const float* dx, double tol, int first_iteration, int iterations,
+                                               const double* S_h, const double* lam_h, const double* S_w, const double* lam_w, void* workspace,
+                                               size_t workspace_bytes, double* scal, int* flags) {
+  return vc_iterate<false, true>(h, "pcnn_varcoef_pcg_iterate_scaled", N, H, W, 0, rho, dx, tol, first_iteration, iterations, VcBasis{S_h, S_h, lam_h, S_w, S_w, lam_w},
+                                 workspace, workspace_bytes, scal, flags);
+}
+
+extern "C" size_t pcnn_varcoef_bc_pcg_workspace_scaled(int N, int H, int W, int neumann_mask) {
+  if (N < 1 || H < 3 || W < 3 || neumann_mask < 0 || neumann_mask > 15) return 0;
+  const FdUnknowns u = fd_unknowns(H, W, neumann_mask);
+  return vc_bytes(N, u.mh, u.mw, true);
+}
+
+extern "C" int pcnn_varcoef_bc_pcg_setup_scaled(pcnn_handle h, int N, int H, int W, int neumann_mask, const float* rho, const float* rhs, const float* left,
+                                                const float* right, const float* bottom, const float* top, const float* dx, const double* x0, double tol,
+                                                const double* Vinv_h, const double* V_h, const double* lam_h, const double* VinvT_w, const double* VT_w,
+                                                const double* lam_w, void* workspace, size_t workspace_bytes, double* scal, int* flags) {
+  return vc_setup<true, true>(h, "pcnn_varcoef_bc_pcg_setup_scaled", N, H, W, neumann_mask, rho, rhs, left, right, bottom, top, dx, x0, tol,
+                              VcBasis{Vinv_h, V_h, lam_h, VinvT_w, VT_w, lam_w}, workspace, workspace_bytes, scal, flags);
+}
+
+extern "C" int pcnn_varcoef_bc_pcg_iterate_scaled(pcnn_handle h, int N, int H, int W, int neumann_mask, const float* rho, const float* dx, double tol,
+                                                  int first_iteration, int iterations, const double* Vinv_h, const double* V_h, const double* lam_h,
+                                                  const double* VinvT_w, const double* VT_w, const double* lam_w, void* workspace, size_t workspace_bytes,
+                                                  double* scal, int* flags) {
+  return vc_iterate<true, true>(h, "pcnn_varcoef_bc_pcg_iterate_scaled", N, H, W, neumann_mask, rho, dx, tol, first_iteration, iterations,
+                                VcBasis{Vinv_h, V_h, lam_h, VinvT_w, VT_w, lam_w}, workspace, workspace_bytes, scal, flags);
+}
+
+extern "C" int pcnn_varcoef_density_smooth(pcnn_handle h, int N, int64_t per, float lo, float hi, float* g) {
+  PCNN_REQUIRE(h, h && g && N >= 1 && N <= 65535 && per >= 1, "pcnn_varcoef_density_smooth: bad argument");
+  PCNN_REQUIRE(h, lo > 0.f && hi >= lo, "pcnn_varcoef_density_smooth: need 0 < lo <= hi, got %g, %g", (double)lo, (double)hi);
+  int64_t blocks = pcnn_cdiv64(per, EW_POINTS);
+  if (blocks > DS_MAX_BLOCKS) blocks = DS_MAX_BLOCKS;
+  if (int rc = pcnn_reserve(h, h->aux_ws, (size_t)N * blocks * 2 * sizeof(float), 0, "pcnn_varcoef_density_smooth")) return rc;
+  float* mm = static_cast<float*>(h->aux_ws.p);
+  hipLaunchKernelGGL(varcoef_density_range_kernel, dim3((unsigned)blocks, N), dim3(EW_THREADS), 0, h->stream, per, (const float*)g, mm);
+  hipLaunchKernelGGL(varcoef_density_smooth_kernel, dim3((unsigned)blocks, N), dim3(EW_THREADS), 0, h->stream, per, lo, hi, (const float*)mm, g);
+  PCNN_CHECK_LAUNCH(h, "pcnn_varcoef_density_smooth");
   return 0;
 }

@@ -509,8 +509,12 @@ def _lead_shape(a, name, dims):
     return s
 
 
+VARIABLE_DENSITY_PRECONDITIONERS = ('dst', 'scaled')
+VARIABLE_DENSITY_PROFILES = ('abs', 'smooth')
+
+
 def variable_density_poisson_solve(rho, rhses, boundaries, dx, dy=None, tol=1e-10, max_iterations=500, initial_guesses=None, check_every=8,
-                                   return_info=False, device=None, check_start=False, boundary_types=None):
+                                   return_info=False, device=None, check_start=False, boundary_types=None, preconditioner='dst'):
     """Solves div((1/rho) grad u) = f with Dirichlet data on the four edges, on the vertex-centred grid of multigrid_poisson_solve (same shapes
     and edge names: rhses (N,1,H,W) or (N,H,W); boundaries: dict with 'left'/'right' (N,W) and 'bottom'/'top' (N,H); dx one spacing per sample).
     rho (N,H,W) or (N,1,H,W) is given on every node, boundary nodes included, and must be positive.
@@ -546,12 +550,22 @@ def variable_density_poisson_solve(rho, rhses, boundaries, dx, dy=None, tol=1e-1
              `compatibility_defect` = |sum w b| / sqrt(sum w * sum w b^2) in [0, 1] tells how incompatible the data were, and `rhs_shift` the
              constant the projection added to f: the solution satisfies the discrete equation of f + rhs_shift.
 
+    preconditioner: 'dst' (default) is the constant-coefficient solve M^-1 described above.  'scaled' is Concus and Golub's diagonal scaling of
+    it, z = s o M^-1 (s o r) with s = d^-1/2 and d the mean of the node's four face coefficients (diag(A) / diag(M); on a Neumann edge the inward
+    face twice): for a SMOOTH rho the iteration count then follows the derivatives of log rho and no longer max rho / min rho - 13 to 25 iterations
+    against 41 to 159 at ratio 1000 in the fp64 twin - at the same launches per iteration (2 to 4 % more time each).  For a rho with kinks or jumps
+    (the generator's default 'abs' profile has kinks) it gains nothing and takes MORE iterations than 'dst' on fine grids (3 to 4 times as many at
+    512^2 and ratio 100 to 1000): opt-in, DESIGN.md section 22 has the counts.  Works with every
+    boundary_types and with initial_guesses; the same system, tolerance and returned info.  Any other value raises ValueError.
+
     Returns soln (N,1,H,W) fp32; with return_info also a dict of per-sample numpy arrays `iterations` (a multiple of check_every), `converged`
     and `relative_residual` (||r|| / ||b|| of the recurrence), and with a Neumann edge `compatibility_defect` and `rhs_shift` (zeros unless all four
     edges are Neumann)."""
     import warnings
     # everything that can be refused without a device is refused first
     neumann = _neumann_flags(boundary_types) if boundary_types is not None else (False,) * 4
+    if preconditioner not in VARIABLE_DENSITY_PRECONDITIONERS:
+        raise ValueError('preconditioner must be one of %r, got %r' % (VARIABLE_DENSITY_PRECONDITIONERS, preconditioner))
     rs = _lead_shape(rhses, 'rhses', 3)
     if _lead_shape(rho, 'rho', 3) != rs:
         raise ValueError('rho %r and rhses %r must have the same (N,H,W)' % (tuple(rho.shape), tuple(rhses.shape)))
@@ -581,8 +595,9 @@ def variable_density_poisson_solve(rho, rhses, boundaries, dx, dy=None, tol=1e-1
     if initial_guesses is not None:
         g = initial_guesses if isinstance(initial_guesses, torch.Tensor) else torch.as_tensor(np.asarray(initial_guesses))
         x0 = g.to(device=dev, dtype=torch.float64).reshape(N, H, W).contiguous()
+    scaled = {'scaled': True} if preconditioner == 'scaled' else {}             # ('dst': the call as it has always been)
     soln, info = K.varcoef_pcg_solve(dens, r, b['left'], b['right'], b['bottom'], b['top'], d, tol=float(tol), max_iterations=int(max_iterations), x0=x0,
-                                     check_every=int(check_every), check_start=bool(check_start), neumann=neumann if any(neumann) else None)
+                                     check_every=int(check_every), check_start=bool(check_start), neumann=neumann if any(neumann) else None, **scaled)
     if not info['converged'].all():           # (a rho <= 0 or NaN on the device was refused inside, straight after the setup kernel's minimum)
         bad = np.flatnonzero(~info['converged'])
         warnings.warn('variable_density_poisson_solve: sample(s) %r not converged to tol = %g after %d iterations (relative residual %r)'
@@ -594,10 +609,10 @@ def variable_density_poisson_solve(rho, rhses, boundaries, dx, dy=None, tol=1e-1
     return soln
 
 
-def compressible_poisson_solve(rho, rhses, boundaries, dx, dy=None, system_matrix=None):
+def compressible_poisson_solve(rho, rhses, boundaries, dx, dy=None, system_matrix=None, preconditioner='dst'):
     """The reference's name and argument order (dataset/generators/variable_density: compressible_poisson_solve).  system_matrix is accepted and
-    ignored: no matrix is assembled."""
-    return variable_density_poisson_solve(rho, rhses, boundaries, dx, dy=dy)
+    ignored: no matrix is assembled.  preconditioner: variable_density_poisson_solve's."""
+    return variable_density_poisson_solve(rho, rhses, boundaries, dx, dy=dy, preconditioner=preconditioner)
 
 
 class variable_density_dataset_generator(numerical_dataset_generator):
@@ -616,11 +631,16 @@ class variable_density_dataset_generator(numerical_dataset_generator):
     du/dn: zeros with boundaries = 'zero', the drawn smooth function with 'random' - the draws are the same whatever the types.  With all four
     edges Neumann the right-hand side returned is the one the solution satisfies: the drawn one plus the constant of the solver's compatibility
     projection (last_info['rhs_shift']).  Homogeneous_Poisson_NN_Legacy(density_input=True, boundary_types=...) trains on such batches (DESIGN.md
-    section 20)."""
+    section 20).
+
+    density_profile: 'abs' (default) is the rho above, which has a kink wherever g changes sign.  'smooth' is rho = lo + (hi - lo) (g - min g) /
+    (max g - min g) per sample (pcnn_varcoef_density_smooth): as smooth as g, minimum lo and maximum hi - the densities preconditioner = 'scaled'
+    (variable_density_poisson_solve's, passed through; default 'dst') is for.  Neither changes the random draws."""
 
     def __init__(self, batch_size=1, batches_per_epoch=1, output_shape=None, random_output_shape_range=((64, 85), (64, 85)), density_range=(1.0, 10.0),
                  rhs_smoothness_range=(5, 20), density_smoothness_range=(5, 20), boundaries='zero', random_dx_range=(0.005, 0.05), rhs_max_magnitude=1.0,
-                 boundary_max_magnitude=1.0, tol=1e-10, max_iterations=500, seed=0, device=None, return_keras_style=True, shard=None, boundary_types=None):
+                 boundary_max_magnitude=1.0, tol=1e-10, max_iterations=500, seed=0, device=None, return_keras_style=True, shard=None, boundary_types=None,
+                 preconditioner='dst', density_profile='abs'):
         super().__init__(batch_size=batch_size, batches_per_epoch=batches_per_epoch, return_keras_style=return_keras_style, seed=seed, device=device,
                          shard=shard)
         self.boundary_types = boundary_types
@@ -630,6 +650,11 @@ class variable_density_dataset_generator(numerical_dataset_generator):
             raise ValueError('density_range = (lo, hi) needs 0 < lo <= hi, got %r' % (density_range,))
         if boundaries not in ('zero', 'random'):
             raise ValueError("boundaries must be 'zero' or 'random'")
+        if preconditioner not in VARIABLE_DENSITY_PRECONDITIONERS:
+            raise ValueError('preconditioner must be one of %r, got %r' % (VARIABLE_DENSITY_PRECONDITIONERS, preconditioner))
+        if density_profile not in VARIABLE_DENSITY_PROFILES:
+            raise ValueError('density_profile must be one of %r, got %r' % (VARIABLE_DENSITY_PROFILES, density_profile))
+        self.preconditioner, self.density_profile = preconditioner, density_profile
         for name, rg in (('rhs_smoothness_range', rhs_smoothness_range), ('density_smoothness_range', density_smoothness_range)):
             if not 2 <= int(rg[0]) <= int(rg[1]):
                 raise ValueError('%s = (lo, hi) needs 2 <= lo <= hi control points, got %r' % (name, rg))
@@ -652,7 +677,8 @@ class variable_density_dataset_generator(numerical_dataset_generator):
         ctrl = lambda rg: [int(rng.integers(rg[0], rg[1] + 1)) for _ in range(2)]
         nf, nr = ctrl(self.rhs_smoothness_range), ctrl(self.density_smoothness_range)
         rhs = self._smooth_field(2 * rng.uniform(size=(N, nf[0], nf[1])) - 1, (H, W), self.rhs_max_magnitude)
-        rho = K.varcoef_density(self._smooth_field(2 * rng.uniform(size=(N, nr[0], nr[1])) - 1, (H, W), 1.0), *self.density_range)
+        density = K.varcoef_density_smooth if self.density_profile == 'smooth' else K.varcoef_density
+        rho = density(self._smooth_field(2 * rng.uniform(size=(N, nr[0], nr[1])) - 1, (H, W), 1.0), *self.density_range)
         lengths = {'left': W, 'right': W, 'top': H, 'bottom': H}
         bc = {}
         for k in _BOUNDARY_KEYS:
@@ -663,7 +689,7 @@ class variable_density_dataset_generator(numerical_dataset_generator):
             bc[k] = self._edge(ctrl, lengths[k], self.boundary_max_magnitude)
         d = self._dev(dx)
         soln, self.last_info = variable_density_poisson_solve(rho, rhs, bc, d, tol=self.tol, max_iterations=self.max_iterations, return_info=True,
-                                                              device=self.device, boundary_types=self.boundary_types)
+                                                              device=self.device, boundary_types=self.boundary_types, preconditioner=self.preconditioner)
         if all(self.neumann_flags):                                        # the equation (rhs, soln) satisfies: the solver projected its b
             rhs = rhs + torch.as_tensor(self.last_info['rhs_shift'], dtype=torch.float32, device=rhs.device).view(N, 1, 1)
         frho = torch.stack([rhs, rho], dim=1)

@@ -184,7 +184,8 @@ def varcoef_apply(rho, dx, p, neumann=None):
 VARCOEF_SCALARS = {'bb': 0, 'rr': 1, 'pq': 2, 'rho_min': 5, 'wb': 6, 'bb_raw': 7}
 
 
-def varcoef_pcg_solve(rho, rhs, left, right, bottom, top, dx, tol=1e-10, max_iterations=500, x0=None, check_every=8, check_start=False, neumann=None):
+def varcoef_pcg_solve(rho, rhs, left, right, bottom, top, dx, tol=1e-10, max_iterations=500, x0=None, check_every=8, check_start=False, neumann=None,
+                      scaled=False):
     """Preconditioned conjugate gradients on the variable-density system (pcnn_varcoef_pcg_setup / _iterate / _finish).  rho, rhs (N,H,W),
     left/right (N,W), bottom/top (N,H), dx (N,): fp32 CUDA tensors; x0: optional (N,H,W) fp64 initial guess (its unknowns are used).
     The device runs check_every iterations per call; the host reads the N convergence flags between calls and nothing else.
@@ -198,7 +199,9 @@ def varcoef_pcg_solve(rho, rhs, left, right, bottom, top, dx, tol=1e-10, max_ite
     run the same problem through the *_bc_* ones and give the same bits.  All four True: the data need not be compatible - setup projects b, and
     compatibility_defect = |sum w b| / sqrt(sum w * sum w b^2) in [0, 1] says how far it was; rhs_shift is the constant (sum w b) / (sum w) the
     projection took from b, i.e. the solution solves the system of rhs + rhs_shift; the solution has zero trapezoidal integral.  Both are 0
-    for every other mask."""
+    for every other mask.
+    scaled: the *_scaled entry points - the preconditioner s o M^-1 (s o r), s = (mean face coefficient)^-1/2 (DESIGN.md section 22), for smooth rho;
+    one more workspace field, the same launches per iteration, the same finish."""
     N, H, W = rho.shape
     for name, t, shape in (('rho', rho, (N, H, W)), ('rhs', rhs, (N, H, W)), ('left', left, (N, W)), ('right', right, (N, W)), ('bottom', bottom, (N, H)),
                            ('top', top, (N, H)), ('dx', dx, (N,))):
@@ -213,17 +216,23 @@ def varcoef_pcg_solve(rho, rhs, left, right, bottom, top, dx, tol=1e-10, max_ite
     if neumann is None:
         Sh, lh = dst_matrices(H, dev)
         Sw, lw = dst_matrices(W, dev)
-        nbytes = int(lib.pcnn_varcoef_pcg_workspace(c_int(N), c_int(H), c_int(W)))
+        nbytes = int(lib.pcnn_varcoef_pcg_workspace_scaled(c_int(N), c_int(H), c_int(W)) if scaled else lib.pcnn_varcoef_pcg_workspace(c_int(N), c_int(H), c_int(W)))
         ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
         setup = lambda: h.call('pcnn_varcoef_pcg_setup', c_int(N), c_int(H), c_int(W), _p(rho), _p(rhs), _p(left), _p(right), _p(bottom), _p(top), _p(dx), _p(x0),
                                c_double(tol), _p(Sh), _p(lh), _p(Sw), _p(lw), _p(ws), c_size_t(nbytes), _p(scal), _p(flags))
         iterate = lambda it: h.call('pcnn_varcoef_pcg_iterate', c_int(N), c_int(H), c_int(W), _p(rho), _p(dx), c_double(tol), c_int(it), c_int(check_every),
                                     _p(Sh), _p(lh), _p(Sw), _p(lw), _p(ws), c_size_t(nbytes), _p(scal), _p(flags))
         finish = lambda: h.call('pcnn_varcoef_pcg_finish', c_int(N), c_int(H), c_int(W), _p(ws), _p(left), _p(right), _p(bottom), _p(top), _p(soln))
+        if scaled:
+            setup = lambda: h.call('pcnn_varcoef_pcg_setup_scaled', c_int(N), c_int(H), c_int(W), _p(rho), _p(rhs), _p(left), _p(right), _p(bottom), _p(top), _p(dx),
+                                   _p(x0), c_double(tol), _p(Sh), _p(lh), _p(Sw), _p(lw), _p(ws), c_size_t(nbytes), _p(scal), _p(flags))
+            iterate = lambda it: h.call('pcnn_varcoef_pcg_iterate_scaled', c_int(N), c_int(H), c_int(W), _p(rho), _p(dx), c_double(tol), c_int(it),
+                                        c_int(check_every), _p(Sh), _p(lh), _p(Sw), _p(lw), _p(ws), c_size_t(nbytes), _p(scal), _p(flags))
     else:
         mask = _neumann_mask(neumann)
         Vih, Vh, lh, ViwT, VwT, lw = _varcoef_bases(H, W, neumann, dev)
-        nbytes = int(lib.pcnn_varcoef_bc_pcg_workspace(c_int(N), c_int(H), c_int(W), c_int(mask)))
+        nbytes = int(lib.pcnn_varcoef_bc_pcg_workspace_scaled(c_int(N), c_int(H), c_int(W), c_int(mask)) if scaled else
+                     lib.pcnn_varcoef_bc_pcg_workspace(c_int(N), c_int(H), c_int(W), c_int(mask)))
         ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
         setup = lambda: h.call('pcnn_varcoef_bc_pcg_setup', c_int(N), c_int(H), c_int(W), c_int(mask), _p(rho), _p(rhs), _p(left), _p(right), _p(bottom), _p(top),
                                _p(dx), _p(x0), c_double(tol), _p(Vih), _p(Vh), _p(lh), _p(ViwT), _p(VwT), _p(lw), _p(ws), c_size_t(nbytes), _p(scal), _p(flags))
@@ -231,6 +240,12 @@ def varcoef_pcg_solve(rho, rhs, left, right, bottom, top, dx, tol=1e-10, max_ite
                                     c_int(check_every), _p(Vih), _p(Vh), _p(lh), _p(ViwT), _p(VwT), _p(lw), _p(ws), c_size_t(nbytes), _p(scal), _p(flags))
         finish = lambda: h.call('pcnn_varcoef_bc_pcg_finish', c_int(N), c_int(H), c_int(W), c_int(mask), _p(ws), _p(left), _p(right), _p(bottom), _p(top),
                                 _p(soln))
+        if scaled:
+            setup = lambda: h.call('pcnn_varcoef_bc_pcg_setup_scaled', c_int(N), c_int(H), c_int(W), c_int(mask), _p(rho), _p(rhs), _p(left), _p(right), _p(bottom),
+                                   _p(top), _p(dx), _p(x0), c_double(tol), _p(Vih), _p(Vh), _p(lh), _p(ViwT), _p(VwT), _p(lw), _p(ws), c_size_t(nbytes), _p(scal),
+                                   _p(flags))
+            iterate = lambda it: h.call('pcnn_varcoef_bc_pcg_iterate_scaled', c_int(N), c_int(H), c_int(W), c_int(mask), _p(rho), _p(dx), c_double(tol), c_int(it),
+                                        c_int(check_every), _p(Vih), _p(Vh), _p(lh), _p(ViwT), _p(VwT), _p(lw), _p(ws), c_size_t(nbytes), _p(scal), _p(flags))
     scal = torch.empty((N, 8), dtype=torch.float64, device=dev)                  # (the closures above find scal, flags and soln when they are called)
     flags = torch.empty((N,), dtype=torch.int32, device=dev)
     setup()
@@ -264,6 +279,14 @@ def varcoef_density(g, lo, hi):
     if g.dtype != torch.float32 or not g.is_cuda or not g.is_contiguous():
         raise ValueError('varcoef_density takes a contiguous CUDA float32 tensor')
     handle().call('pcnn_varcoef_density', c_int64(g.numel()), c_float(lo), c_float(hi), _p(g))
+    return g
+
+
+def varcoef_density_smooth(g, lo, hi):
+    """In place: g[n] -> lo + (hi - lo) (g[n] - min g[n]) / (max g[n] - min g[n]) (pcnn_varcoef_density_smooth); g (N, ...): fp32, any scale."""
+    if g.dtype != torch.float32 or not g.is_cuda or not g.is_contiguous() or g.dim() < 2:
+        raise ValueError('varcoef_density_smooth takes a contiguous CUDA float32 tensor with a leading sample axis')
+    handle().call('pcnn_varcoef_density_smooth', c_int(g.shape[0]), c_int64(g.numel() // g.shape[0]), c_float(lo), c_float(hi), _p(g))
     return g
 
 

@@ -969,7 +969,7 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
             return ops.varcoef_error_stats(pred, None, y_true), (H, W)
         return ops.varcoef_error_stats(pred, rhs[:, 1].contiguous(), y_true, rhs[:, 0].contiguous(), _dx_column(dx), neumann_mask=self.neumann_mask), (H, W)
 
-    def solve(self, inputs, tol=1e-10, max_iterations=500, check_every=8, warm_start=True, compare_cold=False, return_info=False):
+    def solve(self, inputs, tol=1e-10, max_iterations=500, check_every=8, warm_start=True, compare_cold=False, return_info=False, preconditioner='dst'):
         """The variable-density problem solved to `tol`, the conjugate-gradient iteration started from this model's prediction (DESIGN.md section
         18).  inputs = [stack (N,2,H,W) = [rhs, rho], dx] as for call; the edges are zero, as the model's are.  Runs the inference-mode forward,
         ops.varcoef_error_stats on the prediction, and dataset.variable_density_poisson_solve(rho, rhs, zero edges, dx, initial_guesses = the
@@ -984,6 +984,8 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
         unknowns, r from ops.varcoef_pi_loss_partials with the mask - the ||b - A x0||_W / ||b||_W the solver starts from (all four edges Neumann:
         before its projection of b) - and prediction_max_residual is None unless the model was built with residual_metrics=True: then it is the
         max|r| column of ops.varcoef_error_stats(neumann_mask=...), the same r.
+        preconditioner: variable_density_poisson_solve's - 'dst', or 'scaled' for smooth densities; both solves of
+        compare_cold use it.
         How many iterations a prediction saves is measured (tools/bench_varcoef_warmstart.py), not promised.  Nothing in the model changes: no
         BatchNormalization update, no gradient, no optimizer state."""
         if not self.density_input:
@@ -1009,6 +1011,8 @@ class Homogeneous_Poisson_NN_Legacy(_ModelBase):
         kw = dict(tol=tol, max_iterations=max_iterations, check_every=check_every, return_info=True, device=self.device, check_start=True)
         if mask:
             kw['boundary_types'] = self.boundary_types
+        if preconditioner != 'dst':
+            kw['preconditioner'] = preconditioner
         soln, info = D.variable_density_poisson_solve(rho, rhs, zero, d, initial_guesses=pred if warm_start else None, **kw)
         if not return_info:
             return soln

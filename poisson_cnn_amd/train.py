@@ -7,7 +7,8 @@ Under `torchrun` (WORLD_SIZE > 1) the batch is sharded over ranks and gradients 
 `analytical_mixed` (extension): the analytic generator with a boundary type per edge, for a Homogeneous_Poisson_NN_Legacy whose bc_type is a dict.
 `variable_density` (extension): dataset.variable_density_dataset_generator, div((1/rho) grad u) = f with the input stack [rhs, rho], for
 --model hpnn with "density_input": true in the model section; the config's loss is then built as losses.variable_density_loss_wrapper.
-"boundary_types" and "residual_metrics" in that model section reach the model as its keywords of the same names.
+"boundary_types" and "residual_metrics" in that model section reach the model as its keywords of the same names; "preconditioner" ('dst' |
+'scaled') and "density_profile" ('abs' | 'smooth') in the dataset section, when present, reach the generator as its keywords of the same names.
 """
 import argparse
 import json
