@@ -713,6 +713,18 @@ int pcnn_varcoef_density(pcnn_handle h, int64_t total, float lo, float hi, float
 /* The smooth profile: g (N x per) -> lo + (hi - lo) (g - min g) / (max g - min g), minimum and maximum per sample by a fixed-order block reduction
  * (two launches, no atomics); a constant sample gives lo.  No kink where g changes sign: the densities the scaled preconditioner below is for. */
 int pcnn_varcoef_density_smooth(pcnn_handle h, int N, int64_t per, float lo, float hi, float* g);
+/* A (solution, right-hand side) pair of the discrete problem without a solve, one launch:
+ *   u[n,i,j]  = sum_{A<ka,B<kb} c[n,A,B] phi_A(x_i) psi_B(y_j),  x = linspace(0,pi,H), y = linspace(0,pi,W), formed in fp64,
+ *   soln = (float) u on every node (an exact 0 on a node that is not an unknown),
+ *   rhs  = (float) (L_h(rho) u) = -(A u) of pcnn_varcoef_bc_apply on the unknowns of neumann_mask - a Neumann edge's nodes with the doubled inward
+ *          face - and 0 elsewhere: the pair satisfies the equation the solve, the loss and the metrics use, to fp32 rounding of the two fields.
+ * phi / psi are pcnn_series_pair_synthesis' families chosen by the edge types of the axis - (left, right) = bits 0, 1 for axis -2, (bottom, top) =
+ * bits 2, 3 for axis -1: (D,D) sin(A t), (N,N) cos(A t), (D,N) sin((A - 1/2) t), (N,D) cos((A - 1/2) t), A = 1..k - so u = 0 on a Dirichlet edge and
+ * is even about a Neumann edge.  With mask 15 u has zero trapezoidal sum and rhs is compatible by construction.  coef (N,ka,kb), ka, kb <= 16;
+ * rho (N,H,W) must be positive (not checked, as for pcnn_varcoef_apply); dx (N); H, W >= 3.  u is never rounded before it is differenced.
+ * No atomics; a sample's result does not depend on its batch. */
+int pcnn_varcoef_series_pair(pcnn_handle h, int N, int H, int W, int ka, int kb, const float* coef, int neumann_mask, const float* rho,
+                             const float* dx, float* soln, float* rhs);
 /* The solves above with the diagonally scaled preconditioner z = s o M^-1 (s o r) (Concus and Golub): M the constant-coefficient
  * operator of the plain entry points, s = d^-1/2 in fp64, d = diag(A) / diag(M) - the mean of the node's four face coefficients, the inward one twice
  * on a Neumann edge node.  For smooth rho the iteration count then depends on the derivatives of log rho, not on max rho / min rho; for a rho with

@@ -445,6 +445,79 @@ __global__ __launch_bounds__(EW_THREADS) void varcoef_density_smooth_kernel(int6
     gn[k] = fminf(fmaxf(lo + (hi - lo) * ((gn[k] - mn) * inv), lo), hi);
 }
 
+// A (solution, right-hand side) pair of the DISCRETE problem without a solve: u = sum_{A,B} c[A,B] phi_A(x_i) psi_B(y_j) in the
+// homogeneous eigenfunction families of the mask's edge types, and f = L_h(rho) u = -(A u) by the operator above.  u is synthesised in fp64 where
+// it is differenced - differencing an fp32-rounded u puts eps32 4 n^2 / (pi k)^2 of grid-scale noise into f - and only the two results are rounded.
+// One block per FLUX_ROWS x FLUX_COLS tile of NODES of one sample, grid (column tiles, row tiles, N):
+//   1. the trig tables of the tile and its one-node halo, each entry once: F[A][r] = phi_A(x), P[B][c] = psi_B(y); beyond a Neumann end the table
+//      holds the mirrored node's value (the families are even about such an end), beyond the field 0 (no stored point uses it)
+//   2. T[A][c] = sum_B c[A,B] P[B][c]
+//   3. us[r][c] = sum_A F[A][r] T[A][c], an exact 0 on a node that is not an unknown (the sine factor leaves 1e-16 there)
+//   4. a column and FLUX_RPT rows per thread: soln = (float) u on every node, rhs = (float) -stencil_at on the unknowns, 0 elsewhere.
+// No thread leaves before the last barrier; rows >= H and columns >= W are computed and not stored; no atomics.
+constexpr int VSER_MAXK = 16;
+// mode k+1 of the family `kind` (bit 0: cosine, bit 1: quarter waves - dataset._axis_basis) at node idx of an n-point axis: sin / cos of
+// (q / 2) idx pi / (n - 1), q = 2 (k + 1) - (quarter ? 1 : 0).  q idx is reduced modulo the period 4 (n - 1) in integers, so the argument is exact.
+__device__ __forceinline__ double vser_basis(int kind, int k, int idx, int n) {
+  const int64_t q = 2 * (k + 1) - ((kind & 2) ? 1 : 0), period = 4 * (int64_t)(n - 1);
+  const double x = (double)((q * idx) % period) / (double)(2 * (int64_t)(n - 1));
+  return (kind & 1) ? cospi(x) : sinpi(x);
+}
+__device__ __forceinline__ int vser_kind(bool lo, bool hi) { return (lo ? 1 : 0) | (lo != hi ? 2 : 0); }
+
+__global__ __launch_bounds__(FLUX_THREADS) void varcoef_series_pair_kernel(int H, int W, int ka, int kb, int mask, const float* __restrict__ coef,
+                                                                           const float* __restrict__ rho, const float* __restrict__ dx,
+                                                                           float* __restrict__ soln, float* __restrict__ rhs) {
+  __shared__ float rs[VT_LR][VT_LC];
+  __shared__ double us[VT_LR][VT_LC];
+  __shared__ double P[VSER_MAXK][VT_LC], T[VSER_MAXK][VT_LC];
+  __shared__ double F[VSER_MAXK][VT_LR];
+  __shared__ double cs[VSER_MAXK * VSER_MAXK];
+  const FdUnknowns u = fd_unknowns(H, W, mask);
+  const int n = blockIdx.z, I0 = blockIdx.y * FLUX_ROWS, J0 = blockIdx.x * FLUX_COLS, tid = threadIdx.x;
+  const int kind_a = vser_kind(mask & 1, mask & 2), kind_b = vser_kind(mask & 4, mask & 8);
+  load_rho_tile<true>(rs, rho + (int64_t)n * H * W, H, W, I0 - 1, J0 - 1);
+  for (int e = tid; e < ka * kb; e += FLUX_THREADS) cs[e] = (double)coef[(int64_t)n * ka * kb + e];
+  for (int e = tid; e < ka * VT_LR; e += FLUX_THREADS) {
+    const int A = e / VT_LR, r = e % VT_LR, i = vc_mirror(I0 + r - 1, H, mask & 1, mask & 2);
+    F[A][r] = i >= 0 ? vser_basis(kind_a, A, i, H) : 0.0;
+  }
+  for (int e = tid; e < kb * VT_LC; e += FLUX_THREADS) {
+    const int B = e / VT_LC, c = e % VT_LC, j = vc_mirror(J0 + c - 1, W, mask & 4, mask & 8);
+    P[B][c] = j >= 0 ? vser_basis(kind_b, B, j, W) : 0.0;
+  }
+  __syncthreads();
+  for (int e = tid; e < ka * VT_LC; e += FLUX_THREADS) {
+    const int A = e / VT_LC, c = e % VT_LC;
+    double s = 0.0;
+    for (int B = 0; B < kb; ++B) s += cs[A * kb + B] * P[B][c];
+    T[A][c] = s;
+  }
+  __syncthreads();
+  for (int e = tid; e < VT_LR * VT_LC; e += FLUX_THREADS) {
+    const int r = e / VT_LC, c = e % VT_LC;
+    const int i = vc_mirror(I0 + r - 1, H, mask & 1, mask & 2), j = vc_mirror(J0 + c - 1, W, mask & 4, mask & 8);
+    double s = 0.0;
+    for (int A = 0; A < ka; ++A) s += F[A][r] * T[A][c];
+    us[r][c] = (i >= u.i0 && i <= u.i1 && j >= u.j0 && j <= u.j1) ? s : 0.0;
+  }
+  __syncthreads();
+  const double h = (double)dx[n], inv_h2 = 1.0 / (h * h);
+  const int c = tid % FLUX_COLS, r0 = (tid / FLUX_COLS) * FLUX_RPT, j = J0 + c;
+  if (j < W) {
+#pragma unroll
+    for (int k = 0; k < FLUX_RPT; ++k) {
+      const int r = r0 + k, i = I0 + r;
+      if (i < H) {
+        const bool unknown = i >= u.i0 && i <= u.i1 && j >= u.j0 && j <= u.j1;
+        const int64_t o = ((int64_t)n * H + i) * W + j;
+        soln[o] = (float)us[r + 1][c + 1];
+        rhs[o] = unknown ? (float)-stencil_at(faces_at(rs, r, c), us, r, c, inv_h2) : 0.f;
+      }
+    }
+  }
+}
+
 // the six arrays of a preconditioner: per axis the eigenbasis of the constant-coefficient 1-D operator on that axis' unknowns, the second axis'
 // matrices transposed (applied from the right) - pcnn_fd_poisson_mixed's.  All-Dirichlet: the orthonormal DST-I matrix S for all four.
 struct VcBasis { const double *Vinv_h, *V_h, *lam_h, *VinvT_w, *VT_w, *lam_w; };
@@ -649,6 +722,20 @@ extern "C" int pcnn_varcoef_density(pcnn_handle h, int64_t total, float lo, floa
   if (blocks > 16384) blocks = 16384;
   hipLaunchKernelGGL(varcoef_density_kernel, dim3((unsigned)blocks), dim3(256), 0, h->stream, total, lo, hi, g);
   PCNN_CHECK_LAUNCH(h, "pcnn_varcoef_density");
+  return 0;
+}
+
+extern "C" int pcnn_varcoef_series_pair(pcnn_handle h, int N, int H, int W, int ka, int kb, const float* coef, int neumann_mask, const float* rho,
+                                        const float* dx, float* soln, float* rhs) {
+  const char* who = "pcnn_varcoef_series_pair";
+  PCNN_REQUIRE(h, h && coef && rho && dx && soln && rhs, "%s: null argument", who);
+  FdUnknowns u;
+  if (int rc = vc_check_shape(h, who, N, H, W, neumann_mask, &u)) return rc;
+  PCNN_REQUIRE(h, pcnn_cdiv(H, FLUX_ROWS) <= 65535, "%s: grid %d x %d unsupported", who, H, W);             // the tiles cover the nodes, not the unknowns
+  PCNN_REQUIRE(h, ka >= 1 && kb >= 1 && ka <= VSER_MAXK && kb <= VSER_MAXK, "%s: %dx%d coefficients unsupported (<=%d)", who, ka, kb, VSER_MAXK);
+  hipLaunchKernelGGL(varcoef_series_pair_kernel, dim3(pcnn_cdiv(W, FLUX_COLS), pcnn_cdiv(H, FLUX_ROWS), N), dim3(FLUX_THREADS), 0, h->stream, H, W, ka, kb,
+                     neumann_mask, coef, rho, dx, soln, rhs);
+  PCNN_CHECK_LAUNCH(h, who);
   return 0;
 }
 

@@ -144,6 +144,39 @@ class _generator:
             return t.to(self.device)
         return t.pin_memory().to(self.device, non_blocking=True)
 
+    # -- draws and fields more than one family uses (self.rng, self.batch_size, self.device and the named attributes are the subclass')
+    def _grid_sizes(self, rng_range):
+        """generate_grid_sizes (reverse.py:164-171)."""
+        return ((rng_range[:, 1] - rng_range[:, 0]) * self.rng.uniform(size=(2,)) + rng_range[:, 0] + 1).astype(np.int64)
+
+    def _draw_mode_counts(self):
+        """Mode counts per sample and axis from self.fourier_coeff_grid_size_range -> (N,2)."""
+        return np.stack([self._grid_sizes(self.fourier_coeff_grid_size_range) for _ in range(self.batch_size)])
+
+    def _draw_coefficients(self, ncoef):
+        """Series coefficients uniform in [-1, 1), zero beyond a sample's own mode counts -> (N,ka,kb), ka / kb the batch's largest counts."""
+        N = self.batch_size
+        ka, kb = int(ncoef[:, 0].max()), int(ncoef[:, 1].max())
+        coef = np.zeros((N, ka, kb))
+        for b in range(N):
+            coef[b, :ncoef[b, 0], :ncoef[b, 1]] = 2 * self.rng.uniform(size=(ncoef[b, 0], ncoef[b, 1])) - 1
+        return coef
+
+    def _smooth_field(self, ctrl, out_hw, max_magnitude):
+        """generate_random_RHS / generate_random_boundaries core (numerical.py:10-72): control points -> legacy bicubic
+        (align_corners) up-sampling -> per-sample max-magnitude scaling."""
+        N = ctrl.shape[0]
+        x = self._dev(ctrl).view(N, ctrl.shape[1], ctrl.shape[2], 1)
+        y = K.resize_legacy_bicubic(x, out_hw).view(N, out_hw[0], out_hw[1])
+        if max_magnitude != np.inf:
+            K.set_max_magnitude(y, torch.full((N,), float(max_magnitude), device=self.device))
+        return y
+
+    def _density_field(self, ctrl, out_hw):
+        """rho (N,H,W) in self.density_range from control points, by self.density_profile ('abs': kinked, 'smooth'; VARIABLE_DENSITY_PROFILES)."""
+        density = K.varcoef_density_smooth if self.density_profile == 'smooth' else K.varcoef_density
+        return density(self._smooth_field(ctrl, out_hw, 1.0), *self.density_range)
+
 
 # ----------------------------------------------------------------------------- analytic ("reverse") generators
 class reverse_poisson_dataset_generator(_generator):
@@ -168,10 +201,6 @@ class reverse_poisson_dataset_generator(_generator):
         self.fixed_output_shape = None     # set to (H, W) to pin the grid (benchmarks / data-parallel ranks sharing one shape)
 
     # -- host-side draws
-    def _grid_sizes(self, rng_range):
-        """generate_grid_sizes (reverse.py:164-171)."""
-        return ((rng_range[:, 1] - rng_range[:, 0]) * self.rng.uniform(size=(2,)) + rng_range[:, 0] + 1).astype(np.int64)
-
     def _shape_and_spacings(self):
         """generate_grid_sizes_and_spacings_with_uniform_AR (reverse.py:173-177)."""
         # one draw for the GLOBAL batch from the stream every rank shares (one grid shape per step on all replicas, reverse.py:192-193);
@@ -213,14 +242,10 @@ class reverse_poisson_dataset_generator(_generator):
     def _draw_series(self):
         """The host draws every analytic generator starts a batch with, in this order: mode counts per sample, the grid shape and spacings, the
         series coefficients (zero beyond a sample's own mode counts).  -> ncoef (N,2), H, W, dx (N,2), domain_sizes (N,2), coef (N,ka,kb)."""
-        N = self.batch_size
-        ncoef = np.stack([self._grid_sizes(self.fourier_coeff_grid_size_range) for _ in range(N)])       # (N,2)
+        ncoef = self._draw_mode_counts()                                                                  # (N,2)
         shape, dx = self._shape_and_spacings()
         H, W = int(shape[0]), int(shape[1])
-        ka, kb = int(ncoef[:, 0].max()), int(ncoef[:, 1].max())
-        coef = np.zeros((N, ka, kb))
-        for b in range(N):
-            coef[b, :ncoef[b, 0], :ncoef[b, 1]] = 2 * self.rng.uniform(size=(ncoef[b, 0], ncoef[b, 1])) - 1
+        coef = self._draw_coefficients(ncoef)
         domain_sizes = dx * np.array([H, W], dtype=np.float64)[None]     # L = dx * n (reverse.py:203), not dx*(n-1)
         return ncoef, H, W, dx, domain_sizes, coef
 
@@ -340,16 +365,6 @@ class numerical_dataset_generator(_generator):
         self.nda.pop('normalizations', None)
         self.rng, self.shape_rng, self.shard = _streams(seed, shard)
         self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
-
-    def _smooth_field(self, ctrl, out_hw, max_magnitude):
-        """generate_random_RHS / generate_random_boundaries core (numerical.py:10-72): control points -> legacy bicubic
-        (align_corners) up-sampling -> per-sample max-magnitude scaling."""
-        N = ctrl.shape[0]
-        x = self._dev(ctrl).view(N, ctrl.shape[1], ctrl.shape[2], 1)
-        y = K.resize_legacy_bicubic(x, out_hw).view(N, out_hw[0], out_hw[1])
-        if max_magnitude != np.inf:
-            K.set_max_magnitude(y, torch.full((N,), float(max_magnitude), device=self.device))
-        return y
 
     def _edge(self, ctrl, length, max_magnitude):
         """One edge array (N, length): the smooth function through the already drawn control values ctrl (N, k), or zeros when ctrl is None."""
@@ -615,6 +630,24 @@ def compressible_poisson_solve(rho, rhses, boundaries, dx, dy=None, system_matri
     return variable_density_poisson_solve(rho, rhses, boundaries, dx, dy=dy, preconditioner=preconditioner)
 
 
+def _check_density_range(density_range):
+    lo, hi = float(density_range[0]), float(density_range[1])
+    if not 0.0 < lo <= hi:
+        raise ValueError('density_range = (lo, hi) needs 0 < lo <= hi, got %r' % (density_range,))
+    return lo, hi
+
+
+def _check_density_profile(density_profile):
+    if density_profile not in VARIABLE_DENSITY_PROFILES:
+        raise ValueError('density_profile must be one of %r, got %r' % (VARIABLE_DENSITY_PROFILES, density_profile))
+
+
+def _check_smoothness_ranges(**ranges):
+    for name, rg in ranges.items():
+        if not 2 <= int(rg[0]) <= int(rg[1]):
+            raise ValueError('%s = (lo, hi) needs 2 <= lo <= hi control points, got %r' % (name, rg))
+
+
 class variable_density_dataset_generator(numerical_dataset_generator):
     """Random smooth right-hand side F and density rho -> the variable-density solve: generate_dataset of the reference's
     dataset/generators/variable_density, which returns (soln, stack([F, rho], axis=1)).  Keras order here (return_keras_style):
@@ -645,19 +678,14 @@ class variable_density_dataset_generator(numerical_dataset_generator):
                          shard=shard)
         self.boundary_types = boundary_types
         self.neumann_flags = _neumann_flags(boundary_types) if boundary_types is not None else (False,) * 4      # (left, right, bottom, top)
-        lo, hi = float(density_range[0]), float(density_range[1])
-        if not 0.0 < lo <= hi:
-            raise ValueError('density_range = (lo, hi) needs 0 < lo <= hi, got %r' % (density_range,))
+        lo, hi = _check_density_range(density_range)
         if boundaries not in ('zero', 'random'):
             raise ValueError("boundaries must be 'zero' or 'random'")
         if preconditioner not in VARIABLE_DENSITY_PRECONDITIONERS:
             raise ValueError('preconditioner must be one of %r, got %r' % (VARIABLE_DENSITY_PRECONDITIONERS, preconditioner))
-        if density_profile not in VARIABLE_DENSITY_PROFILES:
-            raise ValueError('density_profile must be one of %r, got %r' % (VARIABLE_DENSITY_PROFILES, density_profile))
+        _check_density_profile(density_profile)
         self.preconditioner, self.density_profile = preconditioner, density_profile
-        for name, rg in (('rhs_smoothness_range', rhs_smoothness_range), ('density_smoothness_range', density_smoothness_range)):
-            if not 2 <= int(rg[0]) <= int(rg[1]):
-                raise ValueError('%s = (lo, hi) needs 2 <= lo <= hi control points, got %r' % (name, rg))
+        _check_smoothness_ranges(rhs_smoothness_range=rhs_smoothness_range, density_smoothness_range=density_smoothness_range)
         self.output_shape = None if output_shape is None else (int(output_shape[0]), int(output_shape[1]))
         self.random_output_shape_range = np.asarray(random_output_shape_range, dtype=np.int64).reshape(2, 2)
         self.density_range = (lo, hi)
@@ -677,8 +705,7 @@ class variable_density_dataset_generator(numerical_dataset_generator):
         ctrl = lambda rg: [int(rng.integers(rg[0], rg[1] + 1)) for _ in range(2)]
         nf, nr = ctrl(self.rhs_smoothness_range), ctrl(self.density_smoothness_range)
         rhs = self._smooth_field(2 * rng.uniform(size=(N, nf[0], nf[1])) - 1, (H, W), self.rhs_max_magnitude)
-        density = K.varcoef_density_smooth if self.density_profile == 'smooth' else K.varcoef_density
-        rho = density(self._smooth_field(2 * rng.uniform(size=(N, nr[0], nr[1])) - 1, (H, W), 1.0), *self.density_range)
+        rho = self._density_field(2 * rng.uniform(size=(N, nr[0], nr[1])) - 1, (H, W))
         lengths = {'left': W, 'right': W, 'top': H, 'bottom': H}
         bc = {}
         for k in _BOUNDARY_KEYS:
@@ -699,3 +726,80 @@ class variable_density_dataset_generator(numerical_dataset_generator):
         if self.boundaries == 'random':
             inp += [bc[k].view(N, 1, -1) for k in _BOUNDARY_KEYS]
         return inp + [d], soln
+
+
+class reverse_variable_density_dataset_generator(_generator):
+    """Solve-free pairs of the variable-density problem div((1/rho) grad u) = f: a random series u in the homogeneous
+    eigenfunction families of the edge types (reverse_poisson_dataset_generator_mixed's: u = 0 on a Dirichlet edge, du/dn = 0 on a Neumann one), a
+    random rho, and the DISCRETE right-hand side f = L_h(rho) u of the flux form the solver, the loss, the smoother and the metrics share - one
+    launch (K.varcoef_series_pair: u is synthesised and differenced in fp64, only soln and rhs are rounded), whatever the density ratio.  The target
+    is what variable_density_poisson_solve returns for that rhs and rho, to the fp32 rounding of the two fields.
+
+    Yields variable_density_dataset_generator's structure for boundaries = 'zero': ([stack([rhs, rho], axis=1), dx], soln) with return_keras_style,
+    else the reference's pair (soln, stack); Homogeneous_Poisson_NN_Legacy(density_input=True, boundary_types=...) trains on it (train.py
+    --dataset_type variable_density_analytical).  The data differ in kind: here u is band limited (fourier_coeff_grid_size_range modes per axis,
+    at most 16) and rhs inherits rho's kinks; the solver-made batches have independent smooth rhs and rho.
+
+    Mode counts and coefficients are drawn as reverse_poisson_dataset_generator draws them, rho as variable_density_dataset_generator draws it
+    (density_range, density_smoothness_range, density_profile), one grid shape per batch (output_shape, or drawn from random_output_shape_range)
+    and one spacing per sample from random_dx_range.  The problem is linear in (u, f): each sample's rhs and soln are scaled by one factor so that
+    max|rhs| = rhs_max_magnitude (None: as synthesised); rho is untouched.  boundary_types: dict edge -> 'dirichlet' | 'neumann' (None: all
+    Dirichlet).  With all four edges Neumann the cosine modes A >= 1 have zero trapezoidal sum on the grid: soln has the zero weighted integral
+    of the solver's convention and rhs is compatible by construction - no projection, no rhs_shift."""
+
+    def __init__(self, batch_size=1, batches_per_epoch=1, fourier_coeff_grid_size_range=(1, 8), output_shape=None,
+                 random_output_shape_range=((64, 85), (64, 85)), density_range=(1.0, 10.0), density_smoothness_range=(5, 20), density_profile='abs',
+                 random_dx_range=(0.005, 0.05), boundary_types=None, rhs_max_magnitude=1.0, seed=0, device=None, return_keras_style=True, shard=None):
+        # everything that can be refused without a device is refused first
+        self.batch_size, self.batches_per_epoch = int(batch_size), int(batches_per_epoch)
+        self.boundary_types = boundary_types
+        self.neumann_flags = _neumann_flags(boundary_types) if boundary_types is not None else (False,) * 4      # (left, right, bottom, top)
+        self.density_range = _check_density_range(density_range)
+        _check_density_profile(density_profile)
+        self.density_profile = density_profile
+        _check_smoothness_ranges(density_smoothness_range=density_smoothness_range)
+        self.density_smoothness_range = tuple(density_smoothness_range)
+        fr = np.asarray(fourier_coeff_grid_size_range, dtype=np.float64)
+        fr = np.tile(fr[None], (2, 1)) if fr.ndim == 1 else fr
+        if fr.shape != (2, 2) or not np.all((0 <= fr[:, 0]) & (fr[:, 0] <= fr[:, 1])):
+            raise ValueError('fourier_coeff_grid_size_range = (lo, hi), or one such pair per axis, needs 0 <= lo <= hi, got %r' % (fourier_coeff_grid_size_range,))
+        most = np.where(fr[:, 0] == fr[:, 1], np.floor(fr[:, 1] + 1), np.ceil(fr[:, 1] + 1) - 1)          # the largest count _grid_sizes can return
+        if most.max() > ops.VARCOEF_SERIES_MAX_MODES:
+            raise ValueError('fourier_coeff_grid_size_range %r allows %d modes along an axis: the series kernel takes at most %d'
+                             % (fourier_coeff_grid_size_range, int(most.max()), ops.VARCOEF_SERIES_MAX_MODES))
+        self.fourier_coeff_grid_size_range = fr
+        if output_shape is not None and (len(output_shape) != 2 or min(int(s) for s in output_shape) < 3):
+            raise ValueError('output_shape = (H, W) needs at least 3 points per axis, got %r' % (output_shape,))
+        self.output_shape = None if output_shape is None else (int(output_shape[0]), int(output_shape[1]))
+        self.random_output_shape_range = np.asarray(random_output_shape_range, dtype=np.int64).reshape(2, 2)
+        if output_shape is None and not np.all((3 <= self.random_output_shape_range[:, 0]) & (self.random_output_shape_range[:, 0] <= self.random_output_shape_range[:, 1])):
+            raise ValueError('random_output_shape_range = ((lo, hi), (lo, hi)) needs 3 <= lo <= hi points per axis, got %r' % (random_output_shape_range,))
+        self.random_dx_range = (float(random_dx_range[0]), float(random_dx_range[1]))
+        if not 0.0 < self.random_dx_range[0] <= self.random_dx_range[1]:
+            raise ValueError('random_dx_range = (lo, hi) needs 0 < lo <= hi, got %r' % (random_dx_range,))
+        if rhs_max_magnitude is not None and not float(rhs_max_magnitude) > 0.0:
+            raise ValueError('rhs_max_magnitude must be positive or None, got %r' % (rhs_max_magnitude,))
+        self.rhs_max_magnitude = None if rhs_max_magnitude is None else float(rhs_max_magnitude)
+        self.return_keras_style = return_keras_style
+        self.rng, self.shape_rng, self.shard = _streams(seed, shard)
+        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+
+    def __getitem__(self, idx=0):
+        N, rng = self.batch_size, self.rng
+        if self.output_shape is not None:
+            H, W = self.output_shape
+        else:                                                              # the grid shape comes from the stream all ranks share (see _streams)
+            H, W = [int(self.shape_rng.integers(r[0], r[1] + 1)) for r in self.random_output_shape_range]
+        dx = rng.uniform(size=(N, 1)) * (self.random_dx_range[1] - self.random_dx_range[0]) + self.random_dx_range[0]
+        coef = self._draw_coefficients(self._draw_mode_counts())
+        nr = [int(rng.integers(self.density_smoothness_range[0], self.density_smoothness_range[1] + 1)) for _ in range(2)]
+        rho = self._density_field(2 * rng.uniform(size=(N, nr[0], nr[1])) - 1, (H, W))
+        d = self._dev(dx)
+        soln, rhs = K.varcoef_series_pair(self._dev(coef), rho, d, self.neumann_flags)
+        if self.rhs_max_magnitude is not None:                             # linear in (u, f): one factor per sample for both
+            K.scale_samples(soln, K.set_max_magnitude(rhs, torch.full((N,), self.rhs_max_magnitude, device=self.device)))
+        frho = torch.stack([rhs, rho], dim=1)
+        soln = soln.view(N, 1, H, W)
+        if not self.return_keras_style:
+            return soln, frho
+        return [frho, d], soln

@@ -290,6 +290,12 @@ def varcoef_density_smooth(g, lo, hi):
     return g
 
 
+def varcoef_series_pair(coef, rho, dx, neumann=(False, False, False, False)):
+    """coef (N,ka,kb), rho (N,H,W), dx (N,), `neumann` = (left, right, bottom, top) -> (soln, rhs), each (N,H,W): the series of the edge types'
+    eigenfunction families and the discrete right-hand side L_h(rho) soln of the same launch (ops.varcoef_series_pair, pcnn_varcoef_series_pair)."""
+    return ops.varcoef_series_pair(coef, rho, dx, _neumann_mask(neumann))
+
+
 def series_synthesis(coef, H, W, trig, out=None, accumulate=False):
     """coef (N,ka,kb) -> (N,H,W): sum c[A,B] f((A+1)x) f((B+1)y), f = sin (trig=0) / cos (trig=1)."""
     N, ka, kb = coef.shape

@@ -1176,6 +1176,28 @@ def varcoef_jacobi_bwd(dout, rho, dx, n_sweeps, neumann_mask=0):
     return du
 
 
+VARCOEF_SERIES_MAX_MODES = 16      # VSER_MAXK of csrc/varcoef.hip
+
+
+def varcoef_series_pair(coef, rho, dx, neumann_mask=0):
+    """(soln, rhs), each (N,H,W) float32, of the discrete variable-density problem without a solve (pcnn_varcoef_series_pair):
+    soln = sum c[A,B] phi_A(x) psi_B(y) in the homogeneous eigenfunction families of the mask's edge types, synthesised in fp64, and
+    rhs = L_h(rho) soln on the unknowns of the mask (0 elsewhere), differenced in fp64 before either field is rounded.
+    coef (N,ka,kb) with ka, kb <= 16; rho (N,H,W), (N,1,H,W) or (N,H,W,1), positive (not checked); dx (N,) or (N,1); all CUDA float32.
+    neumann_mask: an int 0..15 (bits as bc_ring_fwd's) or four flags (left, right, bottom, top)."""
+    who = 'varcoef_series_pair'
+    N, H, W, (rho,), dx = _varcoef_fields(who, {'rho': rho}, dx)
+    mask = _varcoef_mask(who, neumann_mask)
+    if not isinstance(coef, torch.Tensor) or coef.dtype != torch.float32 or not coef.is_cuda or coef.dim() != 3 or coef.shape[0] != N or not coef.is_contiguous():
+        raise ValueError('%s: coef must be a contiguous CUDA float32 (%d,ka,kb) tensor, got %s' % (who, N, tuple(getattr(coef, 'shape', ()))))
+    ka, kb = int(coef.shape[1]), int(coef.shape[2])
+    if not (1 <= ka <= VARCOEF_SERIES_MAX_MODES and 1 <= kb <= VARCOEF_SERIES_MAX_MODES):
+        raise ValueError('%s: %d x %d modes unsupported (1..%d per axis)' % (who, ka, kb, VARCOEF_SERIES_MAX_MODES))
+    soln, rhs = empty((N, H, W), rho.device), empty((N, H, W), rho.device)
+    handle().call('pcnn_varcoef_series_pair', c_int(N), c_int(H), c_int(W), c_int(ka), c_int(kb), _p(coef), c_int(mask), _p(rho), _p(dx), _p(soln), _p(rhs))
+    return soln, rhs
+
+
 def assemble_density_input(stack, use_pos=True):
     """The generator's (N,2,H,W) stack [rhs, rho] -> NHWC [rhs | rho | cos(pi y) | cos(pi x)] (the last two with use_pos)."""
     if stack.dim() != 4 or stack.shape[1] != 2 or stack.dtype != torch.float32 or not stack.is_cuda or not stack.is_contiguous():

@@ -1,7 +1,7 @@
 """Optimizers, callbacks and the training entry point (drop-in for poisson_CNN/train/hpnn_legacy_train.py and train/utils.py).
 
-python -m poisson_cnn_amd.train config.json [--checkpoint_dir D] [--continue_from_checkpoint D] [--dataset_type analytical|analytical_mixed|numerical|variable_density]
-                                            [--learning_rate X|from_json]
+python -m poisson_cnn_amd.train config.json [--checkpoint_dir D] [--continue_from_checkpoint D] [--dataset_type analytical|analytical_mixed|numerical|variable_density|
+                                            variable_density_analytical] [--learning_rate X|from_json]
 Under `torchrun` (WORLD_SIZE > 1) the batch is sharded over ranks and gradients are all-reduced over RCCL
 (parallel.DataParallel), replacing the reference's tf.distribute.MirroredStrategy (train/hpnn_legacy_train.py:37-38).
 `analytical_mixed` (extension): the analytic generator with a boundary type per edge, for a Homogeneous_Poisson_NN_Legacy whose bc_type is a dict.
@@ -9,6 +9,9 @@ Under `torchrun` (WORLD_SIZE > 1) the batch is sharded over ranks and gradients 
 --model hpnn with "density_input": true in the model section; the config's loss is then built as losses.variable_density_loss_wrapper.
 "boundary_types" and "residual_metrics" in that model section reach the model as its keywords of the same names; "preconditioner" ('dst' |
 'scaled') and "density_profile" ('abs' | 'smooth') in the dataset section, when present, reach the generator as its keywords of the same names.
+`variable_density_analytical` (extension): dataset.reverse_variable_density_dataset_generator, the same problem, model, loss and consistency rules
+with solve-free data - a random series u, a random rho and the discrete right-hand side L_h(rho) u from one launch; its
+dataset section takes "fourier_coeff_grid_size_range" in place of the solver's keywords.
 """
 import argparse
 import json
@@ -303,13 +306,16 @@ def load_model_checkpoint(model, checkpoint_path, **unused):
         model.load_weights(path)
 
 
+_DENSITY_DATASET_TYPES = ('variable_density', 'variable_density_analytical')      # the dataset types behind a "density_input" model
+
+
 def main(argv=None):
     from . import configs
     from .utils import convert_tf_object_names, neumann_flags
     from .models import Homogeneous_Poisson_NN_Legacy, Dirichlet_BC_NN_Legacy_2, Poisson_CNN_Legacy
     from .losses import loss_wrapper, variable_density_loss_wrapper
     from .dataset import (numerical_dataset_generator, reverse_poisson_dataset_generator, reverse_poisson_dataset_generator_homogeneous_neumann,
-                          reverse_poisson_dataset_generator_mixed, variable_density_dataset_generator)
+                          reverse_poisson_dataset_generator_mixed, reverse_variable_density_dataset_generator, variable_density_dataset_generator)
     from . import parallel
     p = argparse.ArgumentParser(description='Train the Homogeneous Poisson NN')
     p.add_argument('config', type=str)
@@ -322,20 +328,22 @@ def main(argv=None):
                    help='hpnn: train/hpnn_legacy_train.py (train/hpnn_train.py when the model section carries model_type); dbcnn: train/dbcnn_legacy_train.py; '
                         'pcnn: train/pcnn_end_to_end.py; unet: train/UNet.py; dbcnn_rnn: train/dbcnn_rnn_train.py')
     args = p.parse_args(argv)
-    if args.dataset_type not in ('numerical', 'analytical', 'analytical_mixed', 'variable_density'):
+    if args.dataset_type not in ('numerical', 'analytical', 'analytical_mixed') + _DENSITY_DATASET_TYPES:
         raise ValueError('Invalid dataset type. Received: ' + args.dataset_type)
     config = convert_tf_object_names(configs.load_config(args.config))
     msec = config.get('model', {})
     density_model = bool(msec.get('density_input', False))
-    if args.dataset_type == 'variable_density' and (args.model != 'hpnn' or 'model_type' in msec or not density_model):
-        raise ValueError('--dataset_type variable_density yields the two-channel input [rhs, rho]: it needs --model hpnn and "density_input": true in the '
-                         "config's model section (got --model %s, density_input %r)" % (args.model, msec.get('density_input', False)))
-    if args.dataset_type == 'variable_density' and config.get('dataset', {}).get('boundaries', 'zero') != 'zero':
-        raise ValueError("--dataset_type variable_density trains the homogeneous model: it needs boundaries 'zero' in the dataset section (got %r; with "
+    density_data = args.dataset_type in _DENSITY_DATASET_TYPES      # both yield the stack [rhs, rho] and share every consistency rule below
+    flag = '--dataset_type ' + args.dataset_type
+    if density_data and (args.model != 'hpnn' or 'model_type' in msec or not density_model):
+        raise ValueError('%s yields the two-channel input [rhs, rho]: it needs --model hpnn and "density_input": true in the '
+                         "config's model section (got --model %s, density_input %r)" % (flag, args.model, msec.get('density_input', False)))
+    if density_data and config.get('dataset', {}).get('boundaries', 'zero') != 'zero':
+        raise ValueError("%s trains the homogeneous model: it needs boundaries 'zero' in the dataset section (got %r; with "
                          "'random' the generator yields the four edge arrays as further inputs, which no model here reads) - drop the key or set it to "
-                         "'zero'" % (config['dataset']['boundaries'],))
+                         "'zero'" % (flag, config['dataset']['boundaries'],))
     model_bt = msec.get('boundary_types') if density_model else None
-    if args.dataset_type == 'variable_density' and model_bt is not None:
+    if density_data and model_bt is not None:
         # the model, its loss and the generator's ground truth share one set of edge types: the dataset section names the same ones or none
         if not isinstance(model_bt, dict):
             raise ValueError("the model section's boundary_types is a dict edge -> 'dirichlet' | 'neumann', got %r" % (model_bt,))
@@ -343,17 +351,18 @@ def main(argv=None):
         if dsec.get('boundary_types') is None:
             dsec['boundary_types'] = dict(model_bt)
         elif neumann_flags(dsec['boundary_types']) != neumann_flags(model_bt):
-            raise ValueError('--dataset_type variable_density: the model section has boundary_types %r and the dataset section %r - the ground truth '
+            raise ValueError('%s: the model section has boundary_types %r and the dataset section %r - the ground truth '
                              'must be solved with the edge types the model and its loss use; make the two equal or drop the dataset section\'s'
-                             % (model_bt, dsec['boundary_types']))
-    elif args.dataset_type == 'variable_density' and any(neumann_flags(config.get('dataset', {}).get('boundary_types'))):
-        raise ValueError('--dataset_type variable_density with Neumann boundary_types %r in the dataset section: the solver and the generator take '
+                             % (flag, model_bt, dsec['boundary_types']))
+    elif density_data and any(neumann_flags(config.get('dataset', {}).get('boundary_types'))):
+        raise ValueError('%s with Neumann boundary_types %r in the dataset section: the solver and the generator take '
                          'per-edge Neumann boundaries, but the model does not - Homogeneous_Poisson_NN_Legacy(density_input=True) has no Neumann bc_type and '
                          'its flux-form loss and smoother keep every edge fixed; drop boundary_types, or give the model section the same '
-                         '"boundary_types" (the keyword of the variable-density model, loss and smoother)' % (config['dataset']['boundary_types'],))
-    if density_model and args.dataset_type != 'variable_density':
-        raise ValueError('a model with "density_input": true reads the stack [rhs, rho], which only --dataset_type variable_density yields (got '
-                         '--dataset_type %s): pass --dataset_type variable_density or drop density_input from the model section' % args.dataset_type)
+                         '"boundary_types" (the keyword of the variable-density model, loss and smoother)' % (flag, config['dataset']['boundary_types'],))
+    if density_model and not density_data:
+        raise ValueError('a model with "density_input": true reads the stack [rhs, rho], which only --dataset_type variable_density and '
+                         'variable_density_analytical yield (got --dataset_type %s): pass one of the two or drop density_input from the model section'
+                         % args.dataset_type)
     if args.dataset_type == 'analytical_mixed' and (args.model != 'hpnn' or 'model_type' in config['model']
                                                     or not isinstance(config['model'].get('bc_type'), dict)):
         raise ValueError('--dataset_type analytical_mixed is the per-edge analytic generator of Homogeneous_Poisson_NN_Legacy: it needs --model hpnn and '
@@ -403,6 +412,8 @@ def main(argv=None):
         neumann = all(flags)
         if args.dataset_type == 'variable_density':        # random smooth rhs and rho, the DST-preconditioned CG solve as ground truth (zero Dirichlet data)
             dataset = variable_density_dataset_generator(**dcfg)
+        elif args.dataset_type == 'variable_density_analytical':       # a random series u and rho, rhs = L_h(rho) u from the same launch: no solve
+            dataset = reverse_variable_density_dataset_generator(**dcfg)
         elif args.dataset_type == 'analytical_mixed':        # the quarter-wave / whole-wave series of the model's own edge types, homogeneous data
             dataset = reverse_poisson_dataset_generator_mixed(**dict(dcfg, boundary_types=bc_type))
         elif args.dataset_type == 'numerical' and isinstance(bc_type, dict):
