@@ -787,6 +787,23 @@ int pcnn_varcoef_bc_jacobi_fwd(pcnn_handle h, int N, int H, int W, const float* 
                                float* out, int neumann_mask);
 int pcnn_varcoef_bc_jacobi_bwd(pcnn_handle h, int N, int H, int W, const float* rho, const float* dx, const float* dout, int n_sweeps, float* du,
                                int neumann_mask);
+/* Gradients with respect to the DATA of the problem (csrc/varcoef_grad.hip): gathers, one thread per output, no atomics, one
+ * launch each, a spacing per sample; neumann_mask 0..15 as above, H, W >= 3.  With the system (A u - b)_c = sum_k m_k beta_k (u_c - u_k) / dx^2 + f_c
+ * - sum_e 2 g_e / (rho_c dx) on the unknowns and lam (N,H,W) its adjoint variable (A^T lam = d loss / d u on the unknowns, 0 on every other node):
+ *   coef_grad: drho_p = sum over the faces (c, k) that touch p of 1/2 beta^2 m lam_c (u_c - u_k) / dx^2 - lam_p sum_e 2 g_e / (rho_p^2 dx) on ALL
+ *     nodes, written (not accumulated).  u (N,H,W) is the full field, Dirichlet values included; left / right (N,W), bottom / top (N,H) are the
+ *     Neumann data (NULL = 0; a Dirichlet edge's array is not read).  fp32 in, differences and sums in fp64, one rounding.  drho aliases no input.
+ *   edge_grad: the gradient of each edge array (NULL: not wanted) - an entry of a Dirichlet edge gets du_d + sum over the node's unknown neighbours
+ *     c of lam_c m beta / dx^2 (du (N,H,W) the direct term d loss / d u, NULL = 0), an entry the solution writer overwrites at a corner (bottom /
+ *     top at a Dirichlet row 0 / H-1) gets 0; an entry of a Neumann edge gets lam_c 2 / (rho_c dx).  The gradient of f is -lam.
+ *   pi_loss_bwd_inputs: the same gradients of coef[n] * pcnn_varcoef_bc_pi_loss_partials[n] w.r.t. rhs and rho (either may be NULL), fused: the
+ *     residual r (fp32, the loss's own code) and lam = 2 coef w r stay in LDS.  fp32 throughout.  The outputs alias no input. */
+int pcnn_varcoef_bc_coef_grad(pcnn_handle h, int N, int H, int W, int neumann_mask, const float* rho, const float* dx, const float* u,
+                              const float* lam, const float* left, const float* right, const float* bottom, const float* top, float* drho);
+int pcnn_varcoef_bc_edge_grad(pcnn_handle h, int N, int H, int W, int neumann_mask, const float* rho, const float* dx, const float* lam,
+                              const float* du /* may be NULL */, float* dleft, float* dright, float* dbottom, float* dtop);
+int pcnn_varcoef_bc_pi_loss_bwd_inputs(pcnn_handle h, int N, int H, int W, const float* pred, const float* rho, const float* rhs, const float* dx,
+                                       const float* coef /*N*/, float* drhs /* may be NULL */, float* drho /* may be NULL */, int neumann_mask);
 /* out[n,y,x,0:2] = {stack[n,0,y,x], stack[n,1,y,x]} of the generator's (N,2,H,W) stack [rhs, rho], followed - use_pos - by the two positional
  * channels of pcnn_assemble_input; ldo >= 2 (4 with use_pos). */
 int pcnn_assemble_density_input(pcnn_handle h, int N, int H, int W, const float* stack, int use_pos, float* out, int ldo);

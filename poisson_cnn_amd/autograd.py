@@ -25,10 +25,13 @@ autograd is the bucket `store.flat_g` the kernels wrote.  The arithmetic is the 
 Rules (the same the hand-chained form has): one forward per backward and per layer object - a layer keeps the activations of ONE call, so a module
 that is applied twice before `backward()` raises instead of differentiating the wrong call (build two layers, as the reference's models do);
 `torch.no_grad()` / `module.eval()` run the inference path (`training=False`: nothing kept, BatchNormalization on its moving statistics).
+
+Also here, and independent of the layers: `variable_density_solve` and `variable_density_residual` put the variable-density Poisson solve and its
+flux-form residual on the tape with gradients with respect to their DATA - `rho`, `rhs`, the edge arrays.
 """
 import torch
 
-__all__ = ['Differentiable', 'differentiable']
+__all__ = ['Differentiable', 'differentiable', 'variable_density_solve', 'variable_density_residual']
 
 
 def _is_float_tensor(v):
@@ -160,3 +163,124 @@ class Differentiable(torch.nn.Module):
 def differentiable(layer):
     """`Differentiable(layer)`, for use as a decorator-style one-liner around a freshly constructed layer."""
     return Differentiable(layer)
+
+
+# ----------------------------------------------------------------------------- the variable-density problem, differentiable in its data (DESIGN.md section 24)
+_EDGES = ('left', 'right', 'bottom', 'top')
+
+
+def _like(grad, t):
+    """A gradient computed on the solver's normalised layout, in the shape and dtype of the input it belongs to (a batch of 1 that was broadcast: summed)."""
+    if grad.numel() != t.numel():
+        grad = grad.reshape(grad.shape[0], -1).sum(0)
+    return grad.reshape(t.shape).to(t.dtype)
+
+
+class _VariableDensitySolve(torch.autograd.Function):
+    """forward = dataset.variable_density_poisson_solve; backward = one adjoint solve with the same solver, then the gathers of csrc/varcoef_grad.hip."""
+
+    @staticmethod
+    def forward(ctx, rho, rhs, left, right, bottom, top, dx, opts, adjoint_tol, initial_guesses):
+        from . import dataset as D
+        edges = dict(zip(_EDGES, (left, right, bottom, top)))
+        soln = D.variable_density_poisson_solve(rho, rhs, edges, dx, initial_guesses=initial_guesses, **opts)
+        ctx.opts, ctx.adjoint_tol = opts, adjoint_tol
+        ctx.save_for_backward(rho, rhs, left, right, bottom, top, dx, soln)
+        return soln
+
+    @staticmethod
+    def backward(ctx, dy):
+        from . import dataset as D, ops
+        from .dataset import _kernels as K
+        rho, rhs, left, right, bottom, top, dx, soln = ctx.saved_tensors
+        inputs = (rho, rhs, left, right, bottom, top)
+        need = ctx.needs_input_grad[:6]
+        N, _, H, W = soln.shape
+        neumann = D.neumann_flags(ctx.opts['boundary_types']) if ctx.opts['boundary_types'] is not None else (False,) * 4
+        mask = sum(int(f) << k for k, f in enumerate(neumann))
+        r, b, d, dev = D._solver_args(rhs.detach(), {k: v.detach() for k, v in zip(_EDGES, inputs[2:])}, dx.detach(), soln.device)
+        dens = rho.detach().to(device=dev, dtype=torch.float32).reshape(N, H, W).contiguous()
+        # A^T lam = du on the unknowns.  W A is symmetric: A mu = W^-1 du, lam = W mu - the solver's own system with the right-hand side field
+        # -W^-1 du (its b is -f) and zero edge data, cold start.  An adjoint that has not converged raises the solver's RuntimeWarning.
+        du = dy.detach().to(torch.float32).reshape(N, H, W).contiguous()
+        (i0, i1), (j0, j1) = K.varcoef_unknowns(H, W, neumann)
+        wi, wj = K.varcoef_weights(H, W, neumann, dev)
+        w = torch.zeros((H, W), dtype=torch.float32, device=dev)
+        w[i0:i1 + 1, j0:j1 + 1] = (wi[:, None] * wj[None, :]).to(torch.float32)
+        winv = torch.where(w > 0, 1.0 / w.clamp_min(0.25), w)                    # 1, 2 or 4: exact
+        zero = {k: torch.zeros_like(b[k]) for k in _EDGES}
+        mu = D.variable_density_poisson_solve(dens, -(du * winv), zero, d, **dict(ctx.opts, tol=ctx.adjoint_tol))
+        lam = (mu.reshape(N, H, W) * w).contiguous()
+        grads = [None] * 6
+        if need[0]:
+            grads[0] = _like(ops.varcoef_coef_grad(lam, soln.reshape(N, H, W), dens, d, mask, {k: b[k] for k, f in zip(_EDGES, neumann) if f}), rho)
+        if need[1]:
+            grads[1] = _like(-lam, rhs)
+        if any(need[2:]):
+            for i, g in enumerate(ops.varcoef_edge_grad(lam, dens, d, mask, du)):
+                if need[2 + i]:
+                    grads[2 + i] = _like(g, inputs[2 + i])
+        return (*grads, None, None, None, None)
+
+
+def variable_density_solve(rho, rhs, boundaries, dx, boundary_types=None, tol=1e-10, max_iterations=500, check_every=8, preconditioner='dst',
+                           initial_guesses=None, adjoint_tol=None):
+    """`dataset.variable_density_poisson_solve` on the `torch.autograd` tape: the (N,1,H,W) float32 solution of div((1/rho) grad u) = rhs, bit for bit
+    the solver's, differentiable with respect to `rho`, `rhs` and the four arrays of `boundaries` (Dirichlet values or Neumann du/dn) - whichever of
+    them `requires_grad`.  Tensors on the device in the solver's shapes; `dx` and `initial_guesses` get no gradient.
+
+    backward is one more solve of the same system (same rho, dx, boundary_types, preconditioner, max_iterations, check_every; tolerance `adjoint_tol`,
+    default `tol`; cold start) for the adjoint variable lam, then two gather kernels (ops.varcoef_coef_grad, ops.varcoef_edge_grad; d rhs = -lam).
+    An adjoint solve that has not converged raises the solver's RuntimeWarning.  Without an input that requires grad, or under torch.no_grad(),
+    nothing but the forward solve runs.  Refused: all four edges Neumann (the singular system the solver projects and shifts), and the solver's own
+    refusals (anisotropic spacing among them)."""
+    from . import dataset as D
+    if boundary_types is not None and all(D.neumann_flags(boundary_types)):
+        raise NotImplementedError('variable_density_solve: the all-Neumann problem is singular (the solver projects the data and fixes the mean); '
+                                  'its derivative is not built - use variable_density_poisson_solve for the solution itself')
+    missing = [k for k in _EDGES if k not in boundaries]
+    if missing:
+        raise ValueError('boundaries lacks %r' % (missing,))
+    for name, t in (('rho', rho), ('rhs', rhs), ('dx', dx)) + tuple((k, boundaries[k]) for k in _EDGES):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError('variable_density_solve: %s must be a tensor on the device' % name)
+    opts = dict(tol=float(tol), max_iterations=int(max_iterations), check_every=int(check_every), preconditioner=preconditioner, boundary_types=boundary_types)
+    return _VariableDensitySolve.apply(rho, rhs, boundaries['left'], boundaries['right'], boundaries['bottom'], boundaries['top'], dx, opts,
+                                       float(tol if adjoint_tol is None else adjoint_tol), initial_guesses)
+
+
+class _VariableDensityResidual(torch.autograd.Function):
+    """forward = ops.varcoef_pi_loss_partials; backward = ops.varcoef_pi_loss_bwd (pred) and ops.varcoef_pi_loss_bwd_inputs (the stack)."""
+
+    @staticmethod
+    def forward(ctx, pred, stack, dx, mask):
+        from . import ops
+        p = pred.detach().contiguous()
+        rhs, rho, d = stack.detach()[:, 0].contiguous(), stack.detach()[:, 1].contiguous(), dx.detach().reshape(dx.shape[0], -1)[:, 0].contiguous()
+        ctx.mask = mask
+        ctx.save_for_backward(p, rhs, rho, d)
+        return ops.varcoef_pi_loss_partials(p, rho, rhs, d, mask)
+
+    @staticmethod
+    def backward(ctx, dout):
+        from . import ops
+        p, rhs, rho, d = ctx.saved_tensors
+        coef = dout.detach().to(torch.float32).contiguous()
+        dpred = dstack = None
+        if ctx.needs_input_grad[0]:
+            dpred = ops.varcoef_pi_loss_bwd(p, rho, rhs, d, coef, torch.zeros_like(p), ctx.mask)        # the kernel accumulates
+        if ctx.needs_input_grad[1]:
+            dstack = torch.stack(ops.varcoef_pi_loss_bwd_inputs(p, rho, rhs, d, coef, ctx.mask), dim=1)
+        return dpred, dstack, None, None
+
+
+def variable_density_residual(pred, stack, dx, boundary_types=None):
+    """(N,) the physics-informed residual sums `ops.varcoef_pi_loss_partials(pred, rho, rhs, dx, mask)` - sum over the unknowns of w (L_rho pred - rhs)^2
+    - on the tape: `pred` (N,1,H,W) or (N,H,W), `stack` (N,2,H,W) = [rhs, rho] as the generator hands it out, `dx` (N,), (N,1) or (N,2) (the first
+    column), CUDA float32.  The gradient w.r.t. `pred` is ops.varcoef_pi_loss_bwd into zeros, that w.r.t. both channels of `stack` comes from one fused
+    launch (ops.varcoef_pi_loss_bwd_inputs).  boundary_types: dict edge -> 'dirichlet' | 'neumann' (None: all Dirichlet); every mask is allowed."""
+    from . import dataset as D
+    if not isinstance(stack, torch.Tensor) or stack.dim() != 4 or stack.shape[1] != 2:
+        raise ValueError('variable_density_residual: stack must be (N,2,H,W) = [rhs, rho], got %r' % (tuple(getattr(stack, 'shape', ())),))
+    neumann = D.neumann_flags(boundary_types) if boundary_types is not None else (False,) * 4
+    return _VariableDensityResidual.apply(pred, stack, dx, sum(int(f) << k for k, f in enumerate(neumann)))

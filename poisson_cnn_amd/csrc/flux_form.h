@@ -54,3 +54,28 @@ __device__ __forceinline__ void pcnn_load_nodes(T (*t)[LC], const T* __restrict_
     t[r][c] = (i >= 0 && i < H && j >= 0 && j < W) ? src[(int64_t)i * W + j] : fill;
   }
 }
+
+// The residual on an output tile's nodes and a one-node halo, for the gathers that transpose L: es (r, c) is node (I0 - 1 + r, J0 - 1 + c), us / rs hold
+// u / rho one node further out (LDS (a, b) is node (I0 - 2 + a, J0 - 2 + b), loaded by pcnn_load_nodes[_mirrored]).  An entry holds pcnn_flux_residual
+// on an unknown of `un` and 0 on a Dirichlet node or outside the field; BC: beyond a Neumann edge it holds the residual of its mirror image, which
+// lies within the two-node halo.  keep(v, i, j) -> what is stored for the entry of (unmirrored) node (i, j): the identity for the loss gradient,
+// the weighted adjoint of varcoef_grad.hip.  All FLUX_THREADS threads call it between two barriers of their own.
+template <bool BC, int ER, int EC, int LC, class Keep>
+__device__ __forceinline__ void pcnn_flux_residual_halo(float (*es)[EC], const float (*us)[LC], const float (*rs)[LC], const float* __restrict__ rhs,
+                                                        int H, int W, int I0, int J0, int mask, const FdUnknowns& un, float inv_h2, Keep keep) {
+  for (int e = threadIdx.x; e < ER * EC; e += FLUX_THREADS) {
+    const int r = e / EC, c = e % EC;
+    int i = I0 - 1 + r, j = J0 - 1 + c;
+    if (BC) {                        // the node whose residual this entry holds: beyond a Neumann edge the mirror image, within the tile's two-node halo
+      i = vc_mirror(i, H, mask & 1, mask & 2);
+      j = vc_mirror(j, W, mask & 4, mask & 8);
+    }
+    float v = 0.f;
+    if (i >= un.i0 && i <= un.i1 && j >= un.j0 && j <= un.j1) {
+      const int a = i - (I0 - 2), b = j - (J0 - 2);
+      v = pcnn_flux_residual(us[a][b], rs[a][b], us[a - 1][b], rs[a - 1][b], us[a + 1][b], rs[a + 1][b], us[a][b - 1], rs[a][b - 1], us[a][b + 1],
+                             rs[a][b + 1], inv_h2, rhs[(int64_t)i * W + j]);
+    }
+    es[r][c] = keep(v, I0 - 1 + r, J0 - 1 + c);
+  }
+}

@@ -108,21 +108,7 @@ __global__ __launch_bounds__(FLUX_THREADS) void vc_pi_bwd_kernel(int H, int W, i
   }
   __syncthreads();
   const float h = dx[n], inv_h2 = 1.f / (h * h);
-  for (int e = threadIdx.x; e < ER * EC; e += FLUX_THREADS) {
-    const int r = e / EC, c = e % EC;
-    int i = I0 - 1 + r, j = J0 - 1 + c;
-    if (BC) {                        // the node whose residual this entry holds: beyond a Neumann edge the mirror image, within the tile's two-node halo
-      i = vc_mirror(i, H, mask & 1, mask & 2);
-      j = vc_mirror(j, W, mask & 4, mask & 8);
-    }
-    float v = 0.f;
-    if (i >= un.i0 && i <= un.i1 && j >= un.j0 && j <= un.j1) {
-      const int a = i - (I0 - 2), b = j - (J0 - 2);
-      v = pcnn_flux_residual(us[a][b], rs[a][b], us[a - 1][b], rs[a - 1][b], us[a + 1][b], rs[a + 1][b], us[a][b - 1], rs[a][b - 1], us[a][b + 1],
-                             rs[a][b + 1], inv_h2, rhs[img + (int64_t)i * W + j]);
-    }
-    es[r][c] = v;
-  }
+  pcnn_flux_residual_halo<BC, ER, EC, LC>(es, us, rs, rhs + img, H, W, I0, J0, mask, un, inv_h2, [](float v, int, int) { return v; });
   __syncthreads();
   const float scale = 2.f * coef[n] * inv_h2;
   const int c = threadIdx.x % FLUX_COLS, r0 = (threadIdx.x / FLUX_COLS) * FLUX_RPT;

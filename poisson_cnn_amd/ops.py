@@ -1176,6 +1176,71 @@ def varcoef_jacobi_bwd(dout, rho, dx, n_sweeps, neumann_mask=0):
     return du
 
 
+_VARCOEF_EDGES = ('left', 'right', 'bottom', 'top')
+
+
+def _varcoef_edge_arrays(who, data, N, H, W):
+    """The four edge arrays of a variable-density call - None, or a dict with 'left' / 'right' (N,W) and 'bottom' / 'top' (N,H); a missing or None
+    entry is zero data - as contiguous CUDA float32 tensors or None, in the order left, right, bottom, top."""
+    out = []
+    for k in _VARCOEF_EDGES:
+        t = None if data is None else data.get(k)
+        if t is not None:
+            n = W if k in ('left', 'right') else H
+            if t.dtype != torch.float32 or not t.is_cuda or t.numel() != N * n or t.shape[0] != N or not t.is_contiguous():
+                raise ValueError('%s: %s must be a contiguous CUDA float32 tensor of %d x %d values' % (who, k, N, n))
+        out.append(t)
+    return out
+
+
+def varcoef_coef_grad(lam, u, rho, dx, neumann_mask=0, neumann_data=None):
+    """d loss / d rho (N,H,W) of the variable-density system from its adjoint variable (pcnn_varcoef_bc_coef_grad): lam is
+    A^T lam = d loss / d u on the unknowns of the mask and 0 on every other node, u the full solution field.  neumann_data: dict edge -> du/dn array
+    of the Neumann edges (None or a missing edge: zero).  fp32 fields, differenced and summed in fp64, rounded once.  The gradient of rhs is -lam."""
+    who = 'varcoef_coef_grad'
+    N, H, W, (lam, u, rho), dx = _varcoef_fields(who, {'lam': lam, 'u': u, 'rho': rho}, dx)
+    mask = _varcoef_mask(who, neumann_mask)
+    left, right, bottom, top = _varcoef_edge_arrays(who, neumann_data, N, H, W)
+    drho = torch.empty_like(rho)
+    handle().call('pcnn_varcoef_bc_coef_grad', c_int(N), c_int(H), c_int(W), c_int(mask), _p(rho), _p(dx), _p(u), _p(lam), _p(left), _p(right), _p(bottom),
+                  _p(top), _p(drho))
+    return drho
+
+
+def varcoef_edge_grad(lam, rho, dx, neumann_mask=0, du=None):
+    """d loss / d (left, right, bottom, top), (N,W), (N,W), (N,H), (N,H), of the variable-density system from its adjoint variable lam
+    (pcnn_varcoef_bc_edge_grad): a Dirichlet edge's values get du there (the direct term, None: zero) plus what the unknowns next to them pass on - 0
+    where the writer overwrites the entry at a corner -, a Neumann edge's du/dn gets lam 2 / (rho dx)."""
+    who = 'varcoef_edge_grad'
+    fields = {'lam': lam, 'rho': rho}
+    if du is not None:
+        fields['du'] = du
+    N, H, W, f, dx = _varcoef_fields(who, fields, dx)
+    mask = _varcoef_mask(who, neumann_mask)
+    dleft, dright, dbottom, dtop = empty((N, W), rho.device), empty((N, W), rho.device), empty((N, H), rho.device), empty((N, H), rho.device)
+    handle().call('pcnn_varcoef_bc_edge_grad', c_int(N), c_int(H), c_int(W), c_int(mask), _p(f[1]), _p(dx), _p(f[0]), _p(f[2] if du is not None else None),
+                  _p(dleft), _p(dright), _p(dbottom), _p(dtop))
+    return dleft, dright, dbottom, dtop
+
+
+def varcoef_pi_loss_bwd_inputs(pred, rho, rhs, dx, coef, neumann_mask=0, want=('rhs', 'rho')):
+    """(drhs, drho) = coef[n] * d(varcoef_pi_loss_partials[n]) / d(rhs, rho), each (N,H,W) and written, None for one that `want` does not name
+    (pcnn_varcoef_bc_pi_loss_bwd_inputs: one fused launch, the residual and the adjoint variable stay in LDS; fp32 like the loss)."""
+    who = 'varcoef_pi_loss_bwd_inputs'
+    N, H, W, (pred, rho, rhs), dx = _varcoef_fields(who, {'pred': pred, 'rho': rho, 'rhs': rhs}, dx)
+    mask = _varcoef_mask(who, neumann_mask)
+    want = tuple(want)
+    if not want or any(k not in ('rhs', 'rho') for k in want):
+        raise ValueError("%s: want names 'rhs', 'rho' or both, got %r" % (who, want))
+    if coef.dtype != torch.float32 or not coef.is_cuda or tuple(coef.shape) != (N,) or not coef.is_contiguous():
+        raise ValueError('%s: coef must be a contiguous CUDA float32 (%d,) tensor' % (who, N))
+    drhs = torch.empty_like(rhs) if 'rhs' in want else None
+    drho = torch.empty_like(rho) if 'rho' in want else None
+    handle().call('pcnn_varcoef_bc_pi_loss_bwd_inputs', c_int(N), c_int(H), c_int(W), _p(pred), _p(rho), _p(rhs), _p(dx), _p(coef), _p(drhs), _p(drho),
+                  c_int(mask))
+    return drhs, drho
+
+
 VARCOEF_SERIES_MAX_MODES = 16      # VSER_MAXK of csrc/varcoef.hip
 
 
