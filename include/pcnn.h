@@ -828,10 +828,11 @@ int pcnn_varcoef_bc_error_stats(pcnn_handle h, int N, int H, int W, int neumann_
                                 const float* dx /* N; required with rhs */, float* out /* N x 8 */);
 
 /* tf.keras.layers.LayerNormalization() over the last axis of an (N, F) matrix (epsilon 1e-3 in Keras): the optional final layer of the
- * metalearning hyper-networks (layers/metalearning_conv.py:128-129).  fwd also returns the per-row mean and 1/sqrt(var + eps) for bwd. */
+ * metalearning hyper-networks (layers/metalearning_conv.py:128-129).  fwd also returns the per-row mean and 1/sqrt(var + eps) in float32: bwd forms dgamma
+ * with them, and forms dx from x and the SAME eps with the row statistics in double (dx can be a small remainder of large terms). */
 int pcnn_layernorm_fwd(pcnn_handle h, int N, int F, const float* x, const float* gamma, const float* beta, float eps, float* y, float* mean, float* rstd);
 int pcnn_layernorm_bwd(pcnn_handle h, int N, int F, const float* x, const float* gamma, const float* mean, const float* rstd, const float* dy,
-                       float* dx, float* dgamma, float* dbeta);
+                       float eps, float* dx, float* dgamma, float* dbeta);
 
 /* Row softmax of an (N, F) matrix - the 'softmax' activation of a tf.keras Dense layer (models/Dirichlet_BC_NN_Metalearning.py:69-76, its
  * __main__ config :236-239) - and its backward dx = y (dy - sum_f dy y).  dx may alias dy. */

@@ -517,27 +517,35 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(int F, const float* 
   if (threadIdx.x == 0) { mean[n] = mu; rstd[n] = rs; }
 }
 
-// dx[n,f] = rstd (g - mean_f(g) - xhat mean_f(g xhat)), g = dy gamma
-__global__ __launch_bounds__(256) void layernorm_bwd_x_kernel(int F, const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ mean,
-                                                              const float* __restrict__ rstd, const float* __restrict__ dy, float* __restrict__ dx) {
-  __shared__ double red[2][256];
+// dx[n,f] = rstd (g - mean_f(g) - xhat mean_f(g xhat)), g = dy gamma.  The row's mean and rstd are formed again here in double from x and eps and
+// every term stays in double up to the one rounding of dx: where xhat is nearly +-1 (F = 2) dx is the remainder of terms ~500 times its size, and the
+// float32 rstd the forward saves alone was worth up to 5e-5 of it.  sum g xhat = rstd (sum g x - mean sum g).
+__global__ __launch_bounds__(256) void layernorm_bwd_x_kernel(int F, const float* __restrict__ x, const float* __restrict__ gamma, float eps,
+                                                              const float* __restrict__ dy, float* __restrict__ dx) {
+  __shared__ double red[4][256];
   const int n = blockIdx.x;
-  const float mu = mean[n], rs = rstd[n];
-  double s = 0.0, s2 = 0.0;
+  const float* xr = x + (int64_t)n * F;
+  const float* dr = dy + (int64_t)n * F;
+  double sx = 0.0, sxx = 0.0, sg = 0.0, sgx = 0.0;
   for (int f = threadIdx.x; f < F; f += 256) {
-    const double g = (double)dy[(int64_t)n * F + f] * gamma[f], xh = ((double)x[(int64_t)n * F + f] - mu) * rs;
-    s += g; s2 += g * xh;
+    const double v = xr[f], g = (double)dr[f] * gamma[f];
+    sx += v; sxx += v * v; sg += g; sgx += g * v;
   }
-  red[0][threadIdx.x] = s; red[1][threadIdx.x] = s2;
+  red[0][threadIdx.x] = sx; red[1][threadIdx.x] = sxx; red[2][threadIdx.x] = sg; red[3][threadIdx.x] = sgx;
   __syncthreads();
   for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) { red[0][threadIdx.x] += red[0][threadIdx.x + o]; red[1][threadIdx.x] += red[1][threadIdx.x + o]; }
+    if ((int)threadIdx.x < o)
+      for (int k = 0; k < 4; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + o];
     __syncthreads();
   }
-  const float mg = (float)(red[0][0] / F), mgx = (float)(red[1][0] / F);
+  const double m = red[0][0] / F;
+  double var = red[1][0] / F - m * m;                     // as the forward forms it
+  if (var < 0.0) var = 0.0;
+  const double rs = 1.0 / sqrt(var + (double)eps);
+  const double mg = red[2][0] / F, mgx = rs * (red[3][0] - m * red[2][0]) / F;
   for (int f = threadIdx.x; f < F; f += 256) {
-    const float g = dy[(int64_t)n * F + f] * gamma[f], xh = (x[(int64_t)n * F + f] - mu) * rs;
-    dx[(int64_t)n * F + f] = rs * (g - mg - xh * mgx);
+    const double g = (double)dr[f] * gamma[f], xh = ((double)xr[f] - m) * rs;
+    dx[(int64_t)n * F + f] = (float)(rs * (g - mg - xh * mgx));
   }
 }
 
@@ -611,9 +619,9 @@ extern "C" int pcnn_layernorm_fwd(pcnn_handle h, int N, int F, const float* x, c
 }
 
 extern "C" int pcnn_layernorm_bwd(pcnn_handle h, int N, int F, const float* x, const float* gamma, const float* mean, const float* rstd, const float* dy,
-                                  float* dx, float* dgamma, float* dbeta) {
+                                  float eps, float* dx, float* dgamma, float* dbeta) {
   PCNN_REQUIRE(h, h && x && gamma && mean && rstd && dy && dx && dgamma && dbeta && N >= 1 && F >= 1, "pcnn_layernorm_bwd: bad argument");
-  hipLaunchKernelGGL(layernorm_bwd_x_kernel, dim3(N), dim3(256), 0, h->stream, F, x, gamma, mean, rstd, dy, dx);
+  hipLaunchKernelGGL(layernorm_bwd_x_kernel, dim3(N), dim3(256), 0, h->stream, F, x, gamma, eps, dy, dx);
   hipLaunchKernelGGL(layernorm_bwd_params_kernel, dim3((F + 255) / 256), dim3(256), 0, h->stream, N, F, x, mean, rstd, dy, dgamma, dbeta);
   PCNN_CHECK_LAUNCH(h, "pcnn_layernorm_bwd");
   return 0;

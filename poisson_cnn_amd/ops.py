@@ -828,10 +828,11 @@ def layernorm_fwd(x, gamma, beta, eps=1e-3):
     return y, st
 
 
-def layernorm_bwd(x, gamma, stats, dy, dgamma, dbeta):
+def layernorm_bwd(x, gamma, stats, dy, dgamma, dbeta, eps=1e-3):
+    """eps: the one layernorm_fwd was called with."""
     N, F = x.shape
     dx = empty((N, F), x.device)
-    handle().call('pcnn_layernorm_bwd', c_int(N), c_int(F), _p(x), _p(gamma), _p(stats[0]), _p(stats[1]), _p(dy), _p(dx), _p(dgamma), _p(dbeta))
+    handle().call('pcnn_layernorm_bwd', c_int(N), c_int(F), _p(x), _p(gamma), _p(stats[0]), _p(stats[1]), _p(dy), c_float(eps), _p(dx), _p(dgamma), _p(dbeta))
     return dx
 
 

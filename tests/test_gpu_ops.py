@@ -320,19 +320,29 @@ def test_assemble_axpby_adam():
     w, g = f32(rng.standard_normal(n)), f32(rng.standard_normal(n))
     wd, md, vd = dev(w), ops.zeros((n,)), ops.zeros((n,))
     m = np.zeros(n); v = np.zeros(n); wr = w.copy()
+    # Each STEP (w after - w before, formed in float64 from the device values) against the step of the rule: a bound on w alone accepts a step that is off by a
+    # fraction of a percent, or a tail of elements that never moved.  A step of ~1e-3 carries the rounding of the weight ~1 it was added to; the same steps in
+    # float32 on the CPU are within 3.1e-5 (Adam) / 3.8e-5 (AMSGrad) of the float64 rule, the bound is 4 x the larger.
+    STEP_TOL = 4 * 3.82e-5
     for t in range(1, 4):
+        before, wr0 = wd.cpu().numpy().astype(np.float64), wr
         ops.adam_step(wd, dev(g), md, vd, 1e-3, 0.9, 0.999, 1e-7, t)
         m = 0.9 * m + 0.1 * g; v = 0.999 * v + 0.001 * g * g
         wr = wr - 1e-3 * np.sqrt(1 - 0.999 ** t) / (1 - 0.9 ** t) * m / (np.sqrt(v) + 1e-7)
+        after = wd.cpu().numpy().astype(np.float64)
+        assert rel(after - before, wr - wr0) < STEP_TOL and (after != before).all()
     assert rel(wd.cpu().numpy(), wr) < TOL
     # AMSGrad (tf.keras Adam(amsgrad=True)): the denominator keeps the running maximum of v; gradients shrink so that it matters
     wd, md, vd, vh = dev(w), ops.zeros((n,)), ops.zeros((n,)), ops.zeros((n,))
     m = np.zeros(n); v = np.zeros(n); vhat = np.zeros(n); wr = w.copy()
     for t in range(1, 5):
         gt = g / t ** 2
+        before, wr0 = wd.cpu().numpy().astype(np.float64), wr
         ops.adam_step(wd, dev(gt), md, vd, 1e-3, 0.9, 0.999, 1e-7, t, vhat=vh)
         m = 0.9 * m + 0.1 * gt; v = 0.999 * v + 0.001 * gt * gt; vhat = np.maximum(vhat, v)
         wr = wr - 1e-3 * np.sqrt(1 - 0.999 ** t) / (1 - 0.9 ** t) * m / (np.sqrt(vhat) + 1e-7)
+        after = wd.cpu().numpy().astype(np.float64)
+        assert rel(after - before, wr - wr0) < STEP_TOL and (after != before).all()
     assert rel(wd.cpu().numpy(), wr) < TOL and rel(vh.cpu().numpy(), vhat) < 1e-4      # (1 - beta_2) is formed in fp32, as in Keras
 
 
@@ -344,11 +354,17 @@ def test_sgd_momentum(nesterov):
     w0 = f32(rng.standard_normal(1000)); wr = w0.copy(); vr = np.zeros_like(w0)
     w, v = dev(w0), dev(np.zeros(1000))
     lr, mom, gs = 0.05, 0.9, 0.5
+    # each step (w after - w before, in float64 from the device values) against the rule's step; the same steps in float32 on the CPU are within 9.0e-7 (plain) /
+    # 4.9e-7 (nesterov) of the float64 rule: 4 x that, not below TOL
+    step_tol = max(TOL, 4 * (4.9e-7 if nesterov else 9.0e-7))
     for t in range(3):
         g = f32(rng.standard_normal(1000))
+        before, wr0 = w.cpu().numpy().astype(np.float64), wr
         ops.sgd_momentum_step(w, dev(g), v, lr, mom, nesterov, grad_scale=gs)
         vr = mom * vr - lr * gs * g
         wr = wr + (mom * vr - lr * gs * g if nesterov else vr)
+        after = w.cpu().numpy().astype(np.float64)
+        assert rel(after - before, wr - wr0) < step_tol and (after != before).all()
     assert rel(w.cpu().numpy(), wr) < TOL and rel(v.cpu().numpy(), vr) < TOL
     from poisson_cnn_amd.train import SGD
     assert SGD(learning_rate=0.1, momentum=0.9, nesterov=True).momentum == 0.9
