@@ -804,6 +804,20 @@ int pcnn_varcoef_bc_edge_grad(pcnn_handle h, int N, int H, int W, int neumann_ma
                               const float* du /* may be NULL */, float* dleft, float* dright, float* dbottom, float* dtop);
 int pcnn_varcoef_bc_pi_loss_bwd_inputs(pcnn_handle h, int N, int H, int W, const float* pred, const float* rho, const float* rhs, const float* dx,
                                        const float* coef /*N*/, float* drhs /* may be NULL */, float* drho /* may be NULL */, int neumann_mask);
+/* The backward of pcnn_varcoef_bc_jacobi_fwd with respect to ALL its inputs (csrc/varcoef_train.hip): u0 the field the
+ * n_sweeps sweeps started from, dout = d loss / d (their result); du, drho, drhs (N,H,W) are written, each may be NULL (not wanted), all NULL does
+ * nothing.  neumann_mask 0 is the all-Dirichlet smoother.  Per sweep u -> u', walking backwards, with g' = d loss / d u', D_c = sum_k m_k beta_k and
+ * a_c = g'_c / D_c on the unknowns, 0 on every other node:
+ *   du_k = sum over the unknown neighbours c of k of m beta a_c (+ g'_k on a frozen node);   drhs_c += -dx^2 a_c;
+ *   drho_p += sum over the faces (c, k) that touch p, c an unknown, of -1/2 beta^2 m a_c (u_k - u'_c)      on ALL nodes.
+ * du has the bits of pcnn_varcoef_[bc_]jacobi_bwd (which runs when du alone is wanted).  With drho or drhs the n_sweeps iterates are recomputed by
+ * the forward's kernel, one sweep per launch, and kept with two gradient fields in the handle's auxiliary scratch -
+ * pcnn_varcoef_jacobi_bwd_inputs_workspace bytes, (n_sweeps + 2) N H W floats (0 for arguments the call refuses) -, then one gather launch per
+ * sweep: one thread per output, no atomics, equal inputs give equal bits.  fp32 throughout.  No output aliases an input or another output. */
+int pcnn_varcoef_bc_jacobi_bwd_inputs(pcnn_handle h, int N, int H, int W, int neumann_mask, const float* rho, const float* u0, const float* rhs,
+                                      const float* dx, const float* dout, int n_sweeps, float* du /* may be NULL */, float* drho /* may be NULL */,
+                                      float* drhs /* may be NULL */);
+size_t pcnn_varcoef_jacobi_bwd_inputs_workspace(int N, int H, int W, int n_sweeps);
 /* out[n,y,x,0:2] = {stack[n,0,y,x], stack[n,1,y,x]} of the generator's (N,2,H,W) stack [rhs, rho], followed - use_pos - by the two positional
  * channels of pcnn_assemble_input; ldo >= 2 (4 with use_pos). */
 int pcnn_assemble_density_input(pcnn_handle h, int N, int H, int W, const float* stack, int use_pos, float* out, int ldo);

@@ -27,11 +27,12 @@ that is applied twice before `backward()` raises instead of differentiating the 
 `torch.no_grad()` / `module.eval()` run the inference path (`training=False`: nothing kept, BatchNormalization on its moving statistics).
 
 Also here, and independent of the layers: `variable_density_solve` and `variable_density_residual` put the variable-density Poisson solve and its
-flux-form residual on the tape with gradients with respect to their DATA - `rho`, `rhs`, the edge arrays.
+flux-form residual on the tape with gradients with respect to their DATA - `rho`, `rhs`, the edge arrays -, and
+`variable_density_smooth` does the same for the Jacobi smoother between them (`u`, `rho`, `rhs`; section 25).
 """
 import torch
 
-__all__ = ['Differentiable', 'differentiable', 'variable_density_solve', 'variable_density_residual']
+__all__ = ['Differentiable', 'differentiable', 'variable_density_solve', 'variable_density_residual', 'variable_density_smooth']
 
 
 def _is_float_tensor(v):
@@ -284,3 +285,55 @@ def variable_density_residual(pred, stack, dx, boundary_types=None):
         raise ValueError('variable_density_residual: stack must be (N,2,H,W) = [rhs, rho], got %r' % (tuple(getattr(stack, 'shape', ())),))
     neumann = D.neumann_flags(boundary_types) if boundary_types is not None else (False,) * 4
     return _VariableDensityResidual.apply(pred, stack, dx, sum(int(f) << k for k, f in enumerate(neumann)))
+
+
+class _VariableDensitySmooth(torch.autograd.Function):
+    """forward = ops.varcoef_jacobi; backward = one ops.varcoef_jacobi_bwd_inputs for the inputs that need a gradient."""
+
+    @staticmethod
+    def forward(ctx, u, rho, rhs, d, n_sweeps, mask):
+        from . import ops
+        N, H, W = ops._one_channel_shape('variable_density_smooth', u, 'fields must be (N,H,W), (N,1,H,W) or (N,H,W,1)')
+        f = [t.detach().reshape(N, H, W).contiguous() for t in (u, rho, rhs)]
+        ctx.n_sweeps, ctx.mask, ctx.shapes = n_sweeps, mask, tuple(t.shape for t in (u, rho, rhs))
+        ctx.save_for_backward(*f, d)
+        return ops.varcoef_jacobi(*f, d, n_sweeps, mask).reshape(u.shape)
+
+    @staticmethod
+    def backward(ctx, dout):
+        from . import ops
+        u, rho, rhs, d = ctx.saved_tensors
+        want = tuple(k for k, need in zip(('u', 'rho', 'rhs'), ctx.needs_input_grad[:3]) if need)
+        grads = (None, None, None)
+        if want:
+            g = dout.detach().to(torch.float32).reshape(u.shape).contiguous()
+            grads = ops.varcoef_jacobi_bwd_inputs(g, u, rho, rhs, d, ctx.n_sweeps, ctx.mask, want=want)
+        return tuple(None if g is None else g.reshape(s) for g, s in zip(grads, ctx.shapes)) + (None, None, None)
+
+
+def variable_density_smooth(u, rho, rhs, dx, n_sweeps, boundary_types=None):
+    """`ops.varcoef_jacobi(u, rho, rhs, dx, n_sweeps, mask)` on the tape, bit for bit: n_sweeps Jacobi sweeps of div((1/rho) grad u) = rhs from `u`,
+    differentiable with respect to `u`, `rho` and `rhs` - whichever of them `requires_grad`.  The fields are CUDA float32,
+    (N,H,W), (N,1,H,W) or (N,H,W,1), all with the same points; the result has the shape of `u`.  `dx` (N,), (N,1) or (N,2) with equal columns gets no
+    gradient.  boundary_types: dict edge -> 'dirichlet' | 'neumann' (None: all Dirichlet); every mask is allowed.
+
+    backward is one call of ops.varcoef_jacobi_bwd_inputs: the fused adjoint alone when only `u` needs a gradient; otherwise the n_sweeps iterates
+    are recomputed into the handle's scratch ((n_sweeps + 2) fields) and one gather launch per sweep accumulates d rho and d rhs.  Refused:
+    anisotropic spacing (differing `dx` columns), n_sweeps < 1, and what ops.varcoef_jacobi refuses."""
+    from . import dataset as D
+    who = 'variable_density_smooth'
+    for name, t in (('u', u), ('rho', rho), ('rhs', rhs), ('dx', dx)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError('%s: %s must be a tensor on the device' % (who, name))
+    if rho.numel() != u.numel() or rhs.numel() != u.numel():
+        raise ValueError('%s: rho %s and rhs %s must have the points of u %s' % (who, tuple(rho.shape), tuple(rhs.shape), tuple(u.shape)))
+    if int(n_sweeps) < 1:
+        raise ValueError('%s: n_sweeps must be at least 1, got %r' % (who, n_sweeps))
+    d = dx.detach().to(torch.float32).reshape(dx.shape[0], -1)
+    if d.shape[1] == 2:
+        if not bool((d[:, 0] == d[:, 1]).all()):
+            raise NotImplementedError('%s: anisotropic spacing (dy != dx) is not supported' % who)
+    elif d.shape[1] != 1:
+        raise ValueError('%s: dx must be (N,), (N,1) or (N,2), got %s' % (who, tuple(dx.shape)))
+    neumann = D.neumann_flags(boundary_types) if boundary_types is not None else (False,) * 4
+    return _VariableDensitySmooth.apply(u, rho, rhs, d[:, 0].contiguous(), int(n_sweeps), sum(int(f) << k for k, f in enumerate(neumann)))

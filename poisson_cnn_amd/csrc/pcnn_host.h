@@ -21,7 +21,7 @@ struct pcnn_handle_s {
   float* y_absmax = nullptr;      // set by pcnn_conv2d_fwd_absmax for the duration of one forward launch: receives max|y|
   pcnn_buffer spec_ws;            // spectral-convolution workspace (tables, filter spectrum, tile spectra)
   size_t spec_ws_limit = 0;       // caller's cap on the spectral workspace in bytes (0: none), pcnn_set_workspace_limit
-  pcnn_buffer aux_ws;             // intermediates and partial sums of the two-pass resize, pcnn_sweep_chain (sweep_common.h: the fused Jacobi sweeps of stencil.hip and varcoef_train.hip), pcnn_sample_scale_bwd, pcnn_conv2d_dgrad_post, pcnn_grouped_deconv_bwd_filter, pcnn_varcoef_pi_loss_partials
+  pcnn_buffer aux_ws;             // intermediates and partial sums of the two-pass resize, pcnn_sweep_chain (sweep_common.h: the fused Jacobi sweeps of stencil.hip and varcoef_train.hip), pcnn_sample_scale_bwd, pcnn_conv2d_dgrad_post, pcnn_grouped_deconv_bwd_filter, pcnn_varcoef_pi_loss_partials, pcnn_varcoef_bc_jacobi_bwd_inputs (the recomputed iterates)
   int spectral_mode = -1;         // PCNN_SPECTRAL_AUTO (cost model) / _OFF / _FORCE, see pcnn_set_spectral_mode
   int spectral_tile = 0;          // 0: per layer (pick_tile), 32 / 64: that tile size wherever the layer allows it, see pcnn_set_spectral_tile
   int spectral_xform = 1;         // transform kernels of the spectral route: 1 = in-register FFT on the vector ALUs (default since round 5), 0 = DFT as a GEMM on the matrix cores (pcnn_set_spectral_transform)

@@ -1,5 +1,5 @@
 // Training-side operators of the variable-density problem div((1/rho) grad u) = f (DESIGN.md sections 17 and 20): the flux-form residual loss with
-// its gradient, and the Jacobi sweep of the same operator with its adjoint.  fp32 on one-channel (N,H,W) fields, one spacing per sample (dy = dx),
+// its gradient, and the Jacobi sweep of the same operator with its adjoint - w.r.t. u (fused), and w.r.t. u, rho and rhs (section 25).  fp32 on one-channel (N,H,W) fields, one spacing per sample (dy = dx),
 // rho on every node.  The discretisation is that of csrc/varcoef.hip (section 16), held once in flux_form.h (pcnn_beta_face, pcnn_flux_residual, the
 // FLUX_ROWS x FLUX_COLS tile of the loss kernels - that of varcoef_apply_kernel - and its LDS loader pcnn_load_nodes):
 //   beta_face = 2 / (rho_a + rho_b),   (L u)[i,j] = sum over the four faces of beta_face (u[neighbour] - u[i,j]) / dx^2 = -(A u)[i,j]
@@ -246,6 +246,93 @@ int vj_launch(pcnn_handle_s* h, int N, int H, int W, int k, int mask, const floa
   return 0;
 }
 
+// One sweep of the smoother's backward with the gradients of its DATA.  The sweep took u (iterate t) to un (iterate t + 1);
+// gin is d loss / d un.  With a_c = gin_c / D_c on the unknowns (D_c = sum_k m_k beta_k) and 0 on every other node:
+//   gout_k  = sum over the unknown neighbours c of k of m beta a_c  (+ gin_k on a frozen node)      - the arithmetic of vc_jacobi_kernel<true, .>
+//   drhs_c += -h^2 a_c
+//   drho_p += -1/2 (a_p sum_k beta_k^2 (u_k - un_p)  +  sum over the unknown neighbours c of p of m beta^2 a_c (u_p - un_c))
+// the first sum over the four (mirrored: a Neumann edge node's inward face twice) faces of p if p is an unknown, the second p's share of the faces
+// its neighbours read it through.  A gather on the flux_form.h tile: grid (column tiles, row tiles, N) over ALL nodes, one thread per output, no
+// atomics.  a is formed as (1 / D) * gin and gout summed in the order of vc_jacobi_kernel's adjoint, so gout has its bits.  first: drho / drhs are
+// written instead of added to (the last sweep comes first).  gout, drho, drhs may each be NULL.
+__global__ __launch_bounds__(FLUX_THREADS) void vc_jacobi_bwd_inputs_kernel(int H, int W, int mask, int first, const float* __restrict__ rho,
+                                                                            const float* __restrict__ u, const float* __restrict__ un,
+                                                                            const float* __restrict__ gin, const float* __restrict__ dx,
+                                                                            float* __restrict__ gout, float* __restrict__ drho, float* __restrict__ drhs) {
+  constexpr int LR = FLUX_ROWS + 4, LC = FLUX_COLS + 4, ER = FLUX_ROWS + 2, EC = FLUX_COLS + 2;
+  __shared__ float rs[LR][LC];                            // rho: (r, c) is node (I0 - 2 + r, J0 - 2 + c), mirrored beyond a Neumann edge
+  __shared__ float us[ER][EC];                            // u, mirrored: (r, c) is node (I0 - 1 + r, J0 - 1 + c), as are ns and as
+  __shared__ float ns[ER][EC];                            // un, read on unknowns only
+  __shared__ float as[ER][EC];                            // a
+  const FdUnknowns uk = fd_unknowns(H, W, mask);
+  const int n = blockIdx.z, I0 = blockIdx.y * FLUX_ROWS, J0 = blockIdx.x * FLUX_COLS;
+  const int64_t img = (int64_t)n * H * W;
+  pcnn_load_nodes_mirrored<LR, LC>(rs, rho + img, H, W, I0 - 2, J0 - 2, mask, 1.f);
+  pcnn_load_nodes_mirrored<ER, EC>(us, u + img, H, W, I0 - 1, J0 - 1, mask, 0.f);
+  pcnn_load_nodes<ER, EC>(ns, un + img, H, W, I0 - 1, J0 - 1, 0.f);
+  __syncthreads();
+  for (int e = threadIdx.x; e < ER * EC; e += FLUX_THREADS) {
+    const int r = e / EC, c = e % EC, i = I0 - 1 + r, j = J0 - 1 + c;
+    float v = 0.f;
+    if (i >= uk.i0 && i <= uk.i1 && j >= uk.j0 && j <= uk.j1) {
+      const int a = r + 1, b = c + 1;
+      const float rc = rs[a][b];
+      const float inv_d = 1.f / ((pcnn_beta_face(rc, rs[a - 1][b]) + pcnn_beta_face(rc, rs[a + 1][b])) +
+                                 (pcnn_beta_face(rc, rs[a][b - 1]) + pcnn_beta_face(rc, rs[a][b + 1])));
+      v = inv_d * gin[img + (int64_t)i * W + j];
+    }
+    as[r][c] = v;
+  }
+  __syncthreads();
+  const float h = dx[n], h2 = h * h;
+  const int c = threadIdx.x % FLUX_COLS, r0 = (threadIdx.x / FLUX_COLS) * FLUX_RPT;
+  const int j = J0 + c;
+  if (j >= W) return;
+  const bool in_x = j >= uk.j0 && j <= uk.j1;
+  const bool has_l = j - 1 >= uk.j0 && j - 1 <= uk.j1, has_r = j + 1 >= uk.j0 && j + 1 <= uk.j1;      // the neighbour's column holds unknowns
+  const float ml = (mask && j - 1 == 0) ? 2.f : 1.f, mr = (mask && j + 1 == W - 1) ? 2.f : 1.f;       // ... on a Neumann edge: it reads this node twice
+#pragma unroll
+  for (int k = 0; k < FLUX_RPT; ++k) {
+    const int r = r0 + k, i = I0 + r;
+    if (i >= H) break;
+    const int a = r + 1, b = c + 1;                       // in us / ns / as; rs is one further in
+    const int64_t at = img + (int64_t)i * W + j;
+    const bool in_y = i >= uk.i0 && i <= uk.i1, unknown = in_x && in_y;
+    const bool has_u = in_x && i - 1 >= uk.i0 && i - 1 <= uk.i1, has_d = in_x && i + 1 >= uk.i0 && i + 1 <= uk.i1;
+    const float mu = (mask && i - 1 == 0) ? 2.f : 1.f, md = (mask && i + 1 == H - 1) ? 2.f : 1.f;
+    const float rc = rs[a + 1][b + 1];
+    const float b0 = pcnn_beta_face(rc, rs[a][b + 1]), b1 = pcnn_beta_face(rc, rs[a + 2][b + 1]), b2 = pcnn_beta_face(rc, rs[a + 1][b]),
+                b3 = pcnn_beta_face(rc, rs[a + 1][b + 2]);
+    if (gout) {
+      float acc = 0.f;
+      if (has_u) acc += mu * (b0 * as[a - 1][b]);
+      if (has_d) acc += md * (b1 * as[a + 1][b]);
+      if (in_y && has_l) acc += ml * (b2 * as[a][b - 1]);
+      if (in_y && has_r) acc += mr * (b3 * as[a][b + 1]);
+      gout[at] = (unknown ? 0.f : gin[at]) + acc;
+    }
+    const float ac = as[a][b];
+    if (drhs) {
+      const float v = unknown ? -(h2 * ac) : 0.f;
+      drhs[at] = first ? v : drhs[at] + v;
+    }
+    if (drho) {
+      const float up = us[a][b];
+      float own = 0.f, shared = 0.f;
+      if (unknown) {
+        const float q = ns[a][b];
+        own = ac * (((b0 * b0) * (us[a - 1][b] - q) + (b1 * b1) * (us[a + 1][b] - q)) + ((b2 * b2) * (us[a][b - 1] - q) + (b3 * b3) * (us[a][b + 1] - q)));
+      }
+      if (has_u) shared += mu * ((b0 * b0) * (as[a - 1][b] * (up - ns[a - 1][b])));
+      if (has_d) shared += md * ((b1 * b1) * (as[a + 1][b] * (up - ns[a + 1][b])));
+      if (in_y && has_l) shared += ml * ((b2 * b2) * (as[a][b - 1] * (up - ns[a][b - 1])));
+      if (in_y && has_r) shared += mr * ((b3 * b3) * (as[a][b + 1] * (up - ns[a][b + 1])));
+      const float v = -0.5f * (own + shared);
+      drho[at] = first ? v : drho[at] + v;
+    }
+  }
+}
+
 __global__ void assemble_density_input_kernel(int N, int H, int W, const float* __restrict__ stack, int use_pos, float* __restrict__ out, int ldo) {
   const int64_t hw = (int64_t)H * W, total = (int64_t)N * hw;
   const float pi = 3.14159265358979323846f;
@@ -317,7 +404,58 @@ int vt_jacobi_bwd(pcnn_handle h, const char* who, int N, int H, int W, int mask,
   });
 }
 
+// fields of N H W floats the backward below keeps in the handle's auxiliary scratch: the n iterates u^1 .. u^n and two gradients in turn
+size_t vt_bwd_inputs_fields(int n_sweeps) { return (size_t)n_sweeps + 2; }
+
+// The backward of n sweeps w.r.t. u0, rho and rhs.  Sweep t needs the iterates u^t and u^(t+1): they are recomputed with the forward's own kernel, one
+// sweep per launch, into the scratch (n fields), then the sweeps are walked backwards with one vc_jacobi_bwd_inputs_kernel launch each.
+int vt_jacobi_bwd_inputs(pcnn_handle h, const char* who, int N, int H, int W, int mask, const float* rho, const float* u0, const float* rhs, const float* dx,
+                         const float* dout, int n_sweeps, float* du, float* drho, float* drhs) {
+  PCNN_REQUIRE(h, h && rho && u0 && rhs && dx && dout, "%s: null argument", who);
+  PCNN_REQUIRE(h, mask >= 0 && mask < 16, "%s: neumann_mask %d not in 0..15", who, mask);
+  PCNN_REQUIRE(h, vt_shape_ok(N, H, W) && n_sweeps >= 1, "%s: needs N in 1..65535, H, W >= 3, n_sweeps >= 1 (got %d, %d x %d, %d sweeps)", who, N, H, W, n_sweeps);
+  if (!du && !drho && !drhs) return 0;
+  const float* ins[] = {rho, u0, rhs, dout};
+  float* outs[] = {du, drho, drhs};
+  for (int o = 0; o < 3; ++o) {
+    if (!outs[o]) continue;
+    for (const float* in : ins) PCNN_REQUIRE(h, outs[o] != in, "%s: an output must not alias an input", who);
+    for (int p = 0; p < o; ++p) PCNN_REQUIRE(h, outs[o] != outs[p], "%s: the outputs must not alias each other", who);
+  }
+  if (!drho && !drhs) return vt_jacobi_bwd(h, who, N, H, W, mask, rho, dx, dout, n_sweeps, du);      // u alone: the fused adjoint, which needs no iterates
+  const size_t field = (size_t)N * H * W;
+  if (int rc = pcnn_reserve(h, h->aux_ws, vt_bwd_inputs_fields(n_sweeps) * field * sizeof(float), 0, who)) return rc;
+  float* ws = static_cast<float*>(h->aux_ws.p);
+  auto iterate = [&](int t) -> const float* { return t == 0 ? u0 : ws + (size_t)(t - 1) * field; };     // u^t
+  float* g[2] = {ws + (size_t)n_sweeps * field, ws + (size_t)(n_sweeps + 1) * field};
+  for (int t = 0; t < n_sweeps; ++t) {
+    float* to = ws + (size_t)t * field;
+    if (int rc = mask ? vj_launch<false, true>(h, N, H, W, 1, mask, rho, iterate(t), rhs, dx, to) : vj_launch<false, false>(h, N, H, W, 1, 0, rho, iterate(t), rhs, dx, to))
+      return rc;
+  }
+  const dim3 grid(pcnn_cdiv(W, FLUX_COLS), pcnn_cdiv(H, FLUX_ROWS), N);
+  const float* gin = dout;
+  for (int t = n_sweeps - 1; t >= 0; --t) {
+    float* gout = t == 0 ? du : g[t & 1];
+    hipLaunchKernelGGL(vc_jacobi_bwd_inputs_kernel, grid, dim3(FLUX_THREADS), 0, h->stream, H, W, mask, t == n_sweeps - 1 ? 1 : 0, rho, iterate(t), iterate(t + 1), gin,
+                       dx, gout, drho, drhs);
+    gin = gout;
+  }
+  PCNN_CHECK_LAUNCH(h, who);
+  return 0;
+}
+
 }  // namespace
+
+extern "C" int pcnn_varcoef_bc_jacobi_bwd_inputs(pcnn_handle h, int N, int H, int W, int neumann_mask, const float* rho, const float* u0, const float* rhs,
+                                                 const float* dx, const float* dout, int n_sweeps, float* du, float* drho, float* drhs) {
+  return vt_jacobi_bwd_inputs(h, "pcnn_varcoef_bc_jacobi_bwd_inputs", N, H, W, neumann_mask, rho, u0, rhs, dx, dout, n_sweeps, du, drho, drhs);
+}
+
+extern "C" size_t pcnn_varcoef_jacobi_bwd_inputs_workspace(int N, int H, int W, int n_sweeps) {
+  if (!vt_shape_ok(N, H, W) || n_sweeps < 1) return 0;
+  return vt_bwd_inputs_fields(n_sweeps) * (size_t)N * H * W * sizeof(float);
+}
 
 extern "C" int pcnn_varcoef_pi_loss_partials(pcnn_handle h, int N, int H, int W, const float* pred, const float* rho, const float* rhs, const float* dx,
                                              float* out) {

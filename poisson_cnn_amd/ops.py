@@ -1177,6 +1177,24 @@ def varcoef_jacobi_bwd(dout, rho, dx, n_sweeps, neumann_mask=0):
     return du
 
 
+def varcoef_jacobi_bwd_inputs(dout, u, rho, rhs, dx, n_sweeps, neumann_mask=0, want=('u', 'rho', 'rhs')):
+    """(du, drho, drhs): the gradients of varcoef_jacobi(u, rho, rhs, dx, n_sweeps, neumann_mask) w.r.t. its three fields from dout, the gradient of
+    its result - each (N,H,W) and written, None for one that `want` does not name (pcnn_varcoef_bc_jacobi_bwd_inputs).  du has
+    the bits of varcoef_jacobi_bwd; drho and drhs cost a recomputation of the n_sweeps iterates, held in the handle's scratch."""
+    who = 'varcoef_jacobi_bwd_inputs'
+    N, H, W, (dout, u, rho, rhs), dx = _varcoef_fields(who, {'dout': dout, 'u': u, 'rho': rho, 'rhs': rhs}, dx)
+    mask = _varcoef_mask(who, neumann_mask)
+    if int(n_sweeps) < 1:
+        raise ValueError('%s: n_sweeps must be at least 1, got %r' % (who, n_sweeps))
+    want = tuple(want)
+    if not want or any(k not in ('u', 'rho', 'rhs') for k in want):
+        raise ValueError("%s: want names some of 'u', 'rho', 'rhs', got %r" % (who, want))
+    du, drho, drhs = (torch.empty_like(dout) if k in want else None for k in ('u', 'rho', 'rhs'))
+    handle().call('pcnn_varcoef_bc_jacobi_bwd_inputs', c_int(N), c_int(H), c_int(W), c_int(mask), _p(rho), _p(u), _p(rhs), _p(dx), _p(dout),
+                  c_int(int(n_sweeps)), _p(du), _p(drho), _p(drhs))
+    return du, drho, drhs
+
+
 _VARCOEF_EDGES = ('left', 'right', 'bottom', 'top')
 
 
