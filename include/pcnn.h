@@ -751,6 +751,37 @@ int pcnn_varcoef_bc_pcg_iterate_scaled(pcnn_handle h, int N, int H, int W, int n
                                        int first_iteration, int iterations, const double* Vinv_h, const double* V_h, const double* lam_h,
                                        const double* VinvT_w, const double* VT_w, const double* lam_w, void* workspace, size_t workspace_bytes,
                                        double* scal, int* flags);
+/* The *_bc_* family with a reaction term: div((1/rho) grad u) - c u = f, on the unknowns (A + C) u = b with C = diag(c).
+ * A, b, the Neumann closure and the weights are those above; reaction (N,H,W) fp32 is c on every node, read on the unknowns of neumann_mask only
+ * and required >= 0 and finite there.  neumann_mask 0 is the all-Dirichlet problem.  W (A + C) is symmetric, and positive definite once an edge is
+ * Dirichlet or c > 0 somewhere.  Each entry point takes the arguments of its counterpart without the suffix, then `reaction` (the workspace query
+ * needs no pointer and takes none), and keeps every guarantee: fp64, fixed-order reductions, no atomics, results independent of the batch, a
+ * flagged sample frozen bit for bit, no dependence on what the workspace held.
+ *   operator: c of the thread's own point joins the point's sum, q = (A + C) p: 24 B per point and product against 20.
+ *   setup:    r = b - (A + C) x0.  scal is N x 8 doubles with the layout above, FOLLOWED by N x 4 doubles: [n][0] = cbar, the weighted mean
+ *             sum w c / sum w over the unknowns, [n][1] = bbar, the weighted mean of 1 / rho there, [n][2] = min c there, a NaN or an infinity
+ *             counting as -inf, [n][3] unused: 12 N doubles in all.  The caller refuses a negative [n][2], and for mask 15 a cbar of 0 (that sample
+ *             is singular: solve it without the suffix).
+ *   preconditioner: the division is by bbar (lam_h + lam_w) / dx^2 + cbar, the eigenvalues of bbar M + cbar I with M the constant-coefficient
+ *             operator including its 1 / dx^2 (a positive factor no longer cancels).  The lam = 0 mode of mask 15 is kept when cbar > 0.
+ *   mask 15:  no compatibility projection - scal[n][6] and [n][7] stay 0 - and no mean is removed: finish with pcnn_varcoef_bc_pcg_finish_reaction,
+ *             which is pcnn_varcoef_bc_pcg_finish without the mean removal (for masks 0..14 either finish does the same).
+ * The workspace holds three more partial-sum arrays: size it with the *_workspace_reaction query.  The scaled preconditioner has no such variant. */
+int pcnn_varcoef_bc_apply_reaction(pcnn_handle h, int N, int H, int W, int neumann_mask, const float* rho, const float* dx, const double* p, double* q,
+                                   double* pq, const float* reaction);
+size_t pcnn_varcoef_bc_pcg_workspace_reaction(int N, int H, int W, int neumann_mask);
+int pcnn_varcoef_bc_pcg_setup_reaction(pcnn_handle h, int N, int H, int W, int neumann_mask, const float* rho, const float* rhs, const float* left,
+                                       const float* right, const float* bottom, const float* top, const float* dx, const double* x0, double tol,
+                                       const double* Vinv_h, const double* V_h, const double* lam_h, const double* VinvT_w, const double* VT_w,
+                                       const double* lam_w, void* workspace, size_t workspace_bytes, double* scal, int* flags, const float* reaction);
+int pcnn_varcoef_bc_pcg_iterate_reaction(pcnn_handle h, int N, int H, int W, int neumann_mask, const float* rho, const float* dx, double tol,
+                                         int first_iteration, int iterations, const double* Vinv_h, const double* V_h, const double* lam_h,
+                                         const double* VinvT_w, const double* VT_w, const double* lam_w, void* workspace, size_t workspace_bytes,
+                                         double* scal, int* flags, const float* reaction);
+int pcnn_varcoef_bc_pcg_finish_reaction(pcnn_handle h, int N, int H, int W, int neumann_mask, void* workspace, const float* left, const float* right,
+                                        const float* bottom, const float* top, float* soln);
+/* pcnn_varcoef_density's map g[i] = lo + (hi - lo) min(|g[i]|, 1) (the same kernel) for a reaction field: 0 <= lo <= hi, lo = 0 allowed */
+int pcnn_varcoef_reaction_field(pcnn_handle h, int64_t total, float lo, float hi, float* g);
 
 /* ---- training on the variable-density problem (csrc/varcoef_train.hip) ------------------- */
 /* fp32 on one-channel (N,H,W) fields, dx (N) one spacing per sample, rho (N,H,W) read on every node; the discretisation above:

@@ -23,6 +23,11 @@
 // node's four face coefficients (the inward one twice on a Neumann edge, as in A and in M): one more fp64 field s behind the partial sums, built by the
 // setup launch; s o r goes to z - the buffer the transform then reads - from the pass that updates r, and p = s o z + beta p.  The SC = false
 // instantiations are the code of the plain entry points, unchanged.
+// The *_reaction entry points (RX = true) solve div((1/rho) grad u) - c u = f, i.e. (A + C) u = b with C = diag(c), c >= 0 an fp32
+// field read on the unknowns: the operator and setup tiles load c for the thread's own points (no halo: 24 B per point against 20) and add c p inside
+// the point's sum; setup also reduces the weighted means cbar of c and bbar of 1/rho over the unknowns and the minimum of c, and the division pass
+// divides by bbar (lam_h + lam_w) / dx^2 + cbar - the preconditioner's scale matters now.  W (A + C) is definite for mask 15 once cbar > 0: no
+// projection, no mean removal.  The RX = false instantiations are the code of the entry points without the suffix, unchanged.
 #include <math.h>
 #include <type_traits>
 #include "flux_form.h"
@@ -34,6 +39,11 @@ constexpr int EW_THREADS = 256, EW_POINTS = 2048, EW_MAX_BLOCKS = 1024;         
 // per-sample scalars (doubles) of the solve
 // (mask 15 only: VS_WB = sum w b and VS_BBRAW = sum w b^2 of the b before its projection; 0 otherwise)
 enum { VS_BB = 0, VS_RR = 1, VS_PQ = 2, VS_RZ0 = 3, VS_RZ1 = 4, VS_RHOMIN = 5, VS_WB = 6, VS_BBRAW = 7, VS_STRIDE = 8 };
+// reaction family: N x VX_STRIDE more doubles BEHIND the N x VS_STRIDE table above (whose layout every kernel keeps): the weighted means of c and of
+// 1/rho over the unknowns and the minimum of c there (a NaN or an infinity counting as -inf)
+enum { VX_CBAR = 0, VX_BBAR = 1, VX_CMIN = 2, VX_STRIDE = 4 };
+// what the RX = true kernels get on top: c (N,H,W) and 1 / sum w of the mask's unknowns
+struct VcReaction { const float* c; double inv_sum_w; };
 
 // Everything below is sized by the mh x mw unknowns: (H-2) x (W-2) when all four edges are Dirichlet
 static inline int vc_tiles(int mh, int mw) { return pcnn_cdiv(mh, FLUX_ROWS) * pcnn_cdiv(mw, FLUX_COLS); }
@@ -47,16 +57,17 @@ static inline int vc_cap(int mh, int mw) {
 }
 // workspace: x, r, p, q, z (N x mh x mw doubles each; q and z double as the two GEMM intermediates) and three partial-sum arrays of N x cap
 // scaled: the field s follows the partial sums, so x and part sit where the shared finish looks for them
+// reaction (never scaled): three more partial-sum arrays of N x cap in that place - of sum w c, sum w / rho and min c
 struct VcWs { double *x, *r, *p, *q, *z, *part, *s; int cap; };
-static inline size_t vc_bytes(int N, int mh, int mw, bool scaled = false) {
-  return ((scaled ? 6 : 5) * (size_t)N * mh * mw + 3 * (size_t)N * vc_cap(mh, mw)) * sizeof(double);
+static inline size_t vc_bytes(int N, int mh, int mw, bool scaled = false, bool reaction = false) {
+  return ((scaled ? 6 : 5) * (size_t)N * mh * mw + (reaction ? 6 : 3) * (size_t)N * vc_cap(mh, mw)) * sizeof(double);
 }
 static inline VcWs vc_layout(void* ws, int N, int mh, int mw) {
   VcWs l;
   const size_t v = (size_t)N * mh * mw;
   l.cap = vc_cap(mh, mw);
   l.x = static_cast<double*>(ws); l.r = l.x + v; l.p = l.r + v; l.q = l.p + v; l.z = l.q + v; l.part = l.z + v;
-  l.s = l.part + 3 * (size_t)N * l.cap;          // (only the scaled workspace reaches that far)
+  l.s = l.part + 3 * (size_t)N * l.cap;          // (only the scaled and the reaction workspaces reach that far)
   return l;
 }
 
@@ -126,9 +137,11 @@ __device__ __forceinline__ double stencil_at(const Faces& f, const double (*ps)[
 }
 
 // q = A p and the tile's share of p.q (BC: of sum w p q).  grid (column tiles, row tiles, N) over the nh x nw unknowns; part[n][tile]
-template <bool BC>
+// RX: q = (A + C) p - c of the thread's own point joins the point's sum before p.q is formed.
+template <bool BC, bool RX = false>
 __global__ __launch_bounds__(FLUX_THREADS) void varcoef_apply_kernel(int H, int W, int cap, int mask, const float* __restrict__ rho, const float* __restrict__ dx,
-                                                                     const double* __restrict__ p, double* __restrict__ q, double* __restrict__ part) {
+                                                                     const double* __restrict__ p, double* __restrict__ q, double* __restrict__ part,
+                                                                     const float* __restrict__ reaction) {
   __shared__ float rs[VT_LR][VT_LC];
   __shared__ double ps[VT_LR][VT_LC];
   __shared__ double red[FLUX_THREADS];
@@ -155,7 +168,8 @@ __global__ __launch_bounds__(FLUX_THREADS) void varcoef_apply_kernel(int H, int 
     for (int k = 0; k < FLUX_RPT; ++k) {
       const int r = r0 + k;
       if (I0 + r < nh) {
-        const double v = stencil_at(faces_at(rs, r, c), ps, r, c, inv_h2);
+        double v = stencil_at(faces_at(rs, r, c), ps, r, c, inv_h2);
+        if (RX) v += (double)reaction[((int64_t)n * H + u.i0 + I0 + r) * W + u.j0 + J0 + c] * ps[r + 1][c + 1];
         q[(int64_t)n * per + (int64_t)(I0 + r) * nw + J0 + c] = v;
         const double pv = ps[r + 1][c + 1] * v;
         s += BC ? vc_weight(I0 + r, J0 + c, nh, nw, mask) * pv : pv;
@@ -171,14 +185,16 @@ __global__ __launch_bounds__(FLUX_THREADS) void varcoef_apply_kernel(int H, int 
 // on a Neumann edge (BC), du/dn there: such a node's b gains 2 g / (rho_c dx) per Neumann edge it lies on, and the sums are weighted.
 // mask 15 (b_out != NULL): b is kept in b_out for the projection pass, and the second partial is the tile's share of sum w b - r.r is summed there.
 // SC: s = (mean of the four face coefficients)^-1/2 -> s_out and s o r -> t_out (mask 15: the projection pass writes it, from the projected r).
-template <bool BC, bool SC>
+// RX: r = b - (A + C) x0, and three more partials per tile behind the first three (part3): the tile's shares of the weighted means of c and of 1/rho
+// over the unknowns and its minimum of c, a NaN or an infinity counting as -inf.
+template <bool BC, bool SC, bool RX = false>
 __global__ __launch_bounds__(FLUX_THREADS) void varcoef_setup_kernel(int H, int W, int cap, int N, int mask, const float* __restrict__ rho,
                                                                      const float* __restrict__ f, const float* __restrict__ left,
                                                                      const float* __restrict__ right, const float* __restrict__ bottom,
                                                                      const float* __restrict__ top, const float* __restrict__ dx,
                                                                      const double* __restrict__ x0, double* __restrict__ x, double* __restrict__ rr_out,
                                                                      double* __restrict__ b_out, double* __restrict__ part, double* __restrict__ s_out,
-                                                                     double* __restrict__ t_out) {
+                                                                     double* __restrict__ t_out, VcReaction rx, double* __restrict__ part3) {
   __shared__ float rs[VT_LR][VT_LC];
   __shared__ double ps[VT_LR][VT_LC];
   __shared__ double red[FLUX_THREADS];
@@ -198,7 +214,8 @@ __global__ __launch_bounds__(FLUX_THREADS) void varcoef_setup_kernel(int H, int 
   __syncthreads();
   const double h = (double)dx[n], inv_h2 = 1.0 / (h * h);
   const int c = threadIdx.x % FLUX_COLS, r0 = (threadIdx.x / FLUX_COLS) * FLUX_RPT;
-  double sbb = 0.0, srr = 0.0;
+  double sbb = 0.0, srr = 0.0, scc = 0.0, sib = 0.0;
+  float cmn = INFINITY;
   if (J0 + c < nw) {
 #pragma unroll
     for (int k = 0; k < FLUX_RPT; ++k) {
@@ -218,7 +235,16 @@ __global__ __launch_bounds__(FLUX_THREADS) void varcoef_setup_kernel(int H, int 
         else if (j == 1 && !(BC && (mask & 4))) b += fc.lo_j * inv_h2 * gb;
         if (BC && j == W - 1) b += gn * gt;
         else if (j == W - 2 && !(BC && (mask & 8))) b += fc.hi_j * inv_h2 * gt;
-        const double res = b - stencil_at(fc, ps, r, c, inv_h2);
+        double ax = stencil_at(fc, ps, r, c, inv_h2);
+        if (RX) {
+          const float cv = rx.c[((int64_t)n * H + i) * W + j];
+          const double w = BC ? vc_weight(ii, jj, nh, nw, mask) : 1.0;
+          ax += (double)cv * ps[r + 1][c + 1];
+          scc += w * (double)cv;
+          sib += w / (double)rs[r + 1][c + 1];
+          cmn = fminf(cmn, (cv == cv && fabsf(cv) != INFINITY) ? cv : -INFINITY);
+        }
+        const double res = b - ax;
         const int64_t o = (int64_t)n * per + (int64_t)ii * nw + jj;
         x[o] = ps[r + 1][c + 1];
         rr_out[o] = res;
@@ -254,6 +280,19 @@ __global__ __launch_bounds__(FLUX_THREADS) void varcoef_setup_kernel(int H, int 
     part[(int64_t)n * cap + tile] = tbb;
     part[((int64_t)N + n) * cap + tile] = trr;
     part[((int64_t)2 * N + n) * cap + tile] = red[0];
+  }
+  if (RX) {
+    const double tcc = block_sum<FLUX_THREADS>(scc, red);
+    const double tib = block_sum<FLUX_THREADS>(sib, red);
+    __syncthreads();
+    red[threadIdx.x] = (double)cmn;
+    __syncthreads();
+    pcnn_block_reduce<double, FLUX_THREADS>(red, threadIdx.x, pcnn_min_op());
+    if (threadIdx.x == 0) {
+      part3[(int64_t)n * cap + tile] = tcc * rx.inv_sum_w;
+      part3[((int64_t)N + n) * cap + tile] = tib * rx.inv_sum_w;
+      part3[((int64_t)2 * N + n) * cap + tile] = red[0];
+    }
   }
 }
 
@@ -363,18 +402,28 @@ __global__ __launch_bounds__(EW_THREADS) void varcoef_update_xr_kernel(int64_t p
 // so r.z = sum c^2 / (lam_h + lam_w): the block's share of r.z comes from this pass and needs no further read of r and z.
 // BC: c = Vinv_h r Vinv_w^T with V^T W V = I per axis, so Vinv = V^T W and sum w r z is the same sum c^2 / (lam_h + lam_w).  The null mode of the
 // all-Neumann operator (lam_h + lam_w = 0) is dropped, as fd_divide_kernel drops it: z then has no constant part.
-template <bool BC>
+// RX: the divisor is bbar (lam_h + lam_w) / dx^2 + cbar with the sample's two means of extra (VX_*): the eigenvalues of bbar M + cbar I, M with its
+// 1/dx^2 - the scale no longer cancels.  The lam = 0 mode is kept when cbar > 0 (its divisor is cbar) and dropped otherwise.
+template <bool BC, bool RX = false>
 __global__ __launch_bounds__(EW_THREADS) void varcoef_divide_kernel(int nh, int nw, int cap, const double* __restrict__ lam_h, const double* __restrict__ lam_w,
-                                                                    double* __restrict__ T, double* __restrict__ part) {
+                                                                    double* __restrict__ T, double* __restrict__ part, const float* __restrict__ dx,
+                                                                    const double* __restrict__ extra) {
   __shared__ double red[EW_THREADS];
   const int n = blockIdx.y;
   double* Tn = T + (int64_t)n * nh * nw;
   double s = 0.0;
+  double kb = 1.0, cb = 0.0;
+  if (RX) {
+    const double h = (double)dx[n];
+    kb = extra[n * VX_STRIDE + VX_BBAR] / (h * h);
+    cb = extra[n * VX_STRIDE + VX_CBAR];
+  }
   for (int i = blockIdx.x; i < nh; i += gridDim.x) {           // a block takes whole rows: no index division per point
     const double li = lam_h[i];
     double* row = Tn + (int64_t)i * nw;
     for (int j = threadIdx.x; j < nw; j += EW_THREADS) {
-      const double c = row[j], l = li + lam_w[j], z = (!BC || fabs(l) > 1e-13) ? c / l : 0.0;
+      const double c = row[j], l = li + lam_w[j];
+      const double z = RX ? ((fabs(l) > 1e-13 || cb > 0.0) ? c / (kb * l + cb) : 0.0) : ((!BC || fabs(l) > 1e-13) ? c / l : 0.0);
       row[j] = z;
       s += c * z;
     }
@@ -538,53 +587,68 @@ static dim3 vc_tile_grid(int N, const FdUnknowns& u) { return dim3(pcnn_cdiv(u.m
 // r.z (BC: sum w r z) -> scal slot.
 // SC: the transform reads t = s o r, which the pass before left in z, and z comes out as M^-1 t: with c the coefficients of t the division pass' sum
 // c^2 / (lam_h + lam_w) is (s o r).M^-1 (s o r) = r.(s o M^-1 (s o r)), the r.z of the scaled preconditioner (diag(s) commutes with the weights).
-template <bool BC, bool SC>
-static int vc_precondition(pcnn_handle h, int N, const FdUnknowns& u, const VcWs& w, const VcBasis& B, double* scal, int slot) {
+// RX: the division takes dx and the two means behind the scalar table.
+template <bool BC, bool SC, bool RX = false>
+static int vc_precondition(pcnn_handle h, int N, const FdUnknowns& u, const VcWs& w, const VcBasis& B, double* scal, int slot, const float* dx = nullptr) {
   const int64_t per = (int64_t)u.mh * u.mw;
   const int eb = vc_ew_blocks(per);
   if (int rc = pcnn_two_sided_gemm_f64(h, N, u.mh, u.mw, B.Vinv_h, SC ? w.z : w.r, B.VinvT_w, w.q, w.z)) return rc;
-  hipLaunchKernelGGL(varcoef_divide_kernel<BC>, dim3(eb, N), dim3(EW_THREADS), 0, h->stream, u.mh, u.mw, w.cap, B.lam_h, B.lam_w, w.z, w.part);
+  hipLaunchKernelGGL((varcoef_divide_kernel<BC, RX>), dim3(eb, N), dim3(EW_THREADS), 0, h->stream, u.mh, u.mw, w.cap, B.lam_h, B.lam_w, w.z, w.part, dx,
+                     (const double*)(RX ? scal + (size_t)N * VS_STRIDE : nullptr));
   hipLaunchKernelGGL(varcoef_reduce_kernel<0>, dim3(N), dim3(EW_THREADS), 0, h->stream, eb, w.cap, w.part, scal, (int)VS_STRIDE, slot, 0, 0.0, (int*)nullptr);
   PCNN_CHECK_LAUNCH(h, "pcnn_varcoef_pcg(divide)");
   return pcnn_two_sided_gemm_f64(h, N, u.mh, u.mw, B.V_h, w.z, B.VT_w, w.q, w.z);
 }
 
 // The bodies of the entry points: BC = false behind the all-Dirichlet names (mask 0, S for every basis matrix), BC = true behind the *_bc_* names.
-template <bool BC>
-static int vc_apply(pcnn_handle h, const char* who, int N, int H, int W, int mask, const float* rho, const float* dx, const double* p, double* q, double* pq) {
-  PCNN_REQUIRE(h, h && rho && dx && p && q && pq, "%s: null argument", who);
+template <bool BC, bool RX = false>
+static int vc_apply(pcnn_handle h, const char* who, int N, int H, int W, int mask, const float* rho, const float* dx, const double* p, double* q, double* pq,
+                    const float* reaction = nullptr) {
+  PCNN_REQUIRE(h, h && rho && dx && p && q && pq && (!RX || reaction), "%s: null argument", who);
   FdUnknowns u;
   if (int rc = vc_check_shape(h, who, N, H, W, mask, &u)) return rc;
   const int cap = vc_cap(u.mh, u.mw), tiles = vc_tiles(u.mh, u.mw);
   if (int rc = pcnn_reserve(h, h->aux_ws, (size_t)N * cap * sizeof(double), 0, who)) return rc;
   double* part = static_cast<double*>(h->aux_ws.p);
-  hipLaunchKernelGGL(varcoef_apply_kernel<BC>, vc_tile_grid(N, u), dim3(FLUX_THREADS), 0, h->stream, H, W, cap, mask, rho, dx, p, q, part);
+  hipLaunchKernelGGL((varcoef_apply_kernel<BC, RX>), vc_tile_grid(N, u), dim3(FLUX_THREADS), 0, h->stream, H, W, cap, mask, rho, dx, p, q, part, reaction);
   hipLaunchKernelGGL(varcoef_reduce_kernel<0>, dim3(N), dim3(EW_THREADS), 0, h->stream, tiles, cap, part, pq, 1, 0, 0, 0.0, (int*)nullptr);
   PCNN_CHECK_LAUNCH(h, who);
   return 0;
 }
 
-template <bool BC, bool SC>
+template <bool BC, bool SC, bool RX = false>
 static int vc_setup(pcnn_handle h, const char* who, int N, int H, int W, int mask, const float* rho, const float* rhs, const float* left, const float* right,
                     const float* bottom, const float* top, const float* dx, const double* x0, double tol, const VcBasis& B, void* workspace,
-                    size_t workspace_bytes, double* scal, int* flags) {
+                    size_t workspace_bytes, double* scal, int* flags, const float* reaction = nullptr) {
+  static_assert(!(RX && SC), "the scaled preconditioner has no reaction variant");
   PCNN_REQUIRE(h, h && rho && rhs && left && right && bottom && top && dx && B.Vinv_h && B.V_h && B.lam_h && B.VinvT_w && B.VT_w && B.lam_w && workspace && scal &&
-                      flags, "%s: null argument", who);
+                      flags && (!RX || reaction), "%s: null argument", who);
   FdUnknowns u;
   if (int rc = vc_check_shape(h, who, N, H, W, mask, &u)) return rc;
   PCNN_REQUIRE(h, tol > 0.0, "%s: tol must be positive", who);
   const VcWs w = vc_layout(workspace, N, u.mh, u.mw);
-  PCNN_REQUIRE(h, workspace_bytes >= vc_bytes(N, u.mh, u.mw, SC), "%s: workspace of %zu B, %zu B needed", who, workspace_bytes, vc_bytes(N, u.mh, u.mw, SC));
+  PCNN_REQUIRE(h, workspace_bytes >= vc_bytes(N, u.mh, u.mw, SC, RX), "%s: workspace of %zu B, %zu B needed", who, workspace_bytes, vc_bytes(N, u.mh, u.mw, SC, RX));
   const int tiles = vc_tiles(u.mh, u.mw);
   const int64_t per = (int64_t)u.mh * u.mw;
   const int eb = vc_ew_blocks(per);
-  const bool singular = BC && mask == 15;
+  const bool singular = BC && mask == 15 && !RX;             // (with a reaction term mask 15 is definite: no projection)
   double* part_rr = w.part + (size_t)N * w.cap;
-  if (hipMemsetAsync(flags, 0, (size_t)N * sizeof(int), h->stream) != hipSuccess || hipMemsetAsync(scal, 0, (size_t)N * VS_STRIDE * sizeof(double), h->stream) != hipSuccess)
+  if (hipMemsetAsync(flags, 0, (size_t)N * sizeof(int), h->stream) != hipSuccess ||
+      hipMemsetAsync(scal, 0, (size_t)N * (VS_STRIDE + (RX ? VX_STRIDE : 0)) * sizeof(double), h->stream) != hipSuccess)
     PCNN_FAIL(h, "%s: cannot clear the per-sample state", who);
   double* const sc = SC ? w.s : (double*)nullptr;
-  hipLaunchKernelGGL((varcoef_setup_kernel<BC, SC>), vc_tile_grid(N, u), dim3(FLUX_THREADS), 0, h->stream, H, W, w.cap, N, mask, rho, rhs, left, right, bottom, top, dx,
-                     x0, w.x, w.r, singular ? w.q : (double*)nullptr, w.part, sc, SC ? w.z : (double*)nullptr);
+  double* const part3 = RX ? w.s : (double*)nullptr;
+  const VcReaction rx = {reaction, 1.0 / (((double)u.mh - 0.5 * ((mask & 1) + ((mask >> 1) & 1))) * ((double)u.mw - 0.5 * (((mask >> 2) & 1) + ((mask >> 3) & 1))))};
+  hipLaunchKernelGGL((varcoef_setup_kernel<BC, SC, RX>), vc_tile_grid(N, u), dim3(FLUX_THREADS), 0, h->stream, H, W, w.cap, N, mask, rho, rhs, left, right, bottom, top,
+                     dx, x0, w.x, w.r, singular ? w.q : (double*)nullptr, w.part, sc, SC ? w.z : (double*)nullptr, rx, part3);
+  if (RX) {
+    double* extra = scal + (size_t)N * VS_STRIDE;
+    hipLaunchKernelGGL(varcoef_reduce_kernel<0>, dim3(N), dim3(EW_THREADS), 0, h->stream, tiles, w.cap, part3, extra, (int)VX_STRIDE, (int)VX_CBAR, 0, 0.0, (int*)nullptr);
+    hipLaunchKernelGGL(varcoef_reduce_kernel<0>, dim3(N), dim3(EW_THREADS), 0, h->stream, tiles, w.cap, part3 + (size_t)N * w.cap, extra, (int)VX_STRIDE, (int)VX_BBAR, 0,
+                       0.0, (int*)nullptr);
+    hipLaunchKernelGGL(varcoef_reduce_kernel<1>, dim3(N), dim3(EW_THREADS), 0, h->stream, tiles, w.cap, part3 + (size_t)2 * N * w.cap, extra, (int)VX_STRIDE, (int)VX_CMIN,
+                       0, 0.0, (int*)nullptr);
+  }
   int bb_count = tiles;
   if (singular) {            // sum w b^2 and sum w b of the b as given, then the projection: b.b and r.r are the projected fields'
     const double sum_w = (double)(H - 1) * (double)(W - 1);
@@ -599,48 +663,50 @@ static int vc_setup(pcnn_handle h, const char* who, int N, int H, int W, int mas
   hipLaunchKernelGGL(varcoef_reduce_kernel<1>, dim3(N), dim3(EW_THREADS), 0, h->stream, tiles, w.cap, w.part + (size_t)2 * N * w.cap, scal, (int)VS_STRIDE,
                      (int)VS_RHOMIN, 0, 0.0, (int*)nullptr);
   PCNN_CHECK_LAUNCH(h, who);
-  if (int rc = vc_precondition<BC, SC>(h, N, u, w, B, scal, VS_RZ0)) return rc;
+  if (int rc = vc_precondition<BC, SC, RX>(h, N, u, w, B, scal, VS_RZ0, dx)) return rc;
   hipLaunchKernelGGL(varcoef_update_p_kernel<SC>, dim3(eb, N), dim3(EW_THREADS), 0, h->stream, per, 1, 1, scal, flags, w.z, w.p, (const double*)sc);
   PCNN_CHECK_LAUNCH(h, who);
   return 0;
 }
 
-template <bool BC, bool SC>
+template <bool BC, bool SC, bool RX = false>
 static int vc_iterate(pcnn_handle h, const char* who, int N, int H, int W, int mask, const float* rho, const float* dx, double tol, int first_iteration,
-                      int iterations, const VcBasis& B, void* workspace, size_t workspace_bytes, double* scal, int* flags) {
-  PCNN_REQUIRE(h, h && rho && dx && B.Vinv_h && B.V_h && B.lam_h && B.VinvT_w && B.VT_w && B.lam_w && workspace && scal && flags, "%s: null argument", who);
+                      int iterations, const VcBasis& B, void* workspace, size_t workspace_bytes, double* scal, int* flags, const float* reaction = nullptr) {
+  PCNN_REQUIRE(h, h && rho && dx && B.Vinv_h && B.V_h && B.lam_h && B.VinvT_w && B.VT_w && B.lam_w && workspace && scal && flags && (!RX || reaction),
+               "%s: null argument", who);
   FdUnknowns u;
   if (int rc = vc_check_shape(h, who, N, H, W, mask, &u)) return rc;
   PCNN_REQUIRE(h, tol > 0.0 && first_iteration >= 0 && iterations >= 1, "%s: bad tol or iteration range", who);
   const VcWs w = vc_layout(workspace, N, u.mh, u.mw);
-  PCNN_REQUIRE(h, workspace_bytes >= vc_bytes(N, u.mh, u.mw, SC), "%s: workspace of %zu B, %zu B needed", who, workspace_bytes, vc_bytes(N, u.mh, u.mw, SC));
+  PCNN_REQUIRE(h, workspace_bytes >= vc_bytes(N, u.mh, u.mw, SC, RX), "%s: workspace of %zu B, %zu B needed", who, workspace_bytes, vc_bytes(N, u.mh, u.mw, SC, RX));
   const int tiles = vc_tiles(u.mh, u.mw);
   const int64_t per = (int64_t)u.mh * u.mw;
   const int eb = vc_ew_blocks(per);
   double* const sc = SC ? w.s : (double*)nullptr;
   for (int it = first_iteration; it < first_iteration + iterations; ++it) {
     const int cur = it & 1;                      // r.z of the current direction sits in slot VS_RZ0 + cur, the next one goes to the other slot
-    hipLaunchKernelGGL(varcoef_apply_kernel<BC>, vc_tile_grid(N, u), dim3(FLUX_THREADS), 0, h->stream, H, W, w.cap, mask, rho, dx, w.p, w.q, w.part);
+    hipLaunchKernelGGL((varcoef_apply_kernel<BC, RX>), vc_tile_grid(N, u), dim3(FLUX_THREADS), 0, h->stream, H, W, w.cap, mask, rho, dx, w.p, w.q, w.part, reaction);
     hipLaunchKernelGGL(varcoef_reduce_kernel<0>, dim3(N), dim3(EW_THREADS), 0, h->stream, tiles, w.cap, w.part, scal, (int)VS_STRIDE, (int)VS_PQ, 0, 0.0, (int*)nullptr);
     hipLaunchKernelGGL((varcoef_update_xr_kernel<BC, SC>), dim3(eb, N), dim3(EW_THREADS), 0, h->stream, per, u.mh, u.mw, mask, w.cap, cur, scal, flags, w.p, w.q, w.x,
                        w.r, w.part, (const double*)sc, SC ? w.z : (double*)nullptr);
     hipLaunchKernelGGL(varcoef_reduce_kernel<0>, dim3(N), dim3(EW_THREADS), 0, h->stream, eb, w.cap, w.part, scal, (int)VS_STRIDE, (int)VS_RR, 1, tol * tol, flags);
     PCNN_CHECK_LAUNCH(h, who);
-    if (int rc = vc_precondition<BC, SC>(h, N, u, w, B, scal, VS_RZ0 + (cur ^ 1))) return rc;
+    if (int rc = vc_precondition<BC, SC, RX>(h, N, u, w, B, scal, VS_RZ0 + (cur ^ 1), dx)) return rc;
     hipLaunchKernelGGL(varcoef_update_p_kernel<SC>, dim3(eb, N), dim3(EW_THREADS), 0, h->stream, per, cur, 0, scal, flags, w.z, w.p, (const double*)sc);
     PCNN_CHECK_LAUNCH(h, who);
   }
   return 0;
 }
 
-// soln: the unknowns from x, the Dirichlet ring from the boundary arrays, as every FD solve here writes it.  mask 15: x first loses its w-mean.
+// soln: the unknowns from x, the Dirichlet ring from the boundary arrays, as every FD solve here writes it.  mask 15: x first loses its w-mean
+// (keep_mean: not so - the reaction family's mask 15 is nonsingular).
 static int vc_finish(pcnn_handle h, const char* who, int N, int H, int W, int mask, void* workspace, const float* left, const float* right, const float* bottom,
-                     const float* top, float* soln) {
+                     const float* top, float* soln, bool keep_mean = false) {
   PCNN_REQUIRE(h, h && workspace && left && right && bottom && top && soln, "%s: null argument", who);
   FdUnknowns u;
   if (int rc = vc_check_shape(h, who, N, H, W, mask, &u)) return rc;
   const VcWs w = vc_layout(workspace, N, u.mh, u.mw);
-  if (mask == 15) {
+  if (mask == 15 && !keep_mean) {
     const int eb = vc_ew_blocks((int64_t)u.mh * u.mw);
     const double sum_w = (double)(H - 1) * (double)(W - 1);
     double* mean = w.part + (size_t)N * w.cap;     // the second partial-sum array: N doubles are enough
@@ -792,5 +858,48 @@ extern "C" int pcnn_varcoef_density_smooth(pcnn_handle h, int N, int64_t per, fl
   hipLaunchKernelGGL(varcoef_density_range_kernel, dim3((unsigned)blocks, N), dim3(EW_THREADS), 0, h->stream, per, (const float*)g, mm);
   hipLaunchKernelGGL(varcoef_density_smooth_kernel, dim3((unsigned)blocks, N), dim3(EW_THREADS), 0, h->stream, per, lo, hi, (const float*)mm, g);
   PCNN_CHECK_LAUNCH(h, "pcnn_varcoef_density_smooth");
+  return 0;
+}
+
+// ---- the reaction term: the RX = true instantiations of the *_bc_* family
+extern "C" int pcnn_varcoef_bc_apply_reaction(pcnn_handle h, int N, int H, int W, int neumann_mask, const float* rho, const float* dx, const double* p, double* q,
+                                              double* pq, const float* reaction) {
+  return vc_apply<true, true>(h, "pcnn_varcoef_bc_apply_reaction", N, H, W, neumann_mask, rho, dx, p, q, pq, reaction);
+}
+
+extern "C" size_t pcnn_varcoef_bc_pcg_workspace_reaction(int N, int H, int W, int neumann_mask) {
+  if (N < 1 || H < 3 || W < 3 || neumann_mask < 0 || neumann_mask > 15) return 0;
+  const FdUnknowns u = fd_unknowns(H, W, neumann_mask);
+  return vc_bytes(N, u.mh, u.mw, false, true);
+}
+
+extern "C" int pcnn_varcoef_bc_pcg_setup_reaction(pcnn_handle h, int N, int H, int W, int neumann_mask, const float* rho, const float* rhs, const float* left,
+                                                  const float* right, const float* bottom, const float* top, const float* dx, const double* x0, double tol,
+                                                  const double* Vinv_h, const double* V_h, const double* lam_h, const double* VinvT_w, const double* VT_w,
+                                                  const double* lam_w, void* workspace, size_t workspace_bytes, double* scal, int* flags, const float* reaction) {
+  return vc_setup<true, false, true>(h, "pcnn_varcoef_bc_pcg_setup_reaction", N, H, W, neumann_mask, rho, rhs, left, right, bottom, top, dx, x0, tol,
+                                     VcBasis{Vinv_h, V_h, lam_h, VinvT_w, VT_w, lam_w}, workspace, workspace_bytes, scal, flags, reaction);
+}
+
+extern "C" int pcnn_varcoef_bc_pcg_iterate_reaction(pcnn_handle h, int N, int H, int W, int neumann_mask, const float* rho, const float* dx, double tol,
+                                                    int first_iteration, int iterations, const double* Vinv_h, const double* V_h, const double* lam_h,
+                                                    const double* VinvT_w, const double* VT_w, const double* lam_w, void* workspace, size_t workspace_bytes,
+                                                    double* scal, int* flags, const float* reaction) {
+  return vc_iterate<true, false, true>(h, "pcnn_varcoef_bc_pcg_iterate_reaction", N, H, W, neumann_mask, rho, dx, tol, first_iteration, iterations,
+                                       VcBasis{Vinv_h, V_h, lam_h, VinvT_w, VT_w, lam_w}, workspace, workspace_bytes, scal, flags, reaction);
+}
+
+extern "C" int pcnn_varcoef_bc_pcg_finish_reaction(pcnn_handle h, int N, int H, int W, int neumann_mask, void* workspace, const float* left, const float* right,
+                                                   const float* bottom, const float* top, float* soln) {
+  return vc_finish(h, "pcnn_varcoef_bc_pcg_finish_reaction", N, H, W, neumann_mask, workspace, left, right, bottom, top, soln, true);
+}
+
+extern "C" int pcnn_varcoef_reaction_field(pcnn_handle h, int64_t total, float lo, float hi, float* g) {
+  PCNN_REQUIRE(h, h && g && total >= 1, "pcnn_varcoef_reaction_field: bad argument");
+  PCNN_REQUIRE(h, lo >= 0.f && hi >= lo && hi < INFINITY, "pcnn_varcoef_reaction_field: need 0 <= lo <= hi, got %g, %g", (double)lo, (double)hi);
+  int64_t blocks = pcnn_cdiv64(total, 256);
+  if (blocks > 16384) blocks = 16384;
+  hipLaunchKernelGGL(varcoef_density_kernel, dim3((unsigned)blocks), dim3(256), 0, h->stream, total, lo, hi, g);
+  PCNN_CHECK_LAUNCH(h, "pcnn_varcoef_reaction_field");
   return 0;
 }

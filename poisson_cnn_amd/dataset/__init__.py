@@ -528,8 +528,30 @@ VARIABLE_DENSITY_PRECONDITIONERS = ('dst', 'scaled')
 VARIABLE_DENSITY_PROFILES = ('abs', 'smooth')
 
 
+def _reaction_on_host(reaction, rs, neumann, preconditioner):
+    """The refusals of variable_density_poisson_solve's `reaction` that need no device; -> True when it is one number per sample (or one number)."""
+    N, H, W = rs
+    if preconditioner == 'scaled':
+        raise ValueError("preconditioner='scaled' has no reaction variant: use 'dst' with reaction")
+    shape = tuple(reaction.shape) if hasattr(reaction, 'shape') else np.shape(reaction)
+    per_sample = int(np.prod(shape, dtype=np.int64)) in (1, N) and len(shape) <= 4 and all(d == 1 for d in shape[1:])
+    if not per_sample and _lead_shape(reaction, 'reaction', 3) != rs:
+        raise ValueError('reaction %r must match rhses %r, or hold one number per sample' % (shape, rs))
+    if not (isinstance(reaction, torch.Tensor) and reaction.is_cuda):            # a device tensor is checked by the setup launch
+        c = _host_array(reaction).astype(np.float64)
+        (i0, i1), (j0, j1) = K.varcoef_unknowns(H, W, neumann)
+        c = np.broadcast_to(c.reshape(-1, 1, 1), (N, 1, 1)) if per_sample else c.reshape(N, H, W)[:, i0:i1 + 1, j0:j1 + 1]
+        if not np.all(np.isfinite(c) & (c >= 0)):
+            raise ValueError('reaction must be non-negative and finite on every unknown')
+        zero = np.flatnonzero(~(c.reshape(N, -1) > 0).any(axis=1))
+        if all(neumann) and zero.size:
+            raise ValueError('all four edges Neumann and a reaction that is zero on every unknown of sample(s) %r: that system is singular - solve such a '
+                             'sample without the reaction keyword' % (zero.tolist(),))
+    return per_sample
+
+
 def variable_density_poisson_solve(rho, rhses, boundaries, dx, dy=None, tol=1e-10, max_iterations=500, initial_guesses=None, check_every=8,
-                                   return_info=False, device=None, check_start=False, boundary_types=None, preconditioner='dst'):
+                                   return_info=False, device=None, check_start=False, boundary_types=None, preconditioner='dst', reaction=None):
     """Solves div((1/rho) grad u) = f with Dirichlet data on the four edges, on the vertex-centred grid of multigrid_poisson_solve (same shapes
     and edge names: rhses (N,1,H,W) or (N,H,W); boundaries: dict with 'left'/'right' (N,W) and 'bottom'/'top' (N,H); dx one spacing per sample).
     rho (N,H,W) or (N,1,H,W) is given on every node, boundary nodes included, and must be positive.
@@ -573,6 +595,19 @@ def variable_density_poisson_solve(rho, rhses, boundaries, dx, dy=None, tol=1e-1
     512^2 and ratio 100 to 1000): opt-in, DESIGN.md section 22 has the counts.  Works with every
     boundary_types and with initial_guesses; the same system, tolerance and returned info.  Any other value raises ValueError.
 
+    reaction: c >= 0 in div((1/rho) grad u) - c u = f - the implicit diffusion or viscous step (rho / dt) u - div(mu grad u) = g
+    and any backward-Euler step of u_t = div(k grad u) have this form.  fp32, (N,H,W) or (N,1,H,W) on every node, or one number per sample ((N,),
+    (N,1), ..) that is broadcast; read on the unknowns only.  On the unknowns (A + C) u = b with C = diag(c) and the A, b and w above; W (A + C) is
+    symmetric and positive definite once an edge is Dirichlet or c > 0 somewhere.  The preconditioner becomes the constant-coefficient solve of
+    bbar M + cbar I - bbar and cbar the weighted means of 1/rho and of c over the unknowns, M with its 1/dx^2 - and the condition number is at most
+    max(beta/bbar, c/cbar) / min(beta/bbar, c/cbar) at any grid size.  That bound is weak when c dominates the operator's diagonal AND varies as
+    much as 1/rho does: with c = 1e3 s / (rho dx^2), s in [0.5, 1.5], the device needs 56 to 64 iterations at density ratio 10 (40 without c) but
+    472 to more than 504 at ratio 1000 (264 to 288 without c) on 512^2 grids - raise max_iterations there.  With all four edges Neumann and c > 0 somewhere the system is nonsingular:
+    nothing is projected, no mean is removed, `compatibility_defect` and `rhs_shift` are zeros.  ValueError: a c that is negative or not finite on
+    an unknown (a host array: before any device work; a device tensor: straight after the setup launch, a NaN counting as -inf), a shape that
+    matches neither form, preconditioner='scaled' together with reaction, and - all four edges Neumann - a sample whose c is zero on every unknown
+    (singular: solve it without the keyword).  None (default): the solve above, the same calls and the same bits.
+
     Returns soln (N,1,H,W) fp32; with return_info also a dict of per-sample numpy arrays `iterations` (a multiple of check_every), `converged`
     and `relative_residual` (||r|| / ||b|| of the recurrence), and with a Neumann edge `compatibility_defect` and `rhs_shift` (zeros unless all four
     edges are Neumann)."""
@@ -604,15 +639,19 @@ def variable_density_poisson_solve(rho, rhses, boundaries, dx, dy=None, tol=1e-1
         raise ValueError('initial_guesses %r must match rhses %r' % (tuple(initial_guesses.shape), tuple(rhses.shape)))
     if not (isinstance(rho, torch.Tensor) and rho.is_cuda) and not np.all(_host_array(rho) > 0):
         raise ValueError('rho must be positive everywhere')
+    reaction_per_sample = _reaction_on_host(reaction, rs, neumann, preconditioner) if reaction is not None else False
     r, b, d, dev = _solver_args(rhses, boundaries, dx, device)
     dens = _f32(rho, dev).reshape(N, H, W).contiguous()
     x0 = None
     if initial_guesses is not None:
         g = initial_guesses if isinstance(initial_guesses, torch.Tensor) else torch.as_tensor(np.asarray(initial_guesses))
         x0 = g.to(device=dev, dtype=torch.float64).reshape(N, H, W).contiguous()
-    scaled = {'scaled': True} if preconditioner == 'scaled' else {}             # ('dst': the call as it has always been)
+    extra = {'scaled': True} if preconditioner == 'scaled' else {}              # ('dst': the call as it has always been)
+    if reaction is not None:                                                    # (None: the call as it has always been; never with 'scaled')
+        c = _f32(reaction, dev)
+        extra = {'reaction': (c.reshape(-1, 1, 1).expand(N, H, W) if reaction_per_sample else c.reshape(N, H, W)).contiguous()}
     soln, info = K.varcoef_pcg_solve(dens, r, b['left'], b['right'], b['bottom'], b['top'], d, tol=float(tol), max_iterations=int(max_iterations), x0=x0,
-                                     check_every=int(check_every), check_start=bool(check_start), neumann=neumann if any(neumann) else None, **scaled)
+                                     check_every=int(check_every), check_start=bool(check_start), neumann=neumann if any(neumann) else None, **extra)
     if not info['converged'].all():           # (a rho <= 0 or NaN on the device was refused inside, straight after the setup kernel's minimum)
         bad = np.flatnonzero(~info['converged'])
         warnings.warn('variable_density_poisson_solve: sample(s) %r not converged to tol = %g after %d iterations (relative residual %r)'
@@ -624,10 +663,10 @@ def variable_density_poisson_solve(rho, rhses, boundaries, dx, dy=None, tol=1e-1
     return soln
 
 
-def compressible_poisson_solve(rho, rhses, boundaries, dx, dy=None, system_matrix=None, preconditioner='dst'):
+def compressible_poisson_solve(rho, rhses, boundaries, dx, dy=None, system_matrix=None, preconditioner='dst', reaction=None):
     """The reference's name and argument order (dataset/generators/variable_density: compressible_poisson_solve).  system_matrix is accepted and
-    ignored: no matrix is assembled.  preconditioner: variable_density_poisson_solve's."""
-    return variable_density_poisson_solve(rho, rhses, boundaries, dx, dy=dy, preconditioner=preconditioner)
+    ignored: no matrix is assembled.  preconditioner, reaction: variable_density_poisson_solve's."""
+    return variable_density_poisson_solve(rho, rhses, boundaries, dx, dy=dy, preconditioner=preconditioner, reaction=reaction)
 
 
 def _check_density_range(density_range):
@@ -668,14 +707,28 @@ class variable_density_dataset_generator(numerical_dataset_generator):
 
     density_profile: 'abs' (default) is the rho above, which has a kink wherever g changes sign.  'smooth' is rho = lo + (hi - lo) (g - min g) /
     (max g - min g) per sample (pcnn_varcoef_density_smooth): as smooth as g, minimum lo and maximum hi - the densities preconditioner = 'scaled'
-    (variable_density_poisson_solve's, passed through; default 'dst') is for.  Neither changes the random draws."""
+    (variable_density_poisson_solve's, passed through; default 'dst') is for.  Neither changes the random draws.
+
+    reaction_range: (lo, hi) with 0 <= lo <= hi draws one more smooth field c = lo + (hi - lo) |g| / max|g| (density_smoothness_range control
+    points, the density kernel's map), solves div((1/rho) grad u) - c u = f with it (variable_density_poisson_solve's reaction) and yields it as a
+    third channel, stack([rhs, rho, c], axis=1).  The field is drawn last, after the edges: the draws of every other field are those of
+    reaction_range = None, which is the generator above, draw for draw.  Not with preconditioner = 'scaled'; with all four edges Neumann lo or hi
+    must be positive enough that no sample's c vanishes (the solve refuses such a sample).  The model's density_input reads two channels: such
+    batches are for solver studies, not yet for training."""
 
     def __init__(self, batch_size=1, batches_per_epoch=1, output_shape=None, random_output_shape_range=((64, 85), (64, 85)), density_range=(1.0, 10.0),
                  rhs_smoothness_range=(5, 20), density_smoothness_range=(5, 20), boundaries='zero', random_dx_range=(0.005, 0.05), rhs_max_magnitude=1.0,
                  boundary_max_magnitude=1.0, tol=1e-10, max_iterations=500, seed=0, device=None, return_keras_style=True, shard=None, boundary_types=None,
-                 preconditioner='dst', density_profile='abs'):
+                 preconditioner='dst', density_profile='abs', reaction_range=None):
         super().__init__(batch_size=batch_size, batches_per_epoch=batches_per_epoch, return_keras_style=return_keras_style, seed=seed, device=device,
                          shard=shard)
+        if reaction_range is not None:
+            if len(reaction_range) != 2 or not 0.0 <= float(reaction_range[0]) <= float(reaction_range[1]) < np.inf:
+                raise ValueError('reaction_range = (lo, hi) needs 0 <= lo <= hi, got %r' % (reaction_range,))
+            if preconditioner == 'scaled':
+                raise ValueError("preconditioner='scaled' has no reaction variant: use 'dst' with reaction_range")
+            reaction_range = (float(reaction_range[0]), float(reaction_range[1]))
+        self.reaction_range = reaction_range
         self.boundary_types = boundary_types
         self.neumann_flags = _neumann_flags(boundary_types) if boundary_types is not None else (False,) * 4      # (left, right, bottom, top)
         lo, hi = _check_density_range(density_range)
@@ -702,8 +755,8 @@ class variable_density_dataset_generator(numerical_dataset_generator):
         else:
             H, W = [int(self.shape_rng.integers(r[0], r[1] + 1)) for r in self.random_output_shape_range]
         dx = rng.uniform(size=(N, 1)) * (self.random_dx_range[1] - self.random_dx_range[0]) + self.random_dx_range[0]
-        ctrl = lambda rg: [int(rng.integers(rg[0], rg[1] + 1)) for _ in range(2)]
-        nf, nr = ctrl(self.rhs_smoothness_range), ctrl(self.density_smoothness_range)
+        ctrl_counts = lambda rg: [int(rng.integers(rg[0], rg[1] + 1)) for _ in range(2)]
+        nf, nr = ctrl_counts(self.rhs_smoothness_range), ctrl_counts(self.density_smoothness_range)
         rhs = self._smooth_field(2 * rng.uniform(size=(N, nf[0], nf[1])) - 1, (H, W), self.rhs_max_magnitude)
         rho = self._density_field(2 * rng.uniform(size=(N, nr[0], nr[1])) - 1, (H, W))
         lengths = {'left': W, 'right': W, 'top': H, 'bottom': H}
@@ -715,11 +768,16 @@ class variable_density_dataset_generator(numerical_dataset_generator):
                 ctrl = 2 * rng.uniform(size=(N, nb)) - 1
             bc[k] = self._edge(ctrl, lengths[k], self.boundary_max_magnitude)
         d = self._dev(dx)
+        extra = {}
+        if self.reaction_range is not None:                                # drawn last: the streams of the fields above do not move
+            nc = ctrl_counts(self.density_smoothness_range)
+            extra['reaction'] = K.varcoef_reaction_field(self._smooth_field(2 * rng.uniform(size=(N, nc[0], nc[1])) - 1, (H, W), 1.0), *self.reaction_range)
         soln, self.last_info = variable_density_poisson_solve(rho, rhs, bc, d, tol=self.tol, max_iterations=self.max_iterations, return_info=True,
-                                                              device=self.device, boundary_types=self.boundary_types, preconditioner=self.preconditioner)
-        if all(self.neumann_flags):                                        # the equation (rhs, soln) satisfies: the solver projected its b
+                                                              device=self.device, boundary_types=self.boundary_types, preconditioner=self.preconditioner,
+                                                              **extra)
+        if all(self.neumann_flags) and not extra:                          # the equation (rhs, soln) satisfies: the solver projected its b
             rhs = rhs + torch.as_tensor(self.last_info['rhs_shift'], dtype=torch.float32, device=rhs.device).view(N, 1, 1)
-        frho = torch.stack([rhs, rho], dim=1)
+        frho = torch.stack([rhs, rho] + list(extra.values()), dim=1)
         if not self.return_keras_style:
             return soln, frho
         inp = [frho]

@@ -159,11 +159,13 @@ def _varcoef_bases(H, W, neumann, device):
     return Vih, Vh, lh, ViwT, VwT, lw
 
 
-def varcoef_apply(rho, dx, p, neumann=None):
+def varcoef_apply(rho, dx, p, neumann=None, reaction=None):
     """q = A p of the variable-density flux-form operator (include/pcnn.h, pcnn_varcoef_apply) with zero Dirichlet data, and the per-sample p.q
     of the same pass.  rho (N,H,W) fp32, dx (N,) fp32, p (N,H-2,W-2) fp64 -> q (N,H-2,W-2) fp64, pq (N,) fp64.
     neumann = (left, right, bottom, top) flags: pcnn_varcoef_bc_apply - p and q cover the unknowns of varcoef_unknowns, a Neumann edge's nodes
-    included, and pq is the weighted sum w p q (varcoef_weights).  None: the all-Dirichlet entry point."""
+    included, and pq is the weighted sum w p q (varcoef_weights).  None: the all-Dirichlet entry point.
+    reaction: c (N,H,W) fp32 on every node -> q = (A + C) p, C = diag(c) on the unknowns (pcnn_varcoef_bc_apply_reaction; with
+    neumann = None its mask 0).  None: the calls above, untouched."""
     if rho.dim() != 3:
         raise ValueError('rho must be (N,H,W)')
     N, H, W = rho.shape
@@ -173,7 +175,11 @@ def varcoef_apply(rho, dx, p, neumann=None):
     _chk_varcoef(p, 'p', (N, i1 - i0 + 1, j1 - j0 + 1), torch.float64)
     q = torch.empty_like(p)
     pq = torch.empty((N,), dtype=torch.float64, device=p.device)
-    if neumann is None:
+    if reaction is not None:
+        _chk_varcoef(reaction, 'reaction', (N, H, W))
+        handle().call('pcnn_varcoef_bc_apply_reaction', c_int(N), c_int(H), c_int(W), c_int(_neumann_mask(neumann) if neumann is not None else 0), _p(rho), _p(dx),
+                      _p(p), _p(q), _p(pq), _p(reaction))
+    elif neumann is None:
         handle().call('pcnn_varcoef_apply', c_int(N), c_int(H), c_int(W), _p(rho), _p(dx), _p(p), _p(q), _p(pq))
     else:
         handle().call('pcnn_varcoef_bc_apply', c_int(N), c_int(H), c_int(W), c_int(_neumann_mask(neumann)), _p(rho), _p(dx), _p(p), _p(q), _p(pq))
@@ -182,10 +188,12 @@ def varcoef_apply(rho, dx, p, neumann=None):
 
 # columns of the per-sample scalar table of pcnn_varcoef_pcg_* (8 doubles per sample); wb, bb_raw: sum w b and sum w b^2 before the mask-15 projection
 VARCOEF_SCALARS = {'bb': 0, 'rr': 1, 'pq': 2, 'rho_min': 5, 'wb': 6, 'bb_raw': 7}
+# ... and of the 4 doubles per sample the *_reaction entry points keep behind that table: the weighted means of c and of 1/rho, the minimum of c
+VARCOEF_REACTION_SCALARS = {'c_mean': 0, 'inv_rho_mean': 1, 'c_min': 2}
 
 
 def varcoef_pcg_solve(rho, rhs, left, right, bottom, top, dx, tol=1e-10, max_iterations=500, x0=None, check_every=8, check_start=False, neumann=None,
-                      scaled=False):
+                      scaled=False, reaction=None):
     """Preconditioned conjugate gradients on the variable-density system (pcnn_varcoef_pcg_setup / _iterate / _finish).  rho, rhs (N,H,W),
     left/right (N,W), bottom/top (N,H), dx (N,): fp32 CUDA tensors; x0: optional (N,H,W) fp64 initial guess (its unknowns are used).
     The device runs check_every iterations per call; the host reads the N convergence flags between calls and nothing else.
@@ -201,19 +209,41 @@ def varcoef_pcg_solve(rho, rhs, left, right, bottom, top, dx, tol=1e-10, max_ite
     projection took from b, i.e. the solution solves the system of rhs + rhs_shift; the solution has zero trapezoidal integral.  Both are 0
     for every other mask.
     scaled: the *_scaled entry points - the preconditioner s o M^-1 (s o r), s = (mean face coefficient)^-1/2 (DESIGN.md section 22), for smooth rho;
-    one more workspace field, the same launches per iteration, the same finish."""
+    one more workspace field, the same launches per iteration, the same finish.
+    reaction: c (N,H,W) fp32 CUDA tensor, read on the unknowns: div((1/rho) grad u) - c u = f through the pcnn_varcoef_bc_*_reaction entry points
+    (neumann = None is their mask 0).  A c that is negative, NaN or infinite on an unknown raises ValueError straight after the
+    setup launch, as does - with all four edges Neumann - a sample whose c is zero on every unknown (singular: solve it without the keyword).  All
+    four True with c > 0 somewhere is nonsingular: no projection, no mean removed, compatibility_defect and rhs_shift are zeros.  Not with scaled.
+    None: the calls above, untouched."""
     N, H, W = rho.shape
+    if reaction is not None and scaled:
+        raise ValueError('the scaled preconditioner has no reaction variant: scaled and reaction exclude each other')
     for name, t, shape in (('rho', rho, (N, H, W)), ('rhs', rhs, (N, H, W)), ('left', left, (N, W)), ('right', right, (N, W)), ('bottom', bottom, (N, H)),
                            ('top', top, (N, H)), ('dx', dx, (N,))):
         _chk_varcoef(t, name, shape)
     if x0 is not None:
         _chk_varcoef(x0, 'x0', (N, H, W), torch.float64)
+    if reaction is not None:
+        _chk_varcoef(reaction, 'reaction', (N, H, W))
     if not (tol > 0 and max_iterations >= 1 and check_every >= 1):
         raise ValueError('tol must be positive, max_iterations and check_every at least 1')
     dev = rho.device
     lib, h = _lib.load(), handle()
     # the three stages as closures, one set per family of entry points: every call site spelled out (tools/check_ctypes_calls.py reads them)
-    if neumann is None:
+    if reaction is not None:
+        mask = _neumann_mask(neumann) if neumann is not None else 0
+        Vih, Vh, lh, ViwT, VwT, lw = _varcoef_bases(H, W, neumann if neumann is not None else (False,) * 4, dev)
+        nbytes = int(lib.pcnn_varcoef_bc_pcg_workspace_reaction(c_int(N), c_int(H), c_int(W), c_int(mask)))
+        ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+        setup = lambda: h.call('pcnn_varcoef_bc_pcg_setup_reaction', c_int(N), c_int(H), c_int(W), c_int(mask), _p(rho), _p(rhs), _p(left), _p(right), _p(bottom),
+                               _p(top), _p(dx), _p(x0), c_double(tol), _p(Vih), _p(Vh), _p(lh), _p(ViwT), _p(VwT), _p(lw), _p(ws), c_size_t(nbytes), _p(scal_all),
+                               _p(flags), _p(reaction))
+        iterate = lambda it: h.call('pcnn_varcoef_bc_pcg_iterate_reaction', c_int(N), c_int(H), c_int(W), c_int(mask), _p(rho), _p(dx), c_double(tol), c_int(it),
+                                    c_int(check_every), _p(Vih), _p(Vh), _p(lh), _p(ViwT), _p(VwT), _p(lw), _p(ws), c_size_t(nbytes), _p(scal_all), _p(flags),
+                                    _p(reaction))
+        finish = lambda: h.call('pcnn_varcoef_bc_pcg_finish_reaction', c_int(N), c_int(H), c_int(W), c_int(mask), _p(ws), _p(left), _p(right), _p(bottom), _p(top),
+                                _p(soln))
+    elif neumann is None:
         Sh, lh = dst_matrices(H, dev)
         Sw, lw = dst_matrices(W, dev)
         nbytes = int(lib.pcnn_varcoef_pcg_workspace_scaled(c_int(N), c_int(H), c_int(W)) if scaled else lib.pcnn_varcoef_pcg_workspace(c_int(N), c_int(H), c_int(W)))
@@ -246,12 +276,27 @@ def varcoef_pcg_solve(rho, rhs, left, right, bottom, top, dx, tol=1e-10, max_ite
                                    _p(flags))
             iterate = lambda it: h.call('pcnn_varcoef_bc_pcg_iterate_scaled', c_int(N), c_int(H), c_int(W), c_int(mask), _p(rho), _p(dx), c_double(tol), c_int(it),
                                         c_int(check_every), _p(Vih), _p(Vh), _p(lh), _p(ViwT), _p(VwT), _p(lw), _p(ws), c_size_t(nbytes), _p(scal), _p(flags))
-    scal = torch.empty((N, 8), dtype=torch.float64, device=dev)                  # (the closures above find scal, flags and soln when they are called)
+    if reaction is None:
+        scal = torch.empty((N, 8), dtype=torch.float64, device=dev)              # (the closures above find scal, flags and soln when they are called)
+    else:                                                                        # the N x 8 table, then N x 4 more doubles (include/pcnn.h)
+        scal_all = torch.empty((N * 12,), dtype=torch.float64, device=dev)
+        scal = scal_all[:N * 8].view(N, 8)
     flags = torch.empty((N,), dtype=torch.int32, device=dev)
     setup()
-    rho_min = scal[:, VARCOEF_SCALARS['rho_min']].cpu().numpy()
+    if reaction is None:
+        rho_min = scal[:, VARCOEF_SCALARS['rho_min']].cpu().numpy()
+    else:                                                               # one read for both tables
+        s0 = scal_all.cpu().numpy()
+        rho_min, extra = s0[:N * 8].reshape(N, 8)[:, VARCOEF_SCALARS['rho_min']], s0[N * 8:].reshape(N, 4)
     if not np.all(rho_min > 0):                                         # the setup kernel's minimum counts a NaN as -inf; nothing more is launched
         raise ValueError('rho must be positive everywhere (minimum per sample: %r)' % (rho_min.tolist(),))
+    if reaction is not None:
+        c_min, c_mean = extra[:, VARCOEF_REACTION_SCALARS['c_min']], extra[:, VARCOEF_REACTION_SCALARS['c_mean']]
+        if not np.all(c_min >= 0):                                      # (a NaN or an infinity counts as -inf there)
+            raise ValueError('reaction must be non-negative and finite on every unknown (minimum per sample: %r)' % (c_min.tolist(),))
+        if mask == 15 and not np.all(c_mean > 0):
+            raise ValueError('all four edges Neumann and a reaction that is zero on every unknown of sample(s) %r: that system is singular - solve such a '
+                             'sample without the reaction keyword' % (np.flatnonzero(~(c_mean > 0)).tolist(),))
     iterations = np.zeros(N, dtype=np.int64)
     done = (flags.cpu().numpy() != 0) if check_start else np.zeros(N, dtype=bool)
     it = 0
@@ -279,6 +324,14 @@ def varcoef_density(g, lo, hi):
     if g.dtype != torch.float32 or not g.is_cuda or not g.is_contiguous():
         raise ValueError('varcoef_density takes a contiguous CUDA float32 tensor')
     handle().call('pcnn_varcoef_density', c_int64(g.numel()), c_float(lo), c_float(hi), _p(g))
+    return g
+
+
+def varcoef_reaction_field(g, lo, hi):
+    """varcoef_density's map by the same kernel for a reaction field: 0 <= lo <= hi (pcnn_varcoef_reaction_field)."""
+    if g.dtype != torch.float32 or not g.is_cuda or not g.is_contiguous():
+        raise ValueError('varcoef_reaction_field takes a contiguous CUDA float32 tensor')
+    handle().call('pcnn_varcoef_reaction_field', c_int64(g.numel()), c_float(lo), c_float(hi), _p(g))
     return g
 
 
