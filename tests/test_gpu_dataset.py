@@ -62,6 +62,7 @@ def test_rocfft_route_agrees_with_the_gemm_route_at_full_size(H, W, N):
 
 
 def test_gemm_f64_and_dst_orthonormality():
+    # the host-side DST matrices only; pcnn_batched_gemm_f64 itself is called directly in tests/test_gpu_entry_points.py (test_gemm_f64_*)
     from poisson_cnn_amd.dataset import _kernels as K
     S, lam = K.dst_matrices(70, torch.device('cuda'))
     Sn = S.cpu().numpy()
